@@ -361,6 +361,22 @@ def headline_parity(model, opt, ex0, K, N_s, gemm, recurrence, oracle_utterances
     return res
 
 
+DUMP_MAX_ELEMENTS = 1 << 21      # per dumped array (8 MiB as fp32): five arrays stay far below 64 MB
+
+
+def output_sample(t, seed=0):
+    """-> numpy copy of `t` (float32; float64 stays float64).  Above DUMP_MAX_ELEMENTS elements: the flattened values at
+    sorted indices that depend on `seed` and the element count only, so that two runs of the same shape compare."""
+    t = t.detach()
+    if t.is_complex():
+        t = torch.view_as_real(t)
+    t = t.reshape(-1)
+    if t.numel() > DUMP_MAX_ELEMENTS:
+        idx = np.unique(np.random.RandomState(seed).randint(0, t.numel(), DUMP_MAX_ELEMENTS))
+        t = t[torch.as_tensor(idx, device=t.device)]
+    return t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+
+
 def newest_profile(suffix):
     """profiles/r<N>_<suffix> of the latest round that has one (PMC passes are collected per round)."""
     import glob
@@ -401,6 +417,10 @@ def main():
                     help="skip the correctness check of the timed batch (headline arithmetic vs fp32 kernels vs CPU oracle slice)")
     ap.add_argument("--no-exact-f32", action="store_true",
                     help="skip the secondary measurements (fp32 GEMMs, the fp32 end-to-end reference-width line, two-product weight gradients)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline's timed steps, write what its last step computed (loss, logit, time-domain "
+                         "estimate, flat gradient, updated parameters) as DIR/<name>.npy; arrays of more than "
+                         f"{DUMP_MAX_ELEMENTS} elements are a fixed, seeded sample of their flattened values (rank 0)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -449,6 +469,8 @@ def main():
         from tssep_amd.train.graph import GraphedStep
         gstep = GraphedStep(model, opt, adopt_inputs=True)
 
+    last_loss = [None]       # the loss of the latest step (--dump-outputs)
+
     def step(eager=False):
         """One training step: zero the flat gradient bucket, forward, LogMAE loss, backward (weight
         gradients accumulate into the bucket on the side stream), gradient all-reduce over ranks
@@ -456,14 +478,16 @@ def main():
         of everything up to the optimizer as one captured hipGraph (tssep_amd/train/graph.py); the
         speaker permutations are still drawn per step on the host."""
         if gstep is not None and not eager:
-            out, _ = gstep(dict(ex0))
+            out, summary = gstep(dict(ex0))
         else:
             opt.zero_grad()
             if bucketed:
                 opt.bucket.arm()     # every step is the last micro-step of its minibatch: layers reduce as they complete
             ex = dict(ex0)
             out = model(ex)
-            model.review(ex, out)["loss"].backward()
+            summary = model.review(ex, out)
+            summary["loss"].backward()
+        last_loss[0] = summary["loss"].detach()
         opt.step()                   # joins the side stream, all-reduces (what is left of it), clips, updates
         return out
 
@@ -474,7 +498,7 @@ def main():
 
     SETUP_STEPS = 3      # before the W warm-up steps: allocator growth, derived weight layouts, first-launch code loading
 
-    def timed_run(steps, warmup):
+    def timed_run(steps, warmup, dump=False):
         out = None
         for _ in range(SETUP_STEPS + warmup):
             out = step()
@@ -491,6 +515,10 @@ def main():
         barrier()
         dt_ = time.perf_counter() - t0
         timed_run.local_s = dt_              # this rank's own clock (the reported time is the MAX over ranks)
+        if dump:                             # before the eager pass below: a replay's outputs are static buffers
+            timed_run.outputs = {"loss": output_sample(last_loss[0].double()), "logit": output_sample(out.logit, 1),
+                                 "time_estimate": output_sample(out.time_estimate, 2),
+                                 "gradient": output_sample(opt.bucket.flat, 3), "parameters": output_sample(opt.flat_param, 4)}
         H.KERNEL_TIMING = False
         if gstep is not None:                # per-kernel roofline timings: an eager pass after the timed region
             H.KERNEL_TIMING = True
@@ -678,8 +706,12 @@ def main():
             finally:
                 H.RECURRENCE = old_rec
         H.GEMM_PRECISION = args.gemm
-    dt, T, med = timed_run(args.steps, args.warmup)
+    dt, T, med = timed_run(args.steps, args.warmup, dump=args.dump_outputs is not None)
     dt_local = timed_run.local_s
+    if args.dump_outputs is not None and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in timed_run.outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     H.check_cluster_errors(dev)
     roofline, mask_head = rooflines(dt, args.gemm)
     if mask_head is not None and world == 1:

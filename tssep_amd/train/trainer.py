@@ -199,6 +199,7 @@ class Trainer(Configurable):
         # speaker permutations are drawn from np.random per step exactly as in the eager step, so a seeded run computes
         # the same losses and parameters either way (tests: bit-identical over 24 iterations).
         from .. import hip_ops as _H
+        from . import runtime as _runtime
         gstep = None
         on_gpu = next(self.model.parameters()).is_cuda
         bucketed = world > 1 and _H.BUCKETED_ALLREDUCE
@@ -263,7 +264,12 @@ class Trainer(Configurable):
                         self._log_kernel_plan(glog, rlog, chief)
                     elif gstep is not None and gstep.usable(ex) and (
                             _H.GRAPH_STEP == "on" or self._utterances(ex) <= _H.GRAPH_MAX_UTTERANCES):
-                        _, summary = gstep(ex)           # forward + loss + backward as one replayed hipGraph
+                        # forward + loss + backward as one replayed hipGraph, captured as ONE chain of nodes: the weight
+                        # gradients stay on the compute stream inside the graph (same kernels, same order, same sums).  A
+                        # graph with the side-stream branch, replayed while the input pipeline's threads issue their copies
+                        # on a stream of their own, took the process down (SIGSEGV, toy experiments and the two-rank run)
+                        with _runtime.applied(side_stream=False):
+                            _, summary = gstep(ex)
                     else:
                         summary = self.model.review(ex, self.model(ex))
                         summary["loss"].backward()
