@@ -94,8 +94,10 @@ extern "C" int tssep_adam_step_guarded(float* param, float* exp_avg, float* exp_
   if (!aligned16(grad)) return TSSEP_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(SQ_BLOCKS), dim3(256), 0, s, grad, n, (float*)ws);
-  const float bc1 = 1.0f - (float)pow((double)beta1, (double)step);
-  const float bc2 = 1.0f - (float)pow((double)beta2, (double)step);
+  // the bias corrections in double, rounded once: rounding beta^step to float first and subtracting it from 1 in float
+  // cancels -- beta2 = 0.999 at step 2 gave bc2 = 0.002 off by up to 1.5e-5 relative, 7e-6 in every update
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  const float bc2 = (float)(1.0 - pow((double)beta2, (double)step));
   int64_t blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)blocks), dim3(256), 0, s, param, exp_avg,
