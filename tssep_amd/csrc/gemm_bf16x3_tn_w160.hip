@@ -793,6 +793,12 @@ int tssep_gemm_bf16x3_tn_w160_launch(const tssep_gemm_args* g, const gemm_detail
   // masks by out-of-range loads: whole four-column pieces only (the time-shifted kernel exists in this form alone)
   const bool oob = (g->M & 3) == 0 && (g->N & 3) == 0 && !g->b_ones_col;
   if (shift && !oob) return TSSEP_E_UNSUPPORTED;
+  // The two-product eight-wave kernels with a real column on the VALU (XC = 10, 11) sum that column wrongly now and then:
+  // one product of one k row is lost or changed for a quarter wave (rows 4 q + c of one 64-row group), in about half the
+  // launches at 194 304 or 777 216 rows; the three-product kernels are exact on the same operands
+  // (tests/test_gpu_gemm_kernels.py, precision 2).  Declined until the cause is found: the next candidate computes it.
+  if (TNW160_WIDE && two && wide && g->N - (g->b_ones_col ? 1 : 0) > gemm_detail::tn_w160_wide_cols(g, wide))
+    return TSSEP_E_UNSUPPORTED;
   // 32-bit buffer offsets inside a split
   const int64_t ktiles = (g->K + VBK - 1) / VBK, per = (ktiles + splitk - 1) / splitk;
   const int64_t ldmax = g->lda > g->ldb ? g->lda : g->ldb;
