@@ -2,12 +2,17 @@
 """Headline benchmark: STFT frames / second, forward + backward, 4-speaker TS-SEP on
 16 kHz 4 s chunks (BASELINE.json configs[2]), one process per MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--batch B]
+  python bench.py --gpus N --steps K --warmup W [--batch B] [--full]
 
 A step = STFT -> MFCC+log1p features -> RNNP pre-net -> 'mul' conditioning -> 3 RNNP post-net
 layers (TS-VAD speaker combination) -> mask head -> iSTFT -> LogMAE, then backward to every
 parameter, (N > 1) the all-reduce(SUM) of the flat gradient, and the fused global-norm clip +
 Adam update.  Inputs are synthetic and resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run times the headline and nothing else.  --full adds the secondary lines (exact-fp32 GEMMs, the
+reference-width fp32 line, two-product weight gradients, plain-bf16 GEMMs), the parity check of the timed
+batch, the CPU baseline, the stand-alone mask head and, under graph replay, the eager pass the roofline is
+timed on; their keys are null in a plain run.
 """
 import argparse
 import json
@@ -126,6 +131,16 @@ def launch_ranks(n, argv):
 
 
 BAR_GRADIENTS = 1e-3      # of each tensor's largest entry (1e-2 until round 5)
+PARITY_SEED = 4321        # np.random seed of cpu_baseline's parity check: its HIP leg and the oracle draw the same permutations
+
+
+def skip_parity_check(model, parity_batch=4):
+    """Leave the global RNGs as cpu_baseline(model, opt, parity_only=True) leaves them, without running it: torch
+    reseeded with 0, np.random reseeded with PARITY_SEED and then drawn from for the oracle's `parity_batch`
+    permutations.  The weights, the Adam state and the gradient bucket come out of that check as they went in."""
+    torch.manual_seed(0)
+    np.random.seed(PARITY_SEED)
+    model.mask_estimator.draw_permutations(parity_batch, K_SPK)
 
 
 def cpu_baseline(hip_model=None, opt=None, seconds_budget=24.0, batch=16, parity_only=False, parity_batch=4, assert_bars=True):
@@ -156,7 +171,7 @@ def cpu_baseline(hip_model=None, opt=None, seconds_budget=24.0, batch=16, parity
 
     def one_step(keep=False, inputs=None):
         t0 = time.time()
-        np.random.seed(4321)
+        np.random.seed(PARITY_SEED)
         o = omodel.forward_loss(p, *(inputs or x), cfg=cfg, fast=True)
         o["loss"].sum().backward()
         dt_ = time.time() - t0
@@ -172,7 +187,7 @@ def cpu_baseline(hip_model=None, opt=None, seconds_budget=24.0, batch=16, parity
                   speaker_reverberation_early_ch0=x[2].to(dev), reference_channel=0,
                   dataset=["parity"] * B)
         opt.zero_grad()
-        np.random.seed(4321)
+        np.random.seed(PARITY_SEED)
         out = hip_model(ex)
         loss = hip_model.review(ex, out)["loss"]
         loss.backward()
@@ -409,6 +424,9 @@ def main():
                          "for H >= 128); stream / cluster = exact fp32")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the step as a captured hipGraph (auto: small batches, where launches dominate)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the secondary lines, the parity check of the timed batch, the CPU "
+                         "baseline, the stand-alone mask head and (graph replay) the eager roofline pass")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--oracle-slice", type=int, default=-1,
                     help="utterances of the timed batch the CPU oracle re-computes in parity_at_headline_batch (forward; the "
@@ -416,7 +434,8 @@ def main():
     ap.add_argument("--no-headline-parity", action="store_true",
                     help="skip the correctness check of the timed batch (headline arithmetic vs fp32 kernels vs CPU oracle slice)")
     ap.add_argument("--no-exact-f32", action="store_true",
-                    help="skip the secondary measurements (fp32 GEMMs, the fp32 end-to-end reference-width line, two-product weight gradients)")
+                    help="skip the secondary measurements (fp32 GEMMs, the fp32 end-to-end reference-width line, two-product weight "
+                         "gradients) and the steps of the fp32 lines, which precede the headline even in a plain run")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the headline's timed steps, write what its last step computed (loss, logit, time-domain "
                          "estimate, flat gradient, updated parameters) as DIR/<name>.npy; arrays of more than "
@@ -498,7 +517,7 @@ def main():
 
     SETUP_STEPS = 3      # before the W warm-up steps: allocator growth, derived weight layouts, first-launch code loading
 
-    def timed_run(steps, warmup, dump=False):
+    def timed_run(steps, warmup, dump=False, kernel_pass=True):
         out = None
         for _ in range(SETUP_STEPS + warmup):
             out = step()
@@ -520,7 +539,7 @@ def main():
                                  "time_estimate": output_sample(out.time_estimate, 2),
                                  "gradient": output_sample(opt.bucket.flat, 3), "parameters": output_sample(opt.flat_param, 4)}
         H.KERNEL_TIMING = False
-        if gstep is not None:                # per-kernel roofline timings: an eager pass after the timed region
+        if gstep is not None and kernel_pass:          # per-kernel roofline timings: an eager pass after the timed region
             H.KERNEL_TIMING = True
             for _ in range(min(steps, 10)):
                 out = step(eager=True)
@@ -674,15 +693,20 @@ def main():
     exact = ref_width = None
     if args.gemm != "f32" and world == 1 and not args.no_exact_f32 and args.workload == "cfg3":
         # secondary line: the same step with every GEMM in exact fp32 (the reference's GEMM arithmetic) and the
-        # default split-bf16 recurrence, same steps / warm-up, its own roofline
+        # default split-bf16 recurrence, same steps / warm-up, its own roofline.
+        # A plain run reports neither this line nor the reference-width one but still runs their steps: each step updates
+        # the weights and the Adam moments and draws speaker permutations from np.random, and the headline is timed from
+        # the state these lines leave behind.  Skipping them would change what the headline's steps compute and what
+        # --dump-outputs writes; --no-exact-f32 skips them with or without --full.
         H.GEMM_PRECISION = "f32"
         dt_e, T_e, med_e = timed_run(args.steps, args.warmup)
-        roof_e, mh_e = rooflines(dt_e, "f32")
         rec_f32 = args.recurrence in ("stream", "cluster")
-        exact = dict(value=round(B * T_e * args.steps / dt_e, 1), unit="frames/s",
-                     ms_per_step=round(dt_e / args.steps * 1e3, 3), ms_per_step_median=round(med_e, 3),
-                     steps=args.steps, warmup=args.warmup, dtype="f32" if rec_f32 else "f32 GEMMs + bf16x3 recurrence",
-                     arithmetic=arithmetic("f32"), roofline=roof_e, roofline_mask_head=mh_e)
+        if args.full:
+            roof_e, mh_e = rooflines(dt_e, "f32")
+            exact = dict(value=round(B * T_e * args.steps / dt_e, 1), unit="frames/s",
+                         ms_per_step=round(dt_e / args.steps * 1e3, 3), ms_per_step_median=round(med_e, 3),
+                         steps=args.steps, warmup=args.warmup, dtype="f32" if rec_f32 else "f32 GEMMs + bf16x3 recurrence",
+                         arithmetic=arithmetic("f32"), roofline=roof_e, roofline_mask_head=mh_e)
         if not rec_f32:
             # the REFERENCE-WIDTH bookend (VERDICT r3 #5a): fp32 end to end as the reference computes
             # (tssep/train/model.py:502-511) -- exact-fp32 MFMA GEMMs AND an exact-fp32 recurrence: the sequence-parallel
@@ -696,28 +720,31 @@ def main():
                 st_r, wu_r = min(args.steps, 10), min(args.warmup, 2)
                 dt_r, T_r, med_r = timed_run(st_r, wu_r)
                 H.check_cluster_errors(dev)
-                roof_r, mh_r = rooflines(dt_r, "f32", st_r)
-                ref_width = dict(value=round(B * T_r * st_r / dt_r, 1), unit="frames/s",
-                                 ms_per_step=round(dt_r / st_r * 1e3, 3), ms_per_step_median=round(med_r, 3),
-                                 steps=st_r, warmup=wu_r, dtype="f32",
-                                 arithmetic=arithmetic("f32").split(";")[0] + f"; exact fp32 {ref_rec} recurrence",
-                                 roofline=roof_r, roofline_mask_head=mh_r,
-                                 parity_vs_cpu_oracle=None if args.no_cpu_baseline else cpu_baseline(model, opt, parity_only=True))
+                if args.full:
+                    roof_r, mh_r = rooflines(dt_r, "f32", st_r)
+                    ref_width = dict(value=round(B * T_r * st_r / dt_r, 1), unit="frames/s",
+                                     ms_per_step=round(dt_r / st_r * 1e3, 3), ms_per_step_median=round(med_r, 3),
+                                     steps=st_r, warmup=wu_r, dtype="f32",
+                                     arithmetic=arithmetic("f32").split(";")[0] + f"; exact fp32 {ref_rec} recurrence",
+                                     roofline=roof_r, roofline_mask_head=mh_r,
+                                     parity_vs_cpu_oracle=None if args.no_cpu_baseline else cpu_baseline(model, opt, parity_only=True))
+                elif not args.no_cpu_baseline:
+                    skip_parity_check(model)
             finally:
                 H.RECURRENCE = old_rec
         H.GEMM_PRECISION = args.gemm
-    dt, T, med = timed_run(args.steps, args.warmup, dump=args.dump_outputs is not None)
+    dt, T, med = timed_run(args.steps, args.warmup, dump=args.dump_outputs is not None, kernel_pass=args.full)
     dt_local = timed_run.local_s
     if args.dump_outputs is not None and rank == 0:
         os.makedirs(args.dump_outputs, exist_ok=True)
         for name, a in timed_run.outputs.items():
             np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     H.check_cluster_errors(dev)
-    roofline, mask_head = rooflines(dt, args.gemm)
-    if mask_head is not None and world == 1:
+    roofline, mask_head = rooflines(dt, args.gemm)      # (a plain run under graph replay has no kernel timings: None)
+    if args.full and mask_head is not None and world == 1:
         mask_head["standalone_head"] = standalone_head()
     two_prod = None
-    if args.gemm == "bf16x3" and world == 1 and not args.no_exact_f32 and args.workload == "cfg3" and gstep is None:
+    if args.full and args.gemm == "bf16x3" and world == 1 and not args.no_exact_f32 and args.workload == "cfg3" and gstep is None:
         # secondary line, opt-in arithmetic (tssep_gemm_args.precision = 2): the weight-gradient GEMMs drop the dY_lo x X_hi
         # product -- d(gates) enters them as plain bf16, X keeps hi + lo.  The forward (masks, loss) is bit-identical;
         # every term of a weight-gradient sum carries up to 2^-9 instead of 2^-16 relative error, which averages over
@@ -736,7 +763,7 @@ def main():
         finally:
             H.WGRAD_PRODUCTS = 3
     plain_bf16 = None
-    if args.gemm == "bf16x3" and world == 1 and not args.no_exact_f32 and args.workload == "cfg3" and gstep is None:
+    if args.full and args.gemm == "bf16x3" and world == 1 and not args.no_exact_f32 and args.workload == "cfg3" and gstep is None:
         # side line for the literal "bf16" of BASELINE configs[2], NOT the headline: the row x row GEMMs on the
         # persistent kernels with ONE bf16 product per k-step (tssep_gemm_args.precision = 3: operands rounded to bf16, fp32
         # accumulation), the weight gradients with dY as plain bf16 (precision = 2); recurrences, features, mask head, losses
@@ -757,7 +784,7 @@ def main():
         finally:
             H.GEMM_PRECISION = args.gemm
     at_batch = None
-    if world == 1 and not args.no_headline_parity and args.gemm != "f32":
+    if args.full and world == 1 and not args.no_headline_parity and args.gemm != "f32":
         # the batch the headline was timed on, checked against different kernels end to end and the CPU oracle
         at_batch = headline_parity(model, opt, ex0, K, N_s, args.gemm, args.recurrence,
                                    oracle_utterances=args.oracle_slice if args.oracle_slice >= 0 else
@@ -826,8 +853,9 @@ def main():
                        "collective": collective,
                        "arithmetic": arithmetic(args.gemm), "recurrence": args.recurrence,
                        "runtime_policy": {k: v for k, v in RT.current().items() if v != RT.defaults()[k]} or "defaults (tssep_amd/train/runtime.py)",
-                       "hip_graph": ("forward + loss + backward replayed as one captured hipGraph; optimizer eager; "
-                                     "roofline timings from an eager pass after the timed region") if graphed else None,
+                       "hip_graph": ("forward + loss + backward replayed as one captured hipGraph; optimizer eager"
+                                     + ("; roofline timings from an eager pass after the timed region" if args.full else ""))
+                                    if graphed else None,
                        "tflop_per_step": dict(
                            total=round(3 * flops_per_frame(K) * B * T / 1e12, 4),
                            gemm_family=round((3 * flops_per_frame(K, recurrent=False) + 16 * UNITS * UNITS * (2 * K + 2))
@@ -839,7 +867,7 @@ def main():
             "parity_at_headline_batch": at_batch,
             "f32_gemms_bf16x3_recurrence": exact, "reference_width": ref_width,
             "two_product_wgrad": two_prod, "plain_bf16_gemms": plain_bf16,
-            "cpu_baseline": None if (args.no_cpu_baseline or world > 1 or args.workload == "cfg5")
+            "cpu_baseline": None if (not args.full or args.no_cpu_baseline or world > 1 or args.workload == "cfg5")
             else cpu_baseline(model, opt),
         }
         print(json.dumps(line), flush=True)

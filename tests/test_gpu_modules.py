@@ -1341,13 +1341,13 @@ def test_rccl_communicator_single_rank():
 
 
 def test_bench_default_flags_print_one_json_line():
-    """`python bench.py` with its default flags (split-bf16 line + the exact-fp32 secondary line + the rooflines)
+    """`python bench.py --full` with its default flags (split-bf16 line + the exact-fp32 secondary line + the rooflines)
     at a small batch: ONE JSON line on stdout with the contract's keys.  (The exact-fp32 leg once crashed on a
-    variable the main leg defined later -- nothing else in the suite runs that leg.)"""
+    variable the main leg defined later -- nothing else in the suite measures that leg.)"""
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "8", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--batch", "8", "--steps", "2", "--warmup", "1",
                         "--no-cpu-baseline", "--oracle-slice", "4", "--graph", "off"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1383,6 +1383,40 @@ def test_bench_default_flags_print_one_json_line():
     assert d["two_product_wgrad"] is not None and d["two_product_wgrad"]["value"] > 0
 
 
+@pytest.mark.parametrize("graph", ["off", "on"])
+def test_bench_plain_run_computes_the_full_runs_headline(graph, tmp_path):
+    """A plain `python bench.py` measures the headline only; `--full` adds the secondary lines, the parity checks and
+    the CPU baseline.  The headline's timed steps start from the state the fp32 lines and the reference-width parity
+    check leave behind (weights, Adam moments, np.random), so a plain run still runs those lines' steps and leaves the
+    RNGs as that check does (bench.skip_parity_check): its dumped outputs must equal the full run's bit for bit.  Graph
+    replay: the lines' eager roofline passes are steps too, the headline's own is --full only."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "8", "--steps", "2", "--warmup", "1",
+                            "--oracle-slice", "0", "--graph", graph, *extra], capture_output=True, text=True, timeout=900, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+
+    full = run("--full", "--dump-outputs", str(tmp_path / "full"))
+    plain = run("--dump-outputs", str(tmp_path / "plain"))
+    assert full["reference_width"]["parity_vs_cpu_oracle"] is not None and full["cpu_baseline"] is not None
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0
+    for k in ("f32_gemms_bf16x3_recurrence", "reference_width", "two_product_wgrad", "plain_bf16_gemms",
+              "parity_at_headline_batch", "cpu_baseline"):
+        assert plain[k] is None, k
+    assert (plain["roofline"] is None) == (graph == "on")
+    for name in ("loss", "logit", "time_estimate", "gradient", "parameters"):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), name
+
+
 _TWO_RANK_CHECKSUMS = {}
 
 
@@ -1410,7 +1444,7 @@ def test_bench_two_ranks_on_one_gpu(workload, batch, graph, bucketed):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
                         "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", workload, "--batch", str(batch),
-                        "--recurrence", "stream", "--no-cpu-baseline", "--no-exact-f32", "--graph", graph,
+                        "--recurrence", "stream", "--no-cpu-baseline", "--no-exact-f32", "--graph", graph, "--full",
                         *(["--runtime", "bucketed_allreduce=true"] if bucketed else [])],
                        capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

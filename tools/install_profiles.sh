@@ -1,6 +1,6 @@
 #!/bin/bash
 # Copies what tools/collect_r6.sh wrote under gpurun_out/final/ into profiles/ (tracked), names r<round>_*.
-# usage: bash tools/install_profiles.sh [round] [batch] [gemm]      then re-run `python bench.py` on the GPU box
+# usage: bash tools/install_profiles.sh [round] [batch] [gemm]      then re-run `python bench.py --full` on the GPU
 # for the default line with the PMC fields filled (profiles/r<round>_bench_default.json).
 set -e
 R=${1:-6}; B=${2:-768}; G=${3:-bf16x3}; F=gpurun_out/final; P=profiles/r${R}
