@@ -39,6 +39,74 @@ def test_recurrence_policy():
         H.RECURRENCE = old
 
 
+def test_recurrence_plan():
+    """recurrence_plan: kernel and group count of both directions, pinned for a given CU count (the workloads' layers
+    on a 256-CU MI355X included); recurrence_kernel / onchip16_groups above are views of one direction of it."""
+    from tssep_amd.train import runtime
+    O16, O32, STREAM, CLUSTER = "onchip16_bf16x3", "onchip32_bf16x3", ("stream_f32", 0), ("cluster_f32", 0)
+
+    def plan(N, Hh, T=253, cus=256):
+        return H.recurrence_plan(N, T, Hh, cus)
+
+    with runtime.applied(runtime.defaults()):
+        assert plan(8, 300)["fwd"] == (O16, 1)
+        assert plan(1536, 300)["fwd"] == (O16, 2)
+        assert plan(8, 300)["bwd"] == (O16, 1)
+        assert plan(32, 300)["bwd"] == (O16, 1)
+        # VERDICT r3 #4: no cliff at 2 046 frames any more (the step field of the exchange tags wraps); the limit is the
+        # 32-bit lane offset into the gate tensor -- 14 913 frames for the 16-sequence kernels, 7 215 for the 32-sequence
+        # ones -- and a fallback beyond it is announced
+        assert plan(32, 300, T=1878)["bwd"] == (O16, 1) and plan(32, 300, T=4000)["bwd"] == (O16, 1)
+        L = _lib.lib()
+        assert L.tssep_lstm_onchip_max_steps(300, 16) == 14913 and L.tssep_lstm_onchip_max_steps(300, 32) == 7215
+        # (so no supported H stops short of the 2 046 frames of rounds 1-3)
+        assert all(L.tssep_lstm_onchip_max_steps(h, s) >= 2046 for h in range(1, 1025) if L.tssep_lstm_onchip_supported(h)
+                   for s in (16, 32))
+        assert plan(32, 300, T=14913) == dict(fwd=(O16, 1), bwd=(O16, 1))
+        H._WARNED.clear()
+        with pytest.warns(RuntimeWarning, match="streaming fp32 kernel runs instead"):
+            assert plan(32, 300, T=20000)["bwd"] == STREAM
+        # no 16-sequence groups (not even one cluster per XCD): the 32-sequence kernels and their limit
+        assert plan(32, 300, T=7215, cus=16) == dict(fwd=(O32, 0), bwd=(O32, 0))
+        H._WARNED.clear()
+        with pytest.warns(RuntimeWarning, match="7215 at H = 300"):
+            assert plan(32, 300, T=7216, cus=16) == dict(fwd=STREAM, bwd=STREAM)
+        assert plan(33, 300)["bwd"] == (O16, 1)
+        assert plan(768, 300)["bwd"] == (O16, 2)
+        # the interleaved backward serves H = 257...320; H % 4 != 0: no interleaved kernel at all
+        assert plan(8, 256) == dict(fwd=(O16, 1), bwd=(O32, 0))
+        assert plan(40, 260) == dict(fwd=(O16, 1), bwd=(O16, 1))
+        assert plan(8, 130) == dict(fwd=(O32, 0), bwd=(O32, 0))
+        # small or unsupported hidden sizes fall back to the streaming kernels
+        assert plan(64, 12)["fwd"] == STREAM
+        assert plan(64, 512)["fwd"] == STREAM
+        # the workloads' layers (bench.py cfg3 / cfg4 / cfg5) on a 256-CU MI355X
+        for N, T, g in ((768, 253, 2), (3072, 253, 2), (8, 253, 1), (32, 253, 1), (96, 1878, 1), (768, 1878, 2)):
+            assert plan(N, 300, T) == dict(fwd=(O16, g), bwd=(O16, g)), (N, T)
+            with runtime.applied(onchip16_bwd=False):
+                assert plan(N, 300, T) == dict(fwd=(O16, g), bwd=(O32, 0)), (N, T)
+            with runtime.applied(recurrence="cluster"):
+                assert plan(N, 300, T) == dict(fwd=CLUSTER, bwd=CLUSTER), (N, T)
+            with runtime.applied(recurrence="stream"):
+                assert plan(N, 300, T) == dict(fwd=STREAM, bwd=STREAM), (N, T)
+        # forced and capped group counts, the interleaved kernels off
+        with runtime.applied(onchip16_groups=4, onchip16_bwd_groups=4):
+            assert plan(3072, 300) == dict(fwd=(O16, 4), bwd=(O16, 4))
+            assert plan(40, 300) == dict(fwd=(O16, 1), bwd=(O16, 1))      # (3 groups of 16: 4 does not divide them)
+        with runtime.applied(onchip16_bwd_groups=1):
+            assert plan(3072, 300) == dict(fwd=(O16, 2), bwd=(O16, 1))
+        with runtime.applied(onchip16_min_n=100):
+            assert plan(96, 300) == dict(fwd=(O32, 0), bwd=(O32, 0)) and plan(768, 300)["fwd"] == (O16, 2)
+        with runtime.applied(onchip16=False):
+            assert plan(768, 300) == dict(fwd=(O32, 0), bwd=(O32, 0))
+        with runtime.applied(recurrence="stream"):
+            assert plan(8, 300)["fwd"] == STREAM
+        with runtime.applied(recurrence="cluster"):
+            assert plan(8, 512) == dict(fwd=STREAM, bwd=STREAM)          # not supported -> fallback
+        with runtime.applied(recurrence="onchip"):
+            assert plan(8, 512)["bwd"] == STREAM                          # not supported -> fallback
+
+
 def test_splitk_choice():
     """tssep_gemm_wgrad_splits (host-only: runs without a GPU): the split count follows the kernel the library's own
     dispatcher picks for the weight gradient (tssep_gemm_plan), never a second copy of its conditions."""

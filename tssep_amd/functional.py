@@ -74,34 +74,17 @@ class _RNNP(torch.autograd.Function):
         R = N * T
         assert xv.shape[0] == R and xv.shape[1] >= I, (xv.shape, R, I)
         lstm_params = [w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r]
-        pk = dict(H.derived("lstm_pack", lstm_params, lambda: H.lstm_pack(lstm_params, Hh, I)))
+        pk = H.derived("lstm_pack", lstm_params, lambda: H.lstm_pack(lstm_params, Hh, I))
         gates = torch.empty(R, 8 * Hh, device=dev, dtype=torch.float32)
         H.gemm(xv, ld_x, pk["wih_p"], pk["ld_i"], gates, 8 * Hh, R, 8 * Hh, I, bias=pk["bias_p"])
         Hp = _pad4(Hh)
         cell = torch.empty(N, T, 2, Hh, device=dev, dtype=torch.float32)
         hout = (torch.zeros if Hp != Hh else torch.empty)(R, 2 * Hp, device=dev, dtype=torch.float32)
-        kf, kb = H.recurrence_kernel(N, Hh, False, T, dev), H.recurrence_kernel(N, Hh, True, T, dev)
-        cf = cb = wf3 = wb3 = None
-        if "cluster" in (kf, kb):
-            cf, cb = H.derived("pack_cluster", [w_hh, w_hh_r], lambda: H.lstm_pack_cluster(w_hh, w_hh_r, Hh))
-        # the 32-sequence W-stationary kernels' packed weights only where one of the two directions of time runs on them
-        g16 = H.onchip16_groups(N, Hh, dev) if kf == "onchip" and (2 * Hp) % 4 == 0 and Hp % 4 == 0 else 0
-        g16b = H.onchip16_bwd_groups(N, Hh, dev) if kb == "onchip" and Hp % 4 == 0 else 0
-        if (kf == "onchip" and not g16) or (kb == "onchip" and not g16b):
-            wf3, wb3 = H.derived("pack_onchip", [w_hh, w_hh_r], lambda: H.lstm_pack_onchip(w_hh, w_hh_r, Hh))
-        if kf == "cluster":
-            H.blstm_cluster_fwd(gates, cell, hout, 2 * Hp, Hp, cf, N, T, Hh)
-        elif kf == "onchip":
-            if g16:      # interleaved 16-sequence groups (round 3)
-                wf16 = H.derived("pack_onchip16", [w_hh, w_hh_r], lambda: H.lstm_pack_onchip16(w_hh, w_hh_r, Hh))
-                H.blstm_onchip16_fwd(gates, cell, hout, 2 * Hp, Hp, wf16, N, T, Hh, g16)
-            else:
-                H.blstm_onchip_fwd(gates, cell, hout, 2 * Hp, Hp, wf3, N, T, Hh)
-        else:
-            H.blstm_fwd(gates, cell, hout, 2 * Hp, Hp, pk["whh_f"], N, T, Hh)
-        pk["whh_cb"] = cb if kb == "cluster" else None
-        pk["whh_ob"] = wb3 if kb == "onchip" else None
-        pk["bwd_onchip"] = kb == "onchip"
+        # the plan and BOTH directions' W_hh layouts are fetched here, once: the backward launches from what ctx keeps (a
+        # step captured without prepare_derived builds a layout at every ask)
+        plan = H.recurrence_plan(N, T, Hh, H.n_cus(dev))
+        whh = H.recurrence_packs(plan, w_hh, w_hh_r, Hh, pk, memo=True)
+        H.recurrence_launch(plan["fwd"], "fwd", gates, cell, hout, 2 * Hp, Hp, whh["fwd"], N, T, Hh)
         # projection weight in the (possibly padded) [hdim, 2*Hp] column layout of hout
         wp = H.derived("proj_layout", [w_proj], lambda: _proj_layout(w_proj, Hh, Hp))
         if combine:
@@ -116,7 +99,7 @@ class _RNNP(torch.autograd.Function):
             H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, ld_y, R, hdim, 2 * Hp, bias=b_proj.detach(), act=act)
         ctx.save_for_backward(xv, gates, cell, hout, y, wp)
         ctx.params = (w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, w_proj, b_proj)
-        ctx.pk = pk
+        ctx.recurrence = (plan["bwd"], whh["bwd"])
         ctx.meta = (N, T, I, Hh, Hp, hdim, ld_x, ld_y, act, combine)
         # Tanh-backward fold (see rnnp_layer): in_link = the link my producer hung on x, out_link = the one my
         # consumer may answer on.  Both are decided again in backward, when it is known who else uses the tensors.
@@ -129,7 +112,6 @@ class _RNNP(torch.autograd.Function):
     def backward(ctx, dy):
         xv, gates, cell, hout, y, wp = ctx.saved_tensors
         N, T, I, Hh, Hp, hdim, ld_x, ld_y, act, combine = ctx.meta
-        pk = ctx.pk
         dev = dy.device
         R = N * T
         K = combine if combine else 1
@@ -202,18 +184,8 @@ class _RNNP(torch.autograd.Function):
         wpT, ld_t = H.derived("proj_T", [w_proj], lambda: H.transposed(
             H.derived("proj_layout", [w_proj], lambda: _proj_layout(w_proj, Hh, Hp)), hdim, 2 * Hp))
         H.gemm(dz, ld_dz, wpT, ld_t, dhout, 2 * Hp, R, 2 * Hp, hdim)
-        if pk.get("whh_cb") is not None:
-            H.blstm_cluster_bwd(gates, cell, dhout, 2 * Hp, Hp, pk["whh_cb"], N, T, Hh)
-        elif pk.get("bwd_onchip"):
-            g16 = H.onchip16_bwd_groups(N, Hh, gates.device) if Hp % 4 == 0 else 0
-            if g16:      # interleaved 16-sequence groups (round 3)
-                w_hh, w_hh_r = ctx.params[1], ctx.params[5]
-                wb16 = H.derived("pack_onchip16_bwd", [w_hh, w_hh_r], lambda: H.lstm_pack_onchip16_bwd(w_hh, w_hh_r, Hh))
-                H.blstm_onchip16_bwd(gates, cell, dhout, 2 * Hp, Hp, wb16, N, T, Hh, g16)
-            else:
-                H.blstm_onchip_bwd(gates, cell, dhout, 2 * Hp, Hp, pk["whh_ob"], N, T, Hh)
-        else:
-            H.blstm_bwd(gates, cell, dhout, 2 * Hp, Hp, pk["whh_b"], N, T, Hh)
+        planned, whh_bwd = ctx.recurrence
+        H.recurrence_launch(planned, "bwd", gates, cell, dhout, 2 * Hp, Hp, whh_bwd, N, T, Hh)
 
         # ---- LSTM weight / bias gradients from dgates (side stream when direct)
         def lstm_wgrads():

@@ -266,7 +266,7 @@ def feat_fwd(X, fb, dct, n_mfcc, top_db=80.0, statistics_axis="tf"):
 # Arithmetic of the non-recurrent GEMMs: "bf16x3" = split-bf16 on the bf16 MFMA with fp32 accumulation (fp32-class
 # accuracy: masks 3e-6 from the CPU oracle, see gemm_bf16x3.hip) -- the DEFAULT since round 5: what bench.py measures is
 # what `python -m tssep_amd.exp.run_tssep` trains with; "f32" = exact fp32 MFMA (the reference's GEMM arithmetic).  The
-# recurrence kernel (exact fp32 or split-bf16) is chosen separately by recurrence_kernel().
+# recurrence kernel (exact fp32 or split-bf16) is chosen separately by recurrence_plan().
 # This module reads NO environment variable: every policy attribute below has its default here and is set -- recorded
 # in config.yaml / log/runtime.json -- through tssep_amd.train.runtime (`eg.runtime.*`, `bench.py --runtime k=v`).
 GEMM_PRECISION = "bf16x3"
@@ -605,23 +605,7 @@ def lstm_pack(params, H, I):
     return dict(wih_p=wih_p, bias_p=bias_p, whh_f=whh_f, whh_b=whh_b, ld_i=ld_i, _keep=(buf, ps))
 
 
-def blstm_fwd(gates, cell, hout, ldo, dstride, whh_f, N, T, H):
-    _log_recurrence("stream_f32", "fwd", N, T, H, 0)
-    with _timed("blstm_fwd", 2 * 2 * N * T * 4 * H * H):
-        check(_lib.lib().tssep_blstm_fwd(_p(gates), _p(cell), _p(hout), ldo, dstride, _p(whh_f), N,
-                                         T, H, _stream()), "blstm_fwd")
-
-
-def blstm_bwd(gates, cell, dhout, ldo, dstride, whh_b, N, T, H):
-    _log_recurrence("stream_f32", "bwd", N, T, H, 0)
-    with _timed("blstm_bwd", 2 * 2 * N * T * 4 * H * H):
-        check(_lib.lib().tssep_blstm_bwd(_p(gates), _p(cell), _p(dhout), ldo, dstride, _p(whh_b), N,
-                                         T, H, _stream()), "blstm_bwd")
-
-
-# cluster (W-stationary) recurrence ------------------------------------------------------------
 _ERR = {}
-RECURRENCE = "auto"    # "auto" | "stream" (lstm.hip) | "cluster" (lstm_cluster.hip) | "onchip"
 
 
 def _err_flag(device):
@@ -665,116 +649,67 @@ def _warn_once(key, msg):
         warnings.warn(msg, RuntimeWarning, stacklevel=3)
 
 
-def onchip_max_steps(N, H, backward, device=None):
-    """Longest sequence (frames) the W-stationary split-bf16 recurrence takes for this launch: the 16-sequence
-    kernels address (seqs - 1) T 2H 16 bytes of gates from a work item's base with 32 bits -- 14 913 frames at
-    H = 300 (7 215 for the 32-sequence kernels that serve the shapes the interleaved ones do not).  Rounds 1-3
-    stopped at 2 046 (an 11-bit step field in the exchange tags; it wraps now, lstm_onchip.hip)."""
-    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
-    g16 = 0
-    if dev is not None and H % 4 == 0:
-        g16 = onchip16_bwd_groups(N, H, dev) if backward else onchip16_groups(N, H, dev)
-    return int(_lib.lib().tssep_lstm_onchip_max_steps(H, 16 if g16 else 32))
+# recurrence policy (train/runtime.py: recurrence, onchip16, onchip16_groups, onchip16_min_n, onchip16_bwd,
+# onchip16_bwd_groups), read by recurrence_plan alone
+RECURRENCE = "auto"      # "auto" | "stream" (lstm.hip) | "cluster" (lstm_cluster.hip) | "onchip" (lstm_onchip.hip)
+ONCHIP16 = True          # interleaved kernels: groups of 16 sequences in rotation
+ONCHIP16_GROUPS = 0      # 1 | 2 | 4: forced group count where it divides the number of 16-sequence groups (A/B)
+ONCHIP16_MIN_N = 1       # (a one-group step is 3.5 us against 5.2: the latency regime gains too)
+ONCHIP16_BWD = True
+ONCHIP16_BWD_GROUPS = 2  # at most: a backward phase is paced by its three barriers and the publish (7.1 against 7.8 ms
+                         # per launch at 3 072 sequences with four -- profiles/r3_onchip16_backward.jsonl)
+
+KEEP_XBUF = None         # a list: the exchange buffers of the interleaved launches are appended (trace builds, tools)
 
 
-def recurrence_kernel(N, H, backward, T=0, device=None):
-    """-> 'stream' | 'cluster' | 'onchip' for a BLSTM over N sequences (ms per launch on MI355X at H=300,
-    T=253, profiles/r2_recurrence_microbench.jsonl, forward / backward):
+def recurrence_plan(N, T, H, cus):
+    """-> {"fwd": (kernel, groups), "bwd": (kernel, groups)}: the kernel of each direction of time of a BLSTM layer over
+    N sequences of T frames with H units, on a device of `cus` compute units.  kernel: "stream_f32" (lstm.hip),
+    "cluster_f32" (lstm_cluster.hip), "onchip32_bf16x3" or "onchip16_bf16x3" (lstm_onchip.hip); groups: 16-sequence groups
+    in rotation per cluster of the interleaved kernels, 0 for the others.  ms per launch on MI355X at H=300, T=253
+    (profiles/r2_recurrence_microbench.jsonl, forward / backward):
       on-chip bf16x3 (compact granules)  1.34 / 1.32 (8 sequences), 1.58 / 1.53 (32), 1.85 / 1.74 (256),
                                          2.26 / 2.14 (768 = one resident round of 48 XCD-local clusters x
                                          32 sequences x 1 direction), 4.3 / 4.1 (1536), 8.4 / 8.1 (3072)
       fp32 cluster                       1.50 / 1.34 (8), 1.50 / 1.57 (32), 7.8 / 21.5 (768)
       streaming fp32                     4.75 / 6.0 (<= 512), 5.3 / 6.2 (768), 17.0 / 18.7 (3072)
-    Policy: the on-chip kernels for every N where they exist (H >= 128, T up to `onchip_max_steps`: 14 913 frames
-    = 238 s at H = 300); round 1 sent backward launches of <= 32 sequences to the fp32 cluster kernel, which the
-    compact granules overtook.  The fp32 W-stationary (cluster) and streaming kernels remain selectable
-    (RECURRENCE) as the exact-fp32 recurrences, and streaming is the path for H the W-stationary kernels do not
-    support -- a fallback for a SUPPORTED H (sequence too long) is announced, never silent."""
+    Policy: the on-chip kernels for every N where they exist (H >= 128, T up to the 32-bit offset limit
+    tssep_lstm_onchip_max_steps: 14 913 frames = 238 s at H = 300 for the 16-sequence kernels, 7 215 for the 32-sequence
+    ones); the interleaved ones where tssep_blstm_onchip16_groups gives groups, backward for H = 257...320 only.  Round 1
+    sent backward launches of <= 32 sequences to the fp32 cluster kernel, which the compact granules overtook.  The fp32
+    W-stationary (cluster) and streaming kernels remain selectable (RECURRENCE) as the exact-fp32 recurrences, and
+    streaming is the path for H the W-stationary kernels do not support -- a fallback for a SUPPORTED H (sequence too
+    long) is announced, never silent."""
+    return {direction: _plan_direction(N, T, H, cus, direction == "bwd") for direction in ("fwd", "bwd")}
+
+
+def _onchip16_groups(N, H, cus, backward):
+    """16-sequence groups per cluster of the interleaved kernel of one direction (0: the 32-sequence kernel serves it)"""
+    g = int(_lib.lib().tssep_blstm_onchip16_groups(N, H, cus)) if ONCHIP16 else 0
+    if g and ONCHIP16_GROUPS in (1, 2, 4) and ((N + 15) // 16) % ONCHIP16_GROUPS == 0:
+        g = ONCHIP16_GROUPS
+    elif N < ONCHIP16_MIN_N:
+        g = 0
+    if backward:
+        g = min(g, ONCHIP16_BWD_GROUPS) if ONCHIP16_BWD and 256 < H <= 320 else 0
+    return g
+
+
+def _plan_direction(N, T, H, cus, backward):
     L = _lib.lib()
+    g = _onchip16_groups(N, H, cus, backward)
+    limit = int(L.tssep_lstm_onchip_max_steps(H, 16 if g else 32))
     h_ok = bool(L.tssep_lstm_onchip_supported(H))
-    onchip_ok = h_ok and (T <= 2046 or T <= onchip_max_steps(N, H, backward, device))
+    onchip_ok = h_ok and T <= limit
     if h_ok and not onchip_ok and RECURRENCE in ("auto", "onchip") and H >= 128:
-        _warn_once(("onchip_T", H, backward), f"tssep_amd: {T} frames per sequence exceed the W-stationary recurrence's "
-                   f"{onchip_max_steps(N, H, backward, device)} at H = {H}: the streaming fp32 kernel runs instead (about 3x slower)")
-    if RECURRENCE in ("stream", "cluster", "onchip"):
-        ok = {"stream": True, "cluster": bool(L.tssep_lstm_cluster_supported(H)), "onchip": onchip_ok}[RECURRENCE]
-        return RECURRENCE if ok else "stream"
-    if H < 128:
-        return "stream"
-    if onchip_ok:
-        return "onchip"
-    return "stream"
-
-
-def lstm_pack_cluster(w_hh_f, w_hh_r, H):
-    L = _lib.lib()
-    nf, nb = int(L.tssep_lstm_cluster_pack_floats(H, 0)), int(L.tssep_lstm_cluster_pack_floats(H, 1))
-    buf = torch.empty(nf + nb, device=w_hh_f.device, dtype=torch.float32)
-    a, b = _f32(w_hh_f.detach()).contiguous(), _f32(w_hh_r.detach()).contiguous()
-    check(L.tssep_lstm_pack_cluster(_p(a), _p(b), H, _p(buf[:nf]), _p(buf[nf:]), _stream()),
-          "lstm_pack_cluster")
-    return buf[:nf], buf[nf:]
-
-
-def blstm_cluster_fwd(gates, cell, hout, ldo, dstride, whh_cf, N, T, H, ms=2):
-    _log_recurrence("cluster_f32", "fwd", N, T, H, 0)
-    fence_comm(gates.device)
-    L = _lib.lib()
-    cus = n_cus(gates.device)
-    xbuf = torch.empty(int(L.tssep_lstm_cluster_xbuf_bytes(N, H, 0, cus, ms)) // 8 + 1,
-                       device=gates.device, dtype=torch.int64)
-    with _timed("blstm_cluster_fwd", 2 * 2 * N * T * 4 * H * H):
-        check(L.tssep_blstm_cluster_fwd(_p(gates), _p(cell), _p(hout), ldo, dstride, _p(whh_cf),
-                                        _p(xbuf), _p(_err_flag(gates.device)), N, T, H, cus, ms,
-                                        _stream()), "blstm_cluster_fwd")
-
-
-def blstm_cluster_bwd(gates, cell, dhout, ldo, dstride, whh_cb, N, T, H, ms=2):
-    _log_recurrence("cluster_f32", "bwd", N, T, H, 0)
-    fence_comm(gates.device)
-    L = _lib.lib()
-    cus = n_cus(gates.device)
-    xbuf = torch.empty(int(L.tssep_lstm_cluster_xbuf_bytes(N, H, 1, cus, ms)) // 8 + 1,
-                       device=gates.device, dtype=torch.int64)
-    with _timed("blstm_cluster_bwd", 2 * 2 * N * T * 4 * H * H):
-        check(L.tssep_blstm_cluster_bwd(_p(gates), _p(cell), _p(dhout), ldo, dstride, _p(whh_cb),
-                                        _p(xbuf), _p(_err_flag(gates.device)), N, T, H, cus, ms,
-                                        _stream()), "blstm_cluster_bwd")
-
-
-# on-chip-weights recurrence (bf16x3 MFMA, lstm_onchip.hip) -----------------------------------
-def lstm_pack_onchip(w_hh_f, w_hh_r, H):
-    L = _lib.lib()
-    nf, nb = int(L.tssep_lstm_onchip_pack_floats(H, 0)), int(L.tssep_lstm_onchip_pack_floats(H, 1))
-    buf = torch.empty(nf + nb, device=w_hh_f.device, dtype=torch.float32)
-    a, b = _f32(w_hh_f.detach()).contiguous(), _f32(w_hh_r.detach()).contiguous()
-    check(L.tssep_lstm_pack_onchip(_p(a), _p(b), H, _p(buf[:nf]), _p(buf[nf:]), _stream()),
-          "lstm_pack_onchip")
-    return buf[:nf], buf[nf:]
-
-
-def blstm_onchip_fwd(gates, cell, hout, ldo, dstride, wf, N, T, H, layout=0):
-    _log_recurrence("onchip32_bf16x3", "fwd", N, T, H, 0)
-    fence_comm(gates.device)
-    L = _lib.lib()
-    cus = n_cus(gates.device)
-    xbuf = torch.empty(int(L.tssep_lstm_onchip_xbuf_bytes(N, H, 0)) // 8 + 2, device=gates.device,
-                       dtype=torch.int64)
-    with _timed("blstm_onchip_fwd", 2 * 2 * N * T * 4 * H * H, N * T * 2 * H * 40):      # gates in / activations out 16 + 16, c 4, h 4 B per cell
-        check(L.tssep_blstm_onchip_fwd(_p(gates), _p(cell), _p(hout), ldo, dstride, _p(wf), _p(xbuf),
-                                       _p(_err_flag(gates.device)), N, T, H, cus, layout,
-                                       _stream()), "blstm_onchip_fwd")
-
-
-# interleaved forward (16-sequence groups in rotation); policy: runtime.onchip16 / onchip16_groups / onchip16_min_n
-ONCHIP16 = True
-ONCHIP16_GROUPS = 0      # 1 | 2 | 4: forced group count where it divides the number of 16-sequence groups (A/B)
-ONCHIP16_MIN_N = 1       # (a one-group step is 3.5 us against 5.2: the latency regime gains too)
-ONCHIP16_BWD = True
-ONCHIP16_BWD_GROUPS = 2  # at most: a backward phase is paced by its three barriers and the publish (see onchip16_bwd_groups)
-
-
-KEEP_XBUF = None         # a list: the exchange buffers of the interleaved forward launches are appended (trace builds, tools)
+        _warn_once(("onchip_T", H, backward), f"tssep_amd: {T} frames per sequence exceed the W-stationary "
+                   f"recurrence's {limit} at H = {H}: the streaming fp32 kernel runs instead (about 3x slower)")
+    want = RECURRENCE if RECURRENCE in ("stream", "cluster", "onchip") else "onchip" if H >= 128 else "stream"
+    if want == "cluster" and L.tssep_lstm_cluster_supported(H):
+        return "cluster_f32", 0
+    if want == "onchip" and onchip_ok:
+        return ("onchip16_bf16x3", g) if g else ("onchip32_bf16x3", 0)
+    return "stream_f32", 0
 
 
 def _w16(name, restype, argtypes):
@@ -791,96 +726,176 @@ def _w16(name, restype, argtypes):
 _VP, _I64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
 
-def onchip16_groups(N, H, device, waves=8):
-    if not ONCHIP16:
-        return 0
-    forced = ONCHIP16_GROUPS
-    if waves == 8:
-        g = int(_lib.lib().tssep_blstm_onchip16_groups(N, H, n_cus(device)))
+def recurrence_packs(plan, w_hh_f, w_hh_r, H, lstm_pk=None, memo=False, waves=8):
+    """-> {direction: the W_hh layout its planned kernel reads} for the directions of `plan` (recurrence_plan's, or a part
+    of it).  The streaming kernels read lstm_pack's (`lstm_pk`), the W-stationary ones a layout of their own, built once
+    here where both directions read it: through `derived` on (w_hh_f, w_hh_r) with memo=True -- the tags prepare_derived
+    builds at the start of a captured step --, anew otherwise.  waves = 4: the layout of the four-wave interleaved
+    forward (experiment build, `_w16`)."""
+    L = _lib.lib()
+
+    def operands():
+        return _f32(w_hh_f.detach()).contiguous(), _f32(w_hh_r.detach()).contiguous()
+
+    def both(packer, floats):      # one launch packs the two directions
+        nf, nb = int(floats(H, 0)), int(floats(H, 1))
+        buf = torch.empty(nf + nb, device=w_hh_f.device, dtype=torch.float32)
+        a, b = operands()
+        check(packer(_p(a), _p(b), H, _p(buf[:nf]), _p(buf[nf:]), _stream()), packer.__name__[6:])
+        return buf[:nf], buf[nf:]
+
+    def one(packer, floats, *extra):
+        buf = torch.empty(int(floats), device=w_hh_f.device, dtype=torch.float32)
+        a, b = operands()
+        check(packer(_p(a), _p(b), H, *extra, _p(buf), _stream()), packer.__name__[6:])
+        return buf
+
+    def layout(kernel, bwd):      # -> (derived tag, build, which of the built pair or None)
+        if kernel == "cluster_f32":
+            return "pack_cluster", lambda: both(L.tssep_lstm_pack_cluster, L.tssep_lstm_cluster_pack_floats), int(bwd)
+        if kernel == "onchip32_bf16x3":
+            return "pack_onchip", lambda: both(L.tssep_lstm_pack_onchip, L.tssep_lstm_onchip_pack_floats), int(bwd)
+        if bwd:
+            return "pack_onchip16_bwd", lambda: one(L.tssep_lstm_pack_onchip16_bwd, L.tssep_lstm_onchip16_bwd_pack_floats(H)), None
+        if waves != 4:
+            return "pack_onchip16", lambda: one(L.tssep_lstm_pack_onchip16, L.tssep_lstm_onchip16_pack_floats(H)), None
+        return "pack_onchip16_w4", lambda: one(_w16("tssep_lstm_pack_onchip16w", _I, [_VP, _VP, _I, _I, _VP, _VP]),
+                                               _w16("tssep_lstm_onchip16w_pack_floats", _I64, [_I, _I])(H, waves), waves), None
+
+    built, out = {}, {}
+    for direction, (kernel, _) in plan.items():
+        if kernel == "stream_f32":
+            out[direction] = lstm_pk["whh_b" if direction == "bwd" else "whh_f"]
+            continue
+        tag, build, which = layout(kernel, direction == "bwd")
+        if tag not in built:
+            built[tag] = derived(tag, [w_hh_f, w_hh_r], build) if memo else build()
+        out[direction] = built[tag] if which is None else built[tag][which]
+    return out
+
+
+# kernel -> (C entry points forward / backward, _timed name, algorithmic HBM bytes per cell forward / backward: gates in /
+# activations out 16 + 16, c 4, h 4; activations 16, c 4 + 4, dh 4 in, d(gates) 16 out)
+_RECURRENCE_KERNELS = {
+    "stream_f32": (("tssep_blstm_fwd", "tssep_blstm_bwd"), "blstm", (0, 0)),
+    "cluster_f32": (("tssep_blstm_cluster_fwd", "tssep_blstm_cluster_bwd"), "blstm_cluster", (0, 0)),
+    "onchip32_bf16x3": (("tssep_blstm_onchip_fwd", "tssep_blstm_onchip_bwd"), "blstm_onchip", (40, 44)),
+    "onchip16_bf16x3": (("tssep_blstm_onchip16_fwd", "tssep_blstm_onchip16_bwd"), "blstm_onchip", (40, 44)),
+}
+
+
+def recurrence_launch(planned, direction, gates, cell, h, ldo, dstride, whh, N, T, H, ms=2, layout=0, waves=8):
+    """One direction of time ("fwd" | "bwd") of a BLSTM layer on planned = (kernel, groups), recurrence_plan's: h is hout
+    (written forward) or dhout (read backward; d(gates) replace the gates in place), whh the layout recurrence_packs gave
+    for the same kernel and direction.  ms (cluster), layout (on-chip kernels) and waves = 4 (the interleaved forward's
+    four-wave workgroups, experiment build: `_w16`) go to the kernel as they are."""
+    kernel, groups = planned
+    bwd = direction == "bwd"
+    entry, timed, cell_bytes = _RECURRENCE_KERNELS[kernel]
+    entry = entry[bwd]
+    w4 = kernel == "onchip16_bf16x3" and not bwd and waves == 4
+    _log_recurrence(kernel + ("_w4" if w4 else ""), direction, N, T, H, groups)
+    L = _lib.lib()
+    args = (_p(gates), _p(cell), _p(h), ldo, dstride, _p(whh))
+    flops, nbytes = 2 * 2 * N * T * 4 * H * H, N * T * 2 * H * cell_bytes[bwd]
+    if kernel == "stream_f32":
+        with _timed(f"{timed}_{direction}", flops, nbytes):
+            check(getattr(L, entry)(*args, N, T, H, _stream()), entry[6:])
+        return
+    fence_comm(gates.device)
+    cus = n_cus(gates.device)
+    fn = getattr(L, entry)
+    if kernel == "cluster_f32":
+        words, tail = int(L.tssep_lstm_cluster_xbuf_bytes(N, H, int(bwd), cus, ms)) // 8 + 1, (ms,)
+    elif kernel == "onchip32_bf16x3":
+        words, tail = int(L.tssep_lstm_onchip_xbuf_bytes(N, H, int(bwd))) // 8 + 2, (layout,)
+    elif bwd:
+        words, tail = int(L.tssep_lstm_onchip16_bwd_xbuf_bytes(N, H)) // 8 + 2, (layout, groups)
+    elif not w4:
+        words, tail = int(L.tssep_lstm_onchip16_xbuf_bytes(N, H)) // 8 + 2, (layout, groups)
     else:
-        g = int(_w16("tssep_blstm_onchip16w_groups", _I, [_I64, _I, _I, _I])(N, H, n_cus(device), waves))
-    if g and forced in (1, 2, 4) and ((N + 15) // 16) % forced == 0 and not (waves == 4 and forced == 4):
-        return forced
-    return g if N >= ONCHIP16_MIN_N else 0
+        words = int(_w16("tssep_lstm_onchip16w_xbuf_bytes", _I64, [_I64, _I, _I])(N, H, waves)) // 8 + 2
+        tail = (layout, groups, waves)
+        fn = _w16("tssep_blstm_onchip16w_fwd", _I, [_VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _I64, _I64, _I, _I, _I, _I, _I, _VP])
+    xbuf = torch.empty(words, device=gates.device, dtype=torch.int64)
+    if KEEP_XBUF is not None and kernel == "onchip16_bf16x3":
+        KEEP_XBUF.append(xbuf)
+    with _timed(f"{timed}_{direction}", flops, nbytes):
+        check(fn(*args, _p(xbuf), _p(_err_flag(gates.device)), N, T, H, cus, *tail, _stream()), entry[6:])
+
+
+# Each recurrence kernel by name (the kernel tests and tools): the plan, the packs and the launcher above on one fixed
+# kernel and direction.  device: whose CU count decides the groups -- the current device's when None, no interleaved
+# kernels without a GPU.
+def _cus(device):
+    if device is None:
+        if not torch.cuda.is_available():
+            return 0
+        device = torch.device("cuda", torch.cuda.current_device())
+    return n_cus(device)
+
+
+def recurrence_kernel(N, H, backward, T=0, device=None):
+    """-> "stream" | "cluster" | "onchip": the family of the kernel recurrence_plan gives that direction"""
+    return _plan_direction(N, T, H, _cus(device), backward)[0].split("_")[0].rstrip("0123456789")
+
+
+def onchip16_groups(N, H, device):
+    return _onchip16_groups(N, H, n_cus(device), False)
+
+
+def onchip16_bwd_groups(N, H, device):
+    return _onchip16_groups(N, H, n_cus(device), True)
+
+
+def lstm_pack_cluster(w_hh_f, w_hh_r, H):
+    return tuple(recurrence_packs(dict.fromkeys(("fwd", "bwd"), ("cluster_f32", 0)), w_hh_f, w_hh_r, H).values())
+
+
+def lstm_pack_onchip(w_hh_f, w_hh_r, H):
+    return tuple(recurrence_packs(dict.fromkeys(("fwd", "bwd"), ("onchip32_bf16x3", 0)), w_hh_f, w_hh_r, H).values())
 
 
 def lstm_pack_onchip16(w_hh_f, w_hh_r, H, waves=8):
-    L = _lib.lib()
-    a, b = _f32(w_hh_f.detach()).contiguous(), _f32(w_hh_r.detach()).contiguous()
-    if waves == 8:
-        buf = torch.empty(int(L.tssep_lstm_onchip16_pack_floats(H)), device=w_hh_f.device, dtype=torch.float32)
-        check(L.tssep_lstm_pack_onchip16(_p(a), _p(b), H, _p(buf), _stream()), "lstm_pack_onchip16")
-        return buf
-    buf = torch.empty(int(_w16("tssep_lstm_onchip16w_pack_floats", _I64, [_I, _I])(H, waves)), device=w_hh_f.device, dtype=torch.float32)
-    check(_w16("tssep_lstm_pack_onchip16w", _I, [_VP, _VP, _I, _I, _VP, _VP])(_p(a), _p(b), H, waves, _p(buf), _stream()),
-          "lstm_pack_onchip16")
-    return buf
+    return recurrence_packs({"fwd": ("onchip16_bf16x3", 0)}, w_hh_f, w_hh_r, H, waves=waves)["fwd"]
+
+
+def lstm_pack_onchip16_bwd(w_hh_f, w_hh_r, H):
+    return recurrence_packs({"bwd": ("onchip16_bf16x3", 0)}, w_hh_f, w_hh_r, H)["bwd"]
+
+
+def blstm_fwd(gates, cell, hout, ldo, dstride, whh_f, N, T, H):
+    recurrence_launch(("stream_f32", 0), "fwd", gates, cell, hout, ldo, dstride, whh_f, N, T, H)
+
+
+def blstm_bwd(gates, cell, dhout, ldo, dstride, whh_b, N, T, H):
+    recurrence_launch(("stream_f32", 0), "bwd", gates, cell, dhout, ldo, dstride, whh_b, N, T, H)
+
+
+def blstm_cluster_fwd(gates, cell, hout, ldo, dstride, whh_cf, N, T, H, ms=2):
+    recurrence_launch(("cluster_f32", 0), "fwd", gates, cell, hout, ldo, dstride, whh_cf, N, T, H, ms=ms)
+
+
+def blstm_cluster_bwd(gates, cell, dhout, ldo, dstride, whh_cb, N, T, H, ms=2):
+    recurrence_launch(("cluster_f32", 0), "bwd", gates, cell, dhout, ldo, dstride, whh_cb, N, T, H, ms=ms)
+
+
+def blstm_onchip_fwd(gates, cell, hout, ldo, dstride, wf, N, T, H, layout=0):
+    recurrence_launch(("onchip32_bf16x3", 0), "fwd", gates, cell, hout, ldo, dstride, wf, N, T, H, layout=layout)
+
+
+def blstm_onchip_bwd(gates, cell, dhout, ldo, dstride, wb, N, T, H, layout=0):
+    recurrence_launch(("onchip32_bf16x3", 0), "bwd", gates, cell, dhout, ldo, dstride, wb, N, T, H, layout=layout)
 
 
 def blstm_onchip16_fwd(gates, cell, hout, ldo, dstride, wf16, N, T, H, groups, layout=0, waves=8):
     """wf16: the pack made for the SAME `waves` (lstm_pack_onchip16); waves = 4: experiment build only (`_w16`)."""
-    _log_recurrence("onchip16_bf16x3" + ("_w4" if waves == 4 else ""), "fwd", N, T, H, groups)
-    fence_comm(gates.device)
-    L = _lib.lib()
-    cus = n_cus(gates.device)
-    nbytes = int(L.tssep_lstm_onchip16_xbuf_bytes(N, H)) if waves == 8 else \
-        int(_w16("tssep_lstm_onchip16w_xbuf_bytes", _I64, [_I64, _I, _I])(N, H, waves))
-    xbuf = torch.empty(nbytes // 8 + 2, device=gates.device, dtype=torch.int64)
-    if KEEP_XBUF is not None:
-        KEEP_XBUF.append(xbuf)
-    with _timed("blstm_onchip_fwd", 2 * 2 * N * T * 4 * H * H, N * T * 2 * H * 40):      # gates in / activations out 16 + 16, c 4, h 4 B per cell
-        if waves == 8:
-            rc = L.tssep_blstm_onchip16_fwd(_p(gates), _p(cell), _p(hout), ldo, dstride, _p(wf16), _p(xbuf),
-                                            _p(_err_flag(gates.device)), N, T, H, cus, layout, groups, _stream())
-        else:
-            rc = _w16("tssep_blstm_onchip16w_fwd", _I, [_VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _I64, _I64, _I, _I, _I, _I, _I, _VP])(
-                _p(gates), _p(cell), _p(hout), ldo, dstride, _p(wf16), _p(xbuf), _p(_err_flag(gates.device)), N, T, H, cus,
-                layout, groups, waves, _stream())
-        check(rc, "blstm_onchip16_fwd")
-
-
-def onchip16_bwd_groups(N, H, device):
-    """group count of the interleaved backward (0: use the 32-sequence kernel; policy runtime.onchip16_bwd)"""
-    if not ONCHIP16_BWD or not (256 < H <= 320):
-        return 0
-    # (two groups at most: a backward phase is paced by its three barriers and the publish, 7.1 against 7.8 ms per launch
-    # at 3 072 sequences with four -- profiles/r3_onchip16_backward.jsonl)
-    return min(onchip16_groups(N, H, device), ONCHIP16_BWD_GROUPS)
-
-
-def lstm_pack_onchip16_bwd(w_hh_f, w_hh_r, H):
-    L = _lib.lib()
-    buf = torch.empty(int(L.tssep_lstm_onchip16_bwd_pack_floats(H)), device=w_hh_f.device, dtype=torch.float32)
-    a, b = _f32(w_hh_f.detach()).contiguous(), _f32(w_hh_r.detach()).contiguous()
-    check(L.tssep_lstm_pack_onchip16_bwd(_p(a), _p(b), H, _p(buf), _stream()), "lstm_pack_onchip16_bwd")
-    return buf
+    recurrence_launch(("onchip16_bf16x3", groups), "fwd", gates, cell, hout, ldo, dstride, wf16, N, T, H, layout=layout,
+                      waves=waves)
 
 
 def blstm_onchip16_bwd(gates, cell, dhout, ldo, dstride, wb16, N, T, H, groups, layout=0):
-    _log_recurrence("onchip16_bf16x3", "bwd", N, T, H, groups)
-    fence_comm(gates.device)
-    L = _lib.lib()
-    cus = n_cus(gates.device)
-    xbuf = torch.empty(int(L.tssep_lstm_onchip16_bwd_xbuf_bytes(N, H)) // 8 + 2, device=gates.device, dtype=torch.int64)
-    if KEEP_XBUF is not None:
-        KEEP_XBUF.append(xbuf)
-    with _timed("blstm_onchip_bwd", 2 * 2 * N * T * 4 * H * H, N * T * 2 * H * 44):      # activations 16, c 4 + 4, dh 4 in, d(gates) 16 out
-        check(L.tssep_blstm_onchip16_bwd(_p(gates), _p(cell), _p(dhout), ldo, dstride, _p(wb16), _p(xbuf),
-                                         _p(_err_flag(gates.device)), N, T, H, cus, layout, groups, _stream()),
-              "blstm_onchip16_bwd")
-
-
-def blstm_onchip_bwd(gates, cell, dhout, ldo, dstride, wb, N, T, H, layout=0):
-    _log_recurrence("onchip32_bf16x3", "bwd", N, T, H, 0)
-    fence_comm(gates.device)
-    L = _lib.lib()
-    cus = n_cus(gates.device)
-    xbuf = torch.empty(int(L.tssep_lstm_onchip_xbuf_bytes(N, H, 1)) // 8 + 2, device=gates.device,
-                       dtype=torch.int64)
-    with _timed("blstm_onchip_bwd", 2 * 2 * N * T * 4 * H * H, N * T * 2 * H * 44):      # activations 16, c 4 + 4, dh 4 in, d(gates) 16 out
-        check(L.tssep_blstm_onchip_bwd(_p(gates), _p(cell), _p(dhout), ldo, dstride, _p(wb), _p(xbuf),
-                                       _p(_err_flag(gates.device)), N, T, H, cus, layout,
-                                       _stream()), "blstm_onchip_bwd")
+    recurrence_launch(("onchip16_bf16x3", groups), "bwd", gates, cell, dhout, ldo, dstride, wb16, N, T, H, layout=layout)
 
 
 def lstm_unpack(src, ld, nsplit, split_stride, H, ncols, dst_f, dst_r, accumulate=False):
