@@ -122,6 +122,22 @@ int tssep_mask_istft_bwd_loss(const float* est, const float* tgt, const float* s
                               const float* logit, const float* obs, int64_t B, int64_t K, int64_t N,
                               int size, int shift, int fading, const float* wsyn, const float* tw,
                               const int32_t* iperm, int bt_major, float* dlogit, int64_t T, void* stream);
+/* The gated tail of MaskEstimator_v2(explicit_vad=True) (tssep/train/net.py:630, 969-979): logit rows of F + 1 = 514
+ * floats, the VAD logit v at column 0 and the mask logits l_f at 1..513 -- the rows the head GEMM writes.
+ *   forward : as tssep_mask_istft_fwd with the mask sigmoid(l_f) * sigmoid(v).
+ *   backward: as tssep_mask_istft_bwd_loss (est = dy when tgt == NULL; iperm / bt_major alike) with
+ *             d(l_f) = dm_f g s_f (1 - s_f) and d(v) = g (1 - g) sum_f dm_f s_f  (dm_f = Re(conj(obs) dEst_f), s_f =
+ *             sigmoid(l_f), g = sigmoid(v); an in-wave reduction, deterministic) stored at column 0.  vad [B*K, T] and
+ *             gout_vad [B] non-NULL add the SignalAndVADSigmoidBCE term (tssep/train/loss.py:348-395) of the gate:
+ *             + gout_vad[b] (sigmoid(v) - vad) / (K T).  dlogit rows are F + 1 floats. */
+int tssep_mask_istft_gated_fwd(const float* logit, const float* obs, int64_t B, int64_t K, int64_t T, int size,
+                               int shift, int fading, const float* wsyn, const float* tw, float* y, int64_t N,
+                               const float* tgt, float* abs_partial, void* stream);
+int tssep_mask_istft_gated_bwd(const float* est, const float* tgt, const float* sums, const float* gout,
+                               const float* vad, const float* gout_vad, const float* logit, const float* obs,
+                               int64_t B, int64_t K, int64_t N, int size, int shift, int fading,
+                               const float* wsyn, const float* tw, const int32_t* iperm, int bt_major,
+                               float* dlogit, int64_t T, void* stream);
 
 /* --------------------------------------------------------------- features ----
  * ConcaternatedSTFTFeatures(TorchMFCC, Log1pMaxNormAbsSTFT).stft_to_feature
@@ -398,6 +414,14 @@ int tssep_maskhead_fwd(const float* logit, const float* obs, float* mask, float*
 int tssep_maskhead_bwd(const float* dest, const float* dmask, const float* mask,
                        const float* obs, float* dlogit,
                        int64_t B, int64_t K, int64_t T, int F, void* stream);
+/* Gated mask head (explicit_vad, tssep/train/net.py:969-979): logit [B,K,T,F+1] with the VAD logit at column 0 ->
+ * vmask [B,K,T] = g = sigmoid(v), mask [B,K,T,F] = sigmoid(l_f) g, est = Obs * mask (est may be NULL).
+ * bwd: dm_f = Re(conj(obs) dest_f) + dmask_f, dlogit [B,K,T,F+1]: d(l_f) = dm_f g s_f (1 - s_f),
+ * d(v) = (sum_f dm_f s_f + dvmask) g (1 - g); dest, dmask and dvmask may each be NULL. */
+int tssep_maskhead_gated_fwd(const float* logit, const float* obs, float* mask, float* est, float* vmask,
+                             int64_t B, int64_t K, int64_t T, int F, void* stream);
+int tssep_maskhead_gated_bwd(const float* dest, const float* dmask, const float* dvmask, const float* logit,
+                             const float* obs, float* dlogit, int64_t B, int64_t K, int64_t T, int F, void* stream);
 
 /* Masking on a given mask (standalone enhancer call, tssep/train/enhancer.py:98-100):
  * est = Obs * mask, and its backward dmask = Re(conj(Obs) * dest). */
@@ -430,6 +454,14 @@ int tssep_vadbce_fwd(const float* logit, const float* vad, int64_t B, int64_t K,
                      float* loss, float* xmean, void* ws, void* stream);
 int tssep_vadbce_bwd(const float* xmean, const float* vad, const float* gout,
                      int64_t B, int64_t K, int64_t T, int F, float* dlogit, void* stream);
+/* The VAD BCE of SignalAndVADSigmoidBCE (tssep/train/loss.py:348-395) on the gate column of an explicit_vad logit:
+ * x = logit[row * ld] (rows (b,k,t), ld = F + 1), loss[b] = mean_{k,t} BCEWithLogits(x, vad) (ws: B*K*T floats;
+ * the fixed-order reduction of tssep_vadbce_fwd).  bwd writes whole rows of dlogit [B*K*T, ld]:
+ * gout[b] (sigmoid(x) - vad) / (K T) at column 0, zeros elsewhere. */
+int tssep_gatebce_fwd(const float* logit, int64_t ld, const float* vad, int64_t B, int64_t K, int64_t T,
+                      float* loss, void* ws, void* stream);
+int tssep_gatebce_bwd(const float* logit, int64_t ld, const float* vad, const float* gout, int64_t B, int64_t K,
+                      int64_t T, float* dlogit, void* stream);
 
 /* -------------------------------------------------------- logit layout map ---
  * Tail of MaskEstimator_v2.forward: final einops rearrange / reduce-repeat

@@ -322,6 +322,27 @@ __global__ void vadbce_bwd_kernel(const float* __restrict__ xmean, const float* 
   }
 }
 
+// ---- VAD BCE on the gate column of an explicit_vad logit (SignalAndVADSigmoidBCE, loss.py:348-395) ----------------
+// x = logit[row * ld] (column 0 of a row of ld = F + 1 floats); the same per-row loss and fixed-order mean over (k, t) as
+// vadbce; bwd writes whole rows: gout[b] (sigmoid(x) - y) / (K T) at column 0, zeros behind it
+__global__ void gatebce_rows_kernel(const float* __restrict__ logit, int64_t ld, const float* __restrict__ vad,
+                                    int64_t rows, float* __restrict__ lrow) {
+  GRID_STRIDE(row, rows) {
+    const float x = logit[row * ld], y = vad[row];
+    lrow[row] = fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
+  }
+}
+__global__ void gatebce_bwd_kernel(const float* __restrict__ logit, int64_t ld, const float* __restrict__ vad,
+                                   const float* __restrict__ gout, int64_t KT, int64_t total,
+                                   float* __restrict__ dlogit) {
+  GRID_STRIDE(e, total) {
+    const int64_t row = e / ld;
+    float v = 0.f;
+    if (e == row * ld) v = gout[row / KT] * (sigmoidf_acc(logit[e]) - vad[row]) / (float)KT;
+    dlogit[e] = v;
+  }
+}
+
 // ---- logit layout map: raw GEMM output -> [B, K, T, F] (+ trial mean, + 't' broadcast) ------
 // Covers the tail of MaskEstimator_v2.forward: the final einops rearrange / reduce-repeat
 // (net.py:631-659), the mean over permutation trials (net.py:928-951) and the speaker
@@ -549,6 +570,23 @@ extern "C" int tssep_vadbce_bwd(const float* xmean, const float* vad, const floa
   if (B <= 0 || K <= 0 || T <= 0 || F <= 0) return TSSEP_E_SHAPE;
   hipLaunchKernelGGL(vadbce_bwd_kernel, dim3(grid_for(B * K * T * F)), dim3(256), 0, S_, xmean, vad,
                      gout, K * T, F, B * K * T * F, dlogit);
+  return tssep_launch_status();
+}
+extern "C" int tssep_gatebce_fwd(const float* logit, int64_t ld, const float* vad, int64_t B, int64_t K, int64_t T,
+                                 float* loss, void* ws, void* stream) {
+  if (!logit || !vad || !loss || !ws) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || T <= 0 || ld <= 0) return TSSEP_E_SHAPE;
+  const int64_t rows = B * K * T;
+  hipLaunchKernelGGL(gatebce_rows_kernel, dim3(grid_for(rows)), dim3(256), 0, S_, logit, ld, vad, rows, (float*)ws);
+  hipLaunchKernelGGL(vadbce_finalize_kernel, dim3((unsigned)B), dim3(256), 0, S_, (const float*)ws, B, K * T, loss);
+  return tssep_launch_status();
+}
+extern "C" int tssep_gatebce_bwd(const float* logit, int64_t ld, const float* vad, const float* gout, int64_t B,
+                                 int64_t K, int64_t T, float* dlogit, void* stream) {
+  if (!logit || !vad || !gout || !dlogit) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || T <= 0 || ld <= 0) return TSSEP_E_SHAPE;
+  hipLaunchKernelGGL(gatebce_bwd_kernel, dim3(grid_for(B * K * T * ld)), dim3(256), 0, S_, logit, ld, vad, gout,
+                     K * T, B * K * T * ld, dlogit);
   return tssep_launch_status();
 }
 static int map_args(MapArgs& a, const int32_t* perm, const int32_t* iperm, int64_t B, int trials,

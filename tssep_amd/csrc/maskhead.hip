@@ -231,3 +231,86 @@ extern "C" int tssep_mask_mul_bwd(const float* dest, const float* obs, float* dm
                      (float2*)nullptr, dmask, total, KTF, TF);
   return tssep_launch_status();
 }
+
+// ---- explicit_vad (MaskEstimator_v2(explicit_vad=True), net.py:969-979): the unfused gated mask head --------------
+// logit rows of F + 1 floats, the VAD logit v at column 0 and the mask logits l_f at 1..F:
+//   vmask = g = sigmoid(v);  mask_f = sigmoid(l_f) g;  est_f = Obs_f mask_f.
+// One wave per (b, k, t) frame: the gate is loaded once per frame and d(v) is an in-wave reduction over the frame's
+// bins in a fixed order (lane l: bins l, l + 64, ...; then the shuffle tree) -- deterministic, no atomics.  Serves the
+// callers that look at out.mask / out.stft_estimate; the training step runs the fused tail (stft.hip).
+namespace {
+__global__ __launch_bounds__(256) void maskhead_gated_fwd_kernel(
+    const float* __restrict__ logit, const float2* __restrict__ obs, float* __restrict__ mask,
+    float2* __restrict__ est, float* __restrict__ vmask, int64_t frames, int64_t KT, int64_t T, int F) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  for (int64_t fr = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); fr < frames; fr += nwaves) {
+    const int64_t b = fr / KT, t = fr % T;
+    const float* Lr = logit + fr * (F + 1);
+    const float2* Or = obs + (b * T + t) * F;
+    const float g = sigmoidf_mask(Lr[0]);
+    for (int f = lane; f < F; f += 64) {
+      const float m = sigmoidf_mask(Lr[1 + f]) * g;
+      const float2 x = Or[f];
+      mask[fr * F + f] = m;
+      if (est) est[fr * F + f] = make_float2(x.x * m, x.y * m);
+    }
+    if (lane == 0) vmask[fr] = g;
+  }
+}
+
+// dm_f = Re(conj(Obs_f) dest_f) + dmask_f;  d(l_f) = dm_f g s_f (1 - s_f);  d(v) = (sum_f dm_f s_f + dvmask) g (1 - g)
+__global__ __launch_bounds__(256) void maskhead_gated_bwd_kernel(
+    const float2* __restrict__ dest, const float* __restrict__ dmask, const float* __restrict__ dvmask,
+    const float* __restrict__ logit, const float2* __restrict__ obs, float* __restrict__ dlogit, int64_t frames,
+    int64_t KT, int64_t T, int F) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * 4;
+  for (int64_t fr = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); fr < frames; fr += nwaves) {
+    const int64_t b = fr / KT, t = fr % T;
+    const float* Lr = logit + fr * (F + 1);
+    const float2* Or = obs + (b * T + t) * F;
+    float* Dr = dlogit + fr * (F + 1);
+    const float g = sigmoidf_mask(Lr[0]);
+    float part = 0.f;
+    for (int f = lane; f < F; f += 64) {
+      const float s = sigmoidf_mask(Lr[1 + f]);
+      float dm = dmask ? dmask[fr * F + f] : 0.f;
+      if (dest) {
+        const float2 x = Or[f], d = dest[fr * F + f];
+        dm = (x.x * d.x + x.y * d.y) + dm;
+      }
+      Dr[1 + f] = dm * g * s * (1.0f - s);
+      part += dm * s;
+    }
+    part = wave_sum(part);
+    if (lane == 0) Dr[0] = (part + (dvmask ? dvmask[fr] : 0.f)) * g * (1.0f - g);
+  }
+}
+
+inline unsigned frame_grid(int64_t frames) {
+  const int64_t blocks = (frames + 3) / 4, cap = 256 * 8;
+  return (unsigned)(blocks < cap ? (blocks > 0 ? blocks : 1) : cap);
+}
+}  // namespace
+
+extern "C" int tssep_maskhead_gated_fwd(const float* logit, const float* obs, float* mask, float* est, float* vmask,
+                                        int64_t B, int64_t K, int64_t T, int F, void* stream) {
+  if (!logit || !obs || !mask || !vmask) return TSSEP_E_NULL;      // est may be NULL (mask only)
+  if (B <= 0 || K <= 0 || T <= 0 || F <= 0) return TSSEP_E_SHAPE;
+  if ((((uintptr_t)logit) & 3u) || (((uintptr_t)obs) & 7u) || (est && (((uintptr_t)est) & 7u))) return TSSEP_E_ALIGN;
+  hipLaunchKernelGGL(maskhead_gated_fwd_kernel, dim3(frame_grid(B * K * T)), dim3(256), 0, (hipStream_t)stream,
+                     logit, (const float2*)obs, mask, (float2*)est, vmask, B * K * T, K * T, T, F);
+  return tssep_launch_status();
+}
+
+extern "C" int tssep_maskhead_gated_bwd(const float* dest, const float* dmask, const float* dvmask, const float* logit,
+                                        const float* obs, float* dlogit, int64_t B, int64_t K, int64_t T, int F,
+                                        void* stream) {
+  if (!logit || !obs || !dlogit) return TSSEP_E_NULL;       // dest, dmask, dvmask may be NULL (no gradient)
+  if (B <= 0 || K <= 0 || T <= 0 || F <= 0) return TSSEP_E_SHAPE;
+  if ((((uintptr_t)logit) & 3u) || (((uintptr_t)obs) & 7u) || (dest && (((uintptr_t)dest) & 7u))) return TSSEP_E_ALIGN;
+  hipLaunchKernelGGL(maskhead_gated_bwd_kernel, dim3(frame_grid(B * K * T)), dim3(256), 0, (hipStream_t)stream,
+                     (const float2*)dest, dmask, dvmask, logit, (const float2*)obs, dlogit, B * K * T, K * T, T, F);
+  return tssep_launch_status();
+}

@@ -136,17 +136,28 @@ __device__ __forceinline__ void fft512_wave(float2 (&v)[8], float2* buf, const f
 // the epilogue reads the logit (4 B) and the observation bin (8 B, shared by the K speakers of an
 // utterance: L2) and writes d(logit) = Re(conj(Obs) dEst) m (1 - m), m = sigmoid(logit) -- the chain
 // adjoint -> mask head moves 8 K F + 8 F bytes per frame instead of 24 K F + 8 F.
+//
+// GATED (MASKED only; MaskEstimator_v2(explicit_vad=True), net.py:969-979): logit rows hold F + 1 = 514 floats, the frame's
+// VAD logit v at column 0 and the mask logits l_f at 1..F; the mask is sigmoid(l_f) sigmoid(v).  Each d(l_f) is formed
+// like the ungated one with the gate as one more factor, and d(v) = g (1 - g) sum_f dm_f sigmoid(l_f) by an in-wave
+// reduction over the frame's bins (fixed order: deterministic) -- stored by lane 0 at column 0, where the Linear's
+// backward reads it.  vad != NULL folds the VADSigmoidBCE gradient of the gate column into that store:
+// + gbce[b] (sigmoid(v) - vad[row, t]) inv_kt (loss.py:302-310, 348-395).
 #ifndef TSSEP_RFFT_OCC
 #define TSSEP_RFFT_OCC 3
 #endif
-template <bool MASKED>
+template <bool MASKED, bool GATED = false>
 __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     const float* __restrict__ x, int64_t rows, int64_t N, int64_t T, int shift, int pad_left,
     const float* __restrict__ window, const float2* __restrict__ tw, float2* __restrict__ X,
     float s_in, float s_edge, int iters, const float* __restrict__ logit,
     const float2* __restrict__ obs, float* __restrict__ dlogit, int64_t Kspk,
     const float* __restrict__ tgt, const float* __restrict__ sums, const float* __restrict__ gout,
-    const int32_t* __restrict__ iperm, int bt_major) {
+    const int32_t* __restrict__ iperm, int bt_major, const float* __restrict__ vad = nullptr,
+    const float* __restrict__ gbce = nullptr, float inv_kt = 0.f) {
+  static_assert(MASKED || !GATED, "the gate belongs to the mask head");
+  constexpr int LDL = NH + 1 + (GATED ? 1 : 0);   // logit / d(logit) row length
+  constexpr int C0 = GATED ? 1 : 0;               // column of bin 0
   // MASKED with tgt != NULL: x is the time-domain ESTIMATE and the frame's samples are the loss gradient
   // d LogMAE / d est = gout[b] sign(est - tgt) / (N ln10 sums[b])  (sums == NULL: MAE, gout[b] sign / N;
   // tssep/train/loss.py:214-216, 244-247) formed while they are loaded -- tssep_logmae_bwd and its [B,K,N]
@@ -232,30 +243,45 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     // MASKED: row = (utterance b, speaker); the observation frame is the utterance's.  The epilogue's logit and
     // observation bins do not depend on the transform: requested BEFORE it (24 registers), their latency hides
     // behind the FFT instead of ending every frame with a round trip to memory
-    const float* Lr = MASKED ? logit + fidx * (NH + 1) : nullptr;
+    const float* Lr = MASKED ? logit + fidx * LDL : nullptr;
     const float2* Or = MASKED ? obs + ((row / Kspk) * T + t) * (NH + 1) : nullptr;
     float lg8[8];
     float2 ob8[8];
+    float lgate = 0.f;                        // GATED: the frame's VAD logit (every lane the same address)
+    float vadv = 0.f, gbv = 0.f;              // GATED with the BCE fold: Vad[row, t], gbce[b] -- requested here too, so that
+                                              // the d(v) store at the frame's end does not wait for a round trip
+    if (GATED && valid && vad) {
+      vadv = vad[row * T + t];
+      gbv = gbce[row / Kspk];
+    }
     if (MASKED && valid) {
       __builtin_amdgcn_sched_barrier(0);      // (not above the sample loads: the kernel is at its register ceiling there)
-      const srd_t sl = make_srd(Lr, (NH + 1) * 4), so = make_srd(Or, (NH + 1) * 8);
+      const srd_t sl = make_srd(Lr, LDL * 4), so = make_srd(Or, (NH + 1) * 8);
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
         ob8[r] = bload2(so, (unsigned)(lane * 8 + 512 * r));
-        lg8[r] = bload1(sl, (unsigned)(lane * 4 + 256 * r));
+        lg8[r] = bload1(sl, (unsigned)(C0 * 4 + lane * 4 + 256 * r));
       }
+      if (GATED) lgate = bload1(sl, 0u);
     }
     fft512_wave(v, buf, twl, lane);
     if (valid) {
       float2* Xo = MASKED ? nullptr : X + fidx * (NH + 1);
-      float* Dr = MASKED ? dlogit + fidx * (NH + 1) : nullptr;
+      float* Dr = MASKED ? dlogit + fidx * LDL : nullptr;
       if (MASKED && bt_major) {
         const int64_t b = row / Kspk, j = row - b * Kspk;
         const int64_t kpos = iperm ? (int64_t)iperm[b * Kspk + j] : j;
-        Dr = dlogit + ((b * T + t) * Kspk + kpos) * (NH + 1);
+        Dr = dlogit + ((b * T + t) * Kspk + kpos) * LDL;
       }
+      const float gm = GATED ? sigmoidf_mask(lgate) : 1.f;
+      float gpart = 0.f;                      // GATED: this lane's sum_f dm_f sigmoid(l_f)
       auto emit = [&](int k, float2 o, float lgk, float2 ob) {
-        if (MASKED) {
+        if (GATED) {
+          const float s = sigmoidf_mask(lgk);
+          const float dm = ob.x * o.x + ob.y * o.y;
+          Dr[C0 + k] = dm * gm * s * (1.0f - s);
+          gpart += dm * s;
+        } else if (MASKED) {
           const float m = sigmoidf_mask(lgk);
           Dr[k] = (ob.x * o.x + ob.y * o.y) * m * (1.0f - m);
         } else {
@@ -283,7 +309,15 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
       }
       if (lane == 0) {
         const float2 z0 = buf[0];
-        emit(NH, make_float2((z0.x - z0.y) * s_edge, 0.f), MASKED ? Lr[NH] : 0.f, MASKED ? Or[NH] : make_float2(0.f, 0.f));
+        emit(NH, make_float2((z0.x - z0.y) * s_edge, 0.f), MASKED ? Lr[C0 + NH] : 0.f, MASKED ? Or[NH] : make_float2(0.f, 0.f));
+      }
+      if (GATED) {
+        const float tot = wave_sum(gpart);
+        if (lane == 0) {
+          float dv = tot * gm * (1.0f - gm);
+          if (vad) dv += gbv * (sigmoidf_acc(lgate) - vadv) * inv_kt;
+          Dr[0] = dv;
+        }
       }
     }
     WAVE_SYNC();          // the line is rewritten by this wave's next frame
@@ -309,10 +343,13 @@ constexpr int HCB_MAX = 64;              // hops per workgroup (upper bound; the
 // 16 K F + 8 F + 8 K F + 4 K 256.  (Measured, batch 768: 2.07 ms against 1.44 + 1.98 ms; the kernel is bound
 // by the per-wave FFT chain, not by bytes: the hardware exp / rcp sigmoid instead of the accurate one changed
 // nothing, three resident workgroups instead of two gained 20 %.)
+//
+// GATED (MASKED only, explicit_vad): logit rows of F + 1 floats, the VAD logit v at column 0; the spectrum is
+// sigmoid(l_f) sigmoid(v) Obs -- one more 4-B load per frame, requested with the frame's bins.
 #ifndef TSSEP_ISTFT_OCC
 #define TSSEP_ISTFT_OCC 3            // waves per SIMD the register allocation aims at (A/B: build with -D...=2)
 #endif
-template <bool MASKED>
+template <bool MASKED, bool GATED = false>
 __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
     const float2* __restrict__ X, int64_t T, int shift_, int64_t N,
     const float* __restrict__ wsyn, const float2* __restrict__ tw, float* __restrict__ y,
@@ -323,6 +360,9 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
   __shared__ __attribute__((aligned(16))) float fr[RING][1024];       // (51 KB with the rest: three workgroups per CU --
                                                                       // no room for the window table the rfft kernel keeps)
   __shared__ float red[4];
+  static_assert(MASKED || !GATED, "the gate belongs to the mask head");
+  constexpr int LDL = NH + 1 + (GATED ? 1 : 0);   // logit row length
+  constexpr int C0 = GATED ? 1 : 0;               // column of bin 0
   const int tid = threadIdx.x, lane = tid & 63;
   // (wave-uniform; through readfirstlane so that the per-frame buffer resources below are built in SGPRs -- from a
   // VGPR the compiler wraps EVERY buffer access in a waterfall loop: ~10 extra instructions and a serialisation each)
@@ -348,7 +388,7 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
   // MASKED: the logits and observation bins of a frame are requested one iteration ahead (27 registers), right after
   // the previous frame's have been consumed: their latency hides behind that frame's transform and the hop emission
   // instead of opening every iteration (out-of-range frames get an empty resource: the loads return 0)
-  float lg8[8], lgn = 0.f;
+  float lg8[8], lgn = 0.f, lgg = 0.f;
   float2 ob8[8], obn = make_float2(0.f, 0.f);
   const int64_t urow = MASKED ? row / Kspk : 0;        // the utterance of this (utterance, speaker) row
   auto request = [&](int it_) __attribute__((always_inline)) {
@@ -356,15 +396,16 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
     const int64_t t_ = t_lo + lf_;
     const bool ok = it_ < iters && t_ < T && lf_ < hops + 3;
     const int64_t tt = ok ? t_ : 0;
-    const srd_t sl = make_srd(logit + (row * T + tt) * (NH + 1), ok ? (NH + 1) * 4 : 0);
+    const srd_t sl = make_srd(logit + (row * T + tt) * LDL, ok ? LDL * 4 : 0);
     const srd_t so = make_srd(obs + (urow * T + tt) * (NH + 1), ok ? (NH + 1) * 8 : 0);
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
-      lg8[r] = bload1(sl, (unsigned)(lane * 4 + 256 * r));
+      lg8[r] = bload1(sl, (unsigned)(C0 * 4 + lane * 4 + 256 * r));
       ob8[r] = bload2(so, (unsigned)(lane * 8 + 512 * r));
     }
-    lgn = bload1(sl, (unsigned)(NH * 4));          // bin 512 (every lane the same address; lane 0 uses it)
+    lgn = bload1(sl, (unsigned)((C0 + NH) * 4));   // bin 512 (every lane the same address; lane 0 uses it)
     obn = bload2(so, (unsigned)(NH * 8));
+    if (GATED) lgg = bload1(sl, 0u);               // the VAD logit (column 0)
   };
   if (MASKED) request(0);
   for (int it = 0; it < iters; ++it) {
@@ -375,13 +416,14 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
     float2 xnyq = make_float2(0.f, 0.f);              // MASKED: X[512], needed by lane 0 only
     if (MASKED) {
       if (valid) {
+        const float g = GATED ? sigmoidf_mask(lgg) : 1.f;
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
           const int k = lane + 64 * r;
-          const float m = sigmoidf_mask(lg8[r]);
+          const float m = GATED ? sigmoidf_mask(lg8[r]) * g : sigmoidf_mask(lg8[r]);
           buf[PADI(k)] = make_float2(ob8[r].x * m, ob8[r].y * m);
         }
-        const float m = sigmoidf_mask(lgn);
+        const float m = GATED ? sigmoidf_mask(lgn) * g : sigmoidf_mask(lgn);
         xnyq = make_float2(obn.x * m, obn.y * m);
         WAVE_SYNC();
       }
@@ -641,5 +683,49 @@ extern "C" int tssep_mask_istft_fwd(const float* logit, const float* obs, int64_
   hipLaunchKernelGGL(istft_kernel<true>, dim3((unsigned)nchunks, (unsigned)rows), dim3(256), 0,
                      (hipStream_t)stream, (const float2*)nullptr, T, shift, N, wsyn, (const float2*)tw, y,
                      tgt, abs_partial, nchunks, istft_hops_per_chunk(N, nchunks), logit, (const float2*)obs, K);
+  return tssep_launch_status();
+}
+
+// ---- explicit_vad: the gated fused tail (logit rows of F + 1 = 514 floats, the VAD logit at column 0) --------------
+extern "C" int tssep_mask_istft_gated_fwd(const float* logit, const float* obs, int64_t B, int64_t K, int64_t T, int size,
+                                          int shift, int fading, const float* wsyn, const float* tw, float* y, int64_t N,
+                                          const float* tgt, float* abs_partial, void* stream) {
+  if (!logit || !obs || !wsyn || !tw || !y) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
+  if ((tgt == nullptr) != (abs_partial == nullptr)) return TSSEP_E_NULL;
+  if (int e = check_plan(size, shift)) return e;
+  if (!fading) return TSSEP_E_UNSUPPORTED;
+  if ((((uintptr_t)logit) & 3u) || (((uintptr_t)obs) & 7u) || (((uintptr_t)tw) & 7u) || (((uintptr_t)wsyn) & 7u))
+    return TSSEP_E_ALIGN;
+  const int64_t rows = B * K;
+  if (rows > 65535) return TSSEP_E_SHAPE;
+  const int nchunks = (int)tssep_istft_chunks(N);
+  hipLaunchKernelGGL((istft_kernel<true, true>), dim3((unsigned)nchunks, (unsigned)rows), dim3(256), 0,
+                     (hipStream_t)stream, (const float2*)nullptr, T, shift, N, wsyn, (const float2*)tw, y,
+                     tgt, abs_partial, nchunks, istft_hops_per_chunk(N, nchunks), logit, (const float2*)obs, K);
+  return tssep_launch_status();
+}
+
+extern "C" int tssep_mask_istft_gated_bwd(const float* est, const float* tgt, const float* sums, const float* gout,
+                                          const float* vad, const float* gout_vad, const float* logit, const float* obs,
+                                          int64_t B, int64_t K, int64_t N, int size, int shift, int fading,
+                                          const float* wsyn, const float* tw, const int32_t* iperm, int bt_major,
+                                          float* dlogit, int64_t T, void* stream) {
+  // tgt == NULL: `est` is dy itself; sums == NULL: MAE; vad == NULL: no BCE term on the gate column
+  if (!est || (tgt && !gout) || (vad && !gout_vad) || !logit || !obs || !wsyn || !tw || !dlogit) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
+  if (int e = check_plan(size, shift)) return e;
+  if ((((uintptr_t)logit) & 3u) || (((uintptr_t)dlogit) & 3u) || (((uintptr_t)obs) & 7u) || (((uintptr_t)tw) & 7u) ||
+      (((uintptr_t)wsyn) & 7u))
+    return TSSEP_E_ALIGN;
+  const int iters = 4;
+  const int64_t rows = B * K, total = rows * T;
+  const int64_t blocks = (total + 4 * iters - 1) / (4 * iters);
+  if (blocks > 0x7fffffff) return TSSEP_E_SHAPE;
+  hipLaunchKernelGGL((rfft_frames_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                     est, rows, N, T, shift, fading ? size - shift : 0, wsyn, (const float2*)tw,
+                     (float2*)nullptr, 2.0f / (float)size, 1.0f / (float)size, iters, logit,
+                     (const float2*)obs, dlogit, K, tgt, sums, gout, iperm, bt_major, vad, gout_vad,
+                     1.0f / ((float)K * (float)T));
   return tssep_launch_status();
 }

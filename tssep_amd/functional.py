@@ -578,6 +578,129 @@ def mask_istft(logit, obs, wsyn, N, size=1024, shift=256, fading=True, tgt=None)
     return y
 
 
+# ---------------------------------------------------------------- explicit_vad (gated tail)
+# MaskEstimator_v2(explicit_vad=True) (net.py:630, 969-979): the head writes rows of F + 1 logits per (b, k, t), the
+# VAD logit v at column 0 and the mask logits l_f behind it; mask = sigmoid(l_f) sigmoid(v).  The Functions below keep
+# that [B,K,T,F+1] tensor whole -- the gated kernels read the gate where the GEMM wrote it and write d(v) where the
+# Linear's backward reads it -- so neither the gate nor its gradient is ever sliced out or scattered back.
+class _MaskHeadGated(torch.autograd.Function):
+    """sigmoid + gate + Masking: logit [B,K,T,F+1], obs [B,T,F] -> (mask [B,K,T,F], est, vad_mask [B,K,T])."""
+
+    @staticmethod
+    def forward(ctx, logit, obs):
+        mask, est, vmask = H.maskhead_gated_fwd(logit, obs)
+        ctx.save_for_backward(logit, obs)
+        return mask, est, vmask
+
+    @staticmethod
+    def backward(ctx, dmask, dest, dvmask):
+        logit, obs = ctx.saved_tensors
+        return H.maskhead_gated_bwd(dest, dmask, dvmask, logit, obs), None
+
+
+def mask_head_gated(logit, obs):
+    return _MaskHeadGated.apply(logit, obs)
+
+
+class _SigmoidGated(torch.autograd.Function):
+    """mask and vad_mask only (no observation available)."""
+
+    @staticmethod
+    def forward(ctx, logit):
+        B, K, T, F1 = logit.shape
+        obs = torch.zeros(B, T, F1 - 1, device=logit.device, dtype=torch.complex64)
+        mask, _, vmask = H.maskhead_gated_fwd(logit, obs, with_est=False)
+        ctx.save_for_backward(logit, obs)
+        return mask, vmask
+
+    @staticmethod
+    def backward(ctx, dmask, dvmask):
+        logit, obs = ctx.saved_tensors
+        return H.maskhead_gated_bwd(None, dmask, dvmask, logit, obs)
+
+
+def sigmoid_gated(logit):
+    """logit [B,K,T,F+1] -> (mask [B,K,T,F] = sigmoid(l) sigmoid(v), vad_mask [B,K,T] = sigmoid(v))."""
+    return _SigmoidGated.apply(logit)
+
+
+class _MaskISTFTGated(torch.autograd.Function):
+    """_MaskISTFT for the gated logit rows; with ``vad`` the forward also returns SignalAndVADSigmoidBCE's BCE term of
+    the gate column ([B]), and its gradient is folded into the tail's d(v) store: the BCE needs no pass of its own."""
+
+    @staticmethod
+    def forward(ctx, logit, obs, wsyn, N, size, shift, fading, tgt, vad, head_link=None, loss_link=None):
+        y, part = H.mask_istft_gated_fwd(logit, obs, wsyn, N, size, shift, fading, tgt)
+        outs = [y]
+        if part is not None:
+            outs.append(part)
+            ctx.mark_non_differentiable(part)
+        bce = H.gatebce_fwd(logit, vad) if vad is not None else None
+        if bce is not None:
+            outs.append(bce)
+        ctx.save_for_backward(logit, obs, wsyn, vad)
+        ctx.meta = (size, shift, fading, part is not None, bce is not None)
+        ctx.links = (head_link, loss_link)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, dy, *rest):
+        logit, obs, wsyn, vad = ctx.saved_tensors
+        size, shift, fading, has_part, has_bce = ctx.meta
+        head_link, loss_link = ctx.links
+        gbce = rest[-1] if has_bce else None
+        vadarg = (vad, gbce) if gbce is not None else None
+        loss = loss_link.take() if loss_link is not None else None      # (est, tgt, sums, gout) of LogMAE / MAE
+        if loss is not None and not _is_dummy(dy):
+            dy = dy + H.logmae_bwd(loss[0].contiguous(), loss[1].contiguous(), loss[2], loss[3])
+            loss = None
+        if head_link is not None and tuple(head_link.shape) == tuple(logit.shape):
+            d = H.mask_istft_gated_bwd(dy, logit, obs, wsyn, size, shift, fading, loss=loss, vad=vadarg,
+                                       iperm=head_link.iperm, bt_major=True)
+            head_link.payload = d if head_link.payload is None else head_link.payload + d
+            dl = _dummy_grad(logit)
+        else:
+            dl = H.mask_istft_gated_bwd(dy, logit, obs, wsyn, size, shift, fading, loss=loss, vad=vadarg)
+        return (dl, None, None, None, None, None, None, None, None, None, None)
+
+
+def mask_istft_gated(logit, obs, wsyn, N, size=1024, shift=256, fading=True, tgt=None, vad=None):
+    """logit [B,K,T,F+1] (VAD logit at column 0), obs complex [B,T,F] -> (time_estimate [B,K,N], bce [B] or None).
+    vad [B,K,T]: the gate column's BCE against it is returned as well, its backward folded into the tail's."""
+    B, K, T = logit.shape[:3]
+    if tgt is not None and tuple(tgt.shape) != (B, K, N):
+        tgt = None
+    if vad is not None and tuple(vad.shape) != (B, K, T):
+        vad = None
+    fold = H.FOLD_TAIL and logit.requires_grad
+    loss_link = _Link() if fold and tgt is not None and H.FOLD_TAIL != 3 else None
+    head_link = getattr(logit, "_tssep_head_link", None) if fold and H.FOLD_TAIL != 2 else None
+    out = _MaskISTFTGated.apply(logit, obs, wsyn, N, size, shift, fading, tgt, vad, head_link, loss_link)
+    y = out[0]
+    if tgt is not None:
+        y._tssep_absdiff = (out[1], tgt.data_ptr(), tuple(tgt.shape))
+        y._tssep_loss_link = loss_link
+    return y, (out[-1] if vad is not None else None)
+
+
+class _GateBCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logit, vad):
+        ctx.save_for_backward(logit, vad)
+        return H.gatebce_fwd(logit, vad)
+
+    @staticmethod
+    def backward(ctx, g):
+        logit, vad = ctx.saved_tensors
+        return H.gatebce_bwd(logit, vad, g), None
+
+
+def gate_bce(logit, vad):
+    """mean_{k,t} BCEWithLogits(logit[..., 0], vad) -> [B]: SignalAndVADSigmoidBCE's VAD term on the gate column of
+    logit [B,K,T,F+1] (vad [B,K,T])."""
+    return _GateBCE.apply(logit, vad.to(device=logit.device, dtype=torch.float32))
+
+
 # ------------------------------------------------------------------------------ losses
 def _fused_absdiff(est, tgt):
     """Partial sums the fused mask-head + iSTFT forward left on `est` for exactly this target."""

@@ -236,6 +236,58 @@ def mask_istft_bwd(dy, logit, obs, wsyn, size=1024, shift=256, fading=True, loss
     return dlogit
 
 
+def mask_istft_gated_fwd(logit, obs, wsyn, N, size=1024, shift=256, fading=True, tgt=None):
+    """explicit_vad: logit [B,K,T,F+1] (VAD logit at column 0), obs complex64 [B,T,F] -> y [B,K,N] =
+    istft(sigmoid(l) sigmoid(v) * obs) (+ per-chunk sums of |y - tgt| when tgt [B,K,N] is given)."""
+    L = _lib.lib()
+    B, K, T, F1 = logit.shape
+    assert tuple(obs.shape) == (B, T, F1 - 1) and obs.dtype == torch.complex64, (tuple(logit.shape), tuple(obs.shape))
+    assert tgt is None or tuple(tgt.shape) == (B, K, N), (tuple(tgt.shape), (B, K, N))
+    logit = _f32(logit).contiguous()
+    obs_r = torch.view_as_real(obs.contiguous())
+    y = torch.empty(B, K, N, device=logit.device, dtype=torch.float32)
+    part = None
+    if tgt is not None:
+        part = torch.empty(B * K, int(L.tssep_istft_chunks(N)), device=logit.device, dtype=torch.float32)
+        tgt = _f32(tgt).contiguous()
+    with _timed("maskhead_gated_fwd", 0, B * T * (4 * K * F1 + 8 * (F1 - 1)) + 4 * B * K * N):
+        check(L.tssep_mask_istft_gated_fwd(_p(logit), _p(obs_r), B, K, T, size, shift, int(fading), _p(wsyn),
+                                           _p(fft_tables(size, logit.device)), _p(y), N, _p(tgt), _p(part),
+                                           _stream()), "mask_istft_gated_fwd")
+    return y, part
+
+
+def mask_istft_gated_bwd(dy, logit, obs, wsyn, size=1024, shift=256, fading=True, loss=None, vad=None, iperm=None,
+                         bt_major=False):
+    """The backward of mask_istft_gated_fwd -> dlogit [B,K,T,F+1] (bt_major: [B*T, K*(F+1)], speaker k at position
+    iperm[b, k]).  loss = (est, tgt, sums or None, gout) as mask_istft_bwd; vad = (Vad [B,K,T], gout_vad [B]) adds the
+    gate column's BCE gradient in the same store."""
+    L = _lib.lib()
+    B, K, T, F1 = logit.shape
+    assert tuple(obs.shape) == (B, T, F1 - 1) and obs.dtype == torch.complex64, (tuple(logit.shape), tuple(obs.shape))
+    logit = _f32(logit).contiguous()
+    obs_r = torch.view_as_real(obs.contiguous())
+    dlogit = (torch.empty(B * T, K * F1, device=logit.device, dtype=torch.float32) if bt_major
+              else torch.empty_like(logit))
+    if loss is None:
+        x, tgt, sums, gout = _f32(dy).contiguous(), None, None, None
+    else:
+        x, tgt, sums, gout = (_f32(loss[0]).contiguous(), _f32(loss[1]).contiguous(), loss[2],
+                              _f32(loss[3]).contiguous())
+    assert tuple(x.shape[:2]) == (B, K) and (tgt is None or tgt.shape == x.shape), (tuple(x.shape), B, K)
+    assert gout is None or gout.numel() == B
+    v = gv = None
+    if vad is not None:
+        v, gv = _f32(vad[0]).contiguous(), _f32(vad[1]).contiguous()
+        assert tuple(v.shape) == (B, K, T) and gv.numel() == B, (tuple(v.shape), (B, K, T), gv.numel())
+    with _timed("maskhead_gated_bwd", 0, B * T * (8 * K * F1 + 8 * (F1 - 1)) + 4 * B * K * x.shape[-1]):
+        check(L.tssep_mask_istft_gated_bwd(_p(x), _p(tgt), _p(sums), _p(gout), _p(v), _p(gv), _p(logit), _p(obs_r),
+                                           B, K, x.shape[-1], size, shift, int(fading), _p(wsyn),
+                                           _p(fft_tables(size, logit.device)), _p(iperm), int(bt_major), _p(dlogit),
+                                           T, _stream()), "mask_istft_gated_bwd")
+    return dlogit
+
+
 # --------------------------------------------------------------------------- features
 STAT_AXES = {"tf": 0, "t": 1, "f": 2}
 
@@ -1025,6 +1077,39 @@ def maskhead_bwd(dest, dmask, mask, obs):
     return dlogit
 
 
+def maskhead_gated_fwd(logit, obs, with_est=True):
+    """explicit_vad: logit [B,K,T,F+1] (VAD logit at column 0), obs complex64 [B,T,F] -> mask [B,K,T,F] =
+    sigmoid(l) sigmoid(v), est complex64 [B,K,T,F] = obs * mask (None without with_est), vmask [B,K,T] = sigmoid(v)"""
+    B, K, T, F1 = logit.shape
+    assert tuple(obs.shape) == (B, T, F1 - 1) and obs.dtype == torch.complex64, (tuple(logit.shape), tuple(obs.shape))
+    logit = _f32(logit).contiguous()
+    obs_r = torch.view_as_real(obs.contiguous())
+    mask = torch.empty(B, K, T, F1 - 1, device=logit.device, dtype=torch.float32)
+    vmask = torch.empty(B, K, T, device=logit.device, dtype=torch.float32)
+    est = torch.empty(B, K, T, F1 - 1, 2, device=logit.device, dtype=torch.float32) if with_est else None
+    check(_lib.lib().tssep_maskhead_gated_fwd(_p(logit), _p(obs_r), _p(mask), _p(est), _p(vmask), B, K, T, F1 - 1,
+                                              _stream()), "maskhead_gated_fwd")
+    return mask, (torch.view_as_complex(est) if est is not None else None), vmask
+
+
+def maskhead_gated_bwd(dest, dmask, dvmask, logit, obs):
+    """-> dlogit [B,K,T,F+1]; dest (complex64), dmask [B,K,T,F] and dvmask [B,K,T] may each be None."""
+    B, K, T, F1 = logit.shape
+    assert tuple(obs.shape) == (B, T, F1 - 1) and obs.dtype == torch.complex64, (tuple(logit.shape), tuple(obs.shape))
+    for t_, shape in ((dest, (B, K, T, F1 - 1)), (dmask, (B, K, T, F1 - 1)), (dvmask, (B, K, T))):
+        assert t_ is None or tuple(t_.shape) == shape, (tuple(t_.shape), shape)
+    assert dest is None or dest.dtype == torch.complex64
+    logit = _f32(logit).contiguous()
+    obs_r = torch.view_as_real(obs.contiguous())
+    dest_r = torch.view_as_real(dest.contiguous()) if dest is not None else None
+    dmask = _f32(dmask).contiguous() if dmask is not None else None
+    dvmask = _f32(dvmask).contiguous() if dvmask is not None else None
+    dlogit = torch.empty_like(logit)
+    check(_lib.lib().tssep_maskhead_gated_bwd(_p(dest_r), _p(dmask), _p(dvmask), _p(logit), _p(obs_r), _p(dlogit),
+                                              B, K, T, F1 - 1, _stream()), "maskhead_gated_bwd")
+    return dlogit
+
+
 def mask_mul_fwd(mask, obs):
     B, K, T, F = mask.shape
     est = torch.empty(B, K, T, F, 2, device=mask.device, dtype=torch.float32)
@@ -1155,3 +1240,25 @@ def logit_map_bwd(dout, perm, iperm, B, trials, K, T, F, Fr, spk_rows):
                                          trials, K, T, F, Fr, int(spk_rows), _p(draw), _stream()),
           "logit_map_bwd")
     return draw
+
+
+def gatebce_fwd(logit, vad):
+    """SignalAndVADSigmoidBCE's BCE on the gate column of logit [B,K,T,F+1] against vad [B,K,T] -> loss [B]"""
+    B, K, T, F1 = logit.shape
+    assert tuple(vad.shape) == (B, K, T), (tuple(vad.shape), (B, K, T))
+    logit, vad = _f32(logit).contiguous(), _f32(vad).contiguous()
+    loss = torch.empty(B, device=logit.device, dtype=torch.float32)
+    ws = torch.empty(B * K * T, device=logit.device, dtype=torch.float32)
+    check(_lib.lib().tssep_gatebce_fwd(_p(logit), F1, _p(vad), B, K, T, _p(loss), _p(ws), _stream()), "gatebce_fwd")
+    return loss
+
+
+def gatebce_bwd(logit, vad, gout):
+    """-> dlogit [B,K,T,F+1]: the BCE gradient at column 0, zeros elsewhere"""
+    B, K, T, F1 = logit.shape
+    assert tuple(vad.shape) == (B, K, T) and gout.numel() == B, (tuple(vad.shape), (B, K, T), gout.numel())
+    logit = _f32(logit).contiguous()
+    dlogit = torch.empty_like(logit)
+    check(_lib.lib().tssep_gatebce_bwd(_p(logit), F1, _p(_f32(vad).contiguous()), _p(_f32(gout).contiguous()),
+                                       B, K, T, _p(dlogit), _stream()), "gatebce_bwd")
+    return dlogit

@@ -229,16 +229,29 @@ class Model(Configurable, torch.nn.Module):
                      vad_mask=None, vad_logit=None, _lazy=None):
             self._mask, self._stft_estimate, self._lazy, self._lazy0 = mask, stft_estimate, _lazy, _lazy
             self.logit, self.embedding, self.time_estimate = logit, embedding, time_estimate
-            self.vad_mask, self.vad_logit = vad_mask, vad_logit
+            self._vad_mask, self.vad_logit = vad_mask, vad_logit
+            self._gated = None          # explicit_vad: the head's [B,K,T,F+1] logit rows (VAD logit at column 0)
 
         def _materialise(self):
             if self._lazy is not None:
                 lazy, self._lazy = self._lazy, None
-                mask, est = lazy()
+                mask, est, *vad_mask = lazy()
                 if self._mask is None:
                     self._mask = mask
                 if self._stft_estimate is None:
                     self._stft_estimate = est
+                if vad_mask and self._vad_mask is None:
+                    self._vad_mask = vad_mask[0]
+
+        @property
+        def vad_mask(self):
+            if self._vad_mask is None and self._gated is not None:
+                self._materialise()
+            return self._vad_mask
+
+        @vad_mask.setter
+        def vad_mask(self, value):
+            self._vad_mask = value
 
         @property
         def mask(self):
@@ -271,6 +284,8 @@ class Model(Configurable, torch.nn.Module):
             other = copy.copy(self)
             if other._lazy0 is not None:
                 other._mask = other._stft_estimate = None
+                if other._gated is not None:
+                    other._vad_mask = None
                 other._lazy = other._lazy0
             return other
 
@@ -304,6 +319,8 @@ class Model(Configurable, torch.nn.Module):
         batched = ex["Input"].dim() == 3
         logit, emb = self.mask_estimator.logits(ex["Input"], aux)
         logit4 = logit if batched else logit[None]
+        if getattr(self.mask_estimator, "explicit_vad", False):
+            return self._forward_gated(ex, logit, logit4, emb, ref, batched)
         out = self.ForwardOutput(logit=logit.unsqueeze(-3), embedding=emb)
         if "Observation" in ex and isinstance(self.enhancer, _enh.Masking):
             obs = ex["Observation"][..., ref, :, :]
@@ -329,6 +346,37 @@ class Model(Configurable, torch.nn.Module):
         out._lazy = out._lazy0 = lazy
         return out
 
+    def _forward_gated(self, ex, logit, logit4, emb, ref, batched):
+        """explicit_vad (net.py:969-979): logit = None, vad_logit = v [B,K,1,T] (a view of the head's rows), and
+        mask = sigmoid(l) sigmoid(v), vad_mask = sigmoid(v), stft_estimate -- computed on first access, like the ungated
+        mask; the training step runs the gated fused tail from the [B,K,T,F+1] rows instead."""
+        def unb(t):
+            return t if batched else t[0]
+
+        out = self.ForwardOutput(logit=None, embedding=emb, vad_logit=unb(logit4[..., 0]).unsqueeze(-2))
+        out._gated = logit4
+        if "Observation" in ex and isinstance(self.enhancer, _enh.Masking):
+            obs = ex["Observation"][..., ref, :, :]
+            obs3 = (obs if batched else obs[None]).contiguous()
+            out._fusable = (logit4, obs3, batched)
+
+            def lazy():
+                mask, est, vmask = Fn.mask_head_gated(logit4, obs3)
+                return unb(mask).unsqueeze(-3), unb(est), unb(vmask).unsqueeze(-2)
+        elif "Observation" in ex:
+            def lazy():
+                mask, vmask = Fn.sigmoid_gated(logit4)
+                mask = unb(mask).unsqueeze(-3)
+                return mask, self.enhancer(mask, ex, self), unb(vmask).unsqueeze(-2)
+        else:
+            assert isinstance(self.loss, _loss.VADSigmoidBCE), type(self.loss)
+
+            def lazy():
+                mask, vmask = Fn.sigmoid_gated(logit4)
+                return unb(mask).unsqueeze(-3), None, unb(vmask).unsqueeze(-2)
+        out._lazy = out._lazy0 = lazy
+        return out
+
     # ------------------------------------------------------------------------- review
     def review(self, ex, out: "Model.ForwardOutput"):
         summary = ReviewSummary()
@@ -339,12 +387,23 @@ class Model(Configurable, torch.nn.Module):
                 # nobody looked at mask / stft_estimate: sigmoid -> masking -> istft in one kernel, with
                 # the |estimate - target| partial sums of a time-domain loss on the side
                 logit4, obs3, batched = fus
-                tgt = ex.get(getattr(self.loss, "target", None)) if isinstance(self.loss, _loss.TimeDomain) else None
+                sig = self.loss.signal_loss if isinstance(self.loss, _loss.SignalAndVADSigmoidBCE) else self.loss
+                tgt = ex.get(getattr(sig, "target", None)) if isinstance(sig, _loss.TimeDomain) else None
                 if isinstance(tgt, torch.Tensor):
                     tgt = tgt if batched else tgt[None]
                 else:
                     tgt = None
-                te = self.fe.masked_istft(logit4, obs3, num_samples=n, target=tgt)
+                if out._gated is not None:
+                    # explicit_vad: the gated tail; with SignalAndVADSigmoidBCE the BCE of the gate column rides along
+                    # (its value on `out`, its gradient folded into the tail's d(v) store)
+                    vad = self.loss.frame_vad(ex, self) if isinstance(self.loss, _loss.SignalAndVADSigmoidBCE) else None
+                    if vad is not None:
+                        vad = vad if batched else vad[None]
+                    te, bce = self.fe.masked_istft(logit4, obs3, num_samples=n, target=tgt, vad=vad)
+                    if bce is not None:
+                        out._gate_bce = (bce if batched else bce[0], ex[self.loss.target])
+                else:
+                    te = self.fe.masked_istft(logit4, obs3, num_samples=n, target=tgt)
                 out.time_estimate = te if batched else te[0]
             else:
                 out.time_estimate = self.fe.istft(out.stft_estimate, num_samples=n)

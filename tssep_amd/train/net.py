@@ -60,8 +60,8 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
             odim = idim
         if aux_net is not None or input_normalizer is not None or aux_normalizer is not None:
             raise NotImplementedError("aux_net / normalizers are outside the hot path (SURVEY 2.1 #2)")
-        if explicit_vad:
-            raise NotImplementedError("explicit_vad (off in every shipped config)")
+        if explicit_vad and output_resolution == "t":
+            raise AssertionError("explicit_vad needs output_resolution='tf' (net.py:643)")
         if nmask != 1:
             raise NotImplementedError("nmask != 1 (Masking enhancer uses 1, model.py:138-145)")
         self.odim, self.nmask = odim, nmask
@@ -70,7 +70,7 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         self.num_averaged_permutations = num_averaged_permutations
         self.ts_vad = ts_vad
         self.input_normalizer, self.aux_normalizer = input_normalizer, aux_normalizer
-        self.explicit_vad = explicit_vad
+        self.explicit_vad = bool(explicit_vad)
         self.layers, self.projs = layers, projs
         if not self.ts_vad:
             assert self.num_averaged_permutations == 1, (self.ts_vad, self.num_averaged_permutations)
@@ -116,7 +116,7 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
                 put("dropout", torch.nn.Dropout(p=dropout))
                 put("activation", torch.nn.Tanh())
         if output_resolution == "tf":
-            final_out_features = odim * nmask * ts_factor
+            final_out_features = (odim + int(self.explicit_vad)) * nmask * ts_factor    # net.py:630
         elif output_resolution == "t":
             final_out_features = nmask * ts_factor
         else:
@@ -161,7 +161,8 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
 
     # ----------------------------------------------------------------------------------
     def logits(self, xs, aux):
-        """-> (logit [B,K,T,F], embedding [B,K,1,E]).  Batched input only."""
+        """-> (logit [B,K,T,F], embedding [B,K,1,E]).  Batched input only.  explicit_vad: logit [B,K,T,F+1], the VAD
+        logit at column 0 of every row and the mask logits behind it (net.py:969-979 slices them apart)."""
         if xs.dim() == 2:
             lg, emb = self.logits(xs[None], [aux])
             return lg[0], emb[0]
@@ -181,7 +182,7 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         if self.ts_vad is not False:
             assert K == self.ts_vad, (K, self.ts_vad)
         trials = self.num_averaged_permutations
-        F = self.odim
+        F = self.odim + int(self.explicit_vad)         # the head's columns per speaker
         pre = self.pre_net.forward_rows(xs.reshape(B * T, xs.shape[-1]), B, T)       # [B*T, odim]
         h = Fn.condition(pre, aux, B, K, T, trials, self.combination)               # rows (b,tr,k,t)
         nb = len(self._birnns)
@@ -205,6 +206,14 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
 
     def forward(self, xs, aux=None) -> Output:
         logit, emb = self.logits(xs, aux)
-        mask = Fn.sigmoid(logit)
         u = -3
+        if self.explicit_vad:                      # net.py:969-979
+            lg = logit if logit.dim() == 4 else logit[None]
+            mask, vad_mask = Fn.sigmoid_gated(lg)
+            vad_logit = lg[..., 0]
+            if logit.dim() == 3:
+                mask, vad_mask, vad_logit = mask[0], vad_mask[0], vad_logit[0]
+            return Output(mask=mask.unsqueeze(u), logit=None, embedding=emb, vad_mask=vad_mask.unsqueeze(-2),
+                          vad_logit=vad_logit.unsqueeze(-2))
+        mask = Fn.sigmoid(logit)
         return Output(mask=mask.unsqueeze(u), logit=logit.unsqueeze(u), embedding=emb)
