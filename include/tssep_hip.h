@@ -387,6 +387,27 @@ int tssep_blstm_onchip16_bwd(float* gates, const float* cell, const float* dhout
  * [B,T,K*P] of 'spk time feature -> 1 time (spk feature)' (net.py:608-611). */
 int tssep_tanh_bwd(const float* dy, const float* y, float* dz, int64_t rows, int64_t P,
                    int64_t K, int64_t T, int combined_in, void* stream);
+/* Dropout in front of a Tanh: Linear -> Dropout(p) -> Tanh inside RNNP_packed (tssep/train/rnnp.py:98-100) and
+ * birnn -> Dropout(p) -> Tanh between post-net modules (tssep/train/net.py:623-625), training mode.
+ *   keep(e) <=> word(e) >= floor(p * 2^32)   (64-bit compare: p = 0 keeps all, p = 1 none)
+ *   word(e) = output word e % 4 of Philox4x32-10(counter = {e / 4 as lo, hi; draw as lo, hi}, key = seed as lo, hi)
+ *   e = r * P + c: LOGICAL element (row r = (n,t) of the producing layer, column c), whatever layout it is stored in
+ * (one definition for host and device: tssep_amd/csrc/dropout_philox.h).  p outside [0, 1]: TSSEP_E_SHAPE.
+ * The two *_host functions run on the host and touch no GPU (tests, tools): the raw generator, and keep[i] (0 / 1) of the
+ * elements first .. first + n - 1 of the mask {seed, draw}. */
+int tssep_philox4x32_10_host(const uint32_t* ctr /* [4] */, const uint32_t* key /* [2] */, uint32_t* out /* [4] */);
+int tssep_dropout_keep_host(int64_t seed, int64_t draw, int64_t first, int64_t n, double p, uint8_t* keep);
+/* state, used: DEVICE int64[2] = {seed, draw}.  One thread: used <- state, then state.draw += 1.  Runs in front of every
+ * dropout forward; the forward and its backward read `used`, so a replayed hipGraph draws a fresh mask each time. */
+int tssep_dropout_draw(int64_t* state, int64_t* used, void* stream);
+/* y = keep ? tanh(z / (1 - p)) : 0 with the Tanh of the GEMMs' fused store (act = 1) on z * fp32(1 / (1 - p)); y may
+ * be z.  rows x P logical elements; combined == 0: row r at z + r * ld (ld >= P); combined != 0: z and y are the
+ * speaker-combined [B,T,K*P] of rows (b,k,t), addressed as in tssep_tanh_bwd (ld is ignored). */
+int tssep_dropout_tanh_fwd(const float* z, float* y, int64_t rows, int64_t P, int64_t ld, int64_t K, int64_t T,
+                           int combined, double p, const int64_t* used, void* stream);
+/* dz = keep ? dy * (1 - y^2) / (1 - p) : 0; layouts exactly as tssep_tanh_bwd (dz dense rows (b,k,t) x P). */
+int tssep_dropout_tanh_bwd(const float* dy, const float* y, float* dz, int64_t rows, int64_t P, int64_t K, int64_t T,
+                           int combined_in, double p, const int64_t* used, void* stream);
 /* Speaker conditioning (tssep/train/net.py:862-896) fused with the permutation-trial fold
  * (net.py:913-924): xs rows are (b, trial, k, t); trial tr holds speaker (k+tr)%K at position k.
  *   mul: xs[row, f] = pre[(b,t), f] * aux[(b,spk), f]

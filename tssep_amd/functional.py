@@ -61,11 +61,14 @@ class _RNNP(torch.autograd.Function):
 
     x: [R, ld_x] buffer view, rows (n, t) for N sequences of T frames, I valid columns.
     Output: [R, hdim] rows (padded leading dimension), or the speaker-combined layout
-    [B, T, K*hdim] when ``combine=K`` (net.py:608-611 fused into the projection's store)."""
+    [B, T, K*hdim] when ``combine=K`` (net.py:608-611 fused into the projection's store).
+    ``dropout_p`` > 0: the Tanh behind this layer is an ACTIVE dropout site (rnnp.py:98-100, net.py:623-625) -- the
+    projection stores plainly (act = 0) and one pass over y applies mask, 1 / (1 - p) and Tanh in place; the backward
+    regenerates the mask from the {seed, draw} pair the forward drew (hip_ops.dropout_draw)."""
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, w_proj, b_proj,
-                N, T, act, combine, in_tanh=0, in_link=None, out_link=None):
+                N, T, act, combine, in_tanh=0, in_link=None, out_link=None, dropout_p=0.0):
         dev = x.device
         Hh = w_hh.shape[1]
         I = w_ih.shape[1]
@@ -87,16 +90,24 @@ class _RNNP(torch.autograd.Function):
         H.recurrence_launch(plan["fwd"], "fwd", gates, cell, hout, 2 * Hp, Hp, whh["fwd"], N, T, Hh)
         # projection weight in the (possibly padded) [hdim, 2*Hp] column layout of hout
         wp = H.derived("proj_layout", [w_proj], lambda: _proj_layout(w_proj, Hh, Hp))
+        drop = float(dropout_p) if dropout_p else 0.0
+        assert not drop or (act == 1 and out_link is None), "dropout_p: a site is the Tanh behind the layer, never folded"
+        store_act = 0 if drop else act
         if combine:
             K = combine
             B = N // K
             y = torch.empty(B * T, K * hdim, device=dev, dtype=torch.float32)
-            H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, 0, R, hdim, 2 * Hp, bias=b_proj.detach(), act=act,
+            H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, 0, R, hdim, 2 * Hp, bias=b_proj.detach(), act=store_act,
                    remap=dict(T=T, K=K, sb=T * K * hdim, sk=hdim, st=K * hdim))
             ld_y = K * hdim
         else:
             y, ld_y = H.padded(R, hdim, dev, zero=True)
-            H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, ld_y, R, hdim, 2 * Hp, bias=b_proj.detach(), act=act)
+            H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, ld_y, R, hdim, 2 * Hp, bias=b_proj.detach(), act=store_act)
+        used = None
+        if drop:
+            used = H.dropout_draw(dev)
+            H.dropout_tanh_fwd(y, y, R, hdim, ld_y, combine if combine else 1, T, bool(combine), drop, used)
+        ctx.drop = (drop, used)
         ctx.save_for_backward(xv, gates, cell, hout, y, wp)
         ctx.params = (w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, w_proj, b_proj)
         ctx.recurrence = (plan["bwd"], whh["bwd"])
@@ -130,7 +141,11 @@ class _RNNP(torch.autograd.Function):
         elif act:
             dyc = dy.contiguous() if combine else _dense_rows(dy, hdim)
             yc = y if combine else _dense_rows(y[:, :hdim], hdim)
-            dz = H.tanh_bwd(dyc, yc, R, hdim, K, T, bool(combine))
+            drop, used = ctx.drop
+            if drop:
+                dz = H.dropout_tanh_bwd(dyc, yc, R, hdim, K, T, bool(combine), drop, used)
+            else:
+                dz = H.tanh_bwd(dyc, yc, R, hdim, K, T, bool(combine))
         else:
             if combine:   # layout change only: reuse tanh_bwd's gather with y = 0
                 dz = H.tanh_bwd(dy.contiguous(), torch.zeros_like(dy), R, hdim, K, T, True)
@@ -255,7 +270,7 @@ class _RNNP(torch.autograd.Function):
                 dx = dxb[:, :I]
                 if tuple(ctx.x_shape) != tuple(dx.shape):
                     dx = dx.reshape(ctx.x_shape)
-        return (dx, *lstm_grads, d_w_proj, d_b_proj, None, None, None, None, None, None, None)
+        return (dx, *lstm_grads, d_w_proj, d_b_proj, None, None, None, None, None, None, None, None)
 
 
 def _notify_grads(params):
@@ -297,7 +312,7 @@ def _proj_unlayout(dwp, Hh, Hp):
     return torch.cat([dwp[:, :Hh], dwp[:, Hp:Hp + Hh]], dim=1).contiguous()
 
 
-def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=False):
+def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=False, dropout_p=0.0):
     """x rows (n,t); lstm = torch.nn.LSTM parameter container, linear = nn.Linear container.
     The Tanh between two layers (net.py:623-625) runs forward in the producer's projection epilogue (act = 1);
     its BACKWARD may run in the store of the consumer's d(input) GEMM: the producer is called with dz_given and
@@ -306,16 +321,19 @@ def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=Fals
     In backward the consumer leaves d(pre-activation) on the link and returns a dummy for its input; the
     producer adds the Tanh backward of whatever ELSE arrived for its output (a second consumer), and when the
     output is watched (hook / retain_grad) or the consumer never ran, nothing is folded and `tssep_tanh_bwd`
-    runs as without the fold -- correct either way (VERDICT r3 #8)."""
+    runs as without the fold -- correct either way.
+    dropout_p > 0 (with act = 1): that Tanh is an active dropout site, y = keep ? tanh(z / (1 - p)) : 0 (_RNNP); such a
+    site is never folded -- the caller passes in_tanh = 0 to the consumer, and dz_given is ignored here."""
     import weakref
     in_link = getattr(x, "_tssep_tanh_link", None) if in_tanh else None
     if in_link is not None and not (x.requires_grad and torch.is_grad_enabled()):
         in_link = None
-    out_link = _Link() if (dz_given and act == 1 and torch.is_grad_enabled()) else None
+    dropout_p = float(dropout_p) if (dropout_p and act == 1) else 0.0
+    out_link = _Link() if (dz_given and act == 1 and not dropout_p and torch.is_grad_enabled()) else None
     out = _RNNP.apply(x, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0,
                       lstm.weight_ih_l0_reverse, lstm.weight_hh_l0_reverse,
                       lstm.bias_ih_l0_reverse, lstm.bias_hh_l0_reverse,
-                      linear.weight, linear.bias, N, T, act, combine, in_tanh, in_link, out_link)
+                      linear.weight, linear.bias, N, T, act, combine, in_tanh, in_link, out_link, dropout_p)
     if out_link is not None and out.requires_grad:
         out_link.out = weakref.ref(out)
         out._tssep_tanh_link = out_link

@@ -1014,6 +1014,91 @@ def tanh_bwd(dy, y, rows, P, K, T, combined):
     return dz
 
 
+# ---- dropout in front of a Tanh (csrc/dropout.hip, csrc/dropout_philox.h) ----------------------------------------
+# The mask is a pure function of {seed, draw, logical element index, p}.  {seed, draw} lives in DEVICE memory, one
+# int64[2] per device: every active site's forward copies it into a tensor of its own (`used`, kept for the backward) and
+# counts the draw up, on the device -- so nothing about a mask is frozen into a captured graph.  The tensor is created
+# once and only ever written in place (captured graphs hold its address).
+_DROPOUT_STATE = {}
+
+
+def _as_i64(v):
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def _cuda_device(device=None):
+    dev = torch.device("cuda" if device is None else device)
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def dropout_state(device=None):
+    """The device's {seed, draw} tensor; seeded from torch.initial_seed() when first asked for."""
+    dev = _cuda_device(device)
+    st = _DROPOUT_STATE.get(dev.index)
+    if st is None:
+        st = _DROPOUT_STATE[dev.index] = torch.tensor([_as_i64(torch.initial_seed()), 0], dtype=torch.int64, device=dev)
+    return st
+
+
+def manual_seed(seed, device=None):
+    """Seed the dropout masks of `device` (default: the current one) and start counting draws from 0 again."""
+    set_state((seed, 0), device)
+
+
+def get_state(device=None):
+    """-> (seed, draw) of the device's dropout stream as Python ints (one host sync)."""
+    seed, draw = dropout_state(device).tolist()
+    return seed, draw
+
+
+def set_state(state, device=None):
+    seed, draw = state
+    st = dropout_state(device)
+    st.copy_(torch.tensor([_as_i64(seed), _as_i64(draw)], dtype=torch.int64))
+
+
+def dropout_draw(device=None):
+    """One draw for one site: -> `used`, the {seed, draw} its forward and backward kernels read."""
+    st = dropout_state(device)
+    used = torch.empty(2, dtype=torch.int64, device=st.device)
+    check(_lib.lib().tssep_dropout_draw(_p(st), _p(used), _stream()), "dropout_draw")
+    return used
+
+
+def dropout_tanh_fwd(z, y, rows, P, ld, K, T, combined, p, used):
+    """y = keep ? tanh(z / (1 - p)) : 0; y may be z.  combined: both are the speaker-combined [B,T,K*P] (ld unused)."""
+    assert used.dtype == torch.int64 and used.is_cuda and used.numel() == 2, (used.dtype, used.shape)
+    check(_lib.lib().tssep_dropout_tanh_fwd(_p(_f32(z)), _p(_f32(y)), rows, P, ld, K, T, int(bool(combined)), float(p),
+                                            _p(used), _stream()), "dropout_tanh_fwd")
+    return y
+
+
+def dropout_tanh_bwd(dy, y, rows, P, K, T, combined, p, used):
+    """tanh_bwd with the mask of `used`: -> dz dense rows (b,k,t) x P."""
+    assert used.dtype == torch.int64 and used.is_cuda and used.numel() == 2, (used.dtype, used.shape)
+    dz = torch.empty(rows, P, device=dy.device, dtype=torch.float32)
+    check(_lib.lib().tssep_dropout_tanh_bwd(_p(_f32(dy)), _p(_f32(y)), _p(dz), rows, P, K, T, int(bool(combined)),
+                                            float(p), _p(used), _stream()), "dropout_tanh_bwd")
+    return dz
+
+
+def philox4x32_10_host(ctr, key):
+    """Philox4x32-10 on the host (no GPU): 4 counter words, 2 key words -> 4 output words."""
+    c, k, o = (ctypes.c_uint32 * 4)(*ctr), (ctypes.c_uint32 * 2)(*key), (ctypes.c_uint32 * 4)()
+    check(_lib.lib().tssep_philox4x32_10_host(c, k, o), "philox4x32_10_host")
+    return [int(v) for v in o]
+
+
+def dropout_keep_host(seed, draw, first, n, p):
+    """The mask {seed, draw} for the logical elements first .. first + n - 1, on the host (no GPU): uint8 [n], 1 = keep."""
+    keep = np.empty(max(int(n), 0), dtype=np.uint8)
+    buf = keep.ctypes.data_as(ctypes.c_void_p) if keep.size else (ctypes.c_uint8 * 1)()
+    check(_lib.lib().tssep_dropout_keep_host(_as_i64(seed), _as_i64(draw), int(first), int(n), float(p), buf),
+          "dropout_keep_host")
+    return keep
+
+
 def cond_fwd(pre, ld_pre, aux, B, K, T, F, trials, combination):
     """-> (xs view [B*trials*K*T, W], ld)"""
     L = _lib.lib()

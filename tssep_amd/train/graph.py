@@ -17,6 +17,9 @@ What would otherwise be frozen into the graph is routed through device memory:
     order -- and copied into a static device buffer before each replay
     (``MaskEstimator_v2.permutation_source``);
   * the W-stationary recurrences take their launch epoch from device memory (csrc/common.h);
+  * the dropout masks are a function of a {seed, draw} pair in device memory that every active site copies and counts up
+    on the device (hip_ops.dropout_draw): every replay draws fresh masks.  The passes a capture needs count it up too, so
+    it is put back afterwards -- a run through graphs consumes the same draws as the eager run;
   * inputs live in static device tensors (a batch that already IS the static tensor is not copied).
 
 The derived weight layouts (packs, transposes: ~25 small launches) are built at the start of the captured step on the
@@ -43,6 +46,7 @@ class GraphedStep:
         self.adopt_inputs = bool(adopt_inputs)
         self.zero_grad, self.max_graphs = bool(zero_grad), int(max_graphs)
         self._graphs = {}
+        self._dropouts = [m for m in model.modules() if isinstance(m, torch.nn.Dropout)]
         self.replays = 0
         self.eager_steps = 0
 
@@ -57,7 +61,7 @@ class GraphedStep:
         # channel must not replay the graph captured for the first one)
         ref = ex.get("reference_channel")
         return tuple((k, tuple(ex[k].shape), ex[k].dtype) for k in self._tensor_keys(ex)) + \
-            (("training", self.model.training), ("reference_channel", ref if isinstance(ref, (int, type(None))) else repr(ref)))
+            (("training", self.model.training), ("dropout", tuple((m.training, m.p) for m in self._dropouts)), ("reference_channel", ref if isinstance(ref, (int, type(None))) else repr(ref)))
 
     def _eager(self, ex, derived_tags=None):
         if self.zero_grad:
@@ -129,6 +133,7 @@ class GraphedStep:
             me.permutation_source = st["source"]
         # (zero_grad=False: the warm-up and capture passes accumulate into the caller's half-filled bucket -- put it back)
         kept = None if self.zero_grad else [f.clone() for f in self.optimizer.bucket.flats]
+        drawn = H.get_state(dev)          # (also: the state tensor exists before anything is captured)
         try:
             s = torch.cuda.Stream(device=dev)
             s.wait_stream(torch.cuda.current_stream(dev))
@@ -146,6 +151,8 @@ class GraphedStep:
             st["per_example"] = self._per_example_scalars(st["summary"], st["rest"].get("dataset"))
         finally:
             me.permutation_source = prev
+            torch.cuda.synchronize(dev)
+            H.set_state(drawn, dev)
             if kept is not None:
                 torch.cuda.synchronize(dev)
                 for f, k in zip(self.optimizer.bucket.flats, kept):

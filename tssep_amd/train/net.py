@@ -126,6 +126,7 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         self.post_net = Sequential(data)
         self.final_activation = torch.nn.Sigmoid()
         self._birnn_keys = [k for k in data if k.startswith("birnn")]
+        self._dropout_keys = [k for k in data if k.startswith("dropout")]      # the one behind birnn l, l < layers - 1
         self._linear_key = [k for k in data if k.startswith("linear")][0]
         if ts_vad is not False and layers < 2:
             raise NotImplementedError("ts_vad with a single post-net layer")
@@ -133,6 +134,10 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
     @property
     def _birnns(self):
         return [self.post_net._modules[k] for k in self._birnn_keys]
+
+    @property
+    def _dropouts(self):
+        return [self.post_net._modules[k] for k in self._dropout_keys]
 
     @property
     def _linear(self):
@@ -187,17 +192,21 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         h = Fn.condition(pre, aux, B, K, T, trials, self.combination)               # rows (b,tr,k,t)
         nb = len(self._birnns)
         # the Tanh between two post-net modules runs forward in the producer's projection store and backward in
-        # the consumer's d(input) GEMM store (functional.rnnp_layer): `fold` = both ends agree on it
+        # the consumer's d(input) GEMM store (functional.rnnp_layer): `fold` = both ends agree on it.  A Tanh behind an
+        # ACTIVE dropout site (the `dropout<l>` container in training mode, p > 0) is one masked pass of its own instead
         prev_tanh = 0
+        dropouts = self._dropouts
         for l, birnn in enumerate(self._birnns):
             last = l == nb - 1
-            fold = (not last) and birnn.hdim % 4 == 0 and Fn.H.FOLD_TANH
+            site = None if last else dropouts[l]
+            fold = (not last) and birnn.hdim % 4 == 0 and Fn.H.FOLD_TANH and not birnn.site_p(site)
             if last and self.ts_vad is not False:
                 h = birnn.forward_rows(h, B * trials, T, in_tanh=prev_tanh)        # combined input
             else:
                 nxt_combined = (l == nb - 2) and self.ts_vad is not False
                 h = birnn.forward_rows(h, B * trials * K, T, final_act=0 if last else 1,
-                                       combine=K if nxt_combined else 0, in_tanh=prev_tanh, next_folds=fold)
+                                       combine=K if nxt_combined else 0, in_tanh=prev_tanh, next_folds=fold,
+                                       final_dropout=site)
                 prev_tanh = (K if nxt_combined else 1) if fold else 0
         Fr = F if self.output_resolution == "tf" else 1
         logit = Fn.head(h, self._linear, perm_d, iperm_d, B, K, T, F, trials, Fr,

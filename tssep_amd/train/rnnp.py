@@ -4,6 +4,10 @@ Same constructor, attribute names and ``state_dict`` keys (``net.0.weight_ih_l0`
 ``torch.nn.LSTM`` / ``Linear`` / ``Tanh`` members are kept as PARAMETER CONTAINERS so that
 initialisation order (torch.manual_seed parity) and checkpoints are interchangeable; their
 ``forward`` is never called -- the math runs in libtssep_hip.so.
+
+``dropout``: the ``torch.nn.Dropout`` members sit in front of a Tanh (rnnp.py:98-100).  One that is in training mode with
+p > 0 makes that Tanh a dropout site of the HIP path (functional._RNNP); its own ``.training`` / ``.p`` are read at every
+forward, so ``model.eval()`` and per-module switches behave as in the reference.
 """
 import torch
 
@@ -15,8 +19,8 @@ class RNNP_packed(torch.nn.Module):
         super().__init__()
         if typ != "blstm":
             raise NotImplementedError(f"typ={typ!r}: only 'blstm' is on the hot path (rnnp.py:40)")
-        if dropout != 0:
-            raise NotImplementedError("dropout > 0 (every shipped config uses 0)")
+        if dropout < 0 or dropout > 1:      # (torch.nn.Dropout's own check; a single layer builds no Dropout member)
+            raise ValueError(f"dropout probability has to be between 0 and 1, but got {dropout}")
         assert not return_states, return_states          # asserted off at rnnp.py:121
         bidir = True
         net = []
@@ -33,21 +37,32 @@ class RNNP_packed(torch.nn.Module):
         self.dropout, self.return_states = dropout, return_states
         self.hdim = hdim
 
-    def forward_rows(self, rows, N, T, final_act=0, combine=0, in_tanh=0, next_folds=False):
+    @staticmethod
+    def site_p(site):
+        """p of an ACTIVE dropout site (a torch.nn.Dropout in training mode with p > 0), else 0."""
+        return float(site.p) if site is not None and site.training and site.p > 0 else 0.0
+
+    def forward_rows(self, rows, N, T, final_act=0, combine=0, in_tanh=0, next_folds=False, final_dropout=None):
         """rows: [N*T, I] (rows (n,t)) -> [N*T, hdim]; ``final_act``/``combine`` fuse the Tanh
         that follows this module in the post-net and the speaker-combination rearrange.  ``in_tanh``: the
         rows are the output of such a fused Tanh of the module in front (K > 1: in its speaker-combined
         layout) -- its backward is folded into this module's first d(input) GEMM; ``next_folds``: the module
-        behind does the same for this module's final Tanh (functional.rnnp_layer)."""
+        behind does the same for this module's final Tanh (functional.rnnp_layer).  ``final_dropout``: the
+        ``torch.nn.Dropout`` container in front of that final Tanh (post-net, net.py:623-625), if there is one; a Tanh
+        behind an active site is not folded, so the caller passes ``next_folds`` False and the module behind ``in_tanh`` 0."""
         h = rows
+        p_prev = 0.0
         for i in range(self.elayers):
             lstm, lin = self.net[4 * i], self.net[4 * i + 1]
             last = i == self.elayers - 1
+            p_site = self.site_p(final_dropout if final_act == 1 else None) if last else self.site_p(self.net[4 * i + 2])
             fold_ok = self.hdim % 4 == 0 and Fn.H.FOLD_TANH
             h = Fn.rnnp_layer(h, lstm, lin, N, T, act=(final_act if last else 1),
                               combine=(combine if last else 0),
-                              in_tanh=(in_tanh if i == 0 else (1 if fold_ok else 0)),
-                              dz_given=((next_folds and final_act == 1) if last else fold_ok))
+                              in_tanh=(in_tanh if i == 0 else (1 if fold_ok and not p_prev else 0)),
+                              dz_given=((next_folds and final_act == 1) if last else fold_ok) and not p_site,
+                              dropout_p=p_site)
+            p_prev = p_site
         return h
 
     def forward(self, xs_pack, prev_state=None):

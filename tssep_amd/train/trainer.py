@@ -20,6 +20,18 @@ from .. import distributed as _dist
 from ..configurable import Configurable
 
 
+def rank_dropout_seed(seed, rank):
+    """The dropout seed of data-parallel rank `rank`, derived from the run's seed: rank 0 keeps it, every other rank
+    gets a splitmix64 mix of (seed, rank) -- a pure function, so a seeded run stays reproducible; 63 bits."""
+    if rank == 0:
+        return int(seed) & 0x7FFFFFFFFFFFFFFF
+    m = (1 << 64) - 1
+    z = (int(seed) + 0x9E3779B97F4A7C15 * int(rank)) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return (z ^ (z >> 31)) & 0x7FFFFFFFFFFFFFFF
+
+
 class _closing:
     """contextlib.closing for iterators that may not have ``close`` (lists, tuples)."""
 
@@ -142,9 +154,13 @@ class Trainer(Configurable):
         self.check_device_errors()
         self.checkpoint_dir.mkdir(parents=True, exist_ok=True)
         path = self.checkpoint_dir / f"ckpt_{self.iteration}.pth"
-        torch.save({"model": {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
-                    "optimizer": self.optimizer.state_dict(), "iteration": self.iteration,
-                    "epoch": self.epoch}, path)
+        sd = {"model": {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
+              "optimizer": self.optimizer.state_dict(), "iteration": self.iteration, "epoch": self.epoch}
+        dev = self._cuda_device()
+        if dev is not None:      # {seed, draw} of the dropout masks: a resumed run goes on where this one stopped
+            from .. import hip_ops
+            sd["dropout_state"] = list(hip_ops.get_state(dev))
+        torch.save(sd, path)
         links = ["ckpt_latest.pth"]
         if val_loss == val_loss and val_loss <= self.best_loss:
             self.best_loss = val_loss
@@ -155,6 +171,10 @@ class Trainer(Configurable):
                 link.unlink()
             os.symlink(path.name, link)
         return path
+
+    def _cuda_device(self):
+        p = next(self.model.parameters(), None)
+        return p.device if p is not None and p.is_cuda else None
 
     def _chief_checkpoint(self, do_it):
         """Rank 0 validates and writes the checkpoint; EVERY rank calls this and leaves it together
@@ -176,6 +196,10 @@ class Trainer(Configurable):
         if "optimizer" in sd and self.optimizer.bucket is not None:
             self.optimizer.load_state_dict(sd["optimizer"])
         self.iteration, self.epoch = sd.get("iteration", 0), sd.get("epoch", 0)
+        dev = self._cuda_device()
+        if sd.get("dropout_state") is not None and dev is not None:      # (absent in older checkpoints)
+            from .. import hip_ops
+            hip_ops.set_state(tuple(sd["dropout_state"]), dev)
 
     def train(self, train_dataset, resume=False, device=0, **_):
         self.model.to(torch.device("cuda", device) if isinstance(device, int) else device)
@@ -191,6 +215,11 @@ class Trainer(Configurable):
             for t in (self.optimizer.flat_param, self.optimizer.exp_avg, self.optimizer.exp_avg_sq):
                 _dist.broadcast_(t, src=0)
             np.random.seed((int(np.random.get_state()[1][0]) + 7919 * rank) & 0x7FFFFFFF)
+            dev = self._cuda_device()
+            if dev is not None:      # dropout masks of its own per rank, likewise
+                from .. import hip_ops
+                seed, draw = hip_ops.get_state(dev)
+                hip_ops.set_state((rank_dropout_seed(seed, rank), draw), dev)
         chief = rank == 0
         # hipGraph replay of forward + loss + backward (train/graph.py) for launch-bound micro-steps: policy
         # runtime.graph_step = "auto" (batches of at most runtime.graph_max_utterances utterances: 8 x 4 s run 6.9 instead
