@@ -281,7 +281,10 @@ int tssep_lstm_pack(const float* w_ih_f, const float* w_hh_f, const float* b_ih_
                     const float* b_ih_r, const float* b_hh_r, int H, int I, int64_t ld_i,
                     float* wih_p, float* bias_p, float* whh_f, float* whh_b, void* stream);
 /* gates [N,T,2,H,4]: in = pre-activations from the input GEMM; out = activated gates
- * (kept for backward).  cell [N,T,2,H]; hout [N,T,ldo] (cols d*dstride+u).  H <= 512 (round 4; the
+ * (kept for backward).  cell [N,T,2,H]; hout [N,T,ldo] (cols d*dstride+u).  Columns of hout / dhout
+ * outside d*dstride .. d*dstride+H-1 (dstride > H, ldo > dstride + H) are never written and never read by
+ * any recurrence kernel, streaming or W-stationary: a caller whose next GEMM reads them zeroes them once
+ * (tests/test_gpu_recurrence_kernels.py holds every kernel to this).  H <= 512 (round 4; the
  * W-stationary families below cover H <= 320 / 304, which is where the reference's configs live). */
 int tssep_blstm_fwd(float* gates, float* cell, float* hout, int64_t ldo, int64_t dstride,
                     const float* whh_f, int64_t N, int64_t T, int H, void* stream);
