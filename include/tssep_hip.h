@@ -536,6 +536,38 @@ int tssep_mvdr_souden_fwd(const double* obs, const void* masks, int mask_f64, do
                           int F, int reference_channel, double eps, int masking,
                           double masking_eps, void* stream);
 
+/* Segment-wise MVDR: ClassicBF_np('mvdr_souden') of the reference with segment_bf=True,
+ * tssep/train/enhancer.py:451-590, one beamformer per row (k, s, e) of a segment table:
+ *   n_k         = max(sum_{j != k} m_j, distortion_eps)   mode 0, SumCrossTalker (ascending j,
+ *                                                          in the mask's dtype)
+ *               = max(1 - m_k, 0)                          mode 1, OneMinus (K == 1 only)
+ *   psd_0|1     = sum_{t in [s,e)} (m_k | n_k)**mask_power Y[:,t,f] Y[:,t,f]^H / (e - s)
+ *                 psd_real != 0: only the real part is kept -- what _get_psd's
+ *                 (psd + swapaxes(psd, -2, -1)) / 2 (:288) does; 0: the Hermitian matrix
+ *   bf          = phi[:, 0] / max(Re trace(phi), eps),  phi = psd_1^-1 psd_0   (as above)
+ *   enh[k,t,f]  = sum_d conj(bf_d) Y[d,t,f]  (* max(m_k, masking_eps) if masking),  t in [s,e)
+ *               = 0 at every (k, t) that no row of the table covers (written by the kernel).
+ * obs [D,T,F] complex128, D <= 8;  masks [K,1,T,F] fp32 | fp64;  enh [K,T,F] complex128
+ * segments [S,3] int32 on the device; the intervals of one speaker are disjoint (the host mirror
+ *   checks it); a row with k outside [0,K) or an empty interval is ignored.
+ * distortion_eps and masking_eps are compared in the mask's dtype (rounded to fp32 for fp32 masks).
+ * info [S] device ints: the number of bins of segment i whose system had an exactly zero pivot.
+ * A constant number of launches whatever S is, no host sync; workspace (16-byte aligned):
+ * tssep_mvdr_segments_workspace_bytes(), host-only, 0 for an unsupported shape (D > 8 ...).
+ * _segments_psd runs the statistics stage alone and leaves both PSDs at the start of the
+ * workspace as doubles [S][2: target, distortion][D*D][F]: element rows 0..D-1 the diagonal, then
+ * for every pair i < j in row-major order the rows Re psd[i,j], Im psd[i,j]. */
+int64_t tssep_mvdr_segments_workspace_bytes(int K, int S, int D, int64_t T, int F);
+int tssep_mvdr_segments_psd(const double* obs, const void* masks, int mask_f64,
+                            const int32_t* segments, void* workspace, int K, int S, int D,
+                            int64_t T, int F, int mode, double distortion_eps, double mask_power,
+                            int psd_real, void* stream);
+int tssep_mvdr_segments_fwd(const double* obs, const void* masks, int mask_f64,
+                            const int32_t* segments, double* enh, void* workspace, int* info, int K,
+                            int S, int D, int64_t T, int F, int mode, double distortion_eps,
+                            double mask_power, int psd_real, double eps, int masking,
+                            double masking_eps, void* stream);
+
 /* -------------------------------------------------------------- optimizer -----
  * One optimizer step on flat fp32 buffers: global-norm gradient clipping
  * (torch.nn.utils.clip_grad_norm_, max_norm <= 0 disables) + Adam (torch.optim.Adam update rule,

@@ -1,6 +1,8 @@
 """Microbenchmark of the mask-based MVDR beamformer (TorchBF) on one MI355X:
 HIP-event time of the whole pipeline and of each stage vs the algorithmic HBM bytes, and the CPU
-oracle beside it on a frequency slice.  One JSON line per configuration."""
+oracle beside it on a frequency slice.  One JSON line per configuration.  The last line is the segment-wise
+pipeline (ClassicBF_np, hip_ops.segment_mvdr) against the way to the same output without it: a loop of
+hip_ops.mvdr_souden over time slices with host-built two-plane masks (--only-segments: that line alone)."""
 import argparse
 import json
 import os
@@ -29,12 +31,74 @@ def ev_ms(fn, iters):
     return a.elapsed_time(b) / iters
 
 
+def wall_ms(fn, iters):
+    """median wall-clock time of fn (which may synchronise inside), device idle at both ends"""
+    fn()
+    times = []
+    for _ in range(iters):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(times))
+
+
+def segmented(args, L):
+    """8 speakers x 30 s x 6 channels, F = 513, a seeded diarization of about 10 intervals per speaker."""
+    K, D, T, F = 8, 6, 1878, 513
+    g = torch.Generator().manual_seed(0)
+    Y = torch.randn(D, T, F, dtype=torch.complex128, generator=g).cuda()
+    m = torch.rand(K, 1, T, F, generator=g).cuda()
+    rs = np.random.RandomState(0)
+    segments = []
+    for k in range(K):
+        t = int(rs.randint(0, 40))
+        for _ in range(10):
+            n = int(rs.randint(60, 170))
+            if t + n > T:
+                break
+            segments.append((k, t, t + n))
+            t += n + int(rs.randint(5, 60))
+    S = len(segments)
+    table = H.segment_table(segments, "cuda")
+
+    def one_call():
+        return H.segment_mvdr(m, Y, table, distortion_eps=1e-4, psd_real=False)
+
+    def loop():
+        # SumCrossTalker with torch ops, then one whole-utterance beamformer per slice (one .item() each)
+        dist = torch.stack([torch.clamp(sum(m[j, 0] for j in range(K) if j != k), min=1e-4) for k in range(K)])
+        out = torch.zeros(K, T, F, dtype=torch.complex128, device="cuda")
+        for k, s, e in segments:
+            two = torch.stack([m[k, 0, s:e], dist[k, s:e]])[None, None]
+            out[k, s:e] = H.mvdr_souden(two, Y[None, :, s:e], 0)[0, 0]
+        return out
+
+    a, b = one_call(), loop()
+    err = float((a - b).abs().max() / b.abs().max())
+    t_new, t_loop = wall_ms(one_call, args.iters), wall_ms(loop, max(3, args.iters // 4))
+    # library launches only (kernels + the info memset); the loop's torch ops come on top of its count
+    per_slice = [3 + 1 + (L.tssep_mvdr_partial_bytes(1, 1, D, e - s, F) > 8 * 2 * D * D * F) for _, s, e in segments]
+    print(json.dumps({"config": "segment-wise: 8 spk, 6 ch, 30 s", "K": K, "D": D, "T": T, "F": F, "segments": S,
+                      "frames_in_segments": int(sum(e - s for _, s, e in segments)),
+                      "segment_mvdr_ms": round(t_new, 4), "sliced_loop_ms": round(t_loop, 4),
+                      "loop_over_segment_mvdr": round(t_loop / t_new, 2), "segment_mvdr_launches": 6,
+                      "sliced_loop_library_launches": int(sum(per_slice)), "segment_mvdr_host_syncs": 1,
+                      "sliced_loop_host_syncs": S, "max_rel_diff": err,
+                      "workspace_bytes": L.tssep_mvdr_segments_workspace_bytes(K, S, D, T, F)}), flush=True)
+    assert t_new <= t_loop, "segment_mvdr is slower than the loop it replaces"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--only-segments", action="store_true")
     args = ap.parse_args()
     L = _lib.lib()
+    if args.only_segments:
+        return segmented(args, L)
     for name, (B, K, M, D, T, F) in {
             "cfg3 eval: 4 spk, 6 ch, 4 s": (1, 4, 2, 6, 253, 513),
             "cfg5 eval: 8 spk, 6 ch, 30 s": (1, 8, 2, 6, 1878, 513),
@@ -86,6 +150,7 @@ def main():
             row["cpu_sample"] = f"{fs} of {F} bins, numpy complex128, scaled to {F}"
             row["max_rel_err_vs_oracle"] = float(np.abs(got - want).max() / np.abs(want).max())
         print(json.dumps(row), flush=True)
+    segmented(args, L)
 
 
 if __name__ == "__main__":

@@ -19,6 +19,9 @@
 //      mvdr_weights_kernel    with the D x D systems in LDS ([element][lane]) for D = 7, 8.
 //   3. mvdr_apply_kernel<D>   one wave per (64 bins, time chunk, up to 4 speakers): Y read once
 //                             for the speakers of a group.
+// The segment-wise pipeline of ClassicBF_np (one beamformer per activity interval of a speaker, the
+// distortion mask taken from the other speakers' masks) is at the end of this file; it shares the
+// solve kernels.
 #include "common.h"
 
 namespace {
@@ -229,7 +232,7 @@ __global__ __launch_bounds__(256) void mvdr_reduce_kernel(double* __restrict__ p
 template <int D>
 __global__ __launch_bounds__(64) void mvdr_solve_kernel(
     const double* __restrict__ part, double2* __restrict__ wconj, int* __restrict__ info,
-    int64_t B, int K, int F, int chunks, int ref, double eps) {
+    int64_t B, int K, int F, int chunks, int ref, double eps, int info_per_k) {
   const int nf = (F + 63) / 64;
   const int ft = blockIdx.x % nf;
   const int k = (blockIdx.x / nf) % K;
@@ -314,7 +317,7 @@ __global__ __launch_bounds__(64) void mvdr_solve_kernel(
       X[i][j] = cmul(s, r);
     }
   }
-  if (singular) atomicAdd(info, 1);
+  if (singular) atomicAdd(info + k * info_per_k, 1);
   double lam = 0.0;
 #pragma unroll
   for (int i = 0; i < D; ++i) lam += X[i][i].x;
@@ -332,7 +335,7 @@ __global__ __launch_bounds__(64) void mvdr_solve_kernel(
 // General (D <= 8) solve with the systems in LDS; chunk partials already reduced (chunk 0).
 __global__ __launch_bounds__(64) void mvdr_weights_kernel(
     const double* __restrict__ part, double2* __restrict__ wconj, int* __restrict__ info,
-    int64_t B, int K, int D, int F, int chunks, int ref, double eps) {
+    int64_t B, int K, int D, int F, int chunks, int ref, double eps, int info_per_k) {
   extern __shared__ double2 sm[];
   const int lane = threadIdx.x;
   const int nf = (F + 63) / 64;
@@ -401,7 +404,7 @@ __global__ __launch_bounds__(64) void mvdr_weights_kernel(
       B_(i, j) = cmul(s, r);
     }
   }
-  if (singular) atomicAdd(info, 1);
+  if (singular) atomicAdd(info + k * info_per_k, 1);
   double lam = 0.0;
   for (int i = 0; i < D; ++i) lam += B_(i, i).x;
   if (lam < eps) lam = eps;                       // clamp(min=eps); NaN stays NaN
@@ -542,9 +545,37 @@ extern "C" int tssep_mvdr_psd(const double* obs, const void* masks, int mask_f64
 
 template <int D>
 int launch_solve(const double* part, double* wconj, int* info, int64_t B, int K, int F, int nf,
-                 int chunks, int ref, double eps, hipStream_t s) {
+                 int chunks, int ref, double eps, hipStream_t s, int info_per_k = 0) {
   hipLaunchKernelGGL(mvdr_solve_kernel<D>, dim3((unsigned)(B * K * nf)), dim3(64), 0, s, part,
-                     reinterpret_cast<double2*>(wconj), info, B, K, F, chunks, ref, eps);
+                     reinterpret_cast<double2*>(wconj), info, B, K, F, chunks, ref, eps, info_per_k);
+  return tssep_launch_status();
+}
+
+// The per-bin solve of K systems per batch element out of (reduced) chunk 0 of `part`: in registers
+// for D <= 6, in LDS for D = 7, 8.  info_per_k = 0: one counter of singular systems; 1: one per k.
+static int solve_systems(const double* part, double* wconj, int* info, int64_t B, int K, int D, int F,
+                  int nf, int chunks, int ref, double eps, int info_per_k, hipStream_t s) {
+  switch (D) {
+    case 1: return launch_solve<1>(part, wconj, info, B, K, F, nf, chunks, ref, eps, s, info_per_k);
+    case 2: return launch_solve<2>(part, wconj, info, B, K, F, nf, chunks, ref, eps, s, info_per_k);
+    case 3: return launch_solve<3>(part, wconj, info, B, K, F, nf, chunks, ref, eps, s, info_per_k);
+    case 4: return launch_solve<4>(part, wconj, info, B, K, F, nf, chunks, ref, eps, s, info_per_k);
+    case 5: return launch_solve<5>(part, wconj, info, B, K, F, nf, chunks, ref, eps, s, info_per_k);
+    case 6: return launch_solve<6>(part, wconj, info, B, K, F, nf, chunks, ref, eps, s, info_per_k);
+    default: break;
+  }
+  const size_t lds = (size_t)2 * D * D * 64 * sizeof(double2);
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mvdr_weights_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            2 * MAXD * MAXD * 64 * (int)sizeof(double2)) != hipSuccess)
+      return TSSEP_E_LAUNCH;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(mvdr_weights_kernel, dim3((unsigned)(B * K * nf)), dim3(64), lds, s, part,
+                     reinterpret_cast<double2*>(wconj), info, B, K, D, F, chunks, ref, eps,
+                     info_per_k);
   return tssep_launch_status();
 }
 
@@ -564,28 +595,7 @@ extern "C" int tssep_mvdr_weights(double* partials, double* wconj, int* info, in
     hipLaunchKernelGGL(mvdr_reduce_kernel, dim3((unsigned)((rows * F + 255) / 256)), dim3(256), 0, s,
                        partials, rows, F, p.chunks, (int64_t)K * 2 * D * D * F);
   }
-  switch (D) {
-    case 1: return launch_solve<1>(partials, wconj, info, B, K, F, p.nf, p.chunks, reference_channel, eps, s);
-    case 2: return launch_solve<2>(partials, wconj, info, B, K, F, p.nf, p.chunks, reference_channel, eps, s);
-    case 3: return launch_solve<3>(partials, wconj, info, B, K, F, p.nf, p.chunks, reference_channel, eps, s);
-    case 4: return launch_solve<4>(partials, wconj, info, B, K, F, p.nf, p.chunks, reference_channel, eps, s);
-    case 5: return launch_solve<5>(partials, wconj, info, B, K, F, p.nf, p.chunks, reference_channel, eps, s);
-    case 6: return launch_solve<6>(partials, wconj, info, B, K, F, p.nf, p.chunks, reference_channel, eps, s);
-    default: break;
-  }
-  const size_t lds = (size_t)2 * D * D * 64 * sizeof(double2);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mvdr_weights_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            2 * MAXD * MAXD * 64 * (int)sizeof(double2)) != hipSuccess)
-      return TSSEP_E_LAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(mvdr_weights_kernel, dim3((unsigned)(B * K * p.nf)), dim3(64), lds, s, partials,
-                     reinterpret_cast<double2*>(wconj), info, B, K, D, F, p.chunks,
-                     reference_channel, eps);
-  return tssep_launch_status();
+  return solve_systems(partials, wconj, info, B, K, D, F, p.nf, p.chunks, reference_channel, eps, 0, s);
 }
 
 extern "C" int tssep_mvdr_apply(const double* obs, const double* wconj, const void* masks,
@@ -623,4 +633,326 @@ extern "C" int tssep_mvdr_souden_fwd(const double* obs, const void* masks, int m
   if (st != TSSEP_OK) return st;
   return tssep_mvdr_apply(obs, wconj, masks, mask_f64, enh, B, K, M, D, T, F, masking, masking_eps,
                           stream);
+}
+
+// ------------------------------------------------------------------ segment-wise MVDR ----
+// ClassicBF_np.__call__ with segment_bf=True (tssep/train/enhancer.py:451-590): for every row
+// (k, s, e) of a device segment table one Souden MVDR from the statistics of frames [s, e) only,
+//   target weight      m_k ** mask_power
+//   distortion weight  n_k ** mask_power,  n_k = max(sum_{j != k} m_j, eps)   (SumCrossTalker)
+//                                          n_k = max(1 - m_k, 0)              (OneMinus)
+//   psd = sum_t w Y Y^H / (e - s)   [real part only with psd_real: _get_psd, :281-288]
+// applied to [s, e); every other (k, t) of the output is written as zero.  The distortion mask is
+// formed in the mask's own dtype inside the statistics pass and never stored.  A constant number
+// of launches whatever the table holds:
+//   seg_map_kernel        (k, t) -> covering segment or -1, one thread per (k, t)
+//   seg_psd_kernel<D,MT>  one wave per (64 bins, segment, one of C slices of the segment): both
+//                         Hermitian accumulators per lane, slice partials to the workspace
+//   seg_finalize_kernel   slice partials -> slice 0 in a fixed order, / (e - s), psd_real
+//   mvdr_solve_kernel<D> / mvdr_weights_kernel   with "speakers" = segments, one info slot each
+//   seg_apply_kernel<D>   one wave per (64 bins, time chunk, speaker); weights reloaded when the
+//                         covering segment changes
+// A row with k outside [0, K) or an empty [s, e) after clamping to [0, T] takes part in nothing
+// but its own (zero) statistics: no access leaves the buffers whatever the table holds.
+namespace {
+
+struct Seg { int k, s, e; };
+__device__ __forceinline__ Seg load_seg(const int32_t* __restrict__ tab, int i, int K, int64_t T) {
+  Seg g{tab[3 * i], tab[3 * i + 1], tab[3 * i + 2]};
+  if (g.s < 0) g.s = 0;
+  if (g.e > (int)T) g.e = (int)T;
+  if (g.k < 0 || g.k >= K || g.e < g.s) { g.k = 0; g.e = g.s = 0; }
+  return g;
+}
+
+__host__ int seg_chunks(int S, int F) {
+  const int64_t waves = (int64_t)S * ((F + 63) / 64);
+  int64_t c = (4096 + waves - 1) / waves;
+  return (int)(c < 1 ? 1 : c > 16 ? 16 : c);
+}
+
+__global__ __launch_bounds__(256) void seg_map_kernel(const int32_t* __restrict__ tab,
+                                                      int32_t* __restrict__ map, int K, int S,
+                                                      int64_t T) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= K * T) return;
+  const int k = (int)(i / T), t = (int)(i - k * T);
+  int hit = -1;
+  for (int j = 0; j < S; ++j) {
+    const int kk = tab[3 * j], s = tab[3 * j + 1], e = tab[3 * j + 2];
+    if (kk == k && s <= t && t < e) hit = j;
+  }
+  map[i] = hit;
+}
+
+template <typename MT> __device__ __forceinline__ MT mask_pow(MT x, int ipow, double p) {
+  if (ipow == 1) return x;
+  if (ipow == 2) return x * x;
+  return (MT)pow((double)x, p);
+}
+template <> __device__ __forceinline__ float mask_pow<float>(float x, int ipow, double p) {
+  if (ipow == 1) return x;
+  if (ipow == 2) return x * x;
+  return powf(x, (float)p);
+}
+
+template <int D, typename MT>
+__global__ __launch_bounds__(64, D <= 6 ? 2 : 1) void seg_psd_kernel(
+    const double2* __restrict__ obs, const MT* __restrict__ masks, const int32_t* __restrict__ tab,
+    double* __restrict__ part, int K, int S, int64_t T, int F, int nf, int C, int mode,
+    double dist_eps, int ipow, double mask_power) {
+  const int ft = blockIdx.x % nf;
+  const int c = (blockIdx.x / nf) % C;
+  const int sg = blockIdx.x / (nf * C);
+  const Seg g = load_seg(tab, sg, K, T);
+  const int lane = threadIdx.x;
+  const int fraw = ft * 64 + lane;
+  const int f = fraw < F ? fraw : F - 1;
+  const int per = (g.e - g.s + C - 1) / C;
+  const int t0 = g.s + c * per;
+  const int t1 = t0 + per < g.e ? t0 + per : g.e;
+  const MT deps = (MT)dist_eps;
+
+  double diag[2][D];
+  double2 off[2][D * (D - 1) / 2 + 1];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+#pragma unroll
+    for (int i = 0; i < D; ++i) diag[m][i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < D * (D - 1) / 2; ++i) off[m][i] = double2{0.0, 0.0};
+  }
+#pragma unroll 1
+  for (int t = t0; t < t1; ++t) {
+    double2 y[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) y[d] = obs[((int64_t)d * T + t) * F + f];
+    const MT* mrow = masks + (int64_t)t * F + f;
+    const MT tgt = mrow[(int64_t)g.k * T * F];
+    MT dist;
+    if (mode == 0) {
+      // np.sum(np.delete(masks, k, axis=1), axis=1): ascending j without k, in the mask's dtype
+      dist = (MT)0;
+      for (int j = 0; j < K; ++j)
+        if (j != g.k) dist += mrow[(int64_t)j * T * F];
+      dist = dist > deps ? dist : deps;
+    } else {
+      dist = (MT)1 - tgt;
+      dist = dist > (MT)0 ? dist : (MT)0;
+    }
+    const double w0 = (double)mask_pow<MT>(tgt, ipow, mask_power);
+    const double w1 = (double)mask_pow<MT>(dist, ipow, mask_power);
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const double pd = y[i].x * y[i].x + y[i].y * y[i].y;
+      diag[0][i] += w0 * pd;
+      diag[1][i] += w1 * pd;
+#pragma unroll
+      for (int j = i + 1; j < D; ++j, ++p) {
+        const double pr = y[i].x * y[j].x + y[i].y * y[j].y;
+        const double pi = y[i].y * y[j].x - y[i].x * y[j].y;
+        off[0][p].x += w0 * pr;
+        off[0][p].y += w0 * pi;
+        off[1][p].x += w1 * pr;
+        off[1][p].y += w1 * pi;
+      }
+    }
+  }
+  if (fraw >= F) return;
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    double* out = part + ((((int64_t)c * S + sg) * 2 + m) * (int64_t)(D * D)) * F + f;
+#pragma unroll
+    for (int i = 0; i < D; ++i) out[(int64_t)i * F] = diag[m][i];
+#pragma unroll
+    for (int p = 0; p < D * (D - 1) / 2; ++p) {
+      out[(int64_t)(D + 2 * p) * F] = off[m][p].x;
+      out[(int64_t)(D + 2 * p + 1) * F] = off[m][p].y;
+    }
+  }
+}
+
+// slice partials -> slice 0, scaled by 1 / (e - s) the way numpy divides complex by real; with
+// psd_real the imaginary slots become zero: (psd + swapaxes(psd, -2, -1)) / 2 of a Hermitian
+// matrix is its real part (enhancer.py:288)
+__global__ __launch_bounds__(256) void seg_finalize_kernel(double* __restrict__ part,
+                                                           const int32_t* __restrict__ tab, int K,
+                                                           int S, int D, int64_t T, int F, int C,
+                                                           int psd_real) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t per_seg = (int64_t)2 * D * D * F;
+  if (i >= S * per_seg) return;
+  const int sg = (int)(i / per_seg);
+  const int el = (int)((i - sg * per_seg) / F) % (D * D);
+  const Seg g = load_seg(tab, sg, K, T);
+  double s = part[i];
+  for (int c = 1; c < C; ++c) s += part[c * S * per_seg + i];
+  const int len = g.e - g.s;
+  s = len > 0 ? s * (1.0 / (double)len) : 0.0;
+  if (psd_real && el >= D && ((el - D) & 1)) s = 0.0;
+  part[i] = s;
+}
+
+template <int D, typename MT>
+__global__ __launch_bounds__(64) void seg_apply_kernel(
+    const double2* __restrict__ obs, const double2* __restrict__ wconj,
+    const int32_t* __restrict__ map, const MT* __restrict__ masks, double2* __restrict__ enh, int K,
+    int64_t T, int F, int nf, int achunks, int tchunk, int masking, double masking_eps) {
+  // speaker fastest: the waves that read the same Y tile are neighbours in launch order
+  const int k = blockIdx.x % K;
+  const int ft = (blockIdx.x / K) % nf;
+  const int c = blockIdx.x / (K * nf);
+  const int f = ft * 64 + threadIdx.x;
+  if (f >= F) return;
+  const int t0 = c * tchunk;
+  const int t1 = (int64_t)t0 + tchunk < T ? t0 + tchunk : (int)T;
+  const MT meps = (MT)masking_eps;
+  double2 w[D];
+  int cur = -1;
+  for (int t = t0; t < t1; ++t) {
+    const int sg = __builtin_amdgcn_readfirstlane(map[(int64_t)k * T + t]);
+    double2 e = {0.0, 0.0};
+    if (sg >= 0) {
+      if (sg != cur) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) w[d] = wconj[((int64_t)sg * D + d) * F + f];
+        cur = sg;
+      }
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        const double2 y = obs[((int64_t)d * T + t) * F + f];
+        e.x += w[d].x * y.x - w[d].y * y.y;
+        e.y += w[d].x * y.y + w[d].y * y.x;
+      }
+      if (masking) {
+        MT mk = masks[((int64_t)k * T + t) * F + f];
+        mk = mk > meps ? mk : meps;
+        e.x *= (double)mk;
+        e.y *= (double)mk;
+      }
+    }
+    enh[((int64_t)k * T + t) * F + f] = e;
+  }
+}
+
+bool seg_shape_ok(int K, int S, int D, int64_t T, int F) {
+  return K > 0 && S > 0 && D > 0 && T > 0 && F > 0 && T < ((int64_t)1 << 30) &&
+         (int64_t)K * T < ((int64_t)1 << 31) && (int64_t)S * ((F + 63) / 64) * 16 < ((int64_t)1 << 30) &&
+         (int64_t)S * 2 * D * D * F < ((int64_t)1 << 36);
+}
+int64_t seg_part_bytes(int S, int D, int F) {
+  return (int64_t)seg_chunks(S, F) * S * 2 * D * D * F * (int64_t)sizeof(double);
+}
+
+template <int D>
+int launch_seg_psd(const double* obs, const void* masks, int mask_f64, const int32_t* tab,
+                   double* part, int K, int S, int64_t T, int F, int mode, double dist_eps,
+                   double mask_power, hipStream_t s) {
+  const int nf = (F + 63) / 64, C = seg_chunks(S, F);
+  const int ipow = mask_power == 1.0 ? 1 : mask_power == 2.0 ? 2 : 0;
+  const dim3 grid((unsigned)((int64_t)S * C * nf));
+  if (mask_f64)
+    hipLaunchKernelGGL((seg_psd_kernel<D, double>), grid, dim3(64), 0, s,
+                       reinterpret_cast<const double2*>(obs), static_cast<const double*>(masks), tab,
+                       part, K, S, T, F, nf, C, mode, dist_eps, ipow, mask_power);
+  else
+    hipLaunchKernelGGL((seg_psd_kernel<D, float>), grid, dim3(64), 0, s,
+                       reinterpret_cast<const double2*>(obs), static_cast<const float*>(masks), tab,
+                       part, K, S, T, F, nf, C, mode, dist_eps, ipow, mask_power);
+  return tssep_launch_status();
+}
+
+template <int D>
+int launch_seg_apply(const double* obs, const double* wconj, const int32_t* map, const void* masks,
+                     int mask_f64, double* enh, int K, int64_t T, int F, int masking,
+                     double masking_eps, hipStream_t s) {
+  const int nf = (F + 63) / 64;
+  int64_t c = (4096 + (int64_t)nf * K - 1) / ((int64_t)nf * K);
+  const int64_t cmax = (T + 15) / 16;
+  if (c > cmax) c = cmax;
+  if (c < 1) c = 1;
+  const int tchunk = (int)((T + c - 1) / c);
+  const int achunks = (int)((T + tchunk - 1) / tchunk);
+  const dim3 grid((unsigned)((int64_t)achunks * nf * K));
+  if (mask_f64)
+    hipLaunchKernelGGL((seg_apply_kernel<D, double>), grid, dim3(64), 0, s,
+                       reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(wconj),
+                       map, static_cast<const double*>(masks), reinterpret_cast<double2*>(enh), K, T,
+                       F, nf, achunks, tchunk, masking, masking_eps);
+  else
+    hipLaunchKernelGGL((seg_apply_kernel<D, float>), grid, dim3(64), 0, s,
+                       reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(wconj),
+                       map, static_cast<const float*>(masks), reinterpret_cast<double2*>(enh), K, T,
+                       F, nf, achunks, tchunk, masking, masking_eps);
+  return tssep_launch_status();
+}
+
+}  // namespace
+
+extern "C" int64_t tssep_mvdr_segments_workspace_bytes(int K, int S, int D, int64_t T, int F) {
+  if (D > MAXD || !seg_shape_ok(K, S, D, T, F)) return 0;
+  const int64_t pb = (seg_part_bytes(S, D, F) + 15) / 16 * 16;
+  return pb + (int64_t)S * D * F * 16 + ((int64_t)K * T * 4 + 15) / 16 * 16;
+}
+
+extern "C" int tssep_mvdr_segments_psd(const double* obs, const void* masks, int mask_f64,
+                                       const int32_t* segments, void* workspace, int K, int S, int D,
+                                       int64_t T, int F, int mode, double distortion_eps,
+                                       double mask_power, int psd_real, void* stream) {
+  if (!obs || !masks || !segments || !workspace) return TSSEP_E_NULL;
+  if (!seg_shape_ok(K, S, D, T, F) || (mode != 0 && mode != 1) || !(mask_power > 0.0))
+    return TSSEP_E_SHAPE;
+  if (D > MAXD || (mode == 1 && K != 1)) return TSSEP_E_UNSUPPORTED;
+  if (!aligned16(obs) || !aligned16(workspace)) return TSSEP_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  double* part = static_cast<double*>(workspace);
+#define CALL(DD) \
+  launch_seg_psd<DD>(obs, masks, mask_f64, segments, part, K, S, T, F, mode, distortion_eps, mask_power, s)
+  int st;
+  switch (D) {
+    case 1: st = CALL(1); break;
+    case 2: st = CALL(2); break;
+    case 3: st = CALL(3); break;
+    case 4: st = CALL(4); break;
+    case 5: st = CALL(5); break;
+    case 6: st = CALL(6); break;
+    case 7: st = CALL(7); break;
+    default: st = CALL(8); break;
+  }
+#undef CALL
+  if (st != TSSEP_OK) return st;
+  const int64_t n = (int64_t)S * 2 * D * D * F;
+  hipLaunchKernelGGL(seg_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part,
+                     segments, K, S, D, T, F, seg_chunks(S, F), psd_real);
+  return tssep_launch_status();
+}
+
+extern "C" int tssep_mvdr_segments_fwd(const double* obs, const void* masks, int mask_f64,
+                                       const int32_t* segments, double* enh, void* workspace,
+                                       int* info, int K, int S, int D, int64_t T, int F, int mode,
+                                       double distortion_eps, double mask_power, int psd_real,
+                                       double eps, int masking, double masking_eps, void* stream) {
+  if (!enh || !info) return TSSEP_E_NULL;
+  if (!aligned16(enh)) return TSSEP_E_ALIGN;
+  int st = tssep_mvdr_segments_psd(obs, masks, mask_f64, segments, workspace, K, S, D, T, F, mode,
+                                   distortion_eps, mask_power, psd_real, stream);
+  if (st != TSSEP_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t pb = (seg_part_bytes(S, D, F) + 15) / 16 * 16;
+  double* part = static_cast<double*>(workspace);
+  double* wconj = reinterpret_cast<double*>(static_cast<char*>(workspace) + pb);
+  int32_t* map = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + pb + (int64_t)S * D * F * 16);
+  if (hipMemsetAsync(info, 0, sizeof(int) * (size_t)S, s) != hipSuccess) return TSSEP_E_LAUNCH;
+  hipLaunchKernelGGL(seg_map_kernel, dim3((unsigned)(((int64_t)K * T + 255) / 256)), dim3(256), 0, s,
+                     segments, map, K, S, T);
+  st = tssep_launch_status();
+  if (st != TSSEP_OK) return st;
+  // reference channel 0 (bf_kwargs, enhancer.py:497-506); the segments stand where the speakers do
+  st = solve_systems(part, wconj, info, 1, S, D, F, (F + 63) / 64, 1, 0, eps, 1, s);
+  if (st != TSSEP_OK) return st;
+#define CALL(DD) \
+  launch_seg_apply<DD>(obs, wconj, map, masks, mask_f64, enh, K, T, F, masking, masking_eps, s)
+  DISPATCH_D(D, CALL)
+#undef CALL
 }

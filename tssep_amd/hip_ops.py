@@ -1259,6 +1259,100 @@ def mvdr_souden(masks, obs, reference_channel, eps=None, masking=False, masking_
     return torch.view_as_complex(enh)
 
 
+DISTORTION_MODES = {"sum_cross_talker": 0, "one_minus": 1}
+
+
+def segment_table(segments, device):
+    """[(k, s, e), ...] or an int tensor [S,3] -> int32 [S,3] on `device` (a device tensor of that
+    form passes through untouched: nothing is copied, the call stays capturable)."""
+    if isinstance(segments, torch.Tensor):
+        tab = segments
+    else:
+        tab = torch.tensor([tuple(int(v) for v in row) for row in segments], dtype=torch.int32).reshape(-1, 3)
+    assert tab.dim() == 2 and tab.shape[1] == 3, tab.shape
+    return tab.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _segment_args(masks, obs, segments):
+    assert masks.is_cuda and obs.is_cuda, (masks.device, obs.device)
+    assert obs.dtype == torch.complex128, obs.dtype
+    if masks.dtype not in (torch.float32, torch.float64):
+        masks = masks.to(torch.float64)
+    K, M, T, F = masks.shape
+    D, To, Fo = obs.shape
+    assert (T, F) == (To, Fo), (masks.shape, obs.shape)
+    if M != 1:
+        raise NotImplementedError(f"segment_mvdr: masks {tuple(masks.shape)}: one mask per speaker (M = 1), the "
+                                  f"distortion mask comes from the other speakers' masks")
+    tab = segment_table(segments, obs.device)
+    S = tab.shape[0]
+    assert S > 0, "segment_mvdr: empty segment table"
+    ws_bytes = _lib.lib().tssep_mvdr_segments_workspace_bytes(K, S, D, T, F)
+    if ws_bytes <= 0:
+        raise RuntimeError(f"segment_mvdr: unsupported shape masks {tuple(masks.shape)} obs {tuple(obs.shape)} "
+                           f"with {S} segments (at most 8 channels)")
+    ws = torch.empty(ws_bytes // 8 + 2, device=obs.device, dtype=torch.float64)
+    return masks.contiguous(), torch.view_as_real(obs.contiguous()), tab, ws, (K, S, D, T, F)
+
+
+def segment_psd(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1e-4, mask_power=1,
+                psd_real=True):
+    """The statistics stage of segment_mvdr alone: (target, distortion) PSDs [S,2,F,D,D] complex128 of
+    _get_psd (tssep/train/enhancer.py:268-289) for every row of the segment table."""
+    masks, obs_r, tab, ws, (K, S, D, T, F) = _segment_args(masks, obs, segments)
+    check(_lib.lib().tssep_mvdr_segments_psd(_p(obs_r), _p(masks), int(masks.dtype == torch.float64), _p(tab),
+                                             _p(ws), K, S, D, T, F, DISTORTION_MODES[mode],
+                                             float(distortion_eps), float(mask_power), int(bool(psd_real)),
+                                             _stream()), "segment_psd")
+    rows = ws[:S * 2 * D * D * F].view(S, 2, D * D, F)
+    psd = torch.zeros(S, 2, F, D, D, device=obs.device, dtype=torch.complex128)
+    p = 0
+    for i in range(D):
+        psd[..., i, i] = rows[:, :, i]
+        for j in range(i + 1, D):
+            v = torch.complex(rows[:, :, D + 2 * p], rows[:, :, D + 2 * p + 1])
+            psd[..., i, j], psd[..., j, i] = v, v.conj()
+            p += 1
+    return psd
+
+
+def segment_mvdr(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1e-4, mask_power=1,
+                 eps=None, masking=False, masking_eps=0.0, psd_real=True, check_singular=True,
+                 out=None):
+    """ClassicBF_np('mvdr_souden', segment_bf=True), tssep/train/enhancer.py:451-590: one Souden MVDR
+    per row (speaker, start, end) of `segments` from the statistics of that interval, the distortion
+    mask from the other speakers' masks (mode), filtered over the interval; zero elsewhere.
+    masks [K,1,T,F] fp32|fp64, obs [D,T,F] complex128 -> [K,T,F] complex128 (written into `out`
+    when given).  segments: [(k, s, e), ...] or an int32 [S,3] tensor (on the device: no copy, no
+    sync).  A constant number of launches whatever S is.  Raises torch.linalg.LinAlgError naming
+    the (speaker, start, end) segments with a singular distortion PSD (one host read;
+    check_singular=False skips it, the call is then free of host syncs and capturable)."""
+    L = _lib.lib()
+    masks, obs_r, tab, ws, (K, S, D, T, F) = _segment_args(masks, obs, segments)
+    info = torch.empty(S, device=obs.device, dtype=torch.int32)
+    if out is None:
+        out = torch.empty(K, T, F, device=obs.device, dtype=torch.complex128)
+    assert out.shape == (K, T, F) and out.dtype == torch.complex128 and out.is_contiguous(), out.shape
+    eps = float(torch.finfo(torch.float64).tiny) if eps is None else float(eps)
+    msz = masks.element_size()
+    nbytes = T * F * (K * msz + 16 * K) + 2 * T * F * 16 * D
+    with _timed("segment_mvdr", 0, nbytes):
+        check(L.tssep_mvdr_segments_fwd(_p(obs_r), _p(masks), int(masks.dtype == torch.float64), _p(tab),
+                                        _p(torch.view_as_real(out)), _p(ws), _p(info), K, S, D, T, F,
+                                        DISTORTION_MODES[mode], float(distortion_eps), float(mask_power),
+                                        int(bool(psd_real)), eps, int(bool(masking)), float(masking_eps),
+                                        _stream()), "segment_mvdr")
+    if check_singular:
+        bad = info.cpu().numpy()
+        if bad.any():
+            rows = tab.cpu().numpy()
+            failed = [tuple(int(v) for v in rows[i]) for i in bad.nonzero()[0]]
+            raise torch.linalg.LinAlgError(
+                f"segment_mvdr: the solver failed because the distortion PSD matrix is singular in "
+                f"{len(failed)} of {S} segments (speaker, start, end): {failed}")
+    return out
+
+
 # ----------------------------------------------------------------------------- losses
 def logmae_fwd(est, tgt):
     L = _lib.lib()

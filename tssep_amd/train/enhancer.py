@@ -1,11 +1,12 @@
-"""Enhancers -- drop-in for tssep/train/enhancer.py:21-265: the training-time classes (Dummy,
-Nothing, Masking) and the eval-time mask-based MVDR beamformer TorchBF.
-WPE / ClassicBF_np of the reference (numpy + nara_wpe / pb_bss on the CPU) are out of scope."""
+"""Enhancers -- drop-in for tssep/train/enhancer.py:21-590: the training-time classes (Dummy,
+Nothing, Masking), the eval-time mask-based MVDR beamformer TorchBF and the
+segment-wise ClassicBF_np('mvdr_souden').  WPE of the reference (nara_wpe on the CPU) is out of scope."""
 import numpy as np
 import torch
 
 from .. import hip_ops as H
 from ..configurable import Configurable
+from . import enhancer_distortion_mask
 
 
 class ABC(Configurable):
@@ -105,3 +106,123 @@ class TorchBF(ABC):
         enh = H.mvdr_souden(masks.detach(), Observation, reference_channel, eps=self.eps,
                             masking=self.masking, masking_eps=self.masking_eps)
         return enh if batched else enh[0]
+
+
+def normalized_intervals(ai, T):
+    """One speaker's activity -> [(s, e), ...], sorted, disjoint, non-empty, inside [0, T].
+    ai: anything with ``.normalized_intervals`` (paderbox's ArrayInterval), a 0/1 array of length T,
+    or a list of (s, e).  Empty intervals are dropped; overlapping, unsorted or out-of-range ones
+    raise ValueError."""
+    if hasattr(ai, "normalized_intervals"):
+        pairs = ai.normalized_intervals
+    else:
+        arr = np.asarray(ai.detach().cpu() if isinstance(ai, torch.Tensor) else ai)
+        if arr.ndim == 1 and arr.shape[0] == T:
+            if not np.isin(arr, (0, 1)).all():
+                raise ValueError("an activity array holds only 0 and 1")
+            edges = np.flatnonzero(np.diff(np.concatenate([[0], arr.astype(np.int8), [0]])))
+            pairs = edges.reshape(-1, 2)
+        elif arr.size == 0:
+            pairs = []
+        elif arr.ndim == 2 and arr.shape[1] == 2:
+            pairs = arr
+        else:
+            raise ValueError(f"expected .normalized_intervals, a 0/1 array of length {T} or a list of "
+                             f"(start, end); got shape {arr.shape}")
+    out, last = [], 0
+    for s, e in pairs:
+        if int(s) != s or int(e) != e:
+            raise ValueError(f"interval ({s}, {e}) is not integral")
+        s, e = int(s), int(e)
+        if s < 0 or e > T or e < s:
+            raise ValueError(f"interval ({s}, {e}) is not inside [0, {T}]")
+        if s < last:
+            raise ValueError(f"interval ({s}, {e}) overlaps or precedes the one ending at {last}: "
+                             f"intervals must be sorted and disjoint")
+        if e > s:
+            out.append((s, e))
+            last = e
+    return out
+
+
+class ClassicBF_np(ABC):
+    """Segment-wise mask-based MVDR (Souden) -- enhancer.py:370-590, same constructor, same call
+    signature, same checks; `_np` is the reference's name (it runs numpy on pb_bss there), here it
+    is one pipeline of HIP kernels over a segment table (hip_ops.segment_mvdr, csrc/mvdr.hip): for
+    every activity interval of a speaker the PSDs of that interval only (_get_psd, real part), the
+    distortion mask from the other speakers' masks, one beamformer, zeros outside the intervals.
+    The weights are TorchBF's phi[:, 0] / max(Re tr phi, tiny); pb_bss's least-squares fallback for
+    singular systems is not reproduced: those raise torch.linalg.LinAlgError."""
+
+    @classmethod
+    def finalize_dogmatic_config(cls, config):
+        config["distortion_mask"] = {"factory": enhancer_distortion_mask.SumCrossTalker}
+
+    def __init__(self, bf="mvdr_souden", masking=False, masking_eps=0, distortion_mask=None,
+                 pre_wpe=None, segment_wpe=None, mask_power=1):
+        super().__init__()
+        self.bf = bf
+        self.masking = masking
+        self.masking_eps = masking_eps
+        self.distortion_mask = distortion_mask
+        self.mask_power = mask_power
+        self.pre_wpe = pre_wpe
+        self.segment_wpe = segment_wpe
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}()"
+
+    def _kernel_mode(self):
+        dm = self.distortion_mask
+        if isinstance(dm, (enhancer_distortion_mask.SumCrossTalker, enhancer_distortion_mask.OneMinus)):
+            return dm.kernel_mode, float(dm.eps)
+        raise NotImplementedError(f"distortion_mask {dm!r}: the kernels build SumCrossTalker and OneMinus only")
+
+    def __call__(self, masks, Observation, dia, segment_bf=True, numpy_out=False):
+        """masks [K, M=1, T, F], Observation [D, T, F] complex128, dia: one activity per speaker
+        (see normalized_intervals) or None.  numpy_out=True: the dense [K, T, F] device tensor;
+        False: per speaker a dict {(s, e): [e - s, F]} of views of it."""
+        if self.bf != "mvdr_souden":
+            raise NotImplementedError(f"bf={self.bf!r}: only 'mvdr_souden' is implemented")
+        if self.pre_wpe is not None or self.segment_wpe is not None:
+            raise NotImplementedError("pre_wpe / segment_wpe: WPE is not implemented (nara_wpe on the CPU in "
+                                      "the reference)")
+        if not isinstance(masks, torch.Tensor):
+            masks = torch.as_tensor(np.asarray(masks))
+        if not isinstance(Observation, torch.Tensor):
+            Observation = torch.as_tensor(np.asarray(Observation))
+        mics = Observation.shape[0]
+        assert mics >= 6, Observation.shape      # all channels loaded? (training usually loads one or two)
+        K, M, T, F = masks.shape
+        if M != 1:
+            assert M == 2, masks.shape
+            raise NotImplementedError(masks.shape)
+        assert self.mask_power > 0, self.mask_power
+        mode, dist_eps = self._kernel_mode()
+        if mode == "one_minus":
+            assert K == 1, masks.shape
+        if dia is None:
+            assert segment_bf is False, segment_bf
+            assert self.segment_wpe is None, self.segment_wpe
+            assert numpy_out is True, numpy_out
+            intervals = [[(0, T)]] * K
+        else:
+            assert isinstance(dia, (tuple, list)), ("Expect list of ArrayInterval", type(dia), dia)
+            assert len(dia) == K, (len(dia), K)
+            if not segment_bf:
+                raise NotImplementedError("segment_bf=False with a diarization (the reference raises there too)")
+            intervals = [normalized_intervals(ai, T) for ai in dia]
+        table = [(k, s, e) for k, iv in enumerate(intervals) for s, e in iv]
+        device = masks.device if masks.is_cuda else torch.device("cuda")
+        if not table:
+            out = torch.zeros(K, T, F, dtype=torch.complex128, device=device)
+        else:
+            out = H.segment_mvdr(masks.detach().to(device), Observation.to(device), table, mode=mode,
+                                 distortion_eps=dist_eps, mask_power=self.mask_power, masking=self.masking,
+                                 masking_eps=self.masking_eps, psd_real=True)
+        if numpy_out:
+            return out
+        return [{(s, e): out[k, s:e] for s, e in iv} for k, iv in enumerate(intervals)]
+
+
+ClassicBF = ClassicBF_np
