@@ -650,6 +650,7 @@ extern "C" int tssep_mvdr_souden_fwd(const double* obs, const void* masks, int m
 //                         Hermitian accumulators per lane, slice partials to the workspace
 //   seg_finalize_kernel   slice partials -> slice 0 in a fixed order, / (e - s), psd_real
 //   mvdr_solve_kernel<D> / mvdr_weights_kernel   with "speakers" = segments, one info slot each
+//   seg_info_kernel       the info slot of an ignored row back to zero
 //   seg_apply_kernel<D>   one wave per (64 bins, time chunk, speaker); weights reloaded when the
 //                         covering segment changes
 // A row with k outside [0, K) or an empty [s, e) after clamping to [0, T] takes part in nothing
@@ -683,6 +684,15 @@ __global__ __launch_bounds__(256) void seg_map_kernel(const int32_t* __restrict_
     if (kk == k && s <= t && t < e) hit = j;
   }
   map[i] = hit;
+}
+
+// The solve sees the zero statistics of an ignored row as a singular system; an ignored row reports nothing.
+__global__ __launch_bounds__(256) void seg_info_kernel(const int32_t* __restrict__ tab,
+                                                       int* __restrict__ info, int K, int S, int64_t T) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= S) return;
+  const Seg g = load_seg(tab, i, K, T);
+  if (g.e <= g.s) info[i] = 0;
 }
 
 template <typename MT> __device__ __forceinline__ MT mask_pow(MT x, int ipow, double p) {
@@ -950,6 +960,10 @@ extern "C" int tssep_mvdr_segments_fwd(const double* obs, const void* masks, int
   if (st != TSSEP_OK) return st;
   // reference channel 0 (bf_kwargs, enhancer.py:497-506); the segments stand where the speakers do
   st = solve_systems(part, wconj, info, 1, S, D, F, (F + 63) / 64, 1, 0, eps, 1, s);
+  if (st != TSSEP_OK) return st;
+  hipLaunchKernelGGL(seg_info_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, segments, info, K,
+                     S, T);
+  st = tssep_launch_status();
   if (st != TSSEP_OK) return st;
 #define CALL(DD) \
   launch_seg_apply<DD>(obs, wconj, map, masks, mask_f64, enh, K, T, F, masking, masking_eps, s)
