@@ -568,6 +568,56 @@ int tssep_mvdr_segments_fwd(const double* obs, const void* masks, int mask_f64,
                             double mask_power, int psd_real, double eps, int masking,
                             double masking_eps, void* stream);
 
+/* The same on a packed per-row observation, as tssep_wpe_fwd leaves it: obs_seg [D,N,F] complex128, frame t of
+ * row i at packed row row0[i] + t - s_i (row0: int64 [S+1] on the device, the prefix of the row lengths).  Masks,
+ * table, output, workspace and info as above; the statistics and the filtering of a row read its own packed
+ * frames, so every row may carry a differently dereverberated observation. */
+int tssep_mvdr_segments_fwd_obs(const double* obs_seg, const int64_t* row0, int64_t N, const void* masks,
+                                int mask_f64, const int32_t* segments, double* enh, void* workspace,
+                                int* info, int K, int S, int D, int64_t T, int F, int mode,
+                                double distortion_eps, double mask_power, int psd_real, double eps,
+                                int masking, double masking_eps, void* stream);
+
+/* ------------------------------------------------------- WPE dereverberation ----
+ * WPE / ChannelWiseWPE of the reference (tssep/train/enhancer.py:292-367; nara_wpe's wpe_v8 on the host
+ * there), complex128.  Per frequency bin, K = taps * D:
+ *   Yt[tau*D + d, t] = Y[d, t - delay - tau], zero where that frame lies in front of the row's first frame
+ *   X = Y;  `iterations` times:
+ *     p[t] = mean_d |X[d,t]|^2    eps = 1e-10 max_t p[t] (per row and bin)    li[t] = 1 / max(p[t], eps)
+ *     R = sum_t li[t] Yt[:,t] Yt[:,t]^H    P = sum_t li[t] Yt[:,t] Y[:,t]^H
+ *         t over the row's frames (valid_mode = 0, 'full') or those with t - s >= delay + taps - 1 (1, 'valid')
+ *     R G = P    (Cholesky; R is Hermitian positive definite for a row of at least K + delay frames of
+ *                 generic data)                      X = Y - G^H Yt  at all frames of the row
+ * obs      [D,T,F] complex128 (interleaved re,im doubles), bin-contiguous
+ * segments [S,2] int32 on the device, rows (s, e) clamped to [0,T]; rows may overlap or repeat
+ * row0     [S+1] int64 on the device, the prefix of the row lengths e - s; N = row0[S]
+ * obs_seg  [D,N,F] complex128: row i occupies packed rows row0[i] .. row0[i+1].  A row is computed as if its
+ *          slice were the whole array (the taps never reach in front of s), in a summation order that depends on
+ *          its length only: the packed output of a row is bit-identical whatever else the table holds.
+ * lam      [N,F] doubles, the li above;   R [S,F,K,K] complex128, stored FULL (both triangles, exactly real
+ *          diagonal);   P [S,F,K,D];   G [S,K,D,F] (bin-contiguous)
+ * info     [S] device ints: the number of bins of row i whose factorisation met a pivot that is not positive or
+ *          not finite.  tssep_wpe_solve writes the slot; tssep_wpe_fwd writes the count over all iterations.
+ * Limits: D 1..8, taps >= 1, taps * D <= 80, 0 <= delay <= 256, iterations >= 1.
+ * A fixed number of launches per iteration whatever S is, no host sync, everything on `stream` out of one
+ * caller-owned workspace (16-byte aligned) of tssep_wpe_workspace_bytes(): host-only, 0 for an unsupported
+ * shape.  The stages are exported for tests and profiling; each may be called alone with the same workspace.
+ * _power: x_seg NULL reads X = Y from obs through the table, else the packed [D,N,F] estimate. */
+int64_t tssep_wpe_workspace_bytes(int S, int64_t N, int D, int64_t T, int F, int taps, int delay);
+int tssep_wpe_power(const double* obs, const double* x_seg, const int32_t* segments, const int64_t* row0,
+                    double* lam, void* workspace, int S, int64_t N, int D, int64_t T, int F, void* stream);
+int tssep_wpe_correlations(const double* obs, const double* lam, const int32_t* segments,
+                           const int64_t* row0, double* R, double* P, void* workspace, int S, int64_t N,
+                           int D, int64_t T, int F, int taps, int delay, int valid_mode, void* stream);
+int tssep_wpe_solve(const double* R, const double* P, double* G, int* info, int S, int D, int F, int taps,
+                    void* stream);
+int tssep_wpe_filter(const double* obs, const double* G, const int32_t* segments, const int64_t* row0,
+                     double* obs_seg, void* workspace, int S, int64_t N, int D, int64_t T, int F, int taps,
+                     int delay, void* stream);
+int tssep_wpe_fwd(const double* obs, const int32_t* segments, const int64_t* row0, double* obs_seg,
+                  void* workspace, int* info, int S, int64_t N, int D, int64_t T, int F, int taps, int delay,
+                  int iterations, int valid_mode, void* stream);
+
 /* -------------------------------------------------------------- optimizer -----
  * One optimizer step on flat fp32 buffers: global-norm gradient clipping
  * (torch.nn.utils.clip_grad_norm_, max_norm <= 0 disables) + Adam (torch.optim.Adam update rule,

@@ -706,11 +706,12 @@ template <> __device__ __forceinline__ float mask_pow<float>(float x, int ipow, 
   return powf(x, (float)p);
 }
 
-template <int D, typename MT>
+// PACKED: obs is the packed per-row observation [D, N, F] of the WPE stage (frame t of row sg at row0[sg] + t - s)
+template <int D, typename MT, bool PACKED>
 __global__ __launch_bounds__(64, D <= 6 ? 2 : 1) void seg_psd_kernel(
     const double2* __restrict__ obs, const MT* __restrict__ masks, const int32_t* __restrict__ tab,
     double* __restrict__ part, int K, int S, int64_t T, int F, int nf, int C, int mode,
-    double dist_eps, int ipow, double mask_power) {
+    double dist_eps, int ipow, double mask_power, const int64_t* __restrict__ row0, int64_t N) {
   const int ft = blockIdx.x % nf;
   const int c = (blockIdx.x / nf) % C;
   const int sg = blockIdx.x / (nf * C);
@@ -722,6 +723,8 @@ __global__ __launch_bounds__(64, D <= 6 ? 2 : 1) void seg_psd_kernel(
   const int t0 = g.s + c * per;
   const int t1 = t0 + per < g.e ? t0 + per : g.e;
   const MT deps = (MT)dist_eps;
+  const int64_t TO = PACKED ? N : T;                       // frames of the observation buffer
+  const int64_t shift = PACKED ? row0[sg] - g.s : 0;       // frame t -> row t + shift of it
 
   double diag[2][D];
   double2 off[2][D * (D - 1) / 2 + 1];
@@ -735,8 +738,9 @@ __global__ __launch_bounds__(64, D <= 6 ? 2 : 1) void seg_psd_kernel(
 #pragma unroll 1
   for (int t = t0; t < t1; ++t) {
     double2 y[D];
+    const int64_t to = PACKED ? (t + shift < 0 ? 0 : t + shift >= N ? N - 1 : t + shift) : t;
 #pragma unroll
-    for (int d = 0; d < D; ++d) y[d] = obs[((int64_t)d * T + t) * F + f];
+    for (int d = 0; d < D; ++d) y[d] = obs[((int64_t)d * TO + to) * F + f];
     const MT* mrow = masks + (int64_t)t * F + f;
     const MT tgt = mrow[(int64_t)g.k * T * F];
     MT dist;
@@ -804,11 +808,12 @@ __global__ __launch_bounds__(256) void seg_finalize_kernel(double* __restrict__ 
   part[i] = s;
 }
 
-template <int D, typename MT>
+template <int D, typename MT, bool PACKED>
 __global__ __launch_bounds__(64) void seg_apply_kernel(
     const double2* __restrict__ obs, const double2* __restrict__ wconj,
     const int32_t* __restrict__ map, const MT* __restrict__ masks, double2* __restrict__ enh, int K,
-    int64_t T, int F, int nf, int achunks, int tchunk, int masking, double masking_eps) {
+    int64_t T, int F, int nf, int achunks, int tchunk, int masking, double masking_eps,
+    const int32_t* __restrict__ tab, const int64_t* __restrict__ row0, int64_t N) {
   // speaker fastest: the waves that read the same Y tile are neighbours in launch order
   const int k = blockIdx.x % K;
   const int ft = (blockIdx.x / K) % nf;
@@ -820,6 +825,8 @@ __global__ __launch_bounds__(64) void seg_apply_kernel(
   const MT meps = (MT)masking_eps;
   double2 w[D];
   int cur = -1;
+  const int64_t TO = PACKED ? N : T;
+  int64_t shift = 0;
   for (int t = t0; t < t1; ++t) {
     const int sg = __builtin_amdgcn_readfirstlane(map[(int64_t)k * T + t]);
     double2 e = {0.0, 0.0};
@@ -828,10 +835,12 @@ __global__ __launch_bounds__(64) void seg_apply_kernel(
 #pragma unroll
         for (int d = 0; d < D; ++d) w[d] = wconj[((int64_t)sg * D + d) * F + f];
         cur = sg;
+        if (PACKED) shift = row0[sg] - load_seg(tab, sg, K, T).s;
       }
+      const int64_t to = PACKED ? (t + shift < 0 ? 0 : t + shift >= N ? N - 1 : t + shift) : t;
 #pragma unroll
       for (int d = 0; d < D; ++d) {
-        const double2 y = obs[((int64_t)d * T + t) * F + f];
+        const double2 y = obs[((int64_t)d * TO + to) * F + f];
         e.x += w[d].x * y.x - w[d].y * y.y;
         e.y += w[d].x * y.y + w[d].y * y.x;
       }
@@ -855,28 +864,29 @@ int64_t seg_part_bytes(int S, int D, int F) {
   return (int64_t)seg_chunks(S, F) * S * 2 * D * D * F * (int64_t)sizeof(double);
 }
 
-template <int D>
+template <int D, bool PACKED = false>
 int launch_seg_psd(const double* obs, const void* masks, int mask_f64, const int32_t* tab,
                    double* part, int K, int S, int64_t T, int F, int mode, double dist_eps,
-                   double mask_power, hipStream_t s) {
+                   double mask_power, hipStream_t s, const int64_t* row0 = nullptr, int64_t N = 0) {
   const int nf = (F + 63) / 64, C = seg_chunks(S, F);
   const int ipow = mask_power == 1.0 ? 1 : mask_power == 2.0 ? 2 : 0;
   const dim3 grid((unsigned)((int64_t)S * C * nf));
   if (mask_f64)
-    hipLaunchKernelGGL((seg_psd_kernel<D, double>), grid, dim3(64), 0, s,
+    hipLaunchKernelGGL((seg_psd_kernel<D, double, PACKED>), grid, dim3(64), 0, s,
                        reinterpret_cast<const double2*>(obs), static_cast<const double*>(masks), tab,
-                       part, K, S, T, F, nf, C, mode, dist_eps, ipow, mask_power);
+                       part, K, S, T, F, nf, C, mode, dist_eps, ipow, mask_power, row0, N);
   else
-    hipLaunchKernelGGL((seg_psd_kernel<D, float>), grid, dim3(64), 0, s,
+    hipLaunchKernelGGL((seg_psd_kernel<D, float, PACKED>), grid, dim3(64), 0, s,
                        reinterpret_cast<const double2*>(obs), static_cast<const float*>(masks), tab,
-                       part, K, S, T, F, nf, C, mode, dist_eps, ipow, mask_power);
+                       part, K, S, T, F, nf, C, mode, dist_eps, ipow, mask_power, row0, N);
   return tssep_launch_status();
 }
 
-template <int D>
+template <int D, bool PACKED = false>
 int launch_seg_apply(const double* obs, const double* wconj, const int32_t* map, const void* masks,
                      int mask_f64, double* enh, int K, int64_t T, int F, int masking,
-                     double masking_eps, hipStream_t s) {
+                     double masking_eps, hipStream_t s, const int32_t* tab = nullptr,
+                     const int64_t* row0 = nullptr, int64_t N = 0) {
   const int nf = (F + 63) / 64;
   int64_t c = (4096 + (int64_t)nf * K - 1) / ((int64_t)nf * K);
   const int64_t cmax = (T + 15) / 16;
@@ -886,15 +896,15 @@ int launch_seg_apply(const double* obs, const double* wconj, const int32_t* map,
   const int achunks = (int)((T + tchunk - 1) / tchunk);
   const dim3 grid((unsigned)((int64_t)achunks * nf * K));
   if (mask_f64)
-    hipLaunchKernelGGL((seg_apply_kernel<D, double>), grid, dim3(64), 0, s,
+    hipLaunchKernelGGL((seg_apply_kernel<D, double, PACKED>), grid, dim3(64), 0, s,
                        reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(wconj),
                        map, static_cast<const double*>(masks), reinterpret_cast<double2*>(enh), K, T,
-                       F, nf, achunks, tchunk, masking, masking_eps);
+                       F, nf, achunks, tchunk, masking, masking_eps, tab, row0, N);
   else
-    hipLaunchKernelGGL((seg_apply_kernel<D, float>), grid, dim3(64), 0, s,
+    hipLaunchKernelGGL((seg_apply_kernel<D, float, PACKED>), grid, dim3(64), 0, s,
                        reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(wconj),
                        map, static_cast<const float*>(masks), reinterpret_cast<double2*>(enh), K, T,
-                       F, nf, achunks, tchunk, masking, masking_eps);
+                       F, nf, achunks, tchunk, masking, masking_eps, tab, row0, N);
   return tssep_launch_status();
 }
 
@@ -906,10 +916,12 @@ extern "C" int64_t tssep_mvdr_segments_workspace_bytes(int K, int S, int D, int6
   return pb + (int64_t)S * D * F * 16 + ((int64_t)K * T * 4 + 15) / 16 * 16;
 }
 
-extern "C" int tssep_mvdr_segments_psd(const double* obs, const void* masks, int mask_f64,
-                                       const int32_t* segments, void* workspace, int K, int S, int D,
-                                       int64_t T, int F, int mode, double distortion_eps,
-                                       double mask_power, int psd_real, void* stream) {
+namespace {
+
+// row0 == nullptr: obs is [D, T, F]; else the packed [D, N, F] with row i at rows row0[i] .. row0[i + 1]
+int seg_psd_stage(const double* obs, const void* masks, int mask_f64, const int32_t* segments, void* workspace,
+                  int K, int S, int D, int64_t T, int F, int mode, double distortion_eps, double mask_power,
+                  int psd_real, const int64_t* row0, int64_t N, void* stream) {
   if (!obs || !masks || !segments || !workspace) return TSSEP_E_NULL;
   if (!seg_shape_ok(K, S, D, T, F) || (mode != 0 && mode != 1) || !(mask_power > 0.0))
     return TSSEP_E_SHAPE;
@@ -917,8 +929,10 @@ extern "C" int tssep_mvdr_segments_psd(const double* obs, const void* masks, int
   if (!aligned16(obs) || !aligned16(workspace)) return TSSEP_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   double* part = static_cast<double*>(workspace);
-#define CALL(DD) \
-  launch_seg_psd<DD>(obs, masks, mask_f64, segments, part, K, S, T, F, mode, distortion_eps, mask_power, s)
+#define CALL(DD)                                                                                                \
+  (row0 ? launch_seg_psd<DD, true>(obs, masks, mask_f64, segments, part, K, S, T, F, mode, distortion_eps,     \
+                                   mask_power, s, row0, N)                                                     \
+        : launch_seg_psd<DD>(obs, masks, mask_f64, segments, part, K, S, T, F, mode, distortion_eps, mask_power, s))
   int st;
   switch (D) {
     case 1: st = CALL(1); break;
@@ -938,15 +952,14 @@ extern "C" int tssep_mvdr_segments_psd(const double* obs, const void* masks, int
   return tssep_launch_status();
 }
 
-extern "C" int tssep_mvdr_segments_fwd(const double* obs, const void* masks, int mask_f64,
-                                       const int32_t* segments, double* enh, void* workspace,
-                                       int* info, int K, int S, int D, int64_t T, int F, int mode,
-                                       double distortion_eps, double mask_power, int psd_real,
-                                       double eps, int masking, double masking_eps, void* stream) {
+int seg_fwd(const double* obs, const void* masks, int mask_f64, const int32_t* segments, double* enh,
+            void* workspace, int* info, int K, int S, int D, int64_t T, int F, int mode, double distortion_eps,
+            double mask_power, int psd_real, double eps, int masking, double masking_eps, const int64_t* row0,
+            int64_t N, void* stream) {
   if (!enh || !info) return TSSEP_E_NULL;
   if (!aligned16(enh)) return TSSEP_E_ALIGN;
-  int st = tssep_mvdr_segments_psd(obs, masks, mask_f64, segments, workspace, K, S, D, T, F, mode,
-                                   distortion_eps, mask_power, psd_real, stream);
+  int st = seg_psd_stage(obs, masks, mask_f64, segments, workspace, K, S, D, T, F, mode, distortion_eps,
+                         mask_power, psd_real, row0, N, stream);
   if (st != TSSEP_OK) return st;
   hipStream_t s = (hipStream_t)stream;
   const int64_t pb = (seg_part_bytes(S, D, F) + 15) / 16 * 16;
@@ -965,8 +978,41 @@ extern "C" int tssep_mvdr_segments_fwd(const double* obs, const void* masks, int
                      S, T);
   st = tssep_launch_status();
   if (st != TSSEP_OK) return st;
-#define CALL(DD) \
-  launch_seg_apply<DD>(obs, wconj, map, masks, mask_f64, enh, K, T, F, masking, masking_eps, s)
+#define CALL(DD)                                                                                                  \
+  (row0 ? launch_seg_apply<DD, true>(obs, wconj, map, masks, mask_f64, enh, K, T, F, masking, masking_eps, s,    \
+                                     segments, row0, N)                                                          \
+        : launch_seg_apply<DD>(obs, wconj, map, masks, mask_f64, enh, K, T, F, masking, masking_eps, s))
   DISPATCH_D(D, CALL)
 #undef CALL
+}
+
+}  // namespace
+
+extern "C" int tssep_mvdr_segments_psd(const double* obs, const void* masks, int mask_f64,
+                                       const int32_t* segments, void* workspace, int K, int S, int D,
+                                       int64_t T, int F, int mode, double distortion_eps,
+                                       double mask_power, int psd_real, void* stream) {
+  return seg_psd_stage(obs, masks, mask_f64, segments, workspace, K, S, D, T, F, mode, distortion_eps, mask_power,
+                       psd_real, nullptr, 0, stream);
+}
+
+extern "C" int tssep_mvdr_segments_fwd(const double* obs, const void* masks, int mask_f64,
+                                       const int32_t* segments, double* enh, void* workspace,
+                                       int* info, int K, int S, int D, int64_t T, int F, int mode,
+                                       double distortion_eps, double mask_power, int psd_real,
+                                       double eps, int masking, double masking_eps, void* stream) {
+  return seg_fwd(obs, masks, mask_f64, segments, enh, workspace, info, K, S, D, T, F, mode, distortion_eps,
+                 mask_power, psd_real, eps, masking, masking_eps, nullptr, 0, stream);
+}
+
+extern "C" int tssep_mvdr_segments_fwd_obs(const double* obs_seg, const int64_t* row0, int64_t N,
+                                           const void* masks, int mask_f64, const int32_t* segments,
+                                           double* enh, void* workspace, int* info, int K, int S, int D,
+                                           int64_t T, int F, int mode, double distortion_eps,
+                                           double mask_power, int psd_real, double eps, int masking,
+                                           double masking_eps, void* stream) {
+  if (!row0) return TSSEP_E_NULL;
+  if (N <= 0 || N >= ((int64_t)1 << 30)) return TSSEP_E_SHAPE;
+  return seg_fwd(obs_seg, masks, mask_f64, segments, enh, workspace, info, K, S, D, T, F, mode, distortion_eps,
+                 mask_power, psd_real, eps, masking, masking_eps, row0, N, stream);
 }

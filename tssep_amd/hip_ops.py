@@ -1318,7 +1318,7 @@ def segment_psd(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1e
 
 def segment_mvdr(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1e-4, mask_power=1,
                  eps=None, masking=False, masking_eps=0.0, psd_real=True, check_singular=True,
-                 out=None):
+                 out=None, obs_seg=None, row0=None):
     """ClassicBF_np('mvdr_souden', segment_bf=True), tssep/train/enhancer.py:451-590: one Souden MVDR
     per row (speaker, start, end) of `segments` from the statistics of that interval, the distortion
     mask from the other speakers' masks (mode), filtered over the interval; zero elsewhere.
@@ -1326,9 +1326,17 @@ def segment_mvdr(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1
     when given).  segments: [(k, s, e), ...] or an int32 [S,3] tensor (on the device: no copy, no
     sync).  A constant number of launches whatever S is.  Raises torch.linalg.LinAlgError naming
     the (speaker, start, end) segments with a singular distortion PSD (one host read;
-    check_singular=False skips it, the call is then free of host syncs and capturable)."""
+    check_singular=False skips it, the call is then free of host syncs and capturable).
+    obs_seg [D,N,F] with row0 [S+1] (what `wpe` returns for the (s, e) columns of the same table): every row takes
+    its statistics and its filter input from its own packed frames instead of obs[:, s:e]."""
     L = _lib.lib()
     masks, obs_r, tab, ws, (K, S, D, T, F) = _segment_args(masks, obs, segments)
+    if (obs_seg is None) != (row0 is None):
+        raise ValueError("segment_mvdr: obs_seg and row0 come together")
+    if obs_seg is not None:
+        assert obs_seg.is_cuda and obs_seg.dtype == torch.complex128 and obs_seg.is_contiguous(), obs_seg.dtype
+        assert obs_seg.dim() == 3 and obs_seg.shape[0] == D and obs_seg.shape[2] == F, (obs_seg.shape, obs.shape)
+        assert row0.is_cuda and row0.dtype == torch.int64 and row0.shape == (S + 1,), (row0.dtype, row0.shape)
     info = torch.empty(S, device=obs.device, dtype=torch.int32)
     if out is None:
         out = torch.empty(K, T, F, device=obs.device, dtype=torch.complex128)
@@ -1336,12 +1344,17 @@ def segment_mvdr(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1
     eps = float(torch.finfo(torch.float64).tiny) if eps is None else float(eps)
     msz = masks.element_size()
     nbytes = T * F * (K * msz + 16 * K) + 2 * T * F * 16 * D
+    tail = (K, S, D, T, F, DISTORTION_MODES[mode], float(distortion_eps), float(mask_power), int(bool(psd_real)),
+            eps, int(bool(masking)), float(masking_eps), _stream())
     with _timed("segment_mvdr", 0, nbytes):
-        check(L.tssep_mvdr_segments_fwd(_p(obs_r), _p(masks), int(masks.dtype == torch.float64), _p(tab),
-                                        _p(torch.view_as_real(out)), _p(ws), _p(info), K, S, D, T, F,
-                                        DISTORTION_MODES[mode], float(distortion_eps), float(mask_power),
-                                        int(bool(psd_real)), eps, int(bool(masking)), float(masking_eps),
-                                        _stream()), "segment_mvdr")
+        if obs_seg is None:
+            check(L.tssep_mvdr_segments_fwd(_p(obs_r), _p(masks), int(masks.dtype == torch.float64), _p(tab),
+                                            _p(torch.view_as_real(out)), _p(ws), _p(info), *tail), "segment_mvdr")
+        else:
+            check(L.tssep_mvdr_segments_fwd_obs(_p(torch.view_as_real(obs_seg)), _p(row0), obs_seg.shape[1],
+                                                _p(masks), int(masks.dtype == torch.float64), _p(tab),
+                                                _p(torch.view_as_real(out)), _p(ws), _p(info), *tail),
+                  "segment_mvdr (packed observation)")
     if check_singular:
         bad = info.cpu().numpy()
         if bad.any():
@@ -1351,6 +1364,145 @@ def segment_mvdr(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1
                 f"segment_mvdr: the solver failed because the distortion PSD matrix is singular in "
                 f"{len(failed)} of {S} segments (speaker, start, end): {failed}")
     return out
+
+
+# ----------------------------------------------------------------------------- WPE
+WPE_MAX_CHANNELS, WPE_MAX_ROWS, WPE_MAX_DELAY = 8, 80, 256
+
+
+def wpe_check_args(D, taps, delay, iterations, statistics_mode):
+    """The limits of csrc/wpe.hip, checked on the host before anything touches the device."""
+    if statistics_mode not in ("full", "valid"):
+        raise ValueError(f"wpe: statistics_mode {statistics_mode!r}: 'full' or 'valid'")
+    if int(taps) != taps or int(delay) != delay or int(iterations) != iterations:
+        raise ValueError(f"wpe: taps, delay and iterations are integers, got {(taps, delay, iterations)}")
+    if not 1 <= D <= WPE_MAX_CHANNELS:
+        raise ValueError(f"wpe: {D} channels: the kernels are built for 1 to {WPE_MAX_CHANNELS}")
+    if taps < 1 or taps * D > WPE_MAX_ROWS:
+        raise ValueError(f"wpe: taps * channels = {taps} * {D} = {taps * D}: the per-bin systems are built for 1 to "
+                         f"{WPE_MAX_ROWS} rows (the matrix lives in LDS)")
+    if not 0 <= delay <= WPE_MAX_DELAY:
+        raise ValueError(f"wpe: delay {delay}: 0 to {WPE_MAX_DELAY}")
+    if iterations < 1:
+        raise ValueError(f"wpe: iterations {iterations}: at least 1")
+
+
+def wpe_rows(segments, T):
+    """[(s, e), ...] (or an int tensor [S,2]; it is read on the host: the packed size is a host number) ->
+    list of (s, e) ints, each inside [0, T]."""
+    if isinstance(segments, torch.Tensor):
+        segments = segments.detach().cpu().tolist()
+    rows = [(int(s), int(e)) for s, e in segments]
+    for s, e in rows:
+        if not 0 <= s <= e <= T:
+            raise ValueError(f"wpe: row ({s}, {e}) is not inside [0, {T}]")
+    return rows
+
+
+def wpe_validate(obs, segments, taps, delay, iterations, statistics_mode):
+    """Every host-side refusal of `wpe` (dtype, limits, rows inside [0, T], the rank rule) -> rows, (D, T, F)"""
+    if obs.dtype != torch.complex128:
+        raise TypeError(f"wpe: {obs.dtype}: the observation must be complex128 (the per-bin systems reach condition "
+                        f"numbers of 1e11 on reverberant data; complex64 loses the whole result there)")
+    assert obs.dim() == 3, obs.shape
+    D, T, F = obs.shape
+    wpe_check_args(D, taps, delay, iterations, statistics_mode)
+    rows = wpe_rows([(0, T)] if segments is None else segments, T)
+    if not rows:
+        raise ValueError("wpe: empty segment table")
+    hist = delay + (taps - 1 if statistics_mode == "valid" else 0)
+    short = [r for r in rows if r[1] - r[0] - hist < taps * D]
+    if short:
+        raise ValueError(f"wpe: {len(short)} of {len(rows)} rows (start, end) have fewer than taps * channels = "
+                         f"{taps * D} frames behind the first {hist}: the correlation matrix cannot have full rank there: "
+                         f"{short}")
+    return rows, (D, T, F)
+
+
+_WPE_TABLES = {}        # (device, rows) -> (table int32 [S,2], row0 int64 [S+1]) on the device
+
+
+def wpe_table(rows, device):
+    """[(s, e), ...] -> (int32 [S,2] table, int64 [S+1] prefix of the row lengths) on `device`.  The pair is kept: a
+    later call with the same rows copies nothing from the host, so it neither synchronises nor breaks a capture."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, tuple(rows))
+    hit = _WPE_TABLES.get(key)
+    if hit is None:
+        if len(_WPE_TABLES) >= 64:
+            _WPE_TABLES.pop(next(iter(_WPE_TABLES)))
+        r0 = np.concatenate([[0], np.cumsum([e - s for s, e in rows])]).astype(np.int64)
+        hit = (torch.tensor(rows, dtype=torch.int32).reshape(len(rows), 2).to(device), torch.from_numpy(r0).to(device))
+        _WPE_TABLES[key] = hit
+    return hit
+
+
+def wpe(obs, segments=None, taps=10, delay=2, iterations=3, statistics_mode="full", check_singular=True, row0=None,
+        N=None, _rows=None):
+    """WPE dereverberation (nara_wpe's wpe_v8 with psd_context=0; csrc/wpe.hip).  obs [D,T,F] complex128 on the
+    device.  segments None: the whole array -> [D,T,F].  segments [(s, e), ...]: every row dereverberated as if
+    obs[:, s:e] were the whole array (rows may overlap or repeat) -> (obs_seg [D,N,F], row0 int64 [S+1] on the
+    device), row i at obs_seg[:, row0[i]:row0[i+1]].  A fixed number of launches per iteration whatever the table
+    holds.  Rows too short for a full-rank correlation matrix raise ValueError before any launch; a factorisation
+    that meets a pivot that is not positive raises torch.linalg.LinAlgError naming the (start, end) rows (one host
+    read; check_singular=False skips it).
+    Host traffic: a table given as a list is copied to the device the first time it is seen (wpe_table keeps the last
+    64), so with check_singular=False every later call with the same rows is free of host transfers.  A table that is
+    already on the device goes in as `segments` int32 [S,2] with `row0` int64 [S+1] and the host number N = row0[S]
+    (what wpe_table returns): nothing is read back.  The rows of a device table are NOT checked on the host: a row
+    outside [0, T] is clamped by the kernels, and a row too short for the rank rule does not raise ValueError but shows
+    as LinAlgError, or with check_singular=False as NaN in its packed frames.
+    Capture: a graph keeps only the pointers of the table and of row0.  A captured call must therefore pass the device
+    table (segments, row0, N) and the caller keeps those tensors alive as long as the graph; a list table lives in
+    wpe_table's store only until 64 other tables have displaced it.
+    Memory: the workspace holds li [N,F], R [S,F,K,K], P, G and the chunk partials for all rows at once, K = taps * D:
+    16 F (S K (K + 2 D) + 16 tiles (N / 256 + S)) bytes, tiles = K / 4 (K / 4 + 1) / 2 + K / 4 (D + 3) / 4 -- 0.12 GB
+    for one 30-s utterance at K = 60, 5.5 GB for 80 rows; it is allocated per call (torch's caching allocator)."""
+    if isinstance(segments, torch.Tensor) and row0 is not None:
+        if obs.dtype != torch.complex128:
+            raise TypeError(f"wpe: {obs.dtype}: the observation must be complex128")
+        assert obs.dim() == 3, obs.shape
+        D, T, F = obs.shape
+        wpe_check_args(D, taps, delay, iterations, statistics_mode)
+        if N is None:
+            raise ValueError("wpe: a device table comes with row0 and the host number N = row0[S]")
+        assert segments.is_cuda and segments.dtype == torch.int32 and segments.dim() == 2 and segments.shape[1] == 2 \
+            and segments.is_contiguous(), (segments.dtype, segments.shape)
+        S = segments.shape[0]
+        assert row0.is_cuda and row0.dtype == torch.int64 and row0.shape == (S + 1,), (row0.dtype, row0.shape)
+        tab, N, rows = segments, int(N), None
+    else:
+        if row0 is not None or N is not None:
+            raise ValueError("wpe: row0 and N come with a device table")
+        # _rows: what wpe_validate returned to a caller that had to refuse before moving obs to the device
+        rows, (D, T, F) = _rows or wpe_validate(obs, segments, taps, delay, iterations, statistics_mode)
+        tab, row0 = wpe_table(rows, obs.device)
+        S, N = len(rows), sum(e - s for s, e in rows)
+    assert obs.is_cuda, obs.device
+    ws_bytes = _lib.lib().tssep_wpe_workspace_bytes(S, N, D, T, F, int(taps), int(delay))
+    if ws_bytes <= 0:
+        raise RuntimeError(f"wpe: unsupported shape obs {(D, T, F)} with {S} rows, taps {taps}, delay {delay}")
+    ws = torch.empty(ws_bytes // 8 + 2, device=obs.device, dtype=torch.float64)
+    obs_r = torch.view_as_real(obs.contiguous())
+    info = torch.empty(S, device=obs.device, dtype=torch.int32)
+    out = torch.empty(D, N, F, device=obs.device, dtype=torch.complex128)
+    K = taps * D
+    flops = iterations * N * F * 8 * (K * (K + 1) // 2 + 2 * K * D)
+    with _timed("wpe", flops, 0):
+        check(_lib.lib().tssep_wpe_fwd(_p(obs_r), _p(tab), _p(row0), _p(torch.view_as_real(out)), _p(ws), _p(info),
+                                       S, N, D, T, F, int(taps), int(delay), int(iterations),
+                                       int(statistics_mode == "valid"), _stream()), "wpe")
+    if check_singular:
+        bad = info.cpu().numpy()
+        if bad.any():
+            rows = rows if rows is not None else [tuple(r) for r in tab.cpu().tolist()]
+            failed = [rows[i] for i in bad.nonzero()[0]]
+            raise torch.linalg.LinAlgError(
+                f"wpe: the factorisation of the correlation matrix met a pivot that is not positive in "
+                f"{len(failed)} of {S} rows (start, end): {failed}")
+    return out if segments is None else (out, row0)
 
 
 # ----------------------------------------------------------------------------- losses

@@ -1,6 +1,6 @@
 """Enhancers -- drop-in for tssep/train/enhancer.py:21-590: the training-time classes (Dummy,
 Nothing, Masking), the eval-time mask-based MVDR beamformer TorchBF and the
-segment-wise ClassicBF_np('mvdr_souden').  WPE of the reference (nara_wpe on the CPU) is out of scope."""
+segment-wise ClassicBF_np('mvdr_souden') with its WPE / ChannelWiseWPE dereverberation stages."""
 import numpy as np
 import torch
 
@@ -145,12 +145,73 @@ def normalized_intervals(ai, T):
     return out
 
 
+class WPE(ABC):
+    """WPE dereverberation -- enhancer.py:292-348, same constructor and call.  The reference hands the array to
+    nara_wpe's wpe_v8 on the host; here it is one pipeline of HIP kernels (hip_ops.wpe, csrc/wpe.hip; the definition
+    is DESIGN 4.5).  Observation [D, T, F] complex128: a torch tensor gives a device tensor, a numpy array a numpy
+    array.  `inplace` is accepted and ignored: a new array is returned."""
+
+    def __init__(self, taps=10, delay=2, iterations=3, psd_context=0, statistics_mode="full"):
+        super().__init__()
+        self.taps = taps
+        self.delay = delay
+        self.iterations = iterations
+        self.psd_context = psd_context
+        self.statistics_mode = statistics_mode
+
+    def _kwargs(self):
+        if self.psd_context != 0:
+            raise NotImplementedError(f"psd_context={self.psd_context!r}: only 0 is built (the edge normalisation of "
+                                      f"nara_wpe's window mean could not be checked against nara_wpe)")
+        return dict(taps=self.taps, delay=self.delay, iterations=self.iterations,
+                    statistics_mode=self.statistics_mode)
+
+    def _layout(self, obs):
+        return obs, (lambda out: out)
+
+    def __call__(self, Observation, inplace=False):
+        kw = self._kwargs()
+        if isinstance(Observation, np.ndarray):
+            obs, numpy_out = torch.from_numpy(np.ascontiguousarray(Observation)), True
+        elif isinstance(Observation, torch.Tensor):
+            obs, numpy_out = Observation.detach(), False
+        else:
+            raise NotImplementedError(type(Observation), Observation)
+        if obs.dtype != torch.complex128:
+            raise TypeError(f"{self.name}: Observation is {obs.dtype}, complex128 is required (the correlation matrices "
+                            f"reach condition numbers of 1e11 on reverberant data)")
+        assert obs.dim() == 3, obs.shape
+        obs, back = self._layout(obs)
+        checked = H.wpe_validate(obs, None, **kw)             # every refusal before anything touches the device
+        out = back(H.wpe(obs.contiguous() if obs.is_cuda else obs.contiguous().to("cuda"), _rows=checked, **kw))
+        return out.cpu().numpy() if numpy_out else out
+
+    def rows(self, obs, rows):
+        """The segment-wise form: every row (s, e) as if obs[:, s:e] were the whole array -> (obs_seg, row0)."""
+        return H.wpe(obs, rows, **self._kwargs())
+
+
+class ChannelWiseWPE(WPE):
+    """WPE on every channel alone -- enhancer.py:351-367: the D = 1 kernels on '1 t (d f)'."""
+
+    def _layout(self, obs):
+        D, T, F = obs.shape
+        return (obs.permute(1, 0, 2).reshape(1, T, D * F),
+                lambda out: out.reshape(T, D, F).permute(1, 0, 2).contiguous())
+
+    def rows(self, obs, rows):
+        D, T, F = obs.shape
+        seg, row0 = H.wpe(obs.permute(1, 0, 2).reshape(1, T, D * F).contiguous(), rows, **self._kwargs())
+        return seg.reshape(-1, D, F).permute(1, 0, 2).contiguous(), row0
+
+
 class ClassicBF_np(ABC):
     """Segment-wise mask-based MVDR (Souden) -- enhancer.py:370-590, same constructor, same call
     signature, same checks; `_np` is the reference's name (it runs numpy on pb_bss there), here it
     is one pipeline of HIP kernels over a segment table (hip_ops.segment_mvdr, csrc/mvdr.hip): for
     every activity interval of a speaker the PSDs of that interval only (_get_psd, real part), the
     distortion mask from the other speakers' masks, one beamformer, zeros outside the intervals.
+    pre_wpe dereverberates the whole observation first, segment_wpe every interval's slice on its own (WPE above).
     The weights are TorchBF's phi[:, 0] / max(Re tr phi, tiny); pb_bss's least-squares fallback for
     singular systems is not reproduced: those raise torch.linalg.LinAlgError."""
 
@@ -184,9 +245,10 @@ class ClassicBF_np(ABC):
         False: per speaker a dict {(s, e): [e - s, F]} of views of it."""
         if self.bf != "mvdr_souden":
             raise NotImplementedError(f"bf={self.bf!r}: only 'mvdr_souden' is implemented")
-        if self.pre_wpe is not None or self.segment_wpe is not None:
-            raise NotImplementedError("pre_wpe / segment_wpe: WPE is not implemented (nara_wpe on the CPU in "
-                                      "the reference)")
+        for name in ("pre_wpe", "segment_wpe"):
+            w = getattr(self, name)
+            if w is not None and not isinstance(w, WPE):
+                raise NotImplementedError(f"{name}={w!r}: only this module's WPE / ChannelWiseWPE are built")
         if not isinstance(masks, torch.Tensor):
             masks = torch.as_tensor(np.asarray(masks))
         if not isinstance(Observation, torch.Tensor):
@@ -217,9 +279,16 @@ class ClassicBF_np(ABC):
         if not table:
             out = torch.zeros(K, T, F, dtype=torch.complex128, device=device)
         else:
-            out = H.segment_mvdr(masks.detach().to(device), Observation.to(device), table, mode=mode,
+            Observation = Observation.to(device)
+            if self.pre_wpe is not None:
+                Observation = self.pre_wpe(Observation)
+            packed = {}
+            if self.segment_wpe is not None:
+                # one table of all rows: the launches do not grow with the number of segments
+                packed["obs_seg"], packed["row0"] = self.segment_wpe.rows(Observation, [(s, e) for _, s, e in table])
+            out = H.segment_mvdr(masks.detach().to(device), Observation, table, mode=mode,
                                  distortion_eps=dist_eps, mask_power=self.mask_power, masking=self.masking,
-                                 masking_eps=self.masking_eps, psd_real=True)
+                                 masking_eps=self.masking_eps, psd_real=True, **packed)
         if numpy_out:
             return out
         return [{(s, e): out[k, s:e] for s, e in iv} for k, iv in enumerate(intervals)]
