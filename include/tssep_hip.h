@@ -428,6 +428,49 @@ int tssep_cond_cat_fwd(const float* pre, int64_t ld_pre, const float* aux, int64
 int tssep_cond_cat_bwd(const float* dxs, int64_t ld_dxs, float* dpre, int64_t ld_dpre,
                        int64_t B, int64_t K, int64_t T, int F, int trials, void* stream);
 
+/* ------------------------------------------------- learned embeddings (aux.hip) ----
+ * Gradient of the conditioning with respect to the embedding (aux_net / a trainable embedding, net.py:816-838):
+ *   mul: d_aux[(b,s), f] = sum_tr sum_t dxs[(b,tr,(s-tr) mod K,t), f] * pre[(b,t), f]
+ *   cat: d_aux[(b,s), e] = sum_tr sum_t dxs[(b,tr,(s-tr) mod K,t), F+e]
+ * d_aux rows (b,s) with leading dimension ld_daux.  Two launches: partial sums per chunk of 64 frames (wave w of a
+ * workgroup adds the frames t0+w, t0+w+4, ... of trial 0, 1, ... in that order, the four waves are added in ascending
+ * order), then the chunks in ascending order: no atomics, bit-identical from run to run.  16-byte loads when
+ * ld_dxs (and ld_pre) are multiples of 4 covering the 4-aligned column window and the pointers are 16-byte aligned.
+ * ws: caller-owned, tssep_cond_aux_bwd_workspace_bytes(B, K, T, F, E) bytes (E = 0: mul; host-only, 0 = bad shape).
+ * Algorithmic HBM bytes: 4 * B*trials*K*T * C (dxs columns read, C = F or E) [+ 4 * B*T*F of pre, re-read K*trials
+ * times from the caches] + 4 * B*K*C. */
+int64_t tssep_cond_aux_bwd_workspace_bytes(int64_t B, int64_t K, int64_t T, int F, int E);
+int tssep_cond_mul_aux_bwd(const float* dxs, int64_t ld_dxs, const float* pre, int64_t ld_pre, float* d_aux,
+                           int64_t ld_daux, void* ws, int64_t B, int64_t K, int64_t T, int F, int trials,
+                           void* stream);
+int tssep_cond_cat_aux_bwd(const float* dxs, int64_t ld_dxs, float* d_aux, int64_t ld_daux, void* ws,
+                           int64_t B, int64_t K, int64_t T, int F, int E, int trials, void* stream);
+/* InstanceNorm (mode 0, net.py:250-285: (x - mean) / std, unbiased 0 / 1) and InstanceNorm_v2 (mode 1, net.py:288-330:
+ * (x - mean) / (||x - mean|| / sqrt(count))) over x [R, n, C] (rows (r,t), leading dimension ld_x).  axis 0: statistics
+ * along the last axis, mean / rscale [R*n]; axis 1: along the time axis, mean / rscale [R*C].  The variance is summed
+ * from centred values (the sums are accumulated in double, everything stored is fp32); no epsilon (a constant row
+ * gives inf / nan as in the reference).  rscale = 1 / scale.
+ * bwd: dx = rscale * (dy - mean(dy) - yhat * sum(dy * yhat) / dof), yhat = (x - mean) * rscale.
+ * Algorithmic HBM bytes: fwd 8 * R*n*C, bwd 12 * R*n*C (re-reads are served by the caches). */
+int tssep_instnorm_fwd(const float* x, int64_t ld_x, float* y, int64_t ld_y, float* mean, float* rscale,
+                       int64_t R, int64_t n, int C, int axis, int mode, int unbiased, void* stream);
+int tssep_instnorm_bwd(const float* dy, int64_t ld_dy, const float* x, int64_t ld_x, const float* mean,
+                       const float* rscale, float* dx, int64_t ld_dx, int64_t R, int64_t n, int C, int axis,
+                       int mode, int unbiased, void* stream);
+/* ReLU of the AuxNet MLP (net.py:121-123): y = max(y, 0) in place; dx = y > 0 ? dy : 0 from the OUTPUT's sign.
+ * Bytes: fwd 8 * rows*C, bwd 12 * rows*C. */
+int tssep_relu_fwd(float* y, int64_t ld, int64_t rows, int C, void* stream);
+int tssep_relu_bwd(const float* dy, int64_t ld_dy, const float* y, int64_t ld_y, float* dx, int64_t ld_dx,
+                   int64_t rows, int C, void* stream);
+/* Length-aware mean over packed rows (pad_sequence + padded_sequence_reduction 'mean', net.py:142-149):
+ * out[s, :] = mean of the rows row0[s] .. row0[s+1]-1 of h [N, C]; row0: DEVICE int64 [S+1], ascending, no empty
+ * segment.  relu != 0: the mean of max(h, 0) (fwd) and the mask h > 0 on the broadcast (bwd; h is the forward's input).
+ * bwd: dh[row, :] = dout[s, :] / len_s.  One launch for any S.  Bytes: fwd 4 * (N + S) * C, bwd 4 * (S + N [+ N]) * C. */
+int tssep_segment_mean_fwd(const float* h, int64_t ld_h, const int64_t* row0, float* out, int64_t ld_out,
+                           int64_t S, int C, int relu, void* stream);
+int tssep_segment_mean_bwd(const float* dout, int64_t ld_dout, const float* h, int64_t ld_h, const int64_t* row0,
+                           float* dh, int64_t ld_dh, int64_t S, int C, int relu, void* stream);
+
 /* -------------------------------------------------------------- mask head ----
  * mask = sigmoid(logit); est = Obs * mask   (tssep/train/net.py:981-986 +
  * tssep/train/enhancer.py:98-100).   logit/mask [B,K,T,F] fp32, obs [B,T,F] c64,

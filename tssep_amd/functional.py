@@ -342,7 +342,9 @@ def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=Fals
 
 # ---------------------------------------------------------------------- conditioning
 class _Cond(torch.autograd.Function):
-    """tssep/train/net.py:862-896 (+ trial fold :913-924).  pre rows (b,t) -> rows (b,tr,k,t)."""
+    """tssep/train/net.py:862-896 (+ trial fold :913-924).  pre rows (b,t) -> rows (b,tr,k,t).
+    An embedding that requires a gradient (aux_net, a trainable normalised embedding) gets it from one more launch over
+    dxs (hip_ops.cond_aux_bwd); a fixed embedding makes exactly the calls it always made."""
 
     @staticmethod
     def forward(ctx, pre, aux, B, K, T, trials, combination):
@@ -352,6 +354,9 @@ class _Cond(torch.autograd.Function):
         W = F if combination == "mul" else F + aux.shape[-1]
         ctx.info = info
         ctx.meta = (B, K, T, F, trials, combination, ld)
+        ctx.aux_grad = None
+        if aux.requires_grad:
+            ctx.aux_grad = (tuple(aux.shape), (pv, ld_pre) if combination == "mul" else None)
         return xs[:, :W]
 
     @staticmethod
@@ -359,7 +364,12 @@ class _Cond(torch.autograd.Function):
         B, K, T, F, trials, combination, ld = ctx.meta
         dv, ld_d = H.rows_view(dxs)
         dpre, ldp = H.cond_bwd(dv, ld_d, ctx.info, B, K, T, F, trials, combination)
-        return dpre[:, :F], None, None, None, None, None, None
+        d_aux = None
+        if ctx.aux_grad is not None and ctx.needs_input_grad[1]:
+            shape, pre = ctx.aux_grad
+            pv, ld_pre = pre if pre is not None else (None, 0)
+            d_aux = H.cond_aux_bwd(dv, ld_d, pv, ld_pre, B, K, T, F, shape[-1], trials, combination).view(shape)
+        return dpre[:, :F], d_aux, None, None, None, None, None
 
 
 def condition(pre, aux, B, K, T, trials, combination):
@@ -798,3 +808,135 @@ class _VadBCE(torch.autograd.Function):
 
 def vad_bce(logit, vad):
     return _VadBCE.apply(logit, vad)
+
+
+# ---------------------------------------------------------- learned speaker embeddings (net.py:19-158, 250-330)
+class _InstNorm(torch.autograd.Function):
+    """InstanceNorm (mode 0) / InstanceNorm_v2 (mode 1) over the last (axis 0) or the time (axis 1) dimension."""
+
+    @staticmethod
+    def forward(ctx, x, axis, mode, unbiased):
+        y, mean, rscale, xinfo = H.instnorm_fwd(x, axis, mode, unbiased)
+        ctx.save_for_backward(xinfo[0], mean, rscale)
+        ctx.meta = (xinfo[1], tuple(x.shape), axis, mode, unbiased)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xv, mean, rscale = ctx.saved_tensors
+        ld, shape, axis, mode, unbiased = ctx.meta
+        return H.instnorm_bwd(dy, (xv, ld), mean, rscale, shape, axis, mode, unbiased), None, None, None
+
+
+def instance_norm(x, axis, mode, unbiased=False):
+    return _InstNorm.apply(x.to(torch.float32), axis, mode, bool(unbiased))
+
+
+def _affine_wgrads(dv, ld_d, xv, ld_x, R, weight, bias):
+    """dW = dv^T xv and db = column sums of dv for y = x W^T + b: straight into the flat gradient bucket when the
+    parameters live there (-> None, None), through autograd otherwise."""
+    Nout, P = weight.shape
+    sw = _grad_sink(weight)
+    sb = _grad_sink(bias) if bias is not None else None
+    direct = sw is not None and (bias is None or sb is not None)
+    part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R)
+    if direct:
+        H.reduce_splits(part, S, Nout * P, sw, accumulate=True)
+        if bias is not None:
+            H.colsum(dv, ld_d, R, Nout, out=sb, accumulate=True)
+        _notify_grads([weight] + ([bias] if bias is not None else []))
+        return None, None
+    dw = torch.empty(Nout, P, device=dv.device, dtype=torch.float32)
+    H.reduce_splits(part, S, Nout * P, dw)
+    return dw, (H.colsum(dv, ld_d, R, Nout) if bias is not None else None)
+
+
+def _affine_fwd(xv, ld_x, R, weight, bias, out=None):
+    """-> (y, ld_y): rows of x W^T + b in a padded buffer."""
+    Nout, P = weight.shape
+    wv, ld_w = H.rows_view(weight.detach())
+    y, ld_y = H.padded(R, Nout, xv.device, zero=True)
+    H.gemm(xv, ld_x, wv, ld_w, y, ld_y, R, Nout, P, bias=bias.detach() if bias is not None else None)
+    return y, ld_y
+
+
+def _affine_dgrad(dv, ld_d, R, weight):
+    """-> (dx, ld): dv W in a padded buffer."""
+    Nout, P = weight.shape
+    wT, ld_t = H.derived("affine_T", [weight], lambda: H.transposed(H.rows_view(weight.detach())[0], Nout, P))
+    dx, ld_dx = H.padded(R, P, dv.device, zero=True)
+    H.gemm(dv, ld_d, wT, ld_t, dx, ld_dx, R, P, Nout)
+    return dx, ld_dx
+
+
+class _Affine(torch.autograd.Function):
+    """net.Linear (net.py:19-43): y = x W^T + b over the rows of x [..., idim]."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        xv, ld_x = H.rows_view(x)
+        R = xv.shape[0]
+        y, ld_y = _affine_fwd(xv, ld_x, R, weight, bias)
+        ctx.save_for_backward(xv)
+        ctx.params = (weight, bias)
+        ctx.meta = (R, ld_x, tuple(x.shape))
+        return y[:, :weight.shape[0]].reshape(*x.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        (xv,) = ctx.saved_tensors
+        weight, bias = ctx.params
+        R, ld_x, x_shape = ctx.meta
+        dv, ld_d = H.rows_view(dy)
+        dw, db = _affine_wgrads(dv, ld_d, xv, ld_x, R, weight, bias)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dxb, _ = _affine_dgrad(dv, ld_d, R, weight)
+            dx = dxb[:, :weight.shape[1]].reshape(x_shape)
+        return dx, dw, db
+
+
+def affine(x, weight, bias=None):
+    return _Affine.apply(x.to(torch.float32), weight, bias)
+
+
+class _AuxMLP(torch.autograd.Function):
+    """AuxNet (net.py:118-149) on PACKED enrolment rows x [N, idim] (all sequences concatenated, row0 [S+1] their
+    device prefix): Linear, ReLU, Linear, ReLU, length-aware mean, and the last (affine) Linear AFTER the mean --
+    mean(h) W3^T + b3 on [S, idim] equals the reference's mean(h W3^T + b3) and saves a third of the MLP's FLOPs.  The
+    second ReLU is fused into the mean's read.  No gradient goes to the enrolment input."""
+
+    @staticmethod
+    def forward(ctx, x, row0, S, w1, b1, w2, b2, w3, b3):
+        xv, ld_x = H.rows_view(x)
+        N, C = xv.shape[0], w1.shape[0]
+        h1, ld1 = _affine_fwd(xv, ld_x, N, w1, b1)
+        H.relu_fwd(h1, ld1, N, C)
+        z2, ld2 = _affine_fwd(h1, ld1, N, w2, b2)
+        m, ldm = H.segment_mean_fwd(z2, ld2, row0, S, C, relu=True)
+        y, ld_y = _affine_fwd(m, ldm, S, w3, b3)
+        ctx.save_for_backward(xv, h1, z2, m, row0)
+        ctx.params = (w1, b1, w2, b2, w3, b3)
+        ctx.meta = (N, S, C, ld_x, ld1, ld2, ldm)
+        return y[:, :w3.shape[0]]
+
+    @staticmethod
+    def backward(ctx, dy):
+        xv, h1, z2, m, row0 = ctx.saved_tensors
+        w1, b1, w2, b2, w3, b3 = ctx.params
+        N, S, C, ld_x, ld1, ld2, ldm = ctx.meta
+        dv, ld_d = H.rows_view(dy)
+        dw3, db3 = _affine_wgrads(dv, ld_d, m, ldm, S, w3, b3)
+        dm, ld_dm = _affine_dgrad(dv, ld_d, S, w3)
+        dz2, ld_dz2 = H.segment_mean_bwd(dm, ld_dm, z2, ld2, row0, S, N, C, relu=True)
+        dw2, db2 = _affine_wgrads(dz2, ld_dz2, h1, ld1, N, w2, b2)
+        dh1, ld_dh1 = _affine_dgrad(dz2, ld_dz2, N, w2)
+        dz1, ld_dz1 = H.relu_bwd(dh1, ld_dh1, h1, ld1, N, C)
+        dw1, db1 = _affine_wgrads(dz1, ld_dz1, xv, ld_x, N, w1, b1)
+        return None, None, None, dw1, db1, dw2, db2, dw3, db3
+
+
+def aux_mlp(x, row0, S, linears):
+    """x packed [N, idim] -> [S, odim]; linears: the three torch.nn.Linear containers of AuxNet.net."""
+    l1, l2, l3 = linears
+    return _AuxMLP.apply(x.to(torch.float32), row0, S, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)

@@ -1135,6 +1135,92 @@ def cond_bwd(dxs, ld_dxs, auxinfo, B, K, T, F, trials, combination):
     return dpre, ld
 
 
+# ---- learned speaker embeddings (csrc/aux.hip) --------------------------------------------------------------------
+def cond_aux_bwd(dxs, ld_dxs, pre, ld_pre, B, K, T, F, E, trials, combination):
+    """d(conditioning) / d(embedding) -> d_aux [B, K, C] (C = F for mul, E for cat).  A launch of its own, made only
+    when the embedding requires a gradient (pre: the pre-net rows the forward multiplied with; None for cat)."""
+    L = _lib.lib()
+    mul = combination == "mul"
+    C = F if mul else E
+    nbytes = int(L.tssep_cond_aux_bwd_workspace_bytes(B, K, T, F, 0 if mul else E))
+    if nbytes <= 0:
+        check(-1, "cond_aux_bwd_workspace_bytes")
+    ws = torch.empty(nbytes // 4, device=dxs.device, dtype=torch.float32)
+    d_aux = torch.empty(B, K, C, device=dxs.device, dtype=torch.float32)
+    with _timed("cond_aux_bwd", 0, 4 * (B * trials * K * T * C + (B * T * F if mul else 0) + B * K * C)):
+        if mul:
+            check(L.tssep_cond_mul_aux_bwd(_p(_f32(dxs)), ld_dxs, _p(_f32(pre)), ld_pre, _p(d_aux), C, _p(ws), B, K, T, F,
+                                           trials, _stream()), "cond_mul_aux_bwd")
+        else:
+            check(L.tssep_cond_cat_aux_bwd(_p(_f32(dxs)), ld_dxs, _p(d_aux), C, _p(ws), B, K, T, F, E, trials,
+                                           _stream()), "cond_cat_aux_bwd")
+    return d_aux
+
+
+INSTNORM_AXES = {-1: 0, -2: 1}      # statistics along the last axis (one per row) / along the time axis (one per column)
+
+
+def instnorm_fwd(x, axis, mode, unbiased=False):
+    """x [..., n, C] -> (y like x, mean, rscale, (xv, ld)): InstanceNorm (mode 0) / InstanceNorm_v2 (mode 1)."""
+    n, C = (x.shape[-2], x.shape[-1]) if x.dim() >= 2 else (1, x.shape[-1])
+    R = x.numel() // (n * C)
+    xv, ld = rows_view(x)
+    y = torch.empty(R * n, C, device=x.device, dtype=torch.float32)
+    stats = torch.empty(2, R * n if axis == 0 else R * C, device=x.device, dtype=torch.float32)
+    check(_lib.lib().tssep_instnorm_fwd(_p(xv), ld, _p(y), C, _p(stats[0]), _p(stats[1]), R, n, C, axis, mode,
+                                        int(bool(unbiased)), _stream()), "instnorm_fwd")
+    return y.view(x.shape), stats[0], stats[1], (xv, ld)
+
+
+def instnorm_bwd(dy, xinfo, mean, rscale, shape, axis, mode, unbiased=False):
+    xv, ld = xinfo
+    n, C = (shape[-2], shape[-1]) if len(shape) >= 2 else (1, shape[-1])
+    R = int(np.prod(shape)) // (n * C)
+    dv, ld_d = rows_view(dy)
+    dx = torch.empty(R * n, C, device=dy.device, dtype=torch.float32)
+    check(_lib.lib().tssep_instnorm_bwd(_p(dv), ld_d, _p(xv), ld, _p(mean), _p(rscale), _p(dx), C, R, n, C, axis, mode,
+                                        int(bool(unbiased)), _stream()), "instnorm_bwd")
+    return dx.view(shape)
+
+
+def relu_fwd(y, ld, rows, C):
+    """y = max(y, 0) in place on the rows of a [rows, ld] buffer."""
+    check(_lib.lib().tssep_relu_fwd(_p(_f32(y)), ld, rows, C, _stream()), "relu_fwd")
+    return y
+
+
+def relu_bwd(dy, ld_dy, y, ld_y, rows, C):
+    """-> (dx, ld): dx = y > 0 ? dy : 0 in a padded buffer."""
+    dx, ld = padded(rows, C, dy.device, zero=True)
+    check(_lib.lib().tssep_relu_bwd(_p(_f32(dy)), ld_dy, _p(_f32(y)), ld_y, _p(dx), ld, rows, C, _stream()), "relu_bwd")
+    return dx, ld
+
+
+def segment_rows(lengths, device):
+    """Prefix of the packed rows -> int64 [S+1] on the device: built on the host once, one copy."""
+    lengths = [int(n) for n in lengths]
+    assert lengths and min(lengths) > 0, lengths
+    return torch.as_tensor(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)).to(device)
+
+
+def segment_mean_fwd(h, ld_h, row0, S, C, relu=False):
+    """-> (out, ld): out[s] = mean over the rows row0[s] .. row0[s+1] - 1 of h (relu: of max(h, 0))."""
+    assert row0.dtype == torch.int64 and row0.is_cuda and row0.numel() == S + 1, (row0.dtype, row0.shape)
+    out, ld = padded(S, C, h.device, zero=True)
+    check(_lib.lib().tssep_segment_mean_fwd(_p(_f32(h)), ld_h, _p(row0), _p(out), ld, S, C, int(bool(relu)), _stream()),
+          "segment_mean_fwd")
+    return out, ld
+
+
+def segment_mean_bwd(dout, ld_dout, h, ld_h, row0, S, N, C, relu=False):
+    """-> (dh, ld) over the N packed rows: dout[s] / len_s broadcast (relu: masked with h > 0)."""
+    assert row0.dtype == torch.int64 and row0.is_cuda and row0.numel() == S + 1, (row0.dtype, row0.shape)
+    dh, ld = padded(N, C, dout.device, zero=True)
+    check(_lib.lib().tssep_segment_mean_bwd(_p(_f32(dout)), ld_dout, _p(h) if h is not None else None, ld_h, _p(row0),
+                                            _p(dh), ld, S, C, int(bool(relu)), _stream()), "segment_mean_bwd")
+    return dh, ld
+
+
 # -------------------------------------------------------------------------- mask head
 def maskhead_fwd(logit, obs):
     """logit [B,K,T,F] fp32, obs complex64 [B,T,F] -> mask [B,K,T,F], est complex64 [B,K,T,F]"""

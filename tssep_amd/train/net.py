@@ -13,8 +13,116 @@ import numpy as np
 import torch
 
 from .. import functional as Fn
-from ..configurable import Configurable
+from ..configurable import Configurable, resolve
 from .rnnp import RNNP_packed
+
+
+def _signature_repr(module):
+    import inspect
+    sig = inspect.signature(module.__class__)
+    return ", ".join(f"{p.name}={getattr(module, p.name)!r}" for p in sig.parameters.values())
+
+
+class InstanceNorm(torch.nn.Module):                   # net.py:250-285
+    """(x - mean) / std along ``dim``: -1 (one statistic per row) or -2 (the time axis, one per column)."""
+
+    def __init__(self, dim=-1, unbiased=False):
+        super().__init__()
+        if dim not in Fn.H.INSTNORM_AXES:
+            raise NotImplementedError(f"InstanceNorm(dim={dim}): the kernels cover dim -1 and -2")
+        self.dim = dim
+        self.unbiased = unbiased
+
+    def extra_repr(self):
+        return _signature_repr(self)
+
+    def forward(self, x):
+        return Fn.instance_norm(x, Fn.H.INSTNORM_AXES[self.dim], 0, self.unbiased)
+
+
+class InstanceNorm_v2(torch.nn.Module):                # net.py:288-330
+    """(x - mean) / (||x - mean|| / sqrt(n)) along one dim (-1 or -2)."""
+
+    def __init__(self, mean_dim=-1, norm_dim=-1):
+        super().__init__()
+        if mean_dim != norm_dim:
+            raise NotImplementedError(f"InstanceNorm_v2(mean_dim={mean_dim}, norm_dim={norm_dim}): "
+                                      "one kernel pass takes both statistics along the same dim")
+        if mean_dim not in Fn.H.INSTNORM_AXES:
+            raise NotImplementedError(f"InstanceNorm_v2(mean_dim={mean_dim}): the kernels cover dim -1 and -2")
+        self.mean_dim = mean_dim
+        self.norm_dim = norm_dim
+
+    def extra_repr(self):
+        return _signature_repr(self)
+
+    def forward(self, x):
+        return Fn.instance_norm(x, Fn.H.INSTNORM_AXES[self.mean_dim], 1)
+
+
+def _stack_aux(aux):
+    """(lists of) lists of [E] tensors -> one tensor (net.py:38-42, 840-851)."""
+    if isinstance(aux, (tuple, list)):
+        return torch.stack([torch.stack(list(a), 0) if isinstance(a, (tuple, list)) else a for a in aux], 0)
+    return aux
+
+
+class Linear(Configurable, torch.nn.Module):           # net.py:19-43: how i-vectors enter a `mul` model
+    def __init__(self, idim, odim, bias=True):
+        super().__init__()
+        self.idim = idim
+        self.odim = odim
+        self.bias = bias
+        self.net = torch.nn.Linear(idim, odim, bias=bias)
+
+    def forward(self, AuxInput, Input=None, batched=False):
+        return Fn.affine(_stack_aux(AuxInput), self.net.weight, self.net.bias)
+
+
+class AuxNet(Configurable, torch.nn.Module):           # net.py:46-158
+    """SpeakerBeam-style auxiliary network: three Linear layers over the enrolment frames of every speaker and the mean
+    over time.  The reference pads the sequences and takes a length-aware mean; padding rows never reach its result, so
+    the sequences are PACKED here (concatenated, one device prefix of their lengths) and nothing is padded."""
+
+    @classmethod
+    def finalize_dogmatic_config(cls, config):
+        if config.get("odim") is None:
+            config["odim"] = config.get("idim")
+
+    def __init__(self, idim, odim=None, normalizer: "InstanceNorm" = None):
+        super().__init__()
+        if odim is None:
+            odim = idim
+        elif idim != odim:
+            raise NotImplementedError(odim, idim)
+        if normalizer is not None:
+            if not isinstance(normalizer, (InstanceNorm, InstanceNorm_v2)):
+                raise NotImplementedError(f"AuxNet normalizer {type(normalizer).__name__}")
+            if getattr(normalizer, "dim", getattr(normalizer, "mean_dim", None)) != -1:
+                raise NotImplementedError(
+                    "AuxNet normalizer along the time axis: the reference takes its statistics over the PADDED "
+                    "sequences (zeros behind the shorter ones included); only dim=-1 is the same on packed rows")
+        self.idim, self.odim = idim, odim
+        self.net = Sequential(*[e for e in [normalizer] if e is not None],
+                              torch.nn.Linear(idim, idim), torch.nn.ReLU(),
+                              torch.nn.Linear(idim, idim), torch.nn.ReLU(),
+                              torch.nn.Linear(idim, idim))
+
+    def forward(self, AuxInput, Input=None, batched=False):
+        h = AuxInput
+        if batched:
+            assert len({len(a) for a in AuxInput}) == 1, [len(a) for a in AuxInput]
+            h = [e for a in AuxInput for e in a]
+        lengths = [int(e.shape[0]) for e in h]
+        x = torch.cat([e.reshape(-1, self.idim) for e in h], 0)
+        row0 = Fn.H.segment_rows(lengths, x.device)           # built on the host from the lengths, one copy
+        mods = list(self.net)
+        if not isinstance(mods[0], torch.nn.Linear):
+            x = mods[0](x).detach()
+        y = Fn.aux_mlp(x, row0, len(lengths), [m for m in mods if isinstance(m, torch.nn.Linear)])
+        if batched:
+            y = y.reshape(len(AuxInput), -1, y.shape[-1])
+        return y
 
 
 @dataclasses.dataclass
@@ -45,10 +153,17 @@ class _Marker(torch.nn.Module):
 class MaskEstimator_v2(Configurable, torch.nn.Module):
     @classmethod
     def finalize_dogmatic_config(cls, config):        # net.py:342-499
-        if config.get("aux_net") is not None:
-            raise NotImplementedError("aux_net (null in every shipped config, init_cfg_common.yaml:70)")
-        if config.get("combination", "cat") == "cat" and config.get("aux_net_output_size") is None:
-            config["aux_net_output_size"] = 100
+        aux_net = config.get("aux_net")
+        if aux_net is None:
+            if config.get("combination", "cat") == "cat" and config.get("aux_net_output_size") is None:
+                config["aux_net_output_size"] = 100            # i-vectors (net.py:488-490)
+        elif isinstance(aux_net, dict):                        # net.py:491-499
+            if issubclass(resolve(aux_net["factory"]), AuxNet):
+                aux_net["idim"] = config.get("odim") or config.get("idim")
+                if aux_net.get("odim") is None:
+                    aux_net["odim"] = aux_net["idim"]
+            if config.get("combination", "cat") == "cat" and "odim" in aux_net:
+                config["aux_net_output_size"] = aux_net["odim"]
 
     def __init__(self, *, idim=80, odim=None, layers=3, units=300, projs=320, dropout=0, nmask=1,
                  pre_net="RNNP", aux_net=None, aux_net_output_size=None, combination: str = "cat",
@@ -58,8 +173,12 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         super().__init__()
         if odim is None:
             odim = idim
-        if aux_net is not None or input_normalizer is not None or aux_normalizer is not None:
-            raise NotImplementedError("aux_net / normalizers are outside the hot path (SURVEY 2.1 #2)")
+        for name, norm in (("input_normalizer", input_normalizer), ("aux_normalizer", aux_normalizer)):
+            if norm is not None and not isinstance(norm, (InstanceNorm, InstanceNorm_v2)):
+                raise NotImplementedError(f"{name}: {type(norm).__name__} (InstanceNorm / InstanceNorm_v2 are built)")
+        if aux_net is not None and not isinstance(aux_net, (Linear, AuxNet)):
+            raise NotImplementedError(f"aux_net: {type(aux_net).__name__} (Linear / AuxNet are built)")
+        assert aux_net is None or aux_normalizer is None, (aux_normalizer, "Not clear, whether before or after")   # net.py:834
         if explicit_vad and output_resolution == "t":
             raise AssertionError("explicit_vad needs output_resolution='tf' (net.py:643)")
         if nmask != 1:
@@ -97,7 +216,10 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
 
         ts_factor = 1
         if combination == "cat":
-            assert aux_net_output_size is not None, (combination, aux_net_output_size)
+            if aux_net is None:
+                assert aux_net_output_size is not None, (combination, aux_net_output_size)
+            else:                                                # net.py:590-595
+                assert aux_net_output_size == aux_net.odim, (combination, aux_net_output_size, aux_net)
             first_birnn_idim = odim + aux_net_output_size
         elif combination in ["mul"]:
             first_birnn_idim = odim
@@ -172,18 +294,34 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
             lg, emb = self.logits(xs[None], [aux])
             return lg[0], emb[0]
         assert xs.dim() == 3, xs.shape
-        if isinstance(aux, (tuple, list)):
-            aux = torch.stack([torch.stack(list(a), 0) if isinstance(a, (tuple, list)) else a
-                               for a in aux], 0)
         B, T = xs.shape[0], xs.shape[1]
-        K = aux.shape[1]
         dev = xs.device
+        ragged = isinstance(self.aux_net, AuxNet)       # enrolment sequences [T_i, idim]: lists, shuffled on the host
+        if ragged:
+            aux = [list(a) for a in aux]
+        else:
+            aux = _stack_aux(aux)
+        K = len(aux[0]) if ragged else aux.shape[1]
         perm_d = iperm_d = None
-        if self.random_speaker_order:
+        if self.random_speaker_order:                   # the RAW aux entries are shuffled (net.py:823-831)
             perm_d, iperm_d = self._speaker_permutations(B, K, dev)
-            # shuffled aux[b, s] = aux[b, perm[b, s]]: one gather for the whole batch
-            aux = torch.gather(aux, 1, perm_d.long()[..., None].expand(-1, -1, aux.shape[-1]))
-        aux = aux.to(torch.float32).contiguous()
+            if ragged:
+                perm_h = perm_d.tolist()
+                aux = [[a[i] for i in q] for a, q in zip(aux, perm_h)]
+            else:
+                # shuffled aux[b, s] = aux[b, perm[b, s]]: one gather for the whole batch
+                aux = torch.gather(aux, 1, perm_d.long()[..., None].expand(-1, -1, aux.shape[-1]))
+        if self.aux_net is not None:                    # net.py:833-838
+            aux = self.aux_net(aux, xs, batched=True)
+        else:
+            aux = aux.to(torch.float32)
+            if self.aux_normalizer is not None:         # net.py:852-853
+                aux = self.aux_normalizer(aux)
+        if aux.dim() != 3:
+            raise NotImplementedError(f"embeddings with a time axis (the attention branch, net.py:866-867): {tuple(aux.shape)}")
+        aux = aux.contiguous()
+        if self.input_normalizer is not None:           # net.py:858-859
+            xs = self.input_normalizer(xs)
         if self.ts_vad is not False:
             assert K == self.ts_vad, (K, self.ts_vad)
         trials = self.num_averaged_permutations
