@@ -272,10 +272,10 @@ def mask_istft_gated_bwd(dy, logit, obs, wsyn, size=1024, shift=256, fading=True
     if loss is None:
         x, tgt, sums, gout = _f32(dy).contiguous(), None, None, None
     else:
-        x, tgt, sums, gout = (_f32(loss[0]).contiguous(), _f32(loss[1]).contiguous(), loss[2],
-                              _f32(loss[3]).contiguous())
+        x, tgt, sums, gout = (_f32(loss[0]).contiguous(), _f32(loss[1]).contiguous(),
+                              _f32(loss[2]).contiguous() if loss[2] is not None else None, _f32(loss[3]).contiguous())
     assert tuple(x.shape[:2]) == (B, K) and (tgt is None or tgt.shape == x.shape), (tuple(x.shape), B, K)
-    assert gout is None or gout.numel() == B
+    assert (gout is None or gout.numel() == B) and (sums is None or sums.numel() == B)
     v = gv = None
     if vad is not None:
         v, gv = _f32(vad[0]).contiguous(), _f32(vad[1]).contiguous()
