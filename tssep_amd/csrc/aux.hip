@@ -229,12 +229,17 @@ __global__ __launch_bounds__(256) void instnorm_time_bwd_kernel(const float* __r
 }
 
 // ---- ReLU (net.py:121-123) ------------------------------------------------------------------------------------
+// torch.nn.ReLU keeps NaN (fmaxf would return the 0: a NaN in an enrolment activation has to reach the loss, not be trained
+// on as a zero), and its gradient is zero where the activation is <= 0, so it passes at a NaN.  Finite inputs: max(v, 0)
+// and y > 0, bit for bit.
+__device__ __forceinline__ float relu_keep_nan(float v) { return (v > 0.f || v != v) ? v : 0.f; }
+__device__ __forceinline__ bool relu_passes(float y) { return !(y <= 0.f); }
 __global__ void relu_fwd_kernel(float* __restrict__ y, int64_t ld, int64_t rows, int C) {
   const int64_t total = rows * C;
   GRID_STRIDE(e, total) {
     const int64_t row = e / C;
     float* p = y + row * ld + (e - row * C);
-    *p = fmaxf(*p, 0.f);
+    *p = relu_keep_nan(*p);
   }
 }
 __global__ void relu_fwd_v4_kernel(f32x4* __restrict__ y, int64_t ldq, int64_t rows, int nq) {
@@ -243,7 +248,7 @@ __global__ void relu_fwd_v4_kernel(f32x4* __restrict__ y, int64_t ldq, int64_t r
     const int64_t row = e / nq;
     f32x4* p = y + row * ldq + (e - row * nq);
     const f32x4 v = *p;
-    const f32x4 o = {fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+    const f32x4 o = {relu_keep_nan(v[0]), relu_keep_nan(v[1]), relu_keep_nan(v[2]), relu_keep_nan(v[3])};
     *p = o;
   }
 }
@@ -252,7 +257,7 @@ __global__ void relu_bwd_kernel(const float* __restrict__ dy, int64_t ld_dy, con
   const int64_t total = rows * C;
   GRID_STRIDE(e, total) {
     const int64_t row = e / C, c = e - row * C;
-    dx[row * ld_dx + c] = y[row * ld_y + c] > 0.f ? dy[row * ld_dy + c] : 0.f;
+    dx[row * ld_dx + c] = relu_passes(y[row * ld_y + c]) ? dy[row * ld_dy + c] : 0.f;
   }
 }
 __global__ void relu_bwd_v4_kernel(const f32x4* __restrict__ dy, int64_t ld_dy, const f32x4* __restrict__ y,
@@ -261,14 +266,15 @@ __global__ void relu_bwd_v4_kernel(const f32x4* __restrict__ dy, int64_t ld_dy, 
   GRID_STRIDE(e, total) {
     const int64_t row = e / nq, q = e - row * nq;
     const f32x4 g = dy[row * ld_dy + q], v = y[row * ld_y + q];
-    const f32x4 o = {v[0] > 0.f ? g[0] : 0.f, v[1] > 0.f ? g[1] : 0.f, v[2] > 0.f ? g[2] : 0.f,
-                     v[3] > 0.f ? g[3] : 0.f};
+    const f32x4 o = {relu_passes(v[0]) ? g[0] : 0.f, relu_passes(v[1]) ? g[1] : 0.f, relu_passes(v[2]) ? g[2] : 0.f,
+                     relu_passes(v[3]) ? g[3] : 0.f};
     dx[row * ld_dx + q] = o;
   }
 }
 
 // ---- length-aware mean over packed rows (padded_sequence_reduction, net.py:147-149, 989-) ------------------------
-// one workgroup per (segment s, tile of 64 columns): rows row0[s] .. row0[s+1] - 1, summed like time_sum
+// one workgroup per (segment s, tile of 64 columns): rows row0[s] .. row0[s+1] - 1, summed like time_sum; the fused ReLU
+// and its mask are relu_keep_nan / relu_passes above
 __global__ __launch_bounds__(256) void segment_mean_fwd_kernel(const float* __restrict__ h, int64_t ld_h,
                                                                const int64_t* __restrict__ row0,
                                                                float* __restrict__ out, int64_t ld_out, int C,
@@ -282,7 +288,7 @@ __global__ __launch_bounds__(256) void segment_mean_fwd_kernel(const float* __re
   const float* hc = h + r0 * ld_h + c;
   const float sum = time_sum(red, n, lane, w, active, [&](int64_t t) {
     const float v = hc[t * ld_h];
-    return relu ? fmaxf(v, 0.f) : v;
+    return relu ? relu_keep_nan(v) : v;
   });
   if (active && w == 0) out[s * ld_out + c] = sum / (float)n;
 }
@@ -299,7 +305,7 @@ __global__ __launch_bounds__(256) void segment_mean_bwd_kernel(const float* __re
   const float g = dout[s * ld_dout + c] / (float)n;
   for (int64_t t = w; t < n; t += 4) {
     const int64_t row = r0 + t;
-    dh[row * ld_dh + c] = (!relu || h[row * ld_h + c] > 0.f) ? g : 0.f;
+    dh[row * ld_dh + c] = (!relu || relu_passes(h[row * ld_h + c])) ? g : 0.f;
   }
 }
 
