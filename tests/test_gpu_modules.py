@@ -488,8 +488,20 @@ def test_direct_grad_sink_matches_autograd():
     me.zero_grad(set_to_none=True)
     bucket = GradBucket(me.parameters())
     assert hip_ops.OVERLAP_WGRAD
-    run()
-    run()
+    # `_tssep_grad_sink` is buffer 0 of `_tssep_grad_sinks`, the list functional._grad_sink reads: every parameter offers
+    # a sink, and the layers do take the direct path (their unpacks accumulate) instead of returning through autograd
+    from tssep_amd import functional as Fn
+    for p in me.parameters():
+        assert p._tssep_grad_sinks[0] is p._tssep_grad_sink and Fn._grad_sink(p) is p._tssep_grad_sink
+        assert 0 <= p.grad.data_ptr() - bucket.flat.data_ptr() <= 4 * (bucket.flat.numel() - p.numel())
+    direct, unpack = [], hip_ops.lstm_unpack
+    hip_ops.lstm_unpack = lambda *a, accumulate=False: (direct.append(bool(accumulate)), unpack(*a, accumulate=accumulate))[1]
+    try:
+        run()
+        run()
+    finally:
+        hip_ops.lstm_unpack = unpack
+    assert direct and all(direct), direct
     bucket.sync()
     torch.cuda.synchronize()
     for (name, p), r in zip(me.named_parameters(), ref):

@@ -522,6 +522,11 @@ def colsum(A, lda, M, N, out=None, accumulate=False):
 # through torch (its ``_version`` counter moves: load_state_dict, copy_) or through the fused Adam kernel
 # (raw pointer: ``weights_changed()`` is called by the optimizer).  Never used while a stream is being
 # captured: a graph must contain the pack kernels, the weights differ at every replay.
+# The ``.data`` rule: a write that reaches the storage past the parameter object -- ``p.data.copy_(...)``, any torch
+# operation on ``optimizer.flat_param`` (whose views the parameters' ``.data`` are), a collective into it -- moves
+# neither signal (``p._version`` counts writes through ``p`` itself only).  Whoever writes that way calls
+# ``weights_changed()`` afterwards (train/trainer.py: adopt_rank0_state); a layout built before such a write would
+# otherwise serve the forward after it.
 WEIGHTS_VERSION = 0
 
 

@@ -48,6 +48,16 @@ class _closing:
         return False
 
 
+def adopt_rank0_state(optimizer):
+    """Rank 0's parameters and Adam moments into this rank's flat buffers.  The broadcast writes `flat_param` behind the
+    parameters' backs (their ``_version`` does not move), so the derived weight layouts are declared stale here
+    (hip_ops.derived): a forward that ran before this call must not lend its packs to the one after it."""
+    for t in (optimizer.flat_param, optimizer.exp_avg, optimizer.exp_avg_sq):
+        _dist.broadcast_(t, src=0)
+    from .. import hip_ops
+    hip_ops.weights_changed()
+
+
 class Trainer(Configurable):
     def __init__(self, model, storage_dir, optimizer, summary_trigger=(1, "epoch"),
                  checkpoint_trigger=(1, "epoch"), stop_trigger=(1, "epoch"),
@@ -212,8 +222,7 @@ class Trainer(Configurable):
             # identical replicas: rank 0's parameters (and, after a resume, its Adam moments); a speaker
             # permutation / shuffle stream of its own per rank, derived from the current state so that a
             # seeded run stays reproducible
-            for t in (self.optimizer.flat_param, self.optimizer.exp_avg, self.optimizer.exp_avg_sq):
-                _dist.broadcast_(t, src=0)
+            adopt_rank0_state(self.optimizer)
             np.random.seed((int(np.random.get_state()[1][0]) + 7919 * rank) & 0x7FFFFFFF)
             dev = self._cuda_device()
             if dev is not None:      # dropout masks of its own per rank, likewise
