@@ -579,6 +579,37 @@ int tssep_mvdr_souden_fwd(const double* obs, const void* masks, int mask_f64, do
                           int F, int reference_channel, double eps, int masking,
                           double masking_eps, void* stream);
 
+/* Backward of tssep_mvdr_souden_fwd: dmask [B,K,M,T,F] (the masks' dtype) = d(loss)/d(masks) for
+ * genh [B,K,T,F] complex128 = d(loss)/d(enh) in torch's convention for complex tensors; the observation gets no
+ * gradient.  With P = phi, lam = Re trace(P), c = max(lam, eps), g = max(mask 0, masking_eps) (masking) or 1:
+ *   gw   = sum_t conj(genh g) Y[:,t]                  gP = (gw / c) e_ref^T + gc I,
+ *   gc   = -Re(gw^H P[:, ref]) / c^2 where lam >= eps, else 0 (the clamp passes the gradient at equality)
+ *   Z    = psd_1^-H gP       Hs = herm(Z)       Hn = herm(-Z P^H)
+ *   dmask[:,:,0] = Re(y^H Hs y) (+ Re(conj(enh / g) genh) where mask 0 >= masking_eps, with masking)
+ *   dmask[:,:,1] = Re(y^H Hn y)           (M == 1: dmask[:,:,0] uses Hs - Hn instead of Hs)
+ * fwd_workspace: the workspace tssep_mvdr_souden_fwd left behind for the same arguments (the reduced statistics in
+ * chunk 0 of its partials, then wconj); phi is recomputed from it with the forward's own elimination.
+ * bwd_workspace (16-byte aligned, tssep_mvdr_bwd_workspace_bytes(); host-only, 0 for an unsupported shape):
+ *   gw_partials doubles [B][chunks][K][2*D][F] (rows Re gw_d, Im gw_d; the chunks of the forward's statistics pass;
+ *   _bwd_solve adds them into chunk 0), rounded up to 16 bytes, then
+ *   herm        doubles [B][K][M][D*D][F], packed Hermitian like the statistics: rows 0..D-1 the diagonal, then for
+ *   every pair i < j in row-major order the rows Re H[i,j], Im H[i,j];  M == 2: Hs, Hn;  M == 1: Hs - Hn.
+ * masks, genh and wconj may be NULL without masking.  No atomics: every result is identical from run to run; every
+ * element of dmask is written exactly once.  No host sync. */
+int64_t tssep_mvdr_bwd_workspace_bytes(int64_t B, int K, int M, int D, int64_t T, int F);
+int tssep_mvdr_bwd_gw(const double* obs, const double* genh, const void* masks, int mask_f64,
+                      double* gw_partials, int64_t B, int K, int M, int D, int64_t T, int F, int masking,
+                      double masking_eps, void* stream);
+int tssep_mvdr_bwd_solve(const double* fwd_partials, double* gw_partials, double* herm, int64_t B, int K,
+                         int M, int D, int64_t T, int F, int reference_channel, double eps, void* stream);
+int tssep_mvdr_bwd_mask(const double* obs, const double* genh, const double* wconj, const double* herm,
+                        const void* masks, int mask_f64, void* dmask, int64_t B, int K, int M, int D,
+                        int64_t T, int F, int masking, double masking_eps, void* stream);
+int tssep_mvdr_souden_bwd(const double* obs, const void* masks, int mask_f64, const double* genh,
+                          const void* fwd_workspace, void* bwd_workspace, void* dmask, int64_t B, int K,
+                          int M, int D, int64_t T, int F, int reference_channel, double eps, int masking,
+                          double masking_eps, void* stream);
+
 /* Segment-wise MVDR: ClassicBF_np('mvdr_souden') of the reference with segment_bf=True,
  * tssep/train/enhancer.py:451-590, one beamformer per row (k, s, e) of a segment table:
  *   n_k         = max(sum_{j != k} m_j, distortion_eps)   mode 0, SumCrossTalker (ascending j,

@@ -1016,3 +1016,600 @@ extern "C" int tssep_mvdr_segments_fwd_obs(const double* obs_seg, const int64_t*
   return seg_fwd(obs_seg, masks, mask_f64, segments, enh, workspace, info, K, S, D, T, F, mode, distortion_eps,
                  mask_power, psd_real, eps, masking, masking_eps, row0, N, stream);
 }
+
+// ------------------------------------------------------------------ backward of the Souden MVDR ----
+// d(loss)/d(masks) of tssep_mvdr_souden_fwd for a given G = d(loss)/d(enh) (torch's convention for complex
+// tensors); the observation gets no gradient.  Per (b, k, f), with P = Phi_n^-1 Phi_s, lam = Re tr P,
+// c = max(lam, eps), e(t) = w^H y_t, g(t) = max(m_s(t), masking_eps) with masking, else 1:
+//   gw  = sum_t conj(G(t) g(t)) y_t                                       mvdr_bwd_gw_kernel<D>, time pass 1
+//   gP  = (gw / c) e_ref^T + gc I,  gc = -Re(gw^H P[:, ref]) / c^2 where lam >= eps, else 0
+//   Z   = Phi_n^-H gP,  Hs = herm(Z),  Hn = herm(-Z P^H)                  mvdr_bwd_solve_kernel<D>
+//   dm_s(t) = Re(y_t^H Hs y_t) [+ Re(conj(e(t)) G(t)) where m_s(t) >= masking_eps]
+//   dm_n(t) = Re(y_t^H Hn y_t)         (M = 1: one matrix Hs - Hn)        mvdr_bwd_mask_kernel<D>, time pass 2
+// Both time passes keep the forward's layout: lane = bin, one wave per (64 bins, time chunk, speaker), four
+// speakers per workgroup sharing the Y frames through LDS, the chunks of make_plan.  The chunk partials of gw
+// are added in chunk order by mvdr_reduce_kernel; pass 2 writes every element of dmask exactly once (the masking
+// term is formed there, from the forward's wconj): no atomics, run-to-run identical.
+// Saved between forward and backward: nothing but the forward's workspace -- the reduced statistics (chunk 0 of
+// the partials) and wconj.  P and lam are NOT saved: the solve repeats the forward's elimination, the same
+// operations in the same order, so it sees the P and the clamp decision the forward saw, bit for bit.
+namespace {
+
+template <typename MT> struct GradRegs { double2 g[PW]; MT m[PW]; };
+
+template <int D, typename MT>
+__global__ __launch_bounds__(64 * PW, 2) void mvdr_bwd_gw_kernel(
+    const double2* __restrict__ obs, const double2* __restrict__ genh, const MT* __restrict__ masks,
+    double* __restrict__ part, int64_t B, int K, int M, int64_t T, int F, Plan plan, int masking,
+    double masking_eps) {
+  __shared__ double2 ybuf[2][PW][D][64];
+  const int groups = (K + PW - 1) / PW;
+  int64_t tile;
+  int grp;
+  if (!xcd_tile(blockIdx.x, groups, B * plan.chunks * plan.nf, tile, grp)) return;
+  const int ft = (int)(tile % plan.nf);
+  const int c = (int)((tile / plan.nf) % plan.chunks);
+  const int64_t b = tile / ((int64_t)plan.nf * plan.chunks);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int k = grp * PW + wave;
+  const bool kvalid = k < K;
+  const int fraw = ft * 64 + lane;
+  const int f = fraw < F ? fraw : F - 1;
+  const int64_t t0 = c * plan.tchunk;
+  const int64_t t1 = t0 + plan.tchunk < T ? t0 + plan.tchunk : T;
+  const int steps = (int)((t1 - t0 + PW - 1) / PW);
+  const int64_t bk = b * K + (kvalid ? k : 0);
+  const MT* mk0 = masks + (bk * M) * T * F + f;              // only read with masking
+  const double2* g0 = genh + bk * T * F + f;
+  const double2* y0 = obs + b * D * T * F + f;
+
+  double2 acc[D];
+#pragma unroll
+  for (int d = 0; d < D; ++d) acc[d] = double2{0.0, 0.0};
+  // the forward's frame pipeline (mvdr_psd_kernel): wave w brings frame t0 + PW s + w of step s
+  auto fetch_y = [&](int s_) {
+    const int64_t t = t0 + (int64_t)s_ * PW + wave;
+    if (t < t1) {
+#pragma unroll
+      for (int d = 0; d < D; ++d)
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)(y0 + (d * T + t) * F),
+            (__attribute__((address_space(3))) void*)&ybuf[s_ & 1][wave][d][0], 16, 0, 0);
+    } else {
+#pragma unroll
+      for (int d = 0; d < D; ++d) ybuf[s_ & 1][wave][d][lane] = double2{0.0, 0.0};
+    }
+  };
+  auto fetch_g = [&](int s_, GradRegs<MT>& r) {
+    // frames past the chunk read the last frame's G and meet zero-filled Y
+#pragma unroll
+    for (int fr = 0; fr < PW; ++fr) {
+      int64_t tt = t0 + (int64_t)s_ * PW + fr;
+      tt = tt < t1 ? tt : t1 - 1;
+      r.g[fr] = g0[tt * F];
+      r.m[fr] = masking ? mk0[tt * F] : (MT)1;
+    }
+  };
+  auto compute = [&](int s_, const GradRegs<MT>& r) {
+#pragma unroll
+    for (int fr = 0; fr < PW; ++fr) {
+      double2 g = r.g[fr];
+      if (masking) {                                          // Ge = G max(m_s, masking_eps)
+        double mk = (double)r.m[fr];
+        if (mk < masking_eps) mk = masking_eps;
+        g.x *= mk;
+        g.y *= mk;
+      }
+#pragma unroll
+      for (int d = 0; d < D; ++d) {                           // conj(Ge) y_d
+        const double2 y = ybuf[s_ & 1][fr][d][lane];
+        acc[d].x += g.x * y.x + g.y * y.y;
+        acc[d].y += g.x * y.y - g.y * y.x;
+      }
+    }
+  };
+  GradRegs<MT> ra, rb;
+  fetch_y(0);
+  fetch_g(0, ra);
+  for (int s = 0; s < steps; s += 2) {
+    __syncthreads();
+    if (s + 1 < steps) { fetch_y(s + 1); fetch_g(s + 1, rb); }
+    if (kvalid) compute(s, ra);
+    if (s + 1 >= steps) break;
+    __syncthreads();
+    if (s + 2 < steps) { fetch_y(s + 2); fetch_g(s + 2, ra); }
+    if (kvalid) compute(s + 1, rb);
+  }
+  if (!kvalid || fraw >= F) return;
+  double* out = part + (((b * plan.chunks + c) * K + k) * (int64_t)(2 * D)) * F + f;
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    out[(int64_t)(2 * d) * F] = acc[d].x;
+    out[(int64_t)(2 * d + 1) * F] = acc[d].y;
+  }
+}
+
+// The three D x D complex matrices of one system: registers (every index static after unrolling) or LDS
+// ([matrix][element][lane]).  Two matrices as in the forward pair would not do: P is needed next to the
+// factors of Phi_n and Z.
+constexpr bool bwd_in_registers(int D) { return D <= 6; }
+constexpr int bwd_lanes(int D) {        // bins per workgroup: what 3 D^2 complex doubles per lane leave room for in 160 KB
+  return bwd_in_registers(D) || 3 * D * D * 64 * 16 <= 160 * 1024 ? 64 : 32;
+}
+template <int D, bool REG, int LB> struct Sys3 {
+  double2 r[REG ? 3 : 1][REG ? D : 1][REG ? D : 1];
+  double2* s;
+  __device__ __forceinline__ double2 get(int m, int i, int j) const {
+    if constexpr (REG) return r[m][i][j]; else return s[((m * D + i) * D + j) * LB];
+  }
+  __device__ __forceinline__ void set(int m, int i, int j, double2 v) {
+    if constexpr (REG) r[m][i][j] = v; else s[((m * D + i) * D + j) * LB] = v;
+  }
+};
+
+// One lane per (b, k, bin).  part: the forward's partials with the chunk sums in chunk 0; gw: the reduced
+// chunk 0 of pass 1; herm [B, K, M, D*D, F] packed Hermitian (M = 2: Hs, Hn; M = 1: Hs - Hn).
+// Phi_n is read from its packed form and so is exactly Hermitian: Phi_n^H Z = gP is solved with the factors of
+// Phi_n itself, the row exchanges and multipliers of the elimination recorded and replayed on gP.
+// A singular system (the forward raises for those) divides by zero in its own lane only: Inf / NaN stay in the bin.
+template <int D>
+__global__ __launch_bounds__(64) void mvdr_bwd_solve_kernel(
+    const double* __restrict__ part, const double* __restrict__ gw, double* __restrict__ herm,
+    int64_t B, int K, int M, int F, int chunks, int ref, double eps) {
+  constexpr bool REG = bwd_in_registers(D);
+  constexpr int LB = bwd_lanes(D);
+  constexpr int DD = D * D;
+  extern __shared__ double2 sm[];
+  const int lane = threadIdx.x;
+  const int nfl = (F + LB - 1) / LB;
+  const int ft = blockIdx.x % nfl;
+  const int k = (blockIdx.x / nfl) % K;
+  const int64_t b = blockIdx.x / ((int64_t)nfl * K);
+  const int f = ft * LB + lane;
+  if (lane >= LB || f >= F) return;
+  Sys3<D, REG, LB> S;
+  S.s = sm + lane;
+  enum { A = 0, X = 1, Z = 2 };
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const double* q = part + (((b * chunks) * K + k) * 2 + m) * (int64_t)DD * F + f;
+    const int dst = m ? A : X;
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) S.set(dst, i, i, double2{q[(int64_t)i * F], 0.0});
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = i + 1; j < D; ++j, ++p) {
+        const double re = q[(int64_t)(D + 2 * p) * F], im = q[(int64_t)(D + 2 * p + 1) * F];
+        S.set(dst, i, j, double2{re, im});
+        S.set(dst, j, i, double2{re, -im});
+      }
+  }
+  // ---- the forward's elimination of [A | X] (mvdr_solve_kernel), keeping the exchanges and the multipliers
+  int pv[D];
+#pragma unroll
+  for (int p = 0; p < D; ++p) {
+    int piv = p;
+    double best = fabs(S.get(A, p, p).x) + fabs(S.get(A, p, p).y);
+#pragma unroll
+    for (int i = p + 1; i < D; ++i) {
+      const double2 a = S.get(A, i, p);
+      const double v = fabs(a.x) + fabs(a.y);
+      if (v > best) { best = v; piv = i; }
+    }
+    pv[p] = piv;
+#pragma unroll
+    for (int i = p + 1; i < D; ++i) {
+      const bool sw = piv == i;
+#pragma unroll
+      for (int j = p; j < D; ++j) {
+        const double2 t = S.get(A, p, j), u = S.get(A, i, j);
+        S.set(A, p, j, sel(sw, u, t));
+        S.set(A, i, j, sel(sw, t, u));
+      }
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        const double2 t = S.get(X, p, j), u = S.get(X, i, j);
+        S.set(X, p, j, sel(sw, u, t));
+        S.set(X, i, j, sel(sw, t, u));
+      }
+    }
+    const double2 r = crecip(S.get(A, p, p));
+#pragma unroll
+    for (int i = p + 1; i < D; ++i) {
+      const double2 l = cmul(S.get(A, i, p), r);
+      S.set(A, i, p, l);                                      // kept for the replay on gP
+#pragma unroll
+      for (int j = p + 1; j < D; ++j) {
+        const double2 a = S.get(A, p, j), x = S.get(A, i, j);
+        S.set(A, i, j, double2{x.x - (l.x * a.x - l.y * a.y), x.y - (l.x * a.y + l.y * a.x)});
+      }
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        const double2 a = S.get(X, p, j), x = S.get(X, i, j);
+        S.set(X, i, j, double2{x.x - (l.x * a.x - l.y * a.y), x.y - (l.x * a.y + l.y * a.x)});
+      }
+    }
+  }
+#pragma unroll
+  for (int i = D - 1; i >= 0; --i) {
+    const double2 r = crecip(S.get(A, i, i));
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      double2 s = S.get(X, i, j);
+#pragma unroll
+      for (int q = i + 1; q < D; ++q) {
+        const double2 a = S.get(A, i, q), x = S.get(X, q, j);
+        s.x -= a.x * x.x - a.y * x.y;
+        s.y -= a.x * x.y + a.y * x.x;
+      }
+      S.set(X, i, j, cmul(s, r));                             // X holds P from here on
+    }
+  }
+  double lam = 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i) lam += S.get(X, i, i).x;
+  const bool open = lam >= eps;                               // the clamp passes the gradient at equality
+  if (lam < eps) lam = eps;
+  const double scl = 1.0 / lam;
+  // ---- gP = (gw / c) e_ref^T + gc I
+  const double* gq = gw + (((b * chunks) * K + k) * (int64_t)(2 * D)) * F + f;
+  double2 u[D];
+  double dot = 0.0;
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    const double2 g = double2{gq[(int64_t)(2 * d) * F], gq[(int64_t)(2 * d + 1) * F]};
+    double2 p = S.get(X, d, 0);
+#pragma unroll
+    for (int cc = 1; cc < D; ++cc) p = sel(ref == cc, S.get(X, d, cc), p);
+    dot += g.x * p.x + g.y * p.y;                             // Re(conj(gw_d) P[d, ref])
+    u[d] = double2{g.x * scl, g.y * scl};
+  }
+  const double gc = open ? -(dot * scl * scl) : 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      double2 v = sel(ref == j, u[i], double2{0.0, 0.0});
+      if (i == j) v.x += gc;
+      S.set(Z, i, j, v);
+    }
+  // ---- Z = A^-1 gP: the recorded exchanges and multipliers, then the back substitution
+#pragma unroll
+  for (int p = 0; p < D; ++p) {
+#pragma unroll
+    for (int i = p + 1; i < D; ++i) {
+      const bool sw = pv[p] == i;
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        const double2 t = S.get(Z, p, j), v = S.get(Z, i, j);
+        S.set(Z, p, j, sel(sw, v, t));
+        S.set(Z, i, j, sel(sw, t, v));
+      }
+    }
+#pragma unroll
+    for (int i = p + 1; i < D; ++i) {
+      const double2 l = S.get(A, i, p);
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        const double2 a = S.get(Z, p, j), x = S.get(Z, i, j);
+        S.set(Z, i, j, double2{x.x - (l.x * a.x - l.y * a.y), x.y - (l.x * a.y + l.y * a.x)});
+      }
+    }
+  }
+#pragma unroll
+  for (int i = D - 1; i >= 0; --i) {
+    const double2 r = crecip(S.get(A, i, i));
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      double2 s = S.get(Z, i, j);
+#pragma unroll
+      for (int q = i + 1; q < D; ++q) {
+        const double2 a = S.get(A, i, q), x = S.get(Z, q, j);
+        s.x -= a.x * x.x - a.y * x.y;
+        s.y -= a.x * x.y + a.y * x.x;
+      }
+      S.set(Z, i, j, cmul(s, r));
+    }
+  }
+  // ---- Hs = herm(Z), Hn = herm(-Z P^H), an element at a time: W[i][j] = sum_q Z[i][q] conj(P[j][q])
+  double* hs = herm + ((b * K + k) * M) * (int64_t)DD * F + f;
+  double* hn = hs + (int64_t)DD * F;                          // M = 2 only
+  auto zph = [&](int i, int j) {
+    double2 w = {0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < D; ++q) {
+      const double2 z = S.get(Z, i, q), p = S.get(X, j, q);
+      w.x += z.x * p.x + z.y * p.y;
+      w.y += z.y * p.x - z.x * p.y;
+    }
+    return w;
+  };
+  int p = 0;
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    const double s = S.get(Z, i, i).x, n = -zph(i, i).x;
+    if (M == 2) { hs[(int64_t)i * F] = s; hn[(int64_t)i * F] = n; }
+    else hs[(int64_t)i * F] = s - n;
+  }
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int j = i + 1; j < D; ++j, ++p) {
+      const double2 a = S.get(Z, i, j), c = S.get(Z, j, i), wa = zph(i, j), wc = zph(j, i);
+      const double2 s = {0.5 * (a.x + c.x), 0.5 * (a.y - c.y)};
+      const double2 n = {-0.5 * (wa.x + wc.x), -0.5 * (wa.y - wc.y)};
+      if (M == 2) {
+        hs[(int64_t)(D + 2 * p) * F] = s.x;
+        hs[(int64_t)(D + 2 * p + 1) * F] = s.y;
+        hn[(int64_t)(D + 2 * p) * F] = n.x;
+        hn[(int64_t)(D + 2 * p + 1) * F] = n.y;
+      } else {
+        hs[(int64_t)(D + 2 * p) * F] = s.x - n.x;
+        hs[(int64_t)(D + 2 * p + 1) * F] = s.y - n.y;
+      }
+    }
+}
+
+// Time pass 2: q_H(t) = Re(y^H H y) = sum_i H_ii |y_i|^2 + 2 sum_{i<j} (Re H_ij Re(y_i conj y_j) + Im H_ij Im(y_i conj y_j))
+// -- the products of the statistics pass, contracted with one (M = 1) or two (M = 2) Hermitian matrices per lane.
+// 2 D^2 doubles of matrices, D weights and the D frame values per lane: 256 registers (two workgroups per CU) hold
+// that up to D = 5; D = 6 spilled 290 bytes per lane there, so from D = 6 on a workgroup has the CU to itself.
+template <int D, typename MT>
+__global__ __launch_bounds__(64 * PW, D <= 5 ? 2 : 1) void mvdr_bwd_mask_kernel(
+    const double2* __restrict__ obs, const double2* __restrict__ genh, const double2* __restrict__ wconj,
+    const double* __restrict__ herm, const MT* __restrict__ masks, MT* __restrict__ dmask, int64_t B, int K,
+    int M, int64_t T, int F, Plan plan, int masking, double masking_eps) {
+  __shared__ double2 ybuf[2][PW][D][64];
+  constexpr int NP = D * (D - 1) / 2;
+  const int groups = (K + PW - 1) / PW;
+  int64_t tile;
+  int grp;
+  if (!xcd_tile(blockIdx.x, groups, B * plan.chunks * plan.nf, tile, grp)) return;
+  const int ft = (int)(tile % plan.nf);
+  const int c = (int)((tile / plan.nf) % plan.chunks);
+  const int64_t b = tile / ((int64_t)plan.nf * plan.chunks);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int k = grp * PW + wave;
+  const bool kvalid = k < K;
+  const int fraw = ft * 64 + lane;
+  const int f = fraw < F ? fraw : F - 1;
+  const int64_t t0 = c * plan.tchunk;
+  const int64_t t1 = t0 + plan.tchunk < T ? t0 + plan.tchunk : T;
+  const int steps = (int)((t1 - t0 + PW - 1) / PW);
+  const int64_t bk = b * K + (kvalid ? k : 0);
+  const MT* mk0 = masks + (bk * M) * T * F + f;              // only read with masking
+  const double2* g0 = genh + bk * T * F + f;                 // only read with masking
+  const double2* y0 = obs + b * D * T * F + f;
+  MT* dm0 = dmask + (bk * M) * T * F + f;
+
+  double hd[2][D];
+  double2 ho[2][NP + 1];
+  double2 w[D];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const double* q = herm + ((bk * M) + (m < M ? m : 0)) * (int64_t)(D * D) * F + f;
+#pragma unroll
+    for (int i = 0; i < D; ++i) hd[m][i] = q[(int64_t)i * F];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) ho[m][p] = double2{q[(int64_t)(D + 2 * p) * F], q[(int64_t)(D + 2 * p + 1) * F]};
+  }
+#pragma unroll
+  for (int d = 0; d < D; ++d) w[d] = masking ? wconj[(bk * D + d) * (int64_t)F + f] : double2{0.0, 0.0};
+
+  auto fetch_y = [&](int s_) {
+    const int64_t t = t0 + (int64_t)s_ * PW + wave;
+    if (t < t1) {
+#pragma unroll
+      for (int d = 0; d < D; ++d)
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)(y0 + (d * T + t) * F),
+            (__attribute__((address_space(3))) void*)&ybuf[s_ & 1][wave][d][0], 16, 0, 0);
+    } else {
+#pragma unroll
+      for (int d = 0; d < D; ++d) ybuf[s_ & 1][wave][d][lane] = double2{0.0, 0.0};
+    }
+  };
+  auto fetch_g = [&](int s_, GradRegs<MT>& r) {
+    if (!masking) return;
+#pragma unroll
+    for (int fr = 0; fr < PW; ++fr) {
+      int64_t tt = t0 + (int64_t)s_ * PW + fr;
+      tt = tt < t1 ? tt : t1 - 1;
+      r.g[fr] = g0[tt * F];
+      r.m[fr] = mk0[tt * F];
+    }
+  };
+  auto compute = [&](int s_, const GradRegs<MT>& r) {
+#pragma unroll
+    for (int fr = 0; fr < PW; ++fr) {
+      const int64_t t = t0 + (int64_t)s_ * PW + fr;
+      if (t >= t1) break;
+      double2 y[D];
+#pragma unroll
+      for (int d = 0; d < D; ++d) y[d] = ybuf[s_ & 1][fr][d][lane];
+      double qd[2] = {0.0, 0.0}, qo[2] = {0.0, 0.0};
+      int p = 0;
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        const double pd = y[i].x * y[i].x + y[i].y * y[i].y;
+        qd[0] += hd[0][i] * pd;
+        qd[1] += hd[1][i] * pd;
+#pragma unroll
+        for (int j = i + 1; j < D; ++j, ++p) {
+          const double pr = y[i].x * y[j].x + y[i].y * y[j].y;
+          const double pi = y[i].y * y[j].x - y[i].x * y[j].y;
+          qo[0] += ho[0][p].x * pr + ho[0][p].y * pi;
+          qo[1] += ho[1][p].x * pr + ho[1][p].y * pi;
+        }
+      }
+      double q0 = qd[0] + 2.0 * qo[0];
+      const double q1 = qd[1] + 2.0 * qo[1];
+      if (masking && (double)r.m[fr] >= masking_eps) {        // d max(m, eps) / dm = 1 at equality too (torch.clamp)
+        double2 e = {0.0, 0.0};
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+          e.x += w[d].x * y[d].x - w[d].y * y[d].y;
+          e.y += w[d].x * y[d].y + w[d].y * y[d].x;
+        }
+        q0 += e.x * r.g[fr].x + e.y * r.g[fr].y;              // Re(conj(e) G)
+      }
+      if (fraw < F) {
+        dm0[t * F] = (MT)q0;
+        if (M == 2) dm0[(T + t) * F] = (MT)q1;
+      }
+    }
+  };
+  GradRegs<MT> ra, rb;
+  fetch_y(0);
+  fetch_g(0, ra);
+  for (int s = 0; s < steps; s += 2) {
+    __syncthreads();
+    if (s + 1 < steps) { fetch_y(s + 1); fetch_g(s + 1, rb); }
+    if (kvalid) compute(s, ra);
+    if (s + 1 >= steps) break;
+    __syncthreads();
+    if (s + 2 < steps) { fetch_y(s + 2); fetch_g(s + 2, ra); }
+    if (kvalid) compute(s + 1, rb);
+  }
+}
+
+int64_t bwd_gw_bytes(int64_t B, int K, int D, const Plan& p, int F) {
+  return ((B * p.chunks * K * 2 * D * (int64_t)F * (int64_t)sizeof(double)) + 15) / 16 * 16;
+}
+
+template <int D>
+int launch_bwd_gw(const double* obs, const double* genh, const void* masks, int mask_f64, double* part, int64_t B,
+                  int K, int M, int64_t T, int F, const Plan& p, int masking, double masking_eps, hipStream_t s) {
+  const int64_t tiles = B * p.chunks * p.nf;
+  const int64_t grid = ((tiles + 7) / 8) * 8 * ((K + PW - 1) / PW);
+  if (mask_f64)
+    hipLaunchKernelGGL((mvdr_bwd_gw_kernel<D, double>), dim3((unsigned)grid), dim3(64 * PW), 0, s,
+                       reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(genh),
+                       static_cast<const double*>(masks), part, B, K, M, T, F, p, masking, masking_eps);
+  else
+    hipLaunchKernelGGL((mvdr_bwd_gw_kernel<D, float>), dim3((unsigned)grid), dim3(64 * PW), 0, s,
+                       reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(genh),
+                       static_cast<const float*>(masks), part, B, K, M, T, F, p, masking, masking_eps);
+  return tssep_launch_status();
+}
+
+template <int D>
+int launch_bwd_solve(const double* part, const double* gw, double* herm, int64_t B, int K, int M, int F, int chunks,
+                     int ref, double eps, hipStream_t s) {
+  constexpr int LB = bwd_lanes(D);
+  constexpr size_t lds = bwd_in_registers(D) ? 0 : (size_t)3 * D * D * LB * sizeof(double2);
+  if (lds > 0) {
+    static bool attr_set = false;
+    if (!attr_set) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(mvdr_bwd_solve_kernel<D>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return TSSEP_E_LAUNCH;
+      attr_set = true;
+    }
+  }
+  const int nfl = (F + LB - 1) / LB;
+  hipLaunchKernelGGL(mvdr_bwd_solve_kernel<D>, dim3((unsigned)(B * K * nfl)), dim3(64), lds, s, part, gw, herm, B, K,
+                     M, F, chunks, ref, eps);
+  return tssep_launch_status();
+}
+
+template <int D>
+int launch_bwd_mask(const double* obs, const double* genh, const double* wconj, const double* herm, const void* masks,
+                    int mask_f64, void* dmask, int64_t B, int K, int M, int64_t T, int F, const Plan& p, int masking,
+                    double masking_eps, hipStream_t s) {
+  const int64_t tiles = B * p.chunks * p.nf;
+  const int64_t grid = ((tiles + 7) / 8) * 8 * ((K + PW - 1) / PW);
+  if (mask_f64)
+    hipLaunchKernelGGL((mvdr_bwd_mask_kernel<D, double>), dim3((unsigned)grid), dim3(64 * PW), 0, s,
+                       reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(genh),
+                       reinterpret_cast<const double2*>(wconj), herm, static_cast<const double*>(masks),
+                       static_cast<double*>(dmask), B, K, M, T, F, p, masking, masking_eps);
+  else
+    hipLaunchKernelGGL((mvdr_bwd_mask_kernel<D, float>), dim3((unsigned)grid), dim3(64 * PW), 0, s,
+                       reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(genh),
+                       reinterpret_cast<const double2*>(wconj), herm, static_cast<const float*>(masks),
+                       static_cast<float*>(dmask), B, K, M, T, F, p, masking, masking_eps);
+  return tssep_launch_status();
+}
+
+}  // namespace
+
+extern "C" int64_t tssep_mvdr_bwd_workspace_bytes(int64_t B, int K, int M, int D, int64_t T, int F) {
+  if (D > MAXD || !shape_ok(B, K, M, D, T, F)) return 0;
+  const Plan p = make_plan(B, K, T, F);
+  return bwd_gw_bytes(B, K, D, p, F) + B * K * M * (int64_t)(D * D) * F * (int64_t)sizeof(double);
+}
+
+extern "C" int tssep_mvdr_bwd_gw(const double* obs, const double* genh, const void* masks, int mask_f64,
+                                 double* gw_partials, int64_t B, int K, int M, int D, int64_t T, int F, int masking,
+                                 double masking_eps, void* stream) {
+  if (!obs || !genh || !gw_partials || (masking && !masks)) return TSSEP_E_NULL;
+  if (!shape_ok(B, K, M, D, T, F)) return TSSEP_E_SHAPE;
+  if (D > MAXD) return TSSEP_E_UNSUPPORTED;
+  if (!aligned16(obs) || !aligned16(genh)) return TSSEP_E_ALIGN;
+  const Plan p = make_plan(B, K, T, F);
+#define CALL(DD) \
+  launch_bwd_gw<DD>(obs, genh, masks, mask_f64, gw_partials, B, K, M, T, F, p, masking, masking_eps, (hipStream_t)stream)
+  DISPATCH_D(D, CALL)
+#undef CALL
+}
+
+extern "C" int tssep_mvdr_bwd_solve(const double* fwd_partials, double* gw_partials, double* herm, int64_t B, int K,
+                                    int M, int D, int64_t T, int F, int reference_channel, double eps, void* stream) {
+  if (!fwd_partials || !gw_partials || !herm) return TSSEP_E_NULL;
+  if (!shape_ok(B, K, M, D, T, F) || reference_channel < 0 || reference_channel >= D) return TSSEP_E_SHAPE;
+  if (D > MAXD) return TSSEP_E_UNSUPPORTED;
+  const Plan p = make_plan(B, K, T, F);
+  hipStream_t s = (hipStream_t)stream;
+  if (p.chunks > 1) {
+    // the forward's reducer: rows of F doubles, per_b doubles per (batch element, chunk)
+    const int64_t rows = B * K * 2 * D;
+    hipLaunchKernelGGL(mvdr_reduce_kernel, dim3((unsigned)((rows * F + 255) / 256)), dim3(256), 0, s, gw_partials,
+                       rows, F, p.chunks, (int64_t)K * 2 * D * F);
+    const int st = tssep_launch_status();
+    if (st != TSSEP_OK) return st;
+  }
+#define CALL(DD) \
+  launch_bwd_solve<DD>(fwd_partials, gw_partials, herm, B, K, M, F, p.chunks, reference_channel, eps, s)
+  DISPATCH_D(D, CALL)
+#undef CALL
+}
+
+extern "C" int tssep_mvdr_bwd_mask(const double* obs, const double* genh, const double* wconj, const double* herm,
+                                   const void* masks, int mask_f64, void* dmask, int64_t B, int K, int M, int D,
+                                   int64_t T, int F, int masking, double masking_eps, void* stream) {
+  if (!obs || !herm || !dmask || (masking && (!masks || !genh || !wconj))) return TSSEP_E_NULL;
+  if (!shape_ok(B, K, M, D, T, F)) return TSSEP_E_SHAPE;
+  if (D > MAXD) return TSSEP_E_UNSUPPORTED;
+  if (!aligned16(obs) || (masking && (!aligned16(genh) || !aligned16(wconj)))) return TSSEP_E_ALIGN;
+  const Plan p = make_plan(B, K, T, F);
+#define CALL(DD)                                                                                              \
+  launch_bwd_mask<DD>(obs, genh, wconj, herm, masks, mask_f64, dmask, B, K, M, T, F, p, masking, masking_eps, \
+                      (hipStream_t)stream)
+  DISPATCH_D(D, CALL)
+#undef CALL
+}
+
+extern "C" int tssep_mvdr_souden_bwd(const double* obs, const void* masks, int mask_f64, const double* genh,
+                                     const void* fwd_workspace, void* bwd_workspace, void* dmask, int64_t B, int K,
+                                     int M, int D, int64_t T, int F, int reference_channel, double eps, int masking,
+                                     double masking_eps, void* stream) {
+  if (!fwd_workspace || !bwd_workspace) return TSSEP_E_NULL;
+  if (!aligned16(fwd_workspace) || !aligned16(bwd_workspace)) return TSSEP_E_ALIGN;
+  const int64_t pb = tssep_mvdr_partial_bytes(B, K, D, T, F);
+  if (pb == 0 || !shape_ok(B, K, M, D, T, F)) return D > MAXD ? TSSEP_E_UNSUPPORTED : TSSEP_E_SHAPE;
+  const double* part = static_cast<const double*>(fwd_workspace);
+  const double* wconj = reinterpret_cast<const double*>(static_cast<const char*>(fwd_workspace) + ((pb + 15) / 16) * 16);
+  double* gwp = static_cast<double*>(bwd_workspace);
+  double* herm = reinterpret_cast<double*>(static_cast<char*>(bwd_workspace) + bwd_gw_bytes(B, K, D, make_plan(B, K, T, F), F));
+  int st = tssep_mvdr_bwd_gw(obs, genh, masks, mask_f64, gwp, B, K, M, D, T, F, masking, masking_eps, stream);
+  if (st != TSSEP_OK) return st;
+  st = tssep_mvdr_bwd_solve(part, gwp, herm, B, K, M, D, T, F, reference_channel, eps, stream);
+  if (st != TSSEP_OK) return st;
+  return tssep_mvdr_bwd_mask(obs, genh, wconj, herm, masks, mask_f64, dmask, B, K, M, D, T, F, masking, masking_eps,
+                             stream);
+}

@@ -506,6 +506,36 @@ def sigmoid(logit):
     return _Sigmoid.apply(logit)
 
 
+class _MVDRSouden(torch.autograd.Function):
+    """TorchBF.__call__ (enhancer.py:215-265) with a backward: hip_ops.mvdr_souden keeps its workspace (reduced
+    statistics, wconj), hip_ops.mvdr_souden_bwd turns d(loss)/d(enh) into d(loss)/d(masks).  The observation gets no
+    gradient.  The singular check of the forward is a host sync: eager only."""
+
+    @staticmethod
+    def forward(ctx, masks, obs, reference_channel, eps, masking, masking_eps):
+        enh, state = H.mvdr_souden(masks.detach(), obs.detach(), reference_channel, eps=eps, masking=masking,
+                                   masking_eps=masking_eps, return_state=True)
+        # through save_for_backward: autograd then notices an in-place change of any of them before the backward
+        ctx.save_for_backward(state.pop("masks"), state.pop("obs_r"), state.pop("ws"))
+        ctx.scalars, ctx.mask_dtype = state, masks.dtype
+        return enh
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, genh):
+        masks, obs_r, ws = ctx.saved_tensors
+        dmask = H.mvdr_souden_bwd(genh.to(torch.complex128), dict(ctx.scalars, masks=masks, obs_r=obs_r, ws=ws))
+        return dmask.to(ctx.mask_dtype), None, None, None, None, None
+
+
+def mvdr_souden(masks, obs, reference_channel, eps=None, masking=False, masking_eps=0.0):
+    """masks [B,K,M,T,F] fp32|fp64, obs [B,D,T,F] complex128 -> enh [B,K,T,F] complex128, differentiable in masks."""
+    if obs.requires_grad:
+        raise NotImplementedError("mvdr_souden: the Observation requires grad, but the MVDR backward has a gradient for "
+                                  "the masks only (detach the Observation)")
+    return _MVDRSouden.apply(masks, obs, reference_channel, eps, masking, masking_eps)
+
+
 # ------------------------------------------------------------------------- STFT family
 _WINDOWS = {}
 

@@ -1306,12 +1306,13 @@ def mask_mul_bwd(dest, obs):
 
 # ----------------------------------------------------------------------------- beamformer
 def mvdr_souden(masks, obs, reference_channel, eps=None, masking=False, masking_eps=0.0,
-                check_singular=True):
+                check_singular=True, return_state=False):
     """TorchBF('mvdr_souden'), tssep/train/enhancer.py:215-265.
     masks [B,K,M,T,F] fp32|fp64 (M = 1|2), obs [B,D,T,F] complex128 -> enh [B,K,T,F] complex128.
     eps None = torch.finfo(float64).tiny, as the reference.  Raises torch.linalg.LinAlgError for a
     singular interference PSD like torch.linalg.solve does (one host sync; check_singular=False
-    skips it)."""
+    skips it).  return_state=True: (enh, state), state what mvdr_souden_bwd needs -- the workspace
+    of this call (reduced statistics, wconj) and the arguments as the kernels saw them."""
     L = _lib.lib()
     assert masks.is_cuda and obs.is_cuda, (masks.device, obs.device)
     assert obs.dtype == torch.complex128, obs.dtype
@@ -1347,7 +1348,39 @@ def mvdr_souden(masks, obs, reference_channel, eps=None, masking=False, masking_
             raise torch.linalg.LinAlgError(
                 f"mvdr_souden: the solver failed because the interference PSD matrix is singular "
                 f"({n} of {B * K * F} (batch, speaker, frequency) systems)")
+    if return_state:
+        return torch.view_as_complex(enh), dict(ws=ws, masks=masks, obs_r=obs_r, ref=int(reference_channel), eps=eps,
+                                                masking=int(bool(masking)), masking_eps=float(masking_eps))
     return torch.view_as_complex(enh)
+
+
+def mvdr_bwd_workspace(B, K, M, D, T, F, device):
+    """The backward's workspace (tssep_mvdr_bwd_workspace_bytes: the gw partials, then the packed Hermitian matrices)."""
+    nbytes = _lib.lib().tssep_mvdr_bwd_workspace_bytes(B, K, M, D, T, F)
+    if nbytes <= 0:
+        raise RuntimeError(f"mvdr_souden_bwd: unsupported shape B={B} K={K} M={M} D={D} T={T} F={F} (at most 8 channels)")
+    return torch.empty(nbytes // 8, device=device, dtype=torch.float64)
+
+
+def mvdr_souden_bwd(genh, state):
+    """d(loss)/d(masks) of mvdr_souden: genh [B,K,T,F] complex128 = d(loss)/d(enh), `state` from
+    mvdr_souden(..., return_state=True) -> dmask [B,K,M,T,F] in the masks' dtype.  Three HIP stages
+    (csrc/mvdr.hip: gw over time, the per-bin solve, the quadratic forms over time); no host sync."""
+    L = _lib.lib()
+    masks, obs_r = state["masks"], state["obs_r"]
+    B, K, M, T, F = masks.shape
+    D = obs_r.shape[1]
+    assert genh.is_cuda and genh.dtype == torch.complex128 and tuple(genh.shape) == (B, K, T, F), (genh.dtype, genh.shape)
+    g_r = torch.view_as_real(genh.contiguous())
+    ws = mvdr_bwd_workspace(B, K, M, D, T, F, masks.device)
+    dmask = torch.empty_like(masks)
+    msz = masks.element_size()
+    nbytes = B * T * F * (32 * D + 16 * K * (2 if state["masking"] else 1) + K * M * msz + (K * msz if state["masking"] else 0))
+    with _timed("mvdr_souden_bwd", 0, nbytes):
+        check(L.tssep_mvdr_souden_bwd(_p(obs_r), _p(masks), int(masks.dtype == torch.float64), _p(g_r), _p(state["ws"]),
+                                      _p(ws), _p(dmask), B, K, M, D, T, F, state["ref"], state["eps"], state["masking"],
+                                      state["masking_eps"], _stream()), "mvdr_souden_bwd")
+    return dmask
 
 
 DISTORTION_MODES = {"sum_cross_talker": 0, "one_minus": 1}

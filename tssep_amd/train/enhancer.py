@@ -4,7 +4,7 @@ segment-wise ClassicBF_np('mvdr_souden') with its WPE / ChannelWiseWPE dereverbe
 import numpy as np
 import torch
 
-from .. import hip_ops as H
+from .. import functional as Fn, hip_ops as H
 from ..configurable import Configurable
 from . import enhancer_distortion_mask
 
@@ -76,11 +76,17 @@ def trace(input, axis1=-2, axis2=-1):
 class TorchBF(ABC):
     """Mask-based MVDR (Souden) beamformer in complex128 -- enhancer.py:140-265, same constructor
     arguments, same call signature, same checks.  One fused pipeline of three HIP kernels
-    (statistics, per-bin solve, filtering; csrc/mvdr.hip); forward only -- the reference uses it
-    at evaluation time."""
+    (statistics, per-bin solve, filtering; csrc/mvdr.hip).  The reference's class is plain differentiable
+    torch, so a config with this enhancer and a time-domain loss trains the mask estimator through the beamformer
+    there; here that takes ``differentiable=True`` (THIS PROJECT'S keyword, not a key of the reference's config):
+    the call then goes through functional.mvdr_souden, whose backward is three more HIP stages and yields the
+    gradient of the masks (never of the Observation: one that requires grad raises NotImplementedError).  With the
+    default False the class is the evaluation-time enhancer it always was and refuses masks that require grad.
+    Eager only either way: the singular check of the solve is a host sync, a hipGraph capture cannot hold it."""
 
-    def __init__(self, bf="mvdr_souden", masking=False, masking_eps=0.0, eps=None):
+    def __init__(self, bf="mvdr_souden", masking=False, masking_eps=0.0, eps=None, differentiable=False):
         super().__init__()
+        self.differentiable = differentiable
         assert bf == "mvdr_souden", (bf, "Only mvdr_souden is implemented")
         self.bf = bf
         self.eps = eps
@@ -97,14 +103,23 @@ class TorchBF(ABC):
         assert Observation.dtype == torch.complex128, Observation.dtype
         if masks.shape[-3] not in (1, 2):
             raise ValueError(masks.shape)
-        if masks.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError("TorchBF is an evaluation-time enhancer here: call it under "
-                                      "torch.no_grad() (no backward kernel)")
+        if Observation.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("TorchBF: the Observation requires grad, but the MVDR backward has a gradient "
+                                      "for the masks only (detach the Observation)")
+        train = masks.requires_grad and torch.is_grad_enabled()
+        if train and not self.differentiable:
+            raise NotImplementedError("TorchBF is an evaluation-time enhancer by default: call it under "
+                                      "torch.no_grad(), or construct it with differentiable=True to train "
+                                      "through it (no backward kernel is run without that keyword)")
         Observation = Observation.to(masks.device)
         if not batched:
             masks, Observation = masks[None], Observation[None]
-        enh = H.mvdr_souden(masks.detach(), Observation, reference_channel, eps=self.eps,
-                            masking=self.masking, masking_eps=self.masking_eps)
+        if train:
+            enh = Fn.mvdr_souden(masks, Observation, reference_channel, eps=self.eps, masking=self.masking,
+                                 masking_eps=self.masking_eps)
+        else:
+            enh = H.mvdr_souden(masks.detach(), Observation, reference_channel, eps=self.eps,
+                                masking=self.masking, masking_eps=self.masking_eps)
         return enh if batched else enh[0]
 
 

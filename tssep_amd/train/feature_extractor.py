@@ -126,8 +126,11 @@ class STFT(Configurable):
         return full if num_samples is None else min(num_samples, full)
 
     def istft(self, signal, num_samples=None):
-        """complex [..., T, F] -> [..., N]  (fe.istft, model.py:661-664); differentiable."""
+        """complex [..., T, F] -> [..., N]  (fe.istft, model.py:661-664); differentiable.  The transform runs in float32:
+        a complex128 estimate (TorchBF's) is cast to complex64 in front of it, one torch cast each way."""
         self._check_plan()
+        if signal.dtype == torch.complex128:
+            signal = signal.to(torch.complex64)
         if self.window_length % self.shift:
             raise ValueError("istft: window_length must be a multiple of shift (paderbox's biorthogonal window)")
         T = signal.shape[-2]

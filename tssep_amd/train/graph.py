@@ -33,6 +33,17 @@ from .. import hip_ops as H
 _INPUT_KEYS = ("observation", "auxInput", "Input", "Vad", "vad")
 
 
+def host_sync_reason(model):
+    """Why a step of `model` cannot be captured into a hipGraph, or None.  A step through the TorchBF enhancer reads the
+    solver's count of singular systems back on the host (hip_ops.mvdr_souden raises torch.linalg.LinAlgError like
+    torch.linalg.solve): a host sync, which stream capture cannot hold.  Such a step runs eagerly."""
+    from . import enhancer as _enh
+    if isinstance(getattr(model, "enhancer", None), _enh.TorchBF):
+        return ("the TorchBF enhancer checks the MVDR solve for singular systems on the host (a device-to-host copy per "
+                "step): a step through it cannot be captured into a hipGraph and runs eagerly")
+    return None
+
+
 class GraphedStep:
     def __init__(self, model, optimizer, warmup=2, adopt_inputs=False, zero_grad=True, max_graphs=0):
         """adopt_inputs: the tensors of the first batch of a signature BECOME the static inputs (no
@@ -49,6 +60,7 @@ class GraphedStep:
         self._dropouts = [m for m in model.modules() if isinstance(m, torch.nn.Dropout)]
         self.replays = 0
         self.eager_steps = 0
+        self.eager_reason = host_sync_reason(model)      # not None: every step runs eagerly, nothing is ever captured
 
     # ------------------------------------------------------------------------------ helpers
     def _tensor_keys(self, ex):
@@ -90,14 +102,16 @@ class GraphedStep:
 
     def usable(self, ex):
         """Whether this example can go through a graph at all: device-resident inputs, no snapshot this step (the snapshot
-        branch of `review` copies to the host)."""
-        return (isinstance(ex.get("observation", ex.get("Input")), torch.Tensor)
+        branch of `review` copies to the host), no host sync inside the model's own step (host_sync_reason)."""
+        return (self.eager_reason is None and isinstance(ex.get("observation", ex.get("Input")), torch.Tensor)
                 and ex.get("observation", ex.get("Input")).is_cuda
                 and isinstance(ex.get("auxInput"), torch.Tensor) and ex["auxInput"].is_cuda
                 and not getattr(self.model, "create_snapshot", False) and not H.KERNEL_TIMING)
 
     # ------------------------------------------------------------------------------ capture
     def _capture(self, ex):
+        if self.eager_reason is not None:
+            raise RuntimeError(f"GraphedStep: {self.eager_reason}")
         if H.KERNEL_TIMING:
             raise RuntimeError("per-kernel event timing cannot be captured into a graph")
         me = self.model.mask_estimator
@@ -202,6 +216,9 @@ class GraphedStep:
         call overwrites (lazily computed fields -- mask, stft_estimate -- are evaluated from them on
         access).  Gradients are in the optimizer's flat bucket afterwards (call ``optimizer.step()``)."""
         ex = self._host_side_targets(ex)
+        if self.eager_reason is not None:
+            self.eager_steps += 1
+            return self._eager(ex)
         if not self.zero_grad:
             # an EAGER micro-step of the same virtual minibatch may still be accumulating weight gradients into the bucket on
             # the side stream; the captured wgrad nodes += into the same views, ordered only against the launch stream, and

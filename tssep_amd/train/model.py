@@ -336,7 +336,7 @@ class Model(Configurable, torch.nn.Module):
             def lazy():
                 mask = Fn.sigmoid(logit4)
                 mask = (mask if batched else mask[0]).unsqueeze(-3)
-                return mask, self.enhancer(mask, ex, self)
+                return mask, self.enhancer(mask, self._bf_example(ex), self)
         else:
             assert isinstance(self.loss, _loss.VADSigmoidBCE), type(self.loss)
 
@@ -345,6 +345,14 @@ class Model(Configurable, torch.nn.Module):
                 return (mask if batched else mask[0]).unsqueeze(-3), None
         out._lazy = out._lazy0 = lazy
         return out
+
+    def _bf_example(self, ex):
+        """TorchBF works in complex128 and the reference asserts that dtype; fe.stft yields complex64.  For this enhancer
+        only, a complex64 Observation is promoted (a deviation from the reference, whose assertion would fire there)."""
+        if isinstance(self.enhancer, _enh.TorchBF) and isinstance(ex["Observation"], torch.Tensor) \
+                and ex["Observation"].dtype == torch.complex64:
+            return {**ex, "Observation": ex["Observation"].to(torch.complex128)}
+        return ex
 
     def _forward_gated(self, ex, logit, logit4, emb, ref, batched):
         """explicit_vad (net.py:969-979): logit = None, vad_logit = v [B,K,1,T] (a view of the head's rows), and
