@@ -537,13 +537,33 @@ int tssep_gatebce_bwd(const float* logit, int64_t ld, const float* vad, const fl
  *   spk_rows = 0: raw[((b*trials+tr)*T + t) * (K*Fr) + k*Fr + fr]   (ts_vad combination layer)
  *   spk_rows = 1: raw[((b*K + k)*T + t) * Fr + fr]                   (ts_vad off, trials == 1)
  *   Fr = F ('tf') or 1 ('t': the value is repeated over frequency).
- * perm[b,s] = output index of speaker s, iperm its inverse (both NULL = identity). */
+ * perm[b,s] = output index of speaker s, iperm its inverse (both NULL = identity).
+ * Trial mean: trials a power of two: the fp32 sum in trial order, * (1/trials); any other count: sum and division in
+ * double, rounded once -- |error| <= (trials - 1) * 2^-24 * mean|raw| either way. */
 int tssep_logit_map_fwd(const float* raw, const int32_t* perm, const int32_t* iperm, int64_t B,
                         int trials, int64_t K, int64_t T, int F, int Fr, int spk_rows,
                         float* out, void* stream);
 int tssep_logit_map_bwd(const float* dout, const int32_t* perm, const int32_t* iperm, int64_t B,
                         int trials, int64_t K, int64_t T, int F, int Fr, int spk_rows,
                         float* draw, void* stream);
+
+/* Fused two-mask tail (nmask = M masks per speaker, tssep/train/net.py:629-659 with '(spk mask freq)' columns, the
+ * trial mean :928-951, the un-permutation :957-967 and the sigmoid :983): one pass each way between the final
+ * Linear's GEMM and the enhancer.  Any M >= 1.
+ *   spk_rows = 0: raw[((b*trials+tr)*T + t) * (K*M*Fr) + (k*M + m)*Fr + fr]
+ *   spk_rows = 1: raw[((b*K + k)*T + t) * (M*Fr) + m*Fr + fr]                 (trials == 1)
+ *   logit, mask [B,K,M,T,F] fp32: index (((b*K + j)*M + m)*T + t)*F + f;  Fr = F ('tf') or 1 ('t').
+ * fwd: logit with tssep_logit_map_fwd's arithmetic (the same device function: bit-identical at M = 1),
+ *      mask = the mask head's sigmoid of it.  Bytes: 4 * (trials * B*K*M*T*Fr + 2 * B*K*M*T*F).
+ * bwd: draw (raw layout) = (dmask * s * (1 - s) [+ dlogit]) [* 1/trials], every operation rounded on its own; 't': the
+ *      sum over f in tssep_logit_map_bwd's lane order.  dlogit may be NULL.  Bytes: 4 * ((2 | 3) * B*K*M*T*F +
+ *      trials * B*K*M*T*Fr).  Argument checks as tssep_logit_map_*, and TSSEP_E_SHAPE for M <= 0. */
+int tssep_mask_map_fwd(const float* raw, const int32_t* perm, const int32_t* iperm, int64_t B,
+                       int trials, int64_t K, int M, int64_t T, int F, int Fr, int spk_rows,
+                       float* logit, float* mask, void* stream);
+int tssep_mask_map_bwd(const float* dmask, const float* mask, const float* dlogit,
+                       const int32_t* perm, const int32_t* iperm, int64_t B, int trials, int64_t K,
+                       int M, int64_t T, int F, int Fr, int spk_rows, float* draw, void* stream);
 
 /* ------------------------------------------------- mask-based MVDR beamformer ----
  * Eval-time enhancer TorchBF('mvdr_souden') of the reference, tssep/train/enhancer.py:140-265, in

@@ -1,5 +1,6 @@
 // Streaming (HBM-bound) helper kernels of the TS-SEP hot path: speaker conditioning,
-// tanh backward, layout changes, column sums, split reductions and the two losses.
+// tanh backward, layout changes (the logit map and its fused two-mask form with the sigmoid), column sums, split
+// reductions and the two losses.
 // Reference call sites are cited per entry point in include/tssep_hip.h.
 #include <math.h>
 #include "common.h"
@@ -360,16 +361,33 @@ __device__ __forceinline__ int64_t raw_index(const MapArgs& a, int64_t b, int tr
   if (a.spk_rows) return ((b * a.K + k) * a.T + t) * a.Fr + fr;
   return ((b * a.trials + tr) * a.T + t) * (a.K * a.Fr) + (int64_t)k * a.Fr + fr;
 }
+// The trial mean.  A power of two of trials: the fp32 sum in trial order, then * fl(1 / trials), an exact scaling --
+// trials - 1 roundings, (trials - 1) U mean |raw|.  Any other count: fl(1 / trials) and the product with it would be two
+// more roundings and leave that bound (seen at trials = 3: up to 1.27 x), so the sum and the division are carried in
+// double and rounded once, U |mean|.  Shared by logit_map_fwd_kernel and mask_map_fwd_kernel: the same bits in both.
+__device__ __forceinline__ bool odd_trials(int trials) { return (trials & (trials - 1)) != 0; }
+__device__ __forceinline__ float mean_of(double sum, int trials) { return (float)(sum / (double)trials); }
 __global__ void logit_map_fwd_kernel(const float* __restrict__ raw, MapArgs a,
                                      float* __restrict__ out) {
   const int64_t total = a.B * a.K * a.T * a.F;
   const float inv = 1.0f / (float)a.trials;
+  const bool exact_mean = odd_trials(a.trials);
   GRID_STRIDE(e, total) {
     const int64_t row = e / a.F;
     const int f = (int)(e - row * a.F);
     const int64_t t = row % a.T, bj = row / a.T, j = bj % a.K, b = bj / a.K;
     const int s = a.iperm ? a.iperm[b * a.K + j] : (int)j;
     const int fr = a.Fr == 1 ? 0 : f;
+    if (exact_mean) {
+      double acc = 0.0;
+      for (int tr = 0; tr < a.trials; ++tr) {
+        int k = s - tr;
+        if (k < 0) k += (int)a.K;
+        acc += (double)raw[raw_index(a, b, tr, t, k, fr)];
+      }
+      out[e] = mean_of(acc, a.trials);
+      continue;
+    }
     float acc = 0.f;
     for (int tr = 0; tr < a.trials; ++tr) {
       int k = s - tr;
@@ -423,6 +441,124 @@ __global__ __launch_bounds__(256) void logit_map_bwd_t_kernel(const float* __res
   for (int f = lane; f < a.F; f += 64) acc += p[f];
   acc = wave_sum(acc);
   if (lane == 0) draw[e] = acc / (float)a.trials;
+}
+
+// ---- fused two-mask tail: raw GEMM output -> logit and mask [B, K, M, T, F], and back -------------------------
+// The logit map above with M masks per speaker (nmask of MaskEstimator_v2, net.py:629-659: '(spk mask freq)' columns)
+// and the final sigmoid (net.py:983) in the same pass, so the tail's largest tensors are walked once each way.
+//   raw index, speakers in columns (ts_vad):  ((b*trials + tr)*T + t) * (K*M*Fr) + (k*M + m)*Fr + fr
+//   raw index, speakers in rows (ts_vad off): ((b*K + k)*T + t) * (M*Fr) + m*Fr + fr          (trials == 1)
+//   out index:                                (((b*K + j)*M + m)*T + t)*F + f
+// Both raw layouts are runs of Fr floats numbered (b, tr, t, k, m) / (b, k, t, m); the output is runs of F floats numbered
+// (b, j, m, t).  One wave per run, the index decomposition once per run; trial and permutation conventions as above.
+__device__ __forceinline__ int64_t mask_run_base(const MapArgs& a, int M, int64_t b, int64_t t, int m, int s) {
+  // spk_rows: the raw run of speaker s; else the raw run of (trial 0, position 0), trial tr / position k at
+  // + tr * T*K*M + k * M
+  if (a.spk_rows) return ((b * a.K + s) * a.T + t) * M + m;
+  return (b * a.trials * a.T + t) * (a.K * M) + m;
+}
+__global__ __launch_bounds__(256) void mask_map_fwd_kernel(const float* __restrict__ raw, MapArgs a, int M,
+                                                           float* __restrict__ logit, float* __restrict__ mask) {
+  const int lane = threadIdx.x & 63;
+  const int64_t runs = a.B * a.K * M * a.T;
+  const int64_t step = a.T * a.K * M;                    // raw runs per trial
+  const float inv = 1.0f / (float)a.trials;
+  const bool exact_mean = odd_trials(a.trials);
+  for (int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); v < runs; v += (int64_t)gridDim.x * 4) {
+    const int64_t t = v % a.T, q = v / a.T;
+    const int m = (int)(q % M);
+    const int64_t bj = q / M, j = bj % a.K, b = bj / a.K;
+    const int s = a.iperm ? a.iperm[b * a.K + j] : (int)j;
+    const int64_t base = mask_run_base(a, M, b, t, m, s);
+    float* lo = logit + v * a.F;
+    float* mo = mask + v * a.F;
+    for (int f = lane; f < a.F; f += 64) {
+      const int fr = a.Fr == 1 ? 0 : f;
+      float x;
+      if (exact_mean) {                                  // (never with spk_rows: trials == 1 there)
+        double acc = 0.0;
+        for (int tr = 0; tr < a.trials; ++tr) {
+          int k = s - tr;
+          if (k < 0) k += (int)a.K;
+          acc += (double)raw[(base + tr * step + (int64_t)k * M) * a.Fr + fr];
+        }
+        x = mean_of(acc, a.trials);
+      } else {
+        float acc = 0.f;
+        if (a.spk_rows) {
+          acc += raw[base * a.Fr + fr];
+        } else {
+          for (int tr = 0; tr < a.trials; ++tr) {
+            int k = s - tr;
+            if (k < 0) k += (int)a.K;
+            acc += raw[(base + tr * step + (int64_t)k * M) * a.Fr + fr];
+          }
+        }
+        x = a.trials == 1 ? acc : acc * inv;
+      }
+      lo[f] = x;
+      mo[f] = sigmoidf_mask(x);
+    }
+  }
+}
+// raw run u -> (b, tr, t, k, m), then the output run of speaker (k + tr) % K, mask m
+__device__ __forceinline__ int64_t mask_run_source(const MapArgs& a, int M, int64_t u) {
+  const int m = (int)(u % M);
+  const int64_t r = u / M;
+  int64_t b, t; int tr, k;
+  if (a.spk_rows) {
+    t = r % a.T; const int64_t bk = r / a.T; k = (int)(bk % a.K); b = bk / a.K; tr = 0;
+  } else {
+    k = (int)(r % a.K); const int64_t row = r / a.K;
+    t = row % a.T; const int64_t bt = row / a.T; tr = (int)(bt % a.trials); b = bt / a.trials;
+  }
+  int s = k + tr;
+  if (s >= a.K) s -= (int)a.K;
+  const int j = a.perm ? a.perm[b * a.K + s] : s;
+  return (((b * a.K + j) * M + m) * a.T + t) * a.F;
+}
+// d(raw) of one element: fl(fl(dmask * s) * fl(1 - s)) [+ dlogit], every operation rounded on its own
+__device__ __forceinline__ float mask_map_term(const float* __restrict__ dmask, const float* __restrict__ mask,
+                                               const float* __restrict__ dlogit, int64_t i) {
+#pragma clang fp contract(off)
+  const float sg = mask[i];
+  float g = dmask[i] * sg;
+  g = g * (1.0f - sg);
+  if (dlogit) g = g + dlogit[i];
+  return g;
+}
+__global__ __launch_bounds__(256) void mask_map_bwd_tf_kernel(const float* __restrict__ dmask,
+                                                              const float* __restrict__ mask,
+                                                              const float* __restrict__ dlogit, MapArgs a, int M,
+                                                              float* __restrict__ draw) {
+  const int lane = threadIdx.x & 63;
+  const int64_t runs = a.B * a.trials * a.T * a.K * M;
+  const float inv = 1.0f / (float)a.trials;
+  for (int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < runs; u += (int64_t)gridDim.x * 4) {
+    const int64_t src = mask_run_source(a, M, u);
+    float* dst = draw + u * a.F;
+    for (int f = lane; f < a.F; f += 64) {
+      const float g = mask_map_term(dmask, mask, dlogit, src + f);
+      dst[f] = a.trials == 1 ? g : g * inv;
+    }
+  }
+}
+// 't': one raw element per run, the sum over f in logit_map_bwd_t_kernel's order (a lane its bins l, l + 64, ..., then
+// the shuffle tree)
+__global__ __launch_bounds__(256) void mask_map_bwd_t_kernel(const float* __restrict__ dmask,
+                                                             const float* __restrict__ mask,
+                                                             const float* __restrict__ dlogit, MapArgs a, int M,
+                                                             float* __restrict__ draw) {
+  const int lane = threadIdx.x & 63;
+  const int64_t runs = a.B * a.trials * a.T * a.K * M;     // raw elements (Fr == 1)
+  const float inv = 1.0f / (float)a.trials;
+  for (int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < runs; u += (int64_t)gridDim.x * 4) {
+    const int64_t src = mask_run_source(a, M, u);
+    float acc = 0.f;
+    for (int f = lane; f < a.F; f += 64) acc += mask_map_term(dmask, mask, dlogit, src + f);
+    acc = wave_sum(acc);
+    if (lane == 0) draw[u] = a.trials == 1 ? acc : acc * inv;
+  }
 }
 
 }  // namespace
@@ -623,5 +759,31 @@ extern "C" int tssep_logit_map_bwd(const float* dout, const int32_t* perm, const
     hipLaunchKernelGGL(logit_map_bwd_tf_kernel, dim3(grid_for(B * trials * T * K * 64)), dim3(256),
                        0, S_, dout, a, draw);
   }
+  return tssep_launch_status();
+}
+
+extern "C" int tssep_mask_map_fwd(const float* raw, const int32_t* perm, const int32_t* iperm, int64_t B,
+                                  int trials, int64_t K, int M, int64_t T, int F, int Fr, int spk_rows,
+                                  float* logit, float* mask, void* stream) {
+  if (!raw || !logit || !mask) return TSSEP_E_NULL;
+  if (M <= 0) return TSSEP_E_SHAPE;
+  MapArgs a;
+  if (int e = map_args(a, perm, iperm, B, trials, K, T, F, Fr, spk_rows)) return e;
+  hipLaunchKernelGGL(mask_map_fwd_kernel, dim3(grid_for(B * K * M * T * 64)), dim3(256), 0, S_, raw, a, M,
+                     logit, mask);
+  return tssep_launch_status();
+}
+extern "C" int tssep_mask_map_bwd(const float* dmask, const float* mask, const float* dlogit,
+                                  const int32_t* perm, const int32_t* iperm, int64_t B, int trials, int64_t K,
+                                  int M, int64_t T, int F, int Fr, int spk_rows, float* draw, void* stream) {
+  if (!dmask || !mask || !draw) return TSSEP_E_NULL;            // dlogit may be NULL (nobody else used logit)
+  if (M <= 0) return TSSEP_E_SHAPE;
+  MapArgs a;
+  if (int e = map_args(a, perm, iperm, B, trials, K, T, F, Fr, spk_rows)) return e;
+  const unsigned grid = grid_for(B * trials * T * K * M * 64);
+  if (Fr == 1 && F != 1)
+    hipLaunchKernelGGL(mask_map_bwd_t_kernel, dim3(grid), dim3(256), 0, S_, dmask, mask, dlogit, a, M, draw);
+  else
+    hipLaunchKernelGGL(mask_map_bwd_tf_kernel, dim3(grid), dim3(256), 0, S_, dmask, mask, dlogit, a, M, draw);
   return tssep_launch_status();
 }

@@ -377,6 +377,46 @@ def condition(pre, aux, B, K, T, trials, combination):
 
 
 # ------------------------------------------------------------------------ final linear
+def _head_grads(ctx, draw):
+    """d(raw) [R, Nout] of the final Linear -> (dx, dw, db): the weight gradient and the bias column sums (straight into
+    the optimizer's bucket on the side stream where that is set up: dw = db = None then) and the d(input) GEMM.  Shared
+    by _Head and _HeadMasks; ctx carries saved_tensors (xv, wv), params, meta and x_shape."""
+    xv, wv = ctx.saved_tensors[:2]
+    ld_x, ld_w, P, R, Nout = ctx.meta[-5:]
+    dev = draw.device
+    dv, ld_d = H.rows_view(draw)
+    sw, sb = _grad_sink(ctx.params[0]), _grad_sink(ctx.params[1])
+    direct = sw is not None and sb is not None and H.OVERLAP_WGRAD
+    if direct:
+        main, side = torch.cuda.current_stream(), H.side_stream(dev, R)
+        side.wait_stream(main)
+        for t_ in (dv, xv):
+            t_.record_stream(side)
+        with torch.cuda.stream(side):
+            if H.fused_colsum():
+                part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R, with_colsum=True)
+                H.reduce_splits_bias(part, S, Nout, P, H.round_up(P + 1, 4), sw, sb, accumulate=True)
+            else:
+                part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R)
+                H.reduce_splits(part, S, Nout * P, sw, accumulate=True)
+                H.colsum(dv, ld_d, R, Nout, out=sb, accumulate=True)
+        dw = db = None
+        _notify_grads(ctx.params)
+    else:
+        part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R)
+        dw = torch.empty(Nout, P, device=dev, dtype=torch.float32)
+        H.reduce_splits(part, S, Nout * P, dw)
+        db = H.colsum(dv, ld_d, R, Nout)
+    dxb, ld_dx = H.padded(R, P, dev, zero=True)
+    weight = ctx.params[0]
+    wvT, ld_t = H.derived("head_T", [weight], lambda: H.transposed(H.rows_view(weight.detach())[0], Nout, P))
+    H.gemm(dv, ld_d, wvT, ld_t, dxb, ld_dx, R, P, Nout)
+    dx = dxb[:, :P]
+    if tuple(ctx.x_shape) != tuple(dx.shape):
+        dx = dx.reshape(ctx.x_shape)
+    return dx, dw, db
+
+
 class _Head(torch.autograd.Function):
     """post_net.linear + final einops + trial mean + speaker un-permutation
     (tssep/train/net.py:629-666, 928-967): x rows -> logit [B,K,T,F]."""
@@ -409,46 +449,56 @@ class _Head(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        xv, wv = ctx.saved_tensors
         perm, iperm = ctx.aux
-        B, K, T, F, trials, Fr, spk_rows, ld_x, ld_w, P, R, Nout = ctx.meta
-        dev = dout.device
+        B, K, T, F, trials, Fr, spk_rows, _, _, _, R, Nout = ctx.meta
         draw = ctx.link.take() if ctx.link is not None else None
         if draw is None:
             draw = H.logit_map_bwd(dout, perm, iperm, B, trials, K, T, F, Fr, spk_rows).view(R, Nout)
         elif not _is_dummy(dout):      # the fused tail wrote its part already laid out; someone else used logit too
             draw = draw + H.logit_map_bwd(dout, perm, iperm, B, trials, K, T, F, Fr, spk_rows).view(R, Nout)
-        dv, ld_d = H.rows_view(draw)
-        sw, sb = _grad_sink(ctx.params[0]), _grad_sink(ctx.params[1])
-        direct = sw is not None and sb is not None and H.OVERLAP_WGRAD
-        if direct:
-            main, side = torch.cuda.current_stream(), H.side_stream(dev, R)
-            side.wait_stream(main)
-            for t_ in (dv, xv):
-                t_.record_stream(side)
-            with torch.cuda.stream(side):
-                if H.fused_colsum():
-                    part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R, with_colsum=True)
-                    H.reduce_splits_bias(part, S, Nout, P, H.round_up(P + 1, 4), sw, sb, accumulate=True)
-                else:
-                    part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R)
-                    H.reduce_splits(part, S, Nout * P, sw, accumulate=True)
-                    H.colsum(dv, ld_d, R, Nout, out=sb, accumulate=True)
-            dw = db = None
-            _notify_grads(ctx.params)
-        else:
-            part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R)
-            dw = torch.empty(Nout, P, device=dev, dtype=torch.float32)
-            H.reduce_splits(part, S, Nout * P, dw)
-            db = H.colsum(dv, ld_d, R, Nout)
-        dxb, ld_dx = H.padded(R, P, dev, zero=True)
-        weight = ctx.params[0]
-        wvT, ld_t = H.derived("head_T", [weight], lambda: H.transposed(H.rows_view(weight.detach())[0], Nout, P))
-        H.gemm(dv, ld_d, wvT, ld_t, dxb, ld_dx, R, P, Nout)
-        dx = dxb[:, :P]
-        if tuple(ctx.x_shape) != tuple(dx.shape):
-            dx = dx.reshape(ctx.x_shape)
+        dx, dw, db = _head_grads(ctx, draw)
         return dx, dw, db, None, None, None, None, None, None, None, None, None, None
+
+
+class _HeadMasks(torch.autograd.Function):
+    """post_net.linear with nmask = M > 1 masks per speaker + final einops + trial mean + un-permutation + sigmoid
+    (tssep/train/net.py:629-666, 928-967, 983): x rows -> (logit, mask), both [B,K,M,T,F].  The raw GEMM, then ONE fused
+    map kernel each way (hip_ops.mask_map_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, perm, iperm, B, K, M, T, F, trials, Fr, spk_rows):
+        xv, ld_x = H.rows_view(x)
+        P = weight.shape[1]
+        wv, ld_w = H.rows_view(weight.detach())
+        R, Nout = xv.shape[0], weight.shape[0]
+        assert Nout == (1 if spk_rows else K) * M * Fr and R == B * trials * T * (K if spk_rows else 1), \
+            (R, Nout, (B, K, M, T, F, trials, Fr, spk_rows))
+        raw = torch.empty(R, Nout, device=x.device, dtype=torch.float32)
+        H.gemm(xv, ld_x, wv, ld_w, raw, Nout, R, Nout, P, bias=bias.detach())
+        logit, mask = H.mask_map_fwd(raw, perm, iperm, B, trials, K, M, T, F, Fr, spk_rows)
+        ctx.save_for_backward(xv, wv, mask)
+        ctx.params = (weight, bias)
+        ctx.aux = (perm, iperm)
+        ctx.meta = (B, K, M, T, F, trials, Fr, spk_rows, ld_x, ld_w, P, R, Nout)
+        ctx.x_shape = x.shape
+        ctx.set_materialize_grads(False)          # d(logit) is None when nobody else used the logit
+        return logit, mask
+
+    @staticmethod
+    def backward(ctx, dlogit, dmask):
+        perm, iperm = ctx.aux
+        B, K, M, T, F, trials, Fr, spk_rows, _, _, _, R, Nout = ctx.meta
+        mask = ctx.saved_tensors[2]
+        if dmask is None:                         # only the logit was used: the same kernel with d(mask) = 0
+            dmask = torch.zeros_like(mask)
+        draw = H.mask_map_bwd(dmask, mask, dlogit, perm, iperm, B, trials, K, M, T, F, Fr, spk_rows).view(R, Nout)
+        dx, dw, db = _head_grads(ctx, draw)
+        return (dx, dw, db) + (None,) * 10
+
+
+def head_masks(x, linear, perm, iperm, B, K, M, T, F, trials, Fr, spk_rows):
+    """nmask = M > 1 -> (logit, mask) [B,K,M,T,F]"""
+    return _HeadMasks.apply(x, linear.weight, linear.bias, perm, iperm, B, K, M, T, F, trials, Fr, spk_rows)
 
 
 def head(x, linear, perm, iperm, B, K, T, F, trials, Fr, spk_rows):

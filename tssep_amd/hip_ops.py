@@ -366,6 +366,7 @@ GEMM_KERNEL_NAMES = {v: k for k, v in GEMM_KERNELS.items()}
 GEMM_PREFER = ()
 GEMM_LOG = None          # a list: (kernel name, M, N, K) of every launch is appended (tests)
 RECURRENCE_LOG = None    # a list: dict(kernel, direction, N, T, H, groups) of every recurrence launch (Trainer: the kernel plan)
+TAIL_LOG = None          # a list: dict(kernel, ...) of every fused two-mask tail launch (mask_map_fwd / _bwd; the kernel plan)
 
 
 def _log_recurrence(kernel, direction, N, T, H, groups=0):
@@ -1694,6 +1695,39 @@ def logit_map_bwd(dout, perm, iperm, B, trials, K, T, F, Fr, spk_rows):
     check(_lib.lib().tssep_logit_map_bwd(_p(_f32(dout).contiguous()), _p(perm), _p(iperm), B,
                                          trials, K, T, F, Fr, int(spk_rows), _p(draw), _stream()),
           "logit_map_bwd")
+    return draw
+
+
+def mask_map_fwd(raw, perm, iperm, B, trials, K, M, T, F, Fr, spk_rows):
+    """The fused two-mask tail: raw GEMM output -> (logit, mask), both [B,K,M,T,F] fp32, in one launch (the logit map
+    with M masks per speaker + the mask head's sigmoid; include/tssep_hip.h)."""
+    logit = torch.empty(B, K, M, T, F, device=raw.device, dtype=torch.float32)
+    mask = torch.empty_like(logit)
+    n = B * K * M * T
+    if TAIL_LOG is not None:
+        TAIL_LOG.append(dict(kernel="mask_map_fwd", B=B, K=K, M=M, T=T, F=F, Fr=Fr, trials=trials, spk_rows=int(spk_rows)))
+    with _timed("mask_map_fwd", 0, 4 * n * (trials * Fr + 2 * F)):
+        check(_lib.lib().tssep_mask_map_fwd(_p(_f32(raw)), _p(perm), _p(iperm), B, trials, K, M, T, F, Fr, int(spk_rows),
+                                            _p(logit), _p(mask), _stream()), "mask_map_fwd")
+    return logit, mask
+
+
+def mask_map_bwd(dmask, mask, dlogit, perm, iperm, B, trials, K, M, T, F, Fr, spk_rows):
+    """dmask, the saved mask and (or None) dlogit, all [B,K,M,T,F] -> draw in the raw layout [B*trials*K*M*T*Fr], one
+    launch: (dmask s (1 - s) [+ dlogit]) [/ trials], summed over f for Fr == 1."""
+    assert tuple(mask.shape) == (B, K, M, T, F) and mask.is_contiguous(), (tuple(mask.shape), (B, K, M, T, F))
+    assert tuple(dmask.shape) == tuple(mask.shape), (tuple(dmask.shape), tuple(mask.shape))
+    assert dlogit is None or tuple(dlogit.shape) == tuple(mask.shape), tuple(dlogit.shape)
+    n = B * K * M * T
+    draw = torch.empty(n * trials * Fr, device=mask.device, dtype=torch.float32)
+    if TAIL_LOG is not None:
+        TAIL_LOG.append(dict(kernel="mask_map_bwd", B=B, K=K, M=M, T=T, F=F, Fr=Fr, trials=trials, spk_rows=int(spk_rows),
+                             dlogit=dlogit is not None))
+    with _timed("mask_map_bwd", 0, 4 * n * ((2 if dlogit is None else 3) * F + trials * Fr)):
+        check(_lib.lib().tssep_mask_map_bwd(_p(_f32(dmask).contiguous()), _p(_f32(mask)),
+                                            _p(_f32(dlogit).contiguous()) if dlogit is not None else None,
+                                            _p(perm), _p(iperm), B, trials, K, M, T, F, Fr, int(spk_rows), _p(draw),
+                                            _stream()), "mask_map_bwd")
     return draw
 
 

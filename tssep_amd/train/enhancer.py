@@ -47,6 +47,10 @@ class Masking(ABC):
         """masks [B,K,1,T,F] -> complex [B,K,T,F] = Obs[ref] * mask (enhancer.py:98-100).
         Standalone form (mask tensor in).  ``Model.forward`` does not come through here for the
         Masking enhancer: it fuses sigmoid + product into one mask-head kernel."""
+        if masks.shape[-3] != 1:
+            raise ValueError(f"Masking takes one mask per speaker, got {masks.shape[-3]} (masks {tuple(masks.shape)}): the "
+                             "squeeze of the mask axis is a no-op then and the product with the observation does not "
+                             "broadcast (enhancer.py:98-100); train such an estimator through TorchBF")
         Observation, batched = _observation(masks, ex)
         m = torch.squeeze(masks, dim=-3)
         if not batched:

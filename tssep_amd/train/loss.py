@@ -65,6 +65,9 @@ class LogitsSTFTDomain(ABC):
             raise ValueError(
                 f"{self.name} reads out.logit, which an explicit_vad mask estimator does not produce (net.py:969-979); "
                 "train it with SignalAndVADSigmoidBCE(signal_loss=...), whose VAD term reads out.vad_logit")
+        if out.logit.shape[-3] != 1:
+            raise ValueError(f"{self.name} on a logit with {out.logit.shape[-3]} masks per speaker {tuple(out.logit.shape)}: "
+                             "the squeeze of the mask axis (loss.py:122-146) is a no-op then; use nmask=1")
         estimate = torch.squeeze(out.logit, dim=-3)
         assert self.target[0].isupper(), self.target
         if self.target not in ex:

@@ -92,6 +92,20 @@ class Model(Configurable, torch.nn.Module):
         self.enhancer = enhancer
         self.loss = loss
         self.create_snapshot = False
+        self._check_nmask()
+
+    def _check_nmask(self):
+        """nmask > 1 (a target and an interference mask per speaker, the reference's choice for every enhancer but Masking,
+        model.py:135-146) goes to a beamformer; what cannot consume [..., K, M, T, F] is refused here, by name."""
+        nmask = getattr(self.mask_estimator, "nmask", 1)
+        if nmask == 1:
+            return
+        if isinstance(self.enhancer, _enh.Masking):
+            raise ValueError(f"Masking with nmask={nmask}: the enhancer squeezes the mask axis (enhancer.py:98-100), a no-op "
+                             "for more than one mask, and the product with the observation does not broadcast; use nmask=1")
+        if isinstance(self.loss, _loss.VADSigmoidBCE):
+            raise ValueError(f"{type(self.loss).__name__} with nmask={nmask}: the loss squeezes the mask axis of the logit "
+                             "(loss.py:122-146) and compares [..., K, T] with the activity; a two-mask logit has no such form")
 
     # ------------------------------------------------------------------ data helpers
     def example_to_device(self, ex, device):                # model.py:166-180
@@ -317,6 +331,8 @@ class Model(Configurable, torch.nn.Module):
 
         aux = ex["auxInput"] if isinstance(ex["auxInput"], torch.Tensor) else ex["AuxInput"]
         batched = ex["Input"].dim() == 3
+        if getattr(self.mask_estimator, "nmask", 1) > 1:
+            return self._forward_masks(ex)
         logit, emb = self.mask_estimator.logits(ex["Input"], aux)
         logit4 = logit if batched else logit[None]
         if getattr(self.mask_estimator, "explicit_vad", False):
@@ -344,6 +360,19 @@ class Model(Configurable, torch.nn.Module):
                 mask = Fn.sigmoid(logit4)
                 return (mask if batched else mask[0]).unsqueeze(-3), None
         out._lazy = out._lazy0 = lazy
+        return out
+
+    def _forward_masks(self, ex):
+        """nmask > 1: mask and logit [..., K, M, T, F] come out of one fused kernel (functional.head_masks) and go to the
+        enhancer as they are -- TorchBF with differentiable=True while training, any TorchBF under no_grad."""
+        self._check_nmask()
+        aux = ex["auxInput"] if isinstance(ex["auxInput"], torch.Tensor) else ex["AuxInput"]
+        logit, mask, emb = self.mask_estimator.logits(ex["Input"], aux)
+        out = self.ForwardOutput(mask=mask, logit=logit, embedding=emb)
+        if "Observation" in ex:
+            out._lazy = out._lazy0 = lambda: (mask, self.enhancer(mask, self._bf_example(ex), self))
+        else:
+            out._lazy = out._lazy0 = lambda: (mask, None)
         return out
 
     def _bf_example(self, ex):

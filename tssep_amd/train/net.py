@@ -181,8 +181,11 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         assert aux_net is None or aux_normalizer is None, (aux_normalizer, "Not clear, whether before or after")   # net.py:834
         if explicit_vad and output_resolution == "t":
             raise AssertionError("explicit_vad needs output_resolution='tf' (net.py:643)")
-        if nmask != 1:
-            raise NotImplementedError("nmask != 1 (Masking enhancer uses 1, model.py:138-145)")
+        if not isinstance(nmask, int) or isinstance(nmask, bool) or nmask < 1:
+            raise ValueError(f"nmask={nmask!r}: a positive number of masks per speaker")
+        if explicit_vad and nmask != 1:
+            raise NotImplementedError(f"explicit_vad=True with nmask={nmask}: the gate column is built for one mask per speaker, "
+                                      "and the reference's SignalAndVADSigmoidBCE cannot consume more (net.py:969-979)")
         self.odim, self.nmask = odim, nmask
         self.output_resolution = output_resolution
         self.random_speaker_order = random_speaker_order
@@ -288,11 +291,11 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
 
     # ----------------------------------------------------------------------------------
     def logits(self, xs, aux):
-        """-> (logit [B,K,T,F], embedding [B,K,1,E]).  Batched input only.  explicit_vad: logit [B,K,T,F+1], the VAD
-        logit at column 0 of every row and the mask logits behind it (net.py:969-979 slices them apart)."""
+        """-> (logit [B,K,T,F], embedding [B,K,1,E]).  explicit_vad: logit [B,K,T,F+1], the VAD logit at column 0 of
+        every row and the mask logits behind it (net.py:969-979 slices them apart).  nmask > 1: (logit [B,K,M,T,F], mask
+        [B,K,M,T,F], embedding) -- the fused two-mask tail computes the sigmoid in the pass that lays the logit out."""
         if xs.dim() == 2:
-            lg, emb = self.logits(xs[None], [aux])
-            return lg[0], emb[0]
+            return tuple(r[0] for r in self.logits(xs[None], [aux]))
         assert xs.dim() == 3, xs.shape
         B, T = xs.shape[0], xs.shape[1]
         dev = xs.device
@@ -347,11 +350,18 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
                                        final_dropout=site)
                 prev_tanh = (K if nxt_combined else 1) if fold else 0
         Fr = F if self.output_resolution == "tf" else 1
+        if self.nmask > 1:
+            logit, mask = Fn.head_masks(h, self._linear, perm_d, iperm_d, B, K, self.nmask, T, F, trials, Fr,
+                                        spk_rows=self.ts_vad is False)
+            return logit, mask, aux.unsqueeze(-2)
         logit = Fn.head(h, self._linear, perm_d, iperm_d, B, K, T, F, trials, Fr,
                         spk_rows=self.ts_vad is False)
         return logit, aux.unsqueeze(-2)
 
     def forward(self, xs, aux=None) -> Output:
+        if self.nmask > 1:                         # [..., K, M, T, F] as they are (net.py:631-659, 983)
+            logit, mask, emb = self.logits(xs, aux)
+            return Output(mask=mask, logit=logit, embedding=emb)
         logit, emb = self.logits(xs, aux)
         u = -3
         if self.explicit_vad:                      # net.py:969-979

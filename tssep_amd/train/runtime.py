@@ -117,9 +117,10 @@ def describe(device=None):
     return d
 
 
-def summarise_plan(gemm_log, recurrence_log=()):
-    """GEMM_LOG / RECURRENCE_LOG of one step -> {'gemm': {kernel: launches}, 'gemm_requests': [...], 'recurrence': {...}}:
-    which kernels the library picked for THIS model and batch (`tssep_gemm_plan`), written once per run."""
+def summarise_plan(gemm_log, recurrence_log=(), tail_log=()):
+    """GEMM_LOG / RECURRENCE_LOG / TAIL_LOG of one step -> {'gemm': {kernel: launches}, 'gemm_requests': [...],
+    'recurrence': [...], 'tail': [...]}: which kernels the library picked for THIS model and batch (`tssep_gemm_plan`),
+    written once per run.  'tail' lists the fused two-mask launches (mask_map_fwd / _bwd): empty for nmask = 1."""
     gemms, reqs, seen = {}, [], set()
     for name, M, N, K, d in gemm_log:
         gemms[str(name)] = gemms.get(str(name), 0) + 1
@@ -133,4 +134,5 @@ def summarise_plan(gemm_log, recurrence_log=()):
         key = json.dumps(entry, sort_keys=True)
         rec[key] = rec.get(key, 0) + 1
     return dict(gemm=gemms, gemm_requests=reqs,
-                recurrence=[dict(json.loads(k), launches=n) for k, n in rec.items()])
+                recurrence=[dict(json.loads(k), launches=n) for k, n in rec.items()],
+                tail=[dict(e) for e in tail_log or ()])

@@ -133,11 +133,11 @@ class Trainer(Configurable):
         obs = ex.get("observation", ex.get("Input"))
         return int(obs.shape[0]) if isinstance(obs, torch.Tensor) and obs.dim() == 3 else 1
 
-    def _log_kernel_plan(self, gemm_log, recurrence_log, chief):
+    def _log_kernel_plan(self, gemm_log, recurrence_log, chief, tail_log=()):
         """Once per run: the kernels behind the first training step -- GEMM kernel per request (the library's own choice,
         `tssep_gemm_plan`), recurrence family and group counts -- and the runtime policy they ran under."""
         from . import runtime as _runtime
-        plan = _runtime.summarise_plan(gemm_log, recurrence_log)
+        plan = _runtime.summarise_plan(gemm_log, recurrence_log, tail_log)
         self.kernel_plan = plan
         if not chief:
             return
@@ -292,14 +292,15 @@ class Trainer(Configurable):
                     if not plan_logged:
                         # the first micro-step of a run, eagerly, with the launch logs on: which kernels the library picks
                         # for THIS model and batch (tssep_gemm_plan) and which recurrence family runs -> log/kernel_plan.json
-                        _H.GEMM_LOG, _H.RECURRENCE_LOG = [], []
+                        _H.GEMM_LOG, _H.RECURRENCE_LOG, _H.TAIL_LOG = [], [], []
                         try:
                             summary = self.model.review(ex, self.model(ex))
                             summary["loss"].backward()
                         finally:
                             glog, rlog, _H.GEMM_LOG, _H.RECURRENCE_LOG = _H.GEMM_LOG, _H.RECURRENCE_LOG, None, None
+                            tlog, _H.TAIL_LOG = _H.TAIL_LOG, None
                         plan_logged = True
-                        self._log_kernel_plan(glog, rlog, chief)
+                        self._log_kernel_plan(glog, rlog, chief, tlog)
                     elif gstep is not None and gstep.usable(ex) and (
                             _H.GRAPH_STEP == "on" or self._utterances(ex) <= _H.GRAPH_MAX_UTTERANCES):
                         # forward + loss + backward as one replayed hipGraph, captured as ONE chain of nodes: the weight
