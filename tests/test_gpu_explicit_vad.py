@@ -68,14 +68,14 @@ def test_gated_fused_tail_against_float64(B, K, N):
     logit, obs, tgt, vad, T = _inputs(B, K, N, seed=B * 1000 + K)
     _, wsyn = Fn.windows("hann", 1024, 256, logit.device)
     l64, mask, gate, est, y64 = _ref_tail(logit, obs, N)
-    y, part = H.mask_istft_gated_fwd(logit, obs, wsyn, N, tgt=tgt)
+    y, part = H.mask_istft_fwd(logit, obs, wsyn, N, tgt=tgt)
     close(y, y64, rtol=1e-4, atol=2e-6 * _tail_scale(y64), name="y")
     sums64 = (y64.detach() - _d(tgt)).abs().sum(-1)
     close(part.view(B, K, -1).sum(-1), sums64, rtol=1e-4, atol=1e-6, name="|y - tgt| sums")
     # plain backward: dy given
     dy = torch.randn(B, K, N, generator=torch.Generator().manual_seed(5)).cuda()
     (dl64,) = torch.autograd.grad(y64, l64, _d(dy), retain_graph=True)
-    dl = H.mask_istft_gated_bwd(dy, logit, obs, wsyn)
+    dl = H.mask_istft_bwd(dy, logit, obs, wsyn)
     sc = _tail_scale(dl64)
     close(dl[..., 1:], dl64[..., 1:], rtol=1e-3, atol=1e-5 * sc, name="d(mask logits)")
     close(dl[..., 0], dl64[..., 0], rtol=1e-3, atol=1e-5 * _tail_scale(dl64[..., 0]), name="d(vad logit)")
@@ -92,18 +92,18 @@ def test_gated_fused_tail_against_float64(B, K, N):
     _, sums = H.logmae_fwd(yl, tgt)
     perm = torch.stack([torch.randperm(K, generator=torch.Generator().manual_seed(b)) for b in range(B)]).int().cuda()
     iperm = torch.argsort(perm, dim=-1).int()
-    d = H.mask_istft_gated_bwd(None, logit, obs, wsyn, loss=(yl, tgt, sums, gout), vad=(vad, gbce), iperm=iperm,
-                               bt_major=True)
+    d = H.mask_istft_bwd(None, logit, obs, wsyn, loss=(yl, tgt, sums, gout), vad=(vad, gbce), iperm=iperm,
+                         bt_major=True)
     assert tuple(d.shape) == (B * T, K * (F + 1))
     d = d.view(B, T, K, F + 1)
     got = torch.stack([d[b][:, iperm[b].long()] for b in range(B)]).permute(0, 2, 1, 3)     # -> [B, K, T, F + 1]
     close(got[..., 1:], dl64[..., 1:], rtol=1e-3, atol=1e-5 * _tail_scale(dl64[..., 1:]), name="folded d(mask logits)")
     close(got[..., 0], dl64[..., 0], rtol=1e-3, atol=1e-5 * _tail_scale(dl64[..., 0]), name="folded d(vad logit)")
     # the same fold into the [B, K, T, F + 1] layout equals the bt_major one bit for bit
-    d2 = H.mask_istft_gated_bwd(None, logit, obs, wsyn, loss=(yl, tgt, sums, gout), vad=(vad, gbce))
+    d2 = H.mask_istft_bwd(None, logit, obs, wsyn, loss=(yl, tgt, sums, gout), vad=(vad, gbce))
     assert torch.equal(d2, got)
     # deterministic: the in-wave reduction of d(v) is a fixed order
-    assert torch.equal(H.mask_istft_gated_bwd(dy, logit, obs, wsyn), dl)
+    assert torch.equal(H.mask_istft_bwd(dy, logit, obs, wsyn), dl)
 
 
 @pytest.mark.parametrize("B,K,N", SIZES[:2])

@@ -300,12 +300,12 @@ def test_fused_backward(B, K, N):
     # the wrapper hands a non-contiguous `sums` to the kernel as a contiguous fp32 vector, like its other arguments
     strided = torch.stack([d["sums"], torch.full_like(d["sums"], NAN)], 1)[:, 0]
     assert not strided.is_contiguous() or B == 1
-    w = H().mask_istft_gated_bwd(None, d["logit"], d["obs"], ws, loss=(d["est"].view(B, K, N), d["tgt_ties"].view(B, K, N), strided,
-                                                                        d["gout"]), vad=(d["vad"], d["gbce"]))
+    w = H().mask_istft_bwd(None, d["logit"], d["obs"], ws, loss=(d["est"].view(B, K, N), d["tgt_ties"].view(B, K, N), strided,
+                                                                  d["gout"]), vad=(d["vad"], d["gbce"]))
     assert torch.equal(w, ref)
     with pytest.raises(AssertionError):
-        H().mask_istft_gated_bwd(None, d["logit"], d["obs"], ws, loss=(d["est"].view(B, K, N), d["tgt_ties"].view(B, K, N),
-                                                                    d["sums"].double(), d["gout"]))
+        H().mask_istft_bwd(None, d["logit"], d["obs"], ws, loss=(d["est"].view(B, K, N), d["tgt_ties"].view(B, K, N),
+                                                              d["sums"].double(), d["gout"]))
 
 
 def test_fused_backward_agrees_with_the_unfused_head():

@@ -418,3 +418,47 @@ def test_prepare_dataset_follows_the_reference_stages():
     assert [e["example_id"] for e in val] == [f"dummy_id_{i}" for i in range(4)]
     srt = m.prepare_dataset("train", None, training=True, sort=True, batch_size=2, prefetch=False)
     assert [e["example_id"] for e in srt][0] == ["dummy_id_0", "dummy_id_1"]
+
+
+def test_stft_entry_points_share_their_argument_checks():
+    """stft.hip: the eight entry points go through two launchers, so a check one of them has, all of them have -- the tgt /
+    abs_partial pairing, the 65 535-row limit of the iSTFT grid, the 2^31 - 1 blocks of the rfft grid, the alignment of
+    logit / d(logit), NULL.  Every call here is refused before anything is launched: the pointers are never read."""
+    L = _lib.lib()
+    SHAPE, ALIGN, UNSUPPORTED, NULL = -1, -2, -3, -5                   # include/tssep_hip.h
+    p, odd = 0x10000, 0x10002                                          # 8-byte aligned / not even 4-byte aligned
+    B, K, T, N = 2, 4, 20, 4096
+
+    def fwd(entry, lead, rows, size=1024, fading=1, tgt=None, part=None):
+        return entry(*lead, *rows, T, size, 256, fading, p, p, p, N, tgt, part, None)
+
+    forwards = [(L.tssep_istft_fwd, (p,), (B * K,), (65536,)), (L.tssep_mask_istft_fwd, (p, p), (B, K), (16384, 4)),
+                (L.tssep_mask_istft_gated_fwd, (p, p), (B, K), (16384, 4))]
+    for entry, lead, rows, too_many in forwards:
+        assert fwd(entry, lead, rows, tgt=p) == NULL and fwd(entry, lead, rows, part=p) == NULL
+        assert fwd(entry, lead, too_many) == SHAPE
+        assert fwd(entry, lead, rows, fading=0) == UNSUPPORTED
+        assert fwd(entry, (None,) * len(lead), rows) == NULL and fwd(entry, lead, (0,) * len(rows)) == SHAPE
+    for entry in (L.tssep_mask_istft_fwd, L.tssep_mask_istft_gated_fwd):
+        assert fwd(entry, (odd, p), (B, K)) == ALIGN and fwd(entry, (p, odd), (B, K)) == ALIGN
+        assert fwd(entry, (p, p), (B, K), size=512) == UNSUPPORTED
+
+    big = (1 << 20, 1 << 16)                                           # rows, T: 2^36 frames = 2^32 blocks
+    tail = (1024, 256, 1, p, p)                                        # size, shift, fading, window, tw
+
+    def backwards(logit=p, dlogit=p, rows=(B, K), T=T, size=1024, gout=p, gbce=p, only=slice(None)):
+        t = (size,) + tail[1:]
+        calls = [lambda: L.tssep_mask_istft_bwd(p, logit, p, *rows, N, *t, dlogit, T, None),
+                 lambda: L.tssep_mask_istft_bwd_loss(p, p, p, gout, logit, p, *rows, N, *t, None, 1, dlogit, T, None),
+                 lambda: L.tssep_mask_istft_gated_bwd(p, p, p, gout, p, gbce, logit, p, *rows, N, *t, None, 1, dlogit, T,
+                                                      None)]
+        return [call() for call in calls[only]]
+
+    assert backwards(rows=(big[0], 1), T=big[1]) == [SHAPE] * 3
+    assert L.tssep_stft_fwd(p, big[0], N, *tail, p, big[1], None) == SHAPE
+    assert L.tssep_istft_bwd(p, big[0], N, *tail, p, big[1], None) == SHAPE
+    assert backwards(logit=odd) == [ALIGN] * 3 and backwards(dlogit=odd) == [ALIGN] * 3
+    assert backwards(logit=None) == [NULL] * 3 and backwards(rows=(B, 0)) == [SHAPE] * 3
+    assert backwards(rows=(-1, -1)) == [SHAPE] * 3 and backwards(size=512) == [UNSUPPORTED] * 3
+    # (only the entry points that take the argument: for the others the call would be a valid one)
+    assert backwards(gout=None, only=slice(1, 3)) == [NULL] * 2 and backwards(gbce=None, only=slice(2, 3)) == [NULL]

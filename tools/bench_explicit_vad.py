@@ -47,24 +47,12 @@ def main():
         runs = {}
         for gated in (False, True, "nobce"):
             logit = torch.randn(B, K, T, F + int(bool(gated)), device=dev, generator=g)
-            if gated == "nobce":           # the gated tail without the BCE fold: what the gate itself costs
-                fwd = lambda l=logit: h.mask_istft_gated_fwd(l, obs, wsyn, N, tgt=tgt)        # noqa: E731
-                y, _ = fwd()
-                _, sums = h.logmae_fwd(y, tgt)
-                bwd = lambda l=logit, y=y, s=sums: h.mask_istft_gated_bwd(                      # noqa: E731
-                    None, l, obs, wsyn, loss=(y, tgt, s, gout), iperm=iperm, bt_major=True)
-            elif gated:
-                fwd = lambda l=logit: h.mask_istft_gated_fwd(l, obs, wsyn, N, tgt=tgt)        # noqa: E731
-                y, _ = fwd()
-                _, sums = h.logmae_fwd(y, tgt)
-                bwd = lambda l=logit, y=y, s=sums: h.mask_istft_gated_bwd(                      # noqa: E731
-                    None, l, obs, wsyn, loss=(y, tgt, s, gout), vad=(vad, gout), iperm=iperm, bt_major=True)
-            else:
-                fwd = lambda l=logit: h.mask_istft_fwd(l, obs, wsyn, N, tgt=tgt)              # noqa: E731
-                y, _ = fwd()
-                _, sums = h.logmae_fwd(y, tgt)
-                bwd = lambda l=logit, y=y, s=sums: h.mask_istft_bwd(                            # noqa: E731
-                    None, l, obs, wsyn, loss=(y, tgt, s, gout), iperm=iperm, bt_major=True)
+            fwd = lambda l=logit: h.mask_istft_fwd(l, obs, wsyn, N, tgt=tgt)                    # noqa: E731
+            y, _ = fwd()
+            _, sums = h.logmae_fwd(y, tgt)
+            va = (vad, gout) if gated is True else None     # ("nobce": without the BCE fold -- what the gate itself costs)
+            bwd = lambda l=logit, y=y, s=sums, va=va: h.mask_istft_bwd(                          # noqa: E731
+                None, l, obs, wsyn, loss=(y, tgt, s, gout), vad=va, iperm=iperm, bt_major=True)
             fwd(); bwd(); torch.cuda.synchronize()
             runs[gated] = (fwd, bwd, {"fwd": [], "bwd": []})
         for _ in range(a.rounds):                      # interleaved: ungated, gated, gated without the fold, ungated, ...

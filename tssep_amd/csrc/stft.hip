@@ -555,83 +555,51 @@ extern "C" int tssep_stft_plan(int size, int shift) {
   return check_plan(size, shift) == TSSEP_OK ? 1 : (tssep_generic_plan_supported(size, shift) ? 2 : 0);
 }
 
-extern "C" int tssep_stft_fwd(const float* x, int64_t rows, int64_t N, int size, int shift,
-                              int fading, const float* window, const float* tw, float* X,
-                              int64_t T, void* stream) {
-  if (!x || !window || !tw || !X) return TSSEP_E_NULL;
-  if (rows <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
-  if ((((uintptr_t)X) & 7u) || (((uintptr_t)tw) & 7u) || (((uintptr_t)window) & 7u)) return TSSEP_E_ALIGN;
-  if (generic_plan(size, shift))
-    return tssep_generic_rfft(x, rows, N, size, shift, fading ? size - shift : 0, window, tw, X, T, 1.0f, 1.0f, stream);
-  if (int e = check_plan(size, shift)) return e;
-  const int iters = 4;
-  const int64_t total = rows * T;
-  const int64_t blocks = (total + 4 * iters - 1) / (4 * iters);
-  hipLaunchKernelGGL(rfft_frames_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     x, rows, N, T, shift, fading ? size - shift : 0, window, (const float2*)tw,
-                     (float2*)X, 1.0f, 1.0f, iters, (const float*)nullptr, (const float2*)nullptr,
-                     (float*)nullptr, (int64_t)1, (const float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, (const int32_t*)nullptr, 0);
-  return tssep_launch_status();
+static bool misaligned(const void* p, uintptr_t bytes) { return (((uintptr_t)p) & (bytes - 1)) != 0; }
+
+// ---- the two launchers: what varies between the entry points, the checks they share, the grid, the launch ----------
+// One launch of rfft_frames_kernel.  A member an entry point does not name stays zero / NULL.  (The entry point names the
+// instantiation, not the launcher: the compiler emits the device functions in the order the host code names them.)
+using rfft_kernel_t = decltype(&rfft_frames_kernel<false>);
+struct RfftLaunch {
+  rfft_kernel_t kernel;                        // the instantiation, named by the entry point
+  bool masked;                                 // its MASKED flag: which of the members below it reads
+  const float* x;                              // [rows, N]: the signal, dy, or with tgt != NULL the time-domain estimate
+  int64_t rows, N, T;
+  int size, shift, fading;
+  const float *window, *tw;
+  float s_in, s_edge;
+  float* X;                                    // !masked: the spectra [rows, T, 513] (complex)
+  const float *logit, *obs;                    // masked: rows = B K logit rows, the B observation spectra
+  float* dlogit;
+  int64_t K;
+  const float *tgt, *sums, *gout;              // the loss fold (tgt == NULL: x is dy itself; sums == NULL: MAE)
+  const int32_t* iperm;                        // the layout fold
+  int bt_major;
+  const float *vad, *gbce;                     // gated: the BCE fold on the gate column (vad == NULL: none)
+};
+
+// (the checks that do not depend on the plan: the general plan of stft_generic.hip takes the same arguments)
+static int rfft_check(const RfftLaunch& a) {
+  if (!a.x || !a.window || !a.tw) return TSSEP_E_NULL;
+  if (a.masked ? (!a.logit || !a.obs || !a.dlogit || (a.tgt && !a.gout) || (a.vad && !a.gbce)) : !a.X) return TSSEP_E_NULL;
+  if (a.rows <= 0 || (a.masked && a.K <= 0) || a.N <= 0 || a.T <= 0) return TSSEP_E_SHAPE;
+  if (misaligned(a.tw, 8) || misaligned(a.window, 8)) return TSSEP_E_ALIGN;
+  if (a.masked ? (misaligned(a.logit, 4) || misaligned(a.dlogit, 4) || misaligned(a.obs, 8)) : misaligned(a.X, 8))
+    return TSSEP_E_ALIGN;
+  return TSSEP_OK;
 }
 
-extern "C" int tssep_istft_bwd(const float* dy, int64_t rows, int64_t N, int size, int shift,
-                               int fading, const float* wsyn, const float* tw, float* dX,
-                               int64_t T, void* stream) {
-  if (!dy || !wsyn || !tw || !dX) return TSSEP_E_NULL;
-  if (rows <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
-  if ((((uintptr_t)dX) & 7u) || (((uintptr_t)tw) & 7u) || (((uintptr_t)wsyn) & 7u)) return TSSEP_E_ALIGN;
-  if (generic_plan(size, shift))
-    return tssep_generic_rfft(dy, rows, N, size, shift, fading ? size - shift : 0, wsyn, tw, dX, T, 2.0f / (float)size,
-                              1.0f / (float)size, stream);
-  if (int e = check_plan(size, shift)) return e;
-  const int iters = 4;
-  const int64_t total = rows * T;
-  const int64_t blocks = (total + 4 * iters - 1) / (4 * iters);
-  hipLaunchKernelGGL(rfft_frames_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     dy, rows, N, T, shift, fading ? size - shift : 0, wsyn, (const float2*)tw,
-                     (float2*)dX, 2.0f / (float)size, 1.0f / (float)size, iters, (const float*)nullptr,
-                     (const float2*)nullptr, (float*)nullptr, (int64_t)1, (const float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, (const int32_t*)nullptr, 0);
-  return tssep_launch_status();
-}
-
-extern "C" int tssep_mask_istft_bwd(const float* dy, const float* logit, const float* obs, int64_t B,
-                                    int64_t K, int64_t N, int size, int shift, int fading,
-                                    const float* wsyn, const float* tw, float* dlogit, int64_t T,
-                                    void* stream) {
-  if (!dy || !logit || !obs || !wsyn || !tw || !dlogit) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
-  if (int e = check_plan(size, shift)) return e;
-  if ((((uintptr_t)obs) & 7u) || (((uintptr_t)tw) & 7u) || (((uintptr_t)wsyn) & 7u)) return TSSEP_E_ALIGN;
-  const int iters = 4;
-  const int64_t rows = B * K, total = rows * T;
-  const int64_t blocks = (total + 4 * iters - 1) / (4 * iters);
-  hipLaunchKernelGGL(rfft_frames_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     dy, rows, N, T, shift, fading ? size - shift : 0, wsyn, (const float2*)tw,
-                     (float2*)nullptr, 2.0f / (float)size, 1.0f / (float)size, iters, logit,
-                     (const float2*)obs, dlogit, K, (const float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, (const int32_t*)nullptr, 0);
-  return tssep_launch_status();
-}
-
-extern "C" int tssep_mask_istft_bwd_loss(const float* est, const float* tgt, const float* sums, const float* gout,
-                                         const float* logit, const float* obs, int64_t B, int64_t K, int64_t N,
-                                         int size, int shift, int fading, const float* wsyn, const float* tw,
-                                         const int32_t* iperm, int bt_major, float* dlogit, int64_t T,
-                                         void* stream) {
-  // tgt == NULL: `est` is dy itself (only the output layout is folded); sums == NULL: MAE
-  if (!est || (tgt && !gout) || !logit || !obs || !wsyn || !tw || !dlogit) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
-  if (int e = check_plan(size, shift)) return e;
-  if ((((uintptr_t)obs) & 7u) || (((uintptr_t)tw) & 7u) || (((uintptr_t)wsyn) & 7u)) return TSSEP_E_ALIGN;
-  const int iters = 4;
-  const int64_t rows = B * K, total = rows * T;
-  const int64_t blocks = (total + 4 * iters - 1) / (4 * iters);
-  hipLaunchKernelGGL(rfft_frames_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     est, rows, N, T, shift, fading ? size - shift : 0, wsyn, (const float2*)tw,
-                     (float2*)nullptr, 2.0f / (float)size, 1.0f / (float)size, iters, logit,
-                     (const float2*)obs, dlogit, K, tgt, sums, gout, iperm, bt_major);
+static int rfft_launch(const RfftLaunch& a, void* stream) {
+  if (int e = rfft_check(a)) return e;
+  if (int e = check_plan(a.size, a.shift)) return e;
+  const int iters = 4;                         // frames per wave: 4 waves x 4 frames per workgroup
+  const int64_t blocks = (a.rows * a.T + 4 * iters - 1) / (4 * iters);
+  if (blocks > 0x7fffffff) return TSSEP_E_SHAPE;
+  hipLaunchKernelGGL(a.kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a.x, a.rows, a.N, a.T, a.shift,
+                     a.fading ? a.size - a.shift : 0, a.window, (const float2*)a.tw, (float2*)a.X, a.s_in, a.s_edge, iters,
+                     a.logit, (const float2*)a.obs, a.dlogit, a.masked ? a.K : (int64_t)1, a.tgt, a.sums, a.gout, a.iperm,
+                     a.bt_major, a.vad, a.gbce, a.masked ? 1.0f / ((float)a.K * (float)a.T) : 0.f);
   return tssep_launch_status();
 }
 
@@ -640,70 +608,132 @@ extern "C" int64_t tssep_istft_chunks(int64_t N) {
   const int64_t hops = (N + 255) / 256;
   return (hops + HCB_MAX - 1) / HCB_MAX;
 }
-static int istft_hops_per_chunk(int64_t N, int nchunks) {
-  const int64_t hops = (N + 255) / 256;
-  return (int)((hops + nchunks - 1) / nchunks);
+
+// One launch of istft_kernel: X (plain) or logit + obs (masked) -> y, with the |y - tgt| partial sums on the side.
+using istft_kernel_t = decltype(&istft_kernel<false>);
+struct IstftLaunch {
+  istft_kernel_t kernel;                       // the instantiation, named by the entry point
+  bool masked;                                 // its MASKED flag
+  const float* X;                              // !masked: the spectra [rows, T, 513] (complex)
+  const float *logit, *obs;                    // masked: rows = B K logit rows, the B observation spectra
+  int64_t rows, K, T, N;
+  int size, shift, fading;
+  const float *wsyn, *tw;
+  float* y;
+  const float* tgt;                            // both or neither
+  float* abs_partial;
+};
+
+static int istft_launch(const IstftLaunch& a, void* stream) {
+  if ((a.masked ? (!a.logit || !a.obs) : !a.X) || !a.wsyn || !a.tw || !a.y) return TSSEP_E_NULL;
+  if (a.rows <= 0 || (a.masked && a.K <= 0) || a.N <= 0 || a.T <= 0) return TSSEP_E_SHAPE;
+  if ((a.tgt == nullptr) != (a.abs_partial == nullptr)) return TSSEP_E_NULL;
+  if (int e = check_plan(a.size, a.shift)) return e;
+  if (!a.fading) return TSSEP_E_UNSUPPORTED;
+  if (misaligned(a.tw, 8) || misaligned(a.wsyn, 8)) return TSSEP_E_ALIGN;
+  if (a.masked ? (misaligned(a.logit, 4) || misaligned(a.obs, 8)) : misaligned(a.X, 8)) return TSSEP_E_ALIGN;
+  if (a.rows > 65535) return TSSEP_E_SHAPE;    // (the row is blockIdx.y)
+  const int nchunks = (int)tssep_istft_chunks(a.N);
+  const int hcb = (int)(((a.N + 255) / 256 + nchunks - 1) / nchunks);          // hops per chunk
+  hipLaunchKernelGGL(a.kernel, dim3((unsigned)nchunks, (unsigned)a.rows), dim3(256), 0, (hipStream_t)stream,
+                     (const float2*)a.X, a.T, a.shift, a.N, a.wsyn, (const float2*)a.tw, a.y, a.tgt, a.abs_partial, nchunks,
+                     hcb, a.logit, (const float2*)a.obs, a.masked ? a.K : (int64_t)1);
+  return tssep_launch_status();
+}
+
+// ---- the entry points ----------------------------------------------------------------------------------------------
+extern "C" int tssep_stft_fwd(const float* x, int64_t rows, int64_t N, int size, int shift,
+                              int fading, const float* window, const float* tw, float* X,
+                              int64_t T, void* stream) {
+  const RfftLaunch a = {.kernel = rfft_frames_kernel<false>, .x = x, .rows = rows, .N = N, .T = T, .size = size,
+                        .shift = shift, .fading = fading, .window = window, .tw = tw, .s_in = 1.0f, .s_edge = 1.0f, .X = X};
+  if (generic_plan(size, shift)) {
+    if (int e = rfft_check(a)) return e;
+    return tssep_generic_rfft(x, rows, N, size, shift, fading ? size - shift : 0, window, tw, X, T, 1.0f, 1.0f, stream);
+  }
+  return rfft_launch(a, stream);
+}
+
+extern "C" int tssep_istft_bwd(const float* dy, int64_t rows, int64_t N, int size, int shift,
+                               int fading, const float* wsyn, const float* tw, float* dX,
+                               int64_t T, void* stream) {
+  const RfftLaunch a = {.kernel = rfft_frames_kernel<false>, .x = dy, .rows = rows, .N = N, .T = T, .size = size,
+                        .shift = shift, .fading = fading, .window = wsyn, .tw = tw, .s_in = 2.0f / (float)size,
+                        .s_edge = 1.0f / (float)size, .X = dX};
+  if (generic_plan(size, shift)) {
+    if (int e = rfft_check(a)) return e;
+    return tssep_generic_rfft(dy, rows, N, size, shift, fading ? size - shift : 0, wsyn, tw, dX, T, a.s_in, a.s_edge, stream);
+  }
+  return rfft_launch(a, stream);
+}
+
+// the adjoint with the mask head's backward behind it (and, _bwd_loss / _gated_bwd, the loss in front and the final
+// Linear's layout behind): B K rows, the synthesis window, the adjoint's scales
+static RfftLaunch mask_bwd(rfft_kernel_t kernel, const float* x, const float* logit, const float* obs, int64_t B, int64_t K,
+                           int64_t N, int size, int shift, int fading, const float* wsyn, const float* tw, float* dlogit,
+                           int64_t T) {
+  return {.kernel = kernel, .masked = true, .x = x, .rows = B * K, .N = N, .T = T, .size = size, .shift = shift,
+          .fading = fading, .window = wsyn, .tw = tw, .s_in = 2.0f / (float)size, .s_edge = 1.0f / (float)size,
+          .logit = logit, .obs = obs, .dlogit = dlogit, .K = K};
+}
+
+extern "C" int tssep_mask_istft_bwd(const float* dy, const float* logit, const float* obs, int64_t B,
+                                    int64_t K, int64_t N, int size, int shift, int fading,
+                                    const float* wsyn, const float* tw, float* dlogit, int64_t T,
+                                    void* stream) {
+  return rfft_launch(mask_bwd(rfft_frames_kernel<true>, dy, logit, obs, B, K, N, size, shift, fading, wsyn, tw, dlogit, T),
+                     stream);
+}
+
+extern "C" int tssep_mask_istft_bwd_loss(const float* est, const float* tgt, const float* sums, const float* gout,
+                                         const float* logit, const float* obs, int64_t B, int64_t K, int64_t N,
+                                         int size, int shift, int fading, const float* wsyn, const float* tw,
+                                         const int32_t* iperm, int bt_major, float* dlogit, int64_t T,
+                                         void* stream) {
+  // tgt == NULL: `est` is dy itself (only the output layout is folded); sums == NULL: MAE
+  RfftLaunch a = mask_bwd(rfft_frames_kernel<true>, est, logit, obs, B, K, N, size, shift, fading, wsyn, tw, dlogit, T);
+  a.tgt = tgt, a.sums = sums, a.gout = gout, a.iperm = iperm, a.bt_major = bt_major;
+  return rfft_launch(a, stream);
 }
 
 extern "C" int tssep_istft_fwd(const float* X, int64_t rows, int64_t T, int size, int shift,
                                int fading, const float* wsyn, const float* tw, float* y, int64_t N,
                                const float* tgt, float* abs_partial, void* stream) {
-  if (!X || !wsyn || !tw || !y) return TSSEP_E_NULL;
-  if (rows <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
   if (generic_plan(size, shift)) {
+    if (!X || !wsyn || !tw || !y) return TSSEP_E_NULL;
+    if (rows <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
     // (the general plan has no fused |estimate - target| sums: a time-domain loss reads the estimate itself)
     if (tgt || abs_partial) return TSSEP_E_UNSUPPORTED;
-    if ((((uintptr_t)X) & 7u) || (((uintptr_t)tw) & 7u)) return TSSEP_E_ALIGN;
+    if (misaligned(X, 8) || misaligned(tw, 8)) return TSSEP_E_ALIGN;
     return tssep_generic_istft(X, rows, T, size, shift, fading ? size - shift : 0, wsyn, tw, y, N, stream);
   }
-  if (int e = check_plan(size, shift)) return e;
-  if (!fading) return TSSEP_E_UNSUPPORTED;
-  if ((((uintptr_t)X) & 7u) || (((uintptr_t)tw) & 7u) || (((uintptr_t)wsyn) & 7u)) return TSSEP_E_ALIGN;
-  if (rows > 65535) return TSSEP_E_SHAPE;
-  const int nchunks = (int)tssep_istft_chunks(N);
-  hipLaunchKernelGGL(istft_kernel<false>, dim3((unsigned)nchunks, (unsigned)rows), dim3(256), 0,
-                     (hipStream_t)stream, (const float2*)X, T, shift, N, wsyn, (const float2*)tw, y,
-                     tgt, abs_partial, nchunks, istft_hops_per_chunk(N, nchunks), (const float*)nullptr,
-                     (const float2*)nullptr, (int64_t)1);
-  return tssep_launch_status();
+  return istft_launch({.kernel = istft_kernel<false>, .X = X, .rows = rows, .T = T, .N = N, .size = size, .shift = shift,
+                       .fading = fading, .wsyn = wsyn, .tw = tw, .y = y, .tgt = tgt, .abs_partial = abs_partial}, stream);
+}
+
+// sigmoid -> Masking -> inverse STFT over B K logit rows
+static int mask_istft_fwd(istft_kernel_t kernel, const float* logit, const float* obs, int64_t B, int64_t K, int64_t T,
+                          int size, int shift, int fading, const float* wsyn, const float* tw, float* y, int64_t N,
+                          const float* tgt, float* abs_partial, void* stream) {
+  return istft_launch({.kernel = kernel, .masked = true, .logit = logit, .obs = obs, .rows = B * K, .K = K, .T = T, .N = N,
+                       .size = size, .shift = shift, .fading = fading, .wsyn = wsyn, .tw = tw, .y = y, .tgt = tgt,
+                       .abs_partial = abs_partial}, stream);
 }
 
 extern "C" int tssep_mask_istft_fwd(const float* logit, const float* obs, int64_t B, int64_t K,
                                     int64_t T, int size, int shift, int fading, const float* wsyn,
                                     const float* tw, float* y, int64_t N, const float* tgt,
                                     float* abs_partial, void* stream) {
-  if (!logit || !obs || !wsyn || !tw || !y) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
-  if (int e = check_plan(size, shift)) return e;
-  if (!fading) return TSSEP_E_UNSUPPORTED;
-  if ((((uintptr_t)obs) & 7u) || (((uintptr_t)tw) & 7u) || (((uintptr_t)wsyn) & 7u)) return TSSEP_E_ALIGN;
-  const int64_t rows = B * K;
-  if (rows > 65535) return TSSEP_E_SHAPE;
-  const int nchunks = (int)tssep_istft_chunks(N);
-  hipLaunchKernelGGL(istft_kernel<true>, dim3((unsigned)nchunks, (unsigned)rows), dim3(256), 0,
-                     (hipStream_t)stream, (const float2*)nullptr, T, shift, N, wsyn, (const float2*)tw, y,
-                     tgt, abs_partial, nchunks, istft_hops_per_chunk(N, nchunks), logit, (const float2*)obs, K);
-  return tssep_launch_status();
+  return mask_istft_fwd(istft_kernel<true>, logit, obs, B, K, T, size, shift, fading, wsyn, tw, y, N, tgt, abs_partial,
+                        stream);
 }
 
 // ---- explicit_vad: the gated fused tail (logit rows of F + 1 = 514 floats, the VAD logit at column 0) --------------
 extern "C" int tssep_mask_istft_gated_fwd(const float* logit, const float* obs, int64_t B, int64_t K, int64_t T, int size,
                                           int shift, int fading, const float* wsyn, const float* tw, float* y, int64_t N,
                                           const float* tgt, float* abs_partial, void* stream) {
-  if (!logit || !obs || !wsyn || !tw || !y) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
-  if ((tgt == nullptr) != (abs_partial == nullptr)) return TSSEP_E_NULL;
-  if (int e = check_plan(size, shift)) return e;
-  if (!fading) return TSSEP_E_UNSUPPORTED;
-  if ((((uintptr_t)logit) & 3u) || (((uintptr_t)obs) & 7u) || (((uintptr_t)tw) & 7u) || (((uintptr_t)wsyn) & 7u))
-    return TSSEP_E_ALIGN;
-  const int64_t rows = B * K;
-  if (rows > 65535) return TSSEP_E_SHAPE;
-  const int nchunks = (int)tssep_istft_chunks(N);
-  hipLaunchKernelGGL((istft_kernel<true, true>), dim3((unsigned)nchunks, (unsigned)rows), dim3(256), 0,
-                     (hipStream_t)stream, (const float2*)nullptr, T, shift, N, wsyn, (const float2*)tw, y,
-                     tgt, abs_partial, nchunks, istft_hops_per_chunk(N, nchunks), logit, (const float2*)obs, K);
-  return tssep_launch_status();
+  return mask_istft_fwd(istft_kernel<true, true>, logit, obs, B, K, T, size, shift, fading, wsyn, tw, y, N, tgt, abs_partial,
+                        stream);
 }
 
 extern "C" int tssep_mask_istft_gated_bwd(const float* est, const float* tgt, const float* sums, const float* gout,
@@ -712,20 +742,8 @@ extern "C" int tssep_mask_istft_gated_bwd(const float* est, const float* tgt, co
                                           const float* wsyn, const float* tw, const int32_t* iperm, int bt_major,
                                           float* dlogit, int64_t T, void* stream) {
   // tgt == NULL: `est` is dy itself; sums == NULL: MAE; vad == NULL: no BCE term on the gate column
-  if (!est || (tgt && !gout) || (vad && !gout_vad) || !logit || !obs || !wsyn || !tw || !dlogit) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || N <= 0 || T <= 0) return TSSEP_E_SHAPE;
-  if (int e = check_plan(size, shift)) return e;
-  if ((((uintptr_t)logit) & 3u) || (((uintptr_t)dlogit) & 3u) || (((uintptr_t)obs) & 7u) || (((uintptr_t)tw) & 7u) ||
-      (((uintptr_t)wsyn) & 7u))
-    return TSSEP_E_ALIGN;
-  const int iters = 4;
-  const int64_t rows = B * K, total = rows * T;
-  const int64_t blocks = (total + 4 * iters - 1) / (4 * iters);
-  if (blocks > 0x7fffffff) return TSSEP_E_SHAPE;
-  hipLaunchKernelGGL((rfft_frames_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     est, rows, N, T, shift, fading ? size - shift : 0, wsyn, (const float2*)tw,
-                     (float2*)nullptr, 2.0f / (float)size, 1.0f / (float)size, iters, logit,
-                     (const float2*)obs, dlogit, K, tgt, sums, gout, iperm, bt_major, vad, gout_vad,
-                     1.0f / ((float)K * (float)T));
-  return tssep_launch_status();
+  RfftLaunch a = mask_bwd(rfft_frames_kernel<true, true>, est, logit, obs, B, K, N, size, shift, fading, wsyn, tw, dlogit,
+                          T);
+  a.tgt = tgt, a.sums = sums, a.gout = gout, a.iperm = iperm, a.bt_major = bt_major, a.vad = vad, a.gbce = gout_vad;
+  return rfft_launch(a, stream);
 }

@@ -534,26 +534,10 @@ def mask_head(logit, obs):
     return _MaskHead.apply(logit, obs)
 
 
-class _Sigmoid(torch.autograd.Function):
-    """mask only (no observation available): reuses the mask-head kernel with obs = 0."""
-
-    @staticmethod
-    def forward(ctx, logit):
-        B, K, T, F = logit.shape
-        obs = torch.zeros(B, T, F, device=logit.device, dtype=torch.complex64)
-        mask, _ = H.maskhead_fwd(logit, obs)
-        ctx.save_for_backward(mask, obs)
-        return mask
-
-    @staticmethod
-    def backward(ctx, dmask):
-        mask, obs = ctx.saved_tensors
-        dest = torch.zeros(mask.shape, device=mask.device, dtype=torch.complex64)
-        return H.maskhead_bwd(dest, dmask, mask, obs)
-
-
 def sigmoid(logit):
-    return _Sigmoid.apply(logit)
+    """mask only (no observation available): the mask head with obs = 0, its estimate discarded."""
+    B, K, T, F = logit.shape
+    return _MaskHead.apply(logit, torch.zeros(B, T, F, device=logit.device, dtype=torch.complex64))[0]
 
 
 class _MVDRSouden(torch.autograd.Function):
@@ -639,54 +623,65 @@ def istft(X, wsyn, N, size=1024, shift=256, fading=True):
 class _MaskISTFT(torch.autograd.Function):
     """sigmoid (net.py:983) -> Masking (enhancer.py:98-100) -> fe.istft (model.py:661-664) as ONE kernel
     each way; with ``tgt`` the forward also leaves the per-chunk sums of |estimate - tgt| on the result
-    (``_tssep_absdiff``), which ``log_mae`` / ``mae`` consume instead of re-reading both signals."""
+    (``_tssep_absdiff``), which ``log_mae`` / ``mae`` consume instead of re-reading both signals.
+    Gated rows (explicit_vad; hip_ops._tail_rows decides) take the same path; with ``vad`` the forward also returns
+    SignalAndVADSigmoidBCE's BCE term of the gate column ([B]), and its gradient is folded into the tail's d(v) store: the
+    BCE needs no pass of its own."""
 
     @staticmethod
-    def forward(ctx, logit, obs, wsyn, N, size, shift, fading, tgt, head_link=None, loss_link=None):
+    def forward(ctx, logit, obs, wsyn, N, size, shift, fading, tgt, vad, head_link=None, loss_link=None):
         y, part = H.mask_istft_fwd(logit, obs, wsyn, N, size, shift, fading, tgt)
-        ctx.save_for_backward(logit, obs, wsyn)
+        outs = [y]
+        if part is not None:
+            outs.append(part)
+            ctx.mark_non_differentiable(part)
+        if vad is not None:
+            outs.append(H.gatebce_fwd(logit, vad))
+        ctx.save_for_backward(logit, obs, wsyn, vad)
         ctx.meta = (size, shift, fading)
         ctx.links = (head_link, loss_link)
-        ctx.mark_non_differentiable(*([part] if part is not None else []))
-        return (y, part) if part is not None else (y,)
+        return tuple(outs)
 
     @staticmethod
-    def backward(ctx, dy, *_):
-        logit, obs, wsyn = ctx.saved_tensors
-        size, shift, fading = ctx.meta
+    def backward(ctx, dy, *rest):
+        logit, obs, wsyn, vad = ctx.saved_tensors
         head_link, loss_link = ctx.links
+        vadarg = (vad, rest[-1]) if vad is not None else None          # (Vad, d(loss) / d(bce))
         loss = loss_link.take() if loss_link is not None else None      # (est, tgt, sums, gout) of LogMAE / MAE
-        if loss is not None and not _is_dummy(dy):
+        if loss is not None and not _is_dummy(dy):      # someone else used the estimate too: the loss's part, unfused
             dy = dy + H.logmae_bwd(loss[0].contiguous(), loss[1].contiguous(), loss[2], loss[3])
             loss = None
-        if head_link is not None and tuple(head_link.shape) == tuple(logit.shape):
-            d = H.mask_istft_bwd(dy, logit, obs, wsyn, size, shift, fading, loss=loss, iperm=head_link.iperm,
-                                 bt_major=True)
+        to_head = head_link is not None and tuple(head_link.shape) == tuple(logit.shape)
+        d = H.mask_istft_bwd(dy, logit, obs, wsyn, *ctx.meta, loss=loss, vad=vadarg,
+                             iperm=head_link.iperm if to_head else None, bt_major=to_head)
+        if to_head:                                     # written where the Linear's backward reads it
             head_link.payload = d if head_link.payload is None else head_link.payload + d
-            dl = _dummy_grad(logit)
-        elif loss is not None:
-            dl = H.mask_istft_bwd(None, logit, obs, wsyn, size, shift, fading, loss=loss)
-        else:
-            dl = H.mask_istft_bwd(dy, logit, obs, wsyn, size, shift, fading)
-        return (dl, None, None, None, None, None, None, None, None, None)
+            d = _dummy_grad(logit)
+        return (d,) + (None,) * 10
 
 
-def mask_istft(logit, obs, wsyn, N, size=1024, shift=256, fading=True, tgt=None):
-    """logit [B,K,T,F], obs complex [B,T,F] -> time_estimate [B,K,N] (differentiable w.r.t. logit)."""
-    if tgt is not None and tuple(tgt.shape) != (logit.shape[0], logit.shape[1], N):
+def mask_istft(logit, obs, wsyn, N, size=1024, shift=256, fading=True, tgt=None, vad=None):
+    """logit [B,K,T,F], obs complex [B,T,F] -> (time_estimate [B,K,N], None), differentiable w.r.t. logit.
+    explicit_vad: logit [B,K,T,F+1] (VAD logit at column 0); with vad [B,K,T] the gate column's BCE against it ([B]) is
+    returned as well, its backward folded into the tail's."""
+    B, K, T = logit.shape[:3]
+    assert vad is None or logit.shape[-1] == obs.shape[-1] + 1, "mask_istft: vad= needs gated logit rows"
+    if tgt is not None and tuple(tgt.shape) != (B, K, N):
         tgt = None
+    if vad is not None and tuple(vad.shape) != (B, K, T):
+        vad = None
     fold = H.FOLD_TAIL and logit.requires_grad
     loss_link = _Link() if fold and tgt is not None and H.FOLD_TAIL != 3 else None
     head_link = getattr(logit, "_tssep_head_link", None) if fold and H.FOLD_TAIL != 2 else None
-    out = _MaskISTFT.apply(logit, obs, wsyn, N, size, shift, fading, tgt, head_link, loss_link)
+    out = _MaskISTFT.apply(logit, obs, wsyn, N, size, shift, fading, tgt, vad, head_link, loss_link)
     y = out[0]
-    if len(out) > 1:
+    if tgt is not None:
         y._tssep_absdiff = (out[1], tgt.data_ptr(), tuple(tgt.shape))
         y._tssep_loss_link = loss_link
-    return y
+    return y, (out[-1] if vad is not None else None)
 
 
-# ---------------------------------------------------------------- explicit_vad (gated tail)
+# ---------------------------------------------------------------- explicit_vad (gated mask head)
 # MaskEstimator_v2(explicit_vad=True) (net.py:630, 969-979): the head writes rows of F + 1 logits per (b, k, t), the
 # VAD logit v at column 0 and the mask logits l_f behind it; mask = sigmoid(l_f) sigmoid(v).  The Functions below keep
 # that [B,K,T,F+1] tensor whole -- the gated kernels read the gate where the GEMM wrote it and write d(v) where the
@@ -711,7 +706,8 @@ def mask_head_gated(logit, obs):
 
 
 class _SigmoidGated(torch.autograd.Function):
-    """mask and vad_mask only (no observation available)."""
+    """mask and vad_mask only (no observation available).  Not routed through _MaskHeadGated as `sigmoid` is through
+    _MaskHead: these launches pass est == NULL (no estimate is written or read back), that Function's do not."""
 
     @staticmethod
     def forward(ctx, logit):
@@ -730,65 +726,6 @@ class _SigmoidGated(torch.autograd.Function):
 def sigmoid_gated(logit):
     """logit [B,K,T,F+1] -> (mask [B,K,T,F] = sigmoid(l) sigmoid(v), vad_mask [B,K,T] = sigmoid(v))."""
     return _SigmoidGated.apply(logit)
-
-
-class _MaskISTFTGated(torch.autograd.Function):
-    """_MaskISTFT for the gated logit rows; with ``vad`` the forward also returns SignalAndVADSigmoidBCE's BCE term of
-    the gate column ([B]), and its gradient is folded into the tail's d(v) store: the BCE needs no pass of its own."""
-
-    @staticmethod
-    def forward(ctx, logit, obs, wsyn, N, size, shift, fading, tgt, vad, head_link=None, loss_link=None):
-        y, part = H.mask_istft_gated_fwd(logit, obs, wsyn, N, size, shift, fading, tgt)
-        outs = [y]
-        if part is not None:
-            outs.append(part)
-            ctx.mark_non_differentiable(part)
-        bce = H.gatebce_fwd(logit, vad) if vad is not None else None
-        if bce is not None:
-            outs.append(bce)
-        ctx.save_for_backward(logit, obs, wsyn, vad)
-        ctx.meta = (size, shift, fading, part is not None, bce is not None)
-        ctx.links = (head_link, loss_link)
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, dy, *rest):
-        logit, obs, wsyn, vad = ctx.saved_tensors
-        size, shift, fading, has_part, has_bce = ctx.meta
-        head_link, loss_link = ctx.links
-        gbce = rest[-1] if has_bce else None
-        vadarg = (vad, gbce) if gbce is not None else None
-        loss = loss_link.take() if loss_link is not None else None      # (est, tgt, sums, gout) of LogMAE / MAE
-        if loss is not None and not _is_dummy(dy):
-            dy = dy + H.logmae_bwd(loss[0].contiguous(), loss[1].contiguous(), loss[2], loss[3])
-            loss = None
-        if head_link is not None and tuple(head_link.shape) == tuple(logit.shape):
-            d = H.mask_istft_gated_bwd(dy, logit, obs, wsyn, size, shift, fading, loss=loss, vad=vadarg,
-                                       iperm=head_link.iperm, bt_major=True)
-            head_link.payload = d if head_link.payload is None else head_link.payload + d
-            dl = _dummy_grad(logit)
-        else:
-            dl = H.mask_istft_gated_bwd(dy, logit, obs, wsyn, size, shift, fading, loss=loss, vad=vadarg)
-        return (dl, None, None, None, None, None, None, None, None, None, None)
-
-
-def mask_istft_gated(logit, obs, wsyn, N, size=1024, shift=256, fading=True, tgt=None, vad=None):
-    """logit [B,K,T,F+1] (VAD logit at column 0), obs complex [B,T,F] -> (time_estimate [B,K,N], bce [B] or None).
-    vad [B,K,T]: the gate column's BCE against it is returned as well, its backward folded into the tail's."""
-    B, K, T = logit.shape[:3]
-    if tgt is not None and tuple(tgt.shape) != (B, K, N):
-        tgt = None
-    if vad is not None and tuple(vad.shape) != (B, K, T):
-        vad = None
-    fold = H.FOLD_TAIL and logit.requires_grad
-    loss_link = _Link() if fold and tgt is not None and H.FOLD_TAIL != 3 else None
-    head_link = getattr(logit, "_tssep_head_link", None) if fold and H.FOLD_TAIL != 2 else None
-    out = _MaskISTFTGated.apply(logit, obs, wsyn, N, size, shift, fading, tgt, vad, head_link, loss_link)
-    y = out[0]
-    if tgt is not None:
-        y._tssep_absdiff = (out[1], tgt.data_ptr(), tuple(tgt.shape))
-        y._tssep_loss_link = loss_link
-    return y, (out[-1] if vad is not None else None)
 
 
 class _GateBCE(torch.autograd.Function):
@@ -823,53 +760,36 @@ def _loss_link(est, part):
     return getattr(est, "_tssep_loss_link", None) if part is not None else None
 
 
-class _LogMAE(torch.autograd.Function):
+class _AbsErrorLoss(torch.autograd.Function):
+    """log = True: LogMAE, log10(sum_k mean_n |e - t|) (loss.py:244-247); False: MAE, the logarithm's argument
+    (loss.py:214-216) -- one forward kernel computes both, and the backward differs in `sums` being None."""
+
     @staticmethod
-    def forward(ctx, est, tgt, part=None, link=None):
-        if part is not None:
-            loss, sums = H.logmae_finalize(part, *est.shape)
-        else:
-            loss, sums = H.logmae_fwd(est, tgt)
+    def forward(ctx, est, tgt, log, part=None, link=None):
+        loss, sums = H.logmae_finalize(part, *est.shape) if part is not None else H.logmae_fwd(est, tgt)
         ctx.save_for_backward(est, tgt, sums)
-        ctx.link = link
-        return loss
+        ctx.log, ctx.link = log, link
+        return loss if log else sums
 
     @staticmethod
     def backward(ctx, g):
         est, tgt, sums = ctx.saved_tensors
+        if not ctx.log:
+            sums = None
         if ctx.link is not None and ctx.link.payload is None:     # the tail's backward forms this gradient itself
             ctx.link.payload = (est, tgt, sums, g)
-            return _dummy_grad(est), None, None, None
-        return H.logmae_bwd(est.contiguous(), tgt.contiguous(), sums, g), None, None, None
+            return _dummy_grad(est), None, None, None, None
+        return H.logmae_bwd(est.contiguous(), tgt.contiguous(), sums, g), None, None, None, None
 
 
 def log_mae(est, tgt):
     part = _fused_absdiff(est, tgt)
-    return _LogMAE.apply(est, tgt, part, _loss_link(est, part))
-
-
-class _MAE(torch.autograd.Function):
-    """sum_k mean_n |e - t| (loss.py:214-216): the argument of LogMAE's logarithm."""
-
-    @staticmethod
-    def forward(ctx, est, tgt, part=None, link=None):
-        _, sums = H.logmae_finalize(part, *est.shape) if part is not None else H.logmae_fwd(est, tgt)
-        ctx.save_for_backward(est, tgt)
-        ctx.link = link
-        return sums
-
-    @staticmethod
-    def backward(ctx, g):
-        est, tgt = ctx.saved_tensors
-        if ctx.link is not None and ctx.link.payload is None:
-            ctx.link.payload = (est, tgt, None, g)
-            return _dummy_grad(est), None, None, None
-        return H.logmae_bwd(est.contiguous(), tgt.contiguous(), None, g), None, None, None
+    return _AbsErrorLoss.apply(est, tgt, True, part, _loss_link(est, part))
 
 
 def mae(est, tgt):
     part = _fused_absdiff(est, tgt)
-    return _MAE.apply(est, tgt, part, _loss_link(est, part))
+    return _AbsErrorLoss.apply(est, tgt, False, part, _loss_link(est, part))
 
 
 class _VadBCE(torch.autograd.Function):

@@ -185,63 +185,22 @@ def istft_bwd(dy, wsyn, T, size=1024, shift=256, fading=True):
     return torch.view_as_complex(dX)
 
 
+def _tail_rows(logit, obs):
+    """The fused tail's row layout -> (B, K, T, F, gated): logit [B,K,T,F] (plain) or [B,K,T,F+1] with the VAD logit at
+    column 0 (explicit_vad: gated), obs complex64 [B,T,F].  The one place that decides it."""
+    B, K, T, Fl = logit.shape
+    F = obs.shape[-1]
+    assert Fl - F in (0, 1), f"mask_istft: logit rows of {Fl} columns for {F} bins (F: plain rows, F + 1: gated rows)"
+    assert tuple(obs.shape) == (B, T, F) and obs.dtype == torch.complex64, (tuple(logit.shape), tuple(obs.shape), obs.dtype)
+    return B, K, T, F, Fl == F + 1
+
+
 def mask_istft_fwd(logit, obs, wsyn, N, size=1024, shift=256, fading=True, tgt=None):
     """logit [B,K,T,F], obs complex64 [B,T,F] -> y [B,K,N] = istft(sigmoid(logit) * obs), neither the mask
-    nor the masked STFT is materialised (+ per-chunk sums of |y - tgt| when tgt [B,K,N] is given)."""
+    nor the masked STFT is materialised (+ per-chunk sums of |y - tgt| when tgt [B,K,N] is given).
+    explicit_vad: logit [B,K,T,F+1] (VAD logit at column 0) -> y = istft(sigmoid(l) sigmoid(v) * obs)."""
     L = _lib.lib()
-    B, K, T, F = logit.shape
-    logit = _f32(logit).contiguous()
-    obs_r = torch.view_as_real(obs.contiguous())
-    y = torch.empty(B, K, N, device=logit.device, dtype=torch.float32)
-    part = None
-    if tgt is not None:
-        part = torch.empty(B * K, int(L.tssep_istft_chunks(N)), device=logit.device, dtype=torch.float32)
-        tgt = _f32(tgt).contiguous()
-    # roofline bookkeeping: the UNFUSED mask head's algorithmic bytes (SURVEY 8d), whatever is moved; the fused kernel's OWN
-    # bytes (logit + observation in, samples out, target in when the loss sums ride along) are kept beside them
-    _own_bytes("maskhead_fwd", B * T * (4 * K * F + 8 * F) + 4 * B * K * N * (2 if tgt is not None else 1))
-    with _timed("maskhead_fwd", 0, B * T * (16 * K * F + 8 * F)):
-        check(L.tssep_mask_istft_fwd(_p(logit), _p(obs_r), B, K, T, size, shift, int(fading), _p(wsyn),
-                                     _p(fft_tables(size, logit.device)), _p(y), N, _p(tgt), _p(part),
-                                     _stream()), "mask_istft_fwd")
-    return y, part
-
-
-def mask_istft_bwd(dy, logit, obs, wsyn, size=1024, shift=256, fading=True, loss=None, iperm=None, bt_major=False):
-    """dy [B,K,N] -> dlogit [B,K,T,F] through the iSTFT adjoint and the mask head's backward.
-    loss = (est, tgt, sums or None, gout): the loss gradient is formed inside the kernel from the estimate
-    and the target instead of being read from `dy` (LogMAE; sums None: MAE).  bt_major: the result is laid
-    out [B*T, K*F] with speaker k at position iperm[b, k] -- what the final Linear's backward reads."""
-    L = _lib.lib()
-    B, K, T, F = logit.shape
-    obs_r = torch.view_as_real(obs.contiguous())
-    dlogit = torch.empty(B * T, K * F, device=logit.device, dtype=torch.float32) if bt_major else torch.empty_like(logit)
-    _own_bytes("maskhead_bwd", B * T * (8 * K * F + 8 * F) + 4 * B * K * (dy.shape[-1] if loss is None else 2 * loss[0].shape[-1]))
-    with _timed("maskhead_bwd", 0, B * T * (16 * K * F + 8 * F)):
-        if loss is None and not bt_major:
-            dy = _f32(dy).contiguous()
-            check(L.tssep_mask_istft_bwd(_p(dy), _p(logit), _p(obs_r), B, K, dy.shape[-1], size, shift,
-                                         int(fading), _p(wsyn), _p(fft_tables(size, logit.device)), _p(dlogit),
-                                         T, _stream()), "mask_istft_bwd")
-        else:
-            if loss is None:
-                x, tgt, sums, gout = _f32(dy).contiguous(), None, None, None
-            else:
-                x, tgt, sums, gout = (_f32(loss[0]).contiguous(), _f32(loss[1]).contiguous(), loss[2],
-                                      _f32(loss[3]).contiguous())
-            check(L.tssep_mask_istft_bwd_loss(_p(x), _p(tgt), _p(sums), _p(gout), _p(logit), _p(obs_r), B, K,
-                                              x.shape[-1], size, shift, int(fading), _p(wsyn),
-                                              _p(fft_tables(size, logit.device)), _p(iperm), int(bt_major),
-                                              _p(dlogit), T, _stream()), "mask_istft_bwd_loss")
-    return dlogit
-
-
-def mask_istft_gated_fwd(logit, obs, wsyn, N, size=1024, shift=256, fading=True, tgt=None):
-    """explicit_vad: logit [B,K,T,F+1] (VAD logit at column 0), obs complex64 [B,T,F] -> y [B,K,N] =
-    istft(sigmoid(l) sigmoid(v) * obs) (+ per-chunk sums of |y - tgt| when tgt [B,K,N] is given)."""
-    L = _lib.lib()
-    B, K, T, F1 = logit.shape
-    assert tuple(obs.shape) == (B, T, F1 - 1) and obs.dtype == torch.complex64, (tuple(logit.shape), tuple(obs.shape))
+    B, K, T, F, gated = _tail_rows(logit, obs)
     assert tgt is None or tuple(tgt.shape) == (B, K, N), (tuple(tgt.shape), (B, K, N))
     logit = _f32(logit).contiguous()
     obs_r = torch.view_as_real(obs.contiguous())
@@ -250,25 +209,34 @@ def mask_istft_gated_fwd(logit, obs, wsyn, N, size=1024, shift=256, fading=True,
     if tgt is not None:
         part = torch.empty(B * K, int(L.tssep_istft_chunks(N)), device=logit.device, dtype=torch.float32)
         tgt = _f32(tgt).contiguous()
-    with _timed("maskhead_gated_fwd", 0, B * T * (4 * K * F1 + 8 * (F1 - 1)) + 4 * B * K * N):
-        check(L.tssep_mask_istft_gated_fwd(_p(logit), _p(obs_r), B, K, T, size, shift, int(fading), _p(wsyn),
-                                           _p(fft_tables(size, logit.device)), _p(y), N, _p(tgt), _p(part),
-                                           _stream()), "mask_istft_gated_fwd")
+    if gated:
+        entry, name, timer = L.tssep_mask_istft_gated_fwd, "mask_istft_gated_fwd", _timed(
+            "maskhead_gated_fwd", 0, B * T * (4 * K * (F + 1) + 8 * F) + 4 * B * K * N)
+    else:
+        # roofline bookkeeping: the UNFUSED mask head's algorithmic bytes, whatever is moved; the fused kernel's
+        # OWN bytes (logit + observation in, samples out, target in when the loss sums ride along) are kept beside them
+        _own_bytes("maskhead_fwd", B * T * (4 * K * F + 8 * F) + 4 * B * K * N * (2 if tgt is not None else 1))
+        entry, name, timer = L.tssep_mask_istft_fwd, "mask_istft_fwd", _timed("maskhead_fwd", 0, B * T * (16 * K * F + 8 * F))
+    with timer:
+        check(entry(_p(logit), _p(obs_r), B, K, T, size, shift, int(fading), _p(wsyn), _p(fft_tables(size, logit.device)),
+                    _p(y), N, _p(tgt), _p(part), _stream()), name)
     return y, part
 
 
-def mask_istft_gated_bwd(dy, logit, obs, wsyn, size=1024, shift=256, fading=True, loss=None, vad=None, iperm=None,
-                         bt_major=False):
-    """The backward of mask_istft_gated_fwd -> dlogit [B,K,T,F+1] (bt_major: [B*T, K*(F+1)], speaker k at position
-    iperm[b, k]).  loss = (est, tgt, sums or None, gout) as mask_istft_bwd; vad = (Vad [B,K,T], gout_vad [B]) adds the
-    gate column's BCE gradient in the same store."""
+def mask_istft_bwd(dy, logit, obs, wsyn, size=1024, shift=256, fading=True, loss=None, vad=None, iperm=None,
+                   bt_major=False):
+    """dy [B,K,N] -> dlogit (the shape of logit) through the iSTFT adjoint and the mask head's backward.
+    loss = (est, tgt, sums or None, gout): the loss gradient is formed inside the kernel from the estimate
+    and the target instead of being read from `dy` (LogMAE; sums None: MAE).  bt_major: the result is laid
+    out [B*T, K*F] with speaker k at position iperm[b, k] -- what the final Linear's backward reads.
+    Gated rows only: vad = (Vad [B,K,T], gout_vad [B]) adds the gate column's BCE gradient in the same store."""
     L = _lib.lib()
-    B, K, T, F1 = logit.shape
-    assert tuple(obs.shape) == (B, T, F1 - 1) and obs.dtype == torch.complex64, (tuple(logit.shape), tuple(obs.shape))
+    B, K, T, F, gated = _tail_rows(logit, obs)
+    assert vad is None or gated, "mask_istft_bwd: vad= needs gated logit rows (F + 1 columns, the VAD logit at column 0)"
+    Fl = logit.shape[-1]
     logit = _f32(logit).contiguous()
     obs_r = torch.view_as_real(obs.contiguous())
-    dlogit = (torch.empty(B * T, K * F1, device=logit.device, dtype=torch.float32) if bt_major
-              else torch.empty_like(logit))
+    dlogit = torch.empty(B * T, K * Fl, device=logit.device, dtype=torch.float32) if bt_major else torch.empty_like(logit)
     if loss is None:
         x, tgt, sums, gout = _f32(dy).contiguous(), None, None, None
     else:
@@ -276,15 +244,26 @@ def mask_istft_gated_bwd(dy, logit, obs, wsyn, size=1024, shift=256, fading=True
                               _f32(loss[2]).contiguous() if loss[2] is not None else None, _f32(loss[3]).contiguous())
     assert tuple(x.shape[:2]) == (B, K) and (tgt is None or tgt.shape == x.shape), (tuple(x.shape), B, K)
     assert (gout is None or gout.numel() == B) and (sums is None or sums.numel() == B)
-    v = gv = None
-    if vad is not None:
-        v, gv = _f32(vad[0]).contiguous(), _f32(vad[1]).contiguous()
-        assert tuple(v.shape) == (B, K, T) and gv.numel() == B, (tuple(v.shape), (B, K, T), gv.numel())
-    with _timed("maskhead_gated_bwd", 0, B * T * (8 * K * F1 + 8 * (F1 - 1)) + 4 * B * K * x.shape[-1]):
-        check(L.tssep_mask_istft_gated_bwd(_p(x), _p(tgt), _p(sums), _p(gout), _p(v), _p(gv), _p(logit), _p(obs_r),
-                                           B, K, x.shape[-1], size, shift, int(fading), _p(wsyn),
-                                           _p(fft_tables(size, logit.device)), _p(iperm), int(bt_major), _p(dlogit),
-                                           T, _stream()), "mask_istft_gated_bwd")
+    N = x.shape[-1]
+    tail = (size, shift, int(fading), _p(wsyn), _p(fft_tables(size, logit.device)))
+    if gated:
+        v = gv = None
+        if vad is not None:
+            v, gv = _f32(vad[0]).contiguous(), _f32(vad[1]).contiguous()
+            assert tuple(v.shape) == (B, K, T) and gv.numel() == B, (tuple(v.shape), (B, K, T), gv.numel())
+        with _timed("maskhead_gated_bwd", 0, B * T * (8 * K * Fl + 8 * F) + 4 * B * K * N):
+            check(L.tssep_mask_istft_gated_bwd(_p(x), _p(tgt), _p(sums), _p(gout), _p(v), _p(gv), _p(logit), _p(obs_r),
+                                               B, K, N, *tail, _p(iperm), int(bt_major), _p(dlogit), T, _stream()),
+                  "mask_istft_gated_bwd")
+        return dlogit
+    _own_bytes("maskhead_bwd", B * T * (8 * K * F + 8 * F) + 4 * B * K * N * (1 if loss is None else 2))
+    with _timed("maskhead_bwd", 0, B * T * (16 * K * F + 8 * F)):
+        if loss is None and not bt_major:
+            check(L.tssep_mask_istft_bwd(_p(x), _p(logit), _p(obs_r), B, K, N, *tail, _p(dlogit), T, _stream()),
+                  "mask_istft_bwd")
+        else:
+            check(L.tssep_mask_istft_bwd_loss(_p(x), _p(tgt), _p(sums), _p(gout), _p(logit), _p(obs_r), B, K, N, *tail,
+                                              _p(iperm), int(bt_major), _p(dlogit), T, _stream()), "mask_istft_bwd_loss")
     return dlogit
 
 

@@ -152,22 +152,18 @@ class STFT(Configurable):
         """istft(sigmoid(logit) * observation) as one fused kernel each way (functional.mask_istft):
         logit [B,K,T,F], observation complex [B,T,F] -> [B,K,N]; ``target`` [B,K,N] (optional) lets the
         forward accumulate the |estimate - target| sums a LogMAE / MAE loss needs.
-        explicit_vad rows (logit [B,K,T,F+1], the VAD logit at column 0): the gated tail
-        (functional.mask_istft_gated) -> (time estimate, the gate column's BCE against ``vad`` [B,K,T] or None)."""
-        F = observation.shape[-1]
-        gated = logit.shape[-1] == F + 1
-        if not self._plain():         # the fused tail is built for the shipped STFT; any other: mask head, then istft
-            if gated:
-                _, est, _ = Fn.mask_head_gated(logit, observation)
-                bce = Fn.gate_bce(logit, vad) if vad is not None else None
-                return self.istft(est, num_samples=num_samples), bce
-            _, est = Fn.mask_head(logit, observation)
-            return self.istft(est, num_samples=num_samples)
-        N = self._num_samples(logit.shape[-2], num_samples)
-        _, wsyn = self._windows(logit.device)
-        if gated:
-            return Fn.mask_istft_gated(logit, observation, wsyn, N, self.size, self.shift, True, tgt=target, vad=vad)
-        return Fn.mask_istft(logit, observation, wsyn, N, self.size, self.shift, True, tgt=target)
+        explicit_vad rows (logit [B,K,T,F+1], the VAD logit at column 0) -> (time estimate, the gate column's BCE against
+        ``vad`` [B,K,T] or None)."""
+        gated = logit.shape[-1] == observation.shape[-1] + 1
+        if self._plain():
+            _, wsyn = self._windows(logit.device)
+            est, bce = Fn.mask_istft(logit, observation, wsyn, self._num_samples(logit.shape[-2], num_samples), self.size,
+                                     self.shift, True, tgt=target, vad=vad if gated else None)
+        else:                         # the fused tail is built for the shipped STFT; any other: mask head, then istft
+            est = (Fn.mask_head_gated if gated else Fn.mask_head)(logit, observation)[1]
+            est = self.istft(est, num_samples=num_samples)
+            bce = Fn.gate_bce(logit, vad) if gated and vad is not None else None
+        return (est, bce) if gated else est
 
     def stft_to_feature(self, stft_signals):
         raise NotImplementedError(type(self))

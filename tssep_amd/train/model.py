@@ -335,30 +335,42 @@ class Model(Configurable, torch.nn.Module):
             return self._forward_masks(ex)
         logit, emb = self.mask_estimator.logits(ex["Input"], aux)
         logit4 = logit if batched else logit[None]
+
+        def unb(t):
+            return t if batched else t[0]
+
         if getattr(self.mask_estimator, "explicit_vad", False):
-            return self._forward_gated(ex, logit, logit4, emb, ref, batched)
-        out = self.ForwardOutput(logit=logit.unsqueeze(-3), embedding=emb)
+            # net.py:969-979: logit = None, vad_logit = v [B,K,1,T] (a view of the head's [B,K,T,F+1] rows), and
+            # mask = sigmoid(l) sigmoid(v), vad_mask = sigmoid(v), stft_estimate lazy like the ungated mask
+            out = self.ForwardOutput(logit=None, embedding=emb, vad_logit=unb(logit4[..., 0]).unsqueeze(-2))
+            out._gated = logit4
+            mask_head, sigmoid = Fn.mask_head_gated, Fn.sigmoid_gated          # -> (mask, est, vad_mask), (mask, vad_mask)
+        else:
+            out = self.ForwardOutput(logit=logit.unsqueeze(-3), embedding=emb)
+            mask_head, sigmoid = Fn.mask_head, lambda lg: (Fn.sigmoid(lg),)
+
+        def shaped(mask, *vmask):             # -> mask [..., K, 1, T, F] (, vad_mask [..., K, 1, T])
+            return (unb(mask).unsqueeze(-3), *(unb(v).unsqueeze(-2) for v in vmask))
+
         if "Observation" in ex and isinstance(self.enhancer, _enh.Masking):
             obs = ex["Observation"][..., ref, :, :]
             obs3 = (obs if batched else obs[None]).contiguous()
             out._fusable = (logit4, obs3, batched)           # review() runs the fused chain from here
 
             def lazy():                                     # sigmoid (net.py:983) + Masking (enhancer.py:98-100)
-                mask, est = Fn.mask_head(logit4, obs3)
-                if not batched:
-                    mask, est = mask[0], est[0]
-                return mask.unsqueeze(-3), est
+                mask, est, *vmask = mask_head(logit4, obs3)
+                mask, *vmask = shaped(mask, *vmask)
+                return (mask, unb(est), *vmask)
         elif "Observation" in ex:
             def lazy():
-                mask = Fn.sigmoid(logit4)
-                mask = (mask if batched else mask[0]).unsqueeze(-3)
-                return mask, self.enhancer(mask, self._bf_example(ex), self)
+                mask, *vmask = shaped(*sigmoid(logit4))
+                return (mask, self.enhancer(mask, self._bf_example(ex), self), *vmask)
         else:
             assert isinstance(self.loss, _loss.VADSigmoidBCE), type(self.loss)
 
             def lazy():
-                mask = Fn.sigmoid(logit4)
-                return (mask if batched else mask[0]).unsqueeze(-3), None
+                mask, *vmask = shaped(*sigmoid(logit4))
+                return (mask, None, *vmask)
         out._lazy = out._lazy0 = lazy
         return out
 
@@ -383,37 +395,6 @@ class Model(Configurable, torch.nn.Module):
             return {**ex, "Observation": ex["Observation"].to(torch.complex128)}
         return ex
 
-    def _forward_gated(self, ex, logit, logit4, emb, ref, batched):
-        """explicit_vad (net.py:969-979): logit = None, vad_logit = v [B,K,1,T] (a view of the head's rows), and
-        mask = sigmoid(l) sigmoid(v), vad_mask = sigmoid(v), stft_estimate -- computed on first access, like the ungated
-        mask; the training step runs the gated fused tail from the [B,K,T,F+1] rows instead."""
-        def unb(t):
-            return t if batched else t[0]
-
-        out = self.ForwardOutput(logit=None, embedding=emb, vad_logit=unb(logit4[..., 0]).unsqueeze(-2))
-        out._gated = logit4
-        if "Observation" in ex and isinstance(self.enhancer, _enh.Masking):
-            obs = ex["Observation"][..., ref, :, :]
-            obs3 = (obs if batched else obs[None]).contiguous()
-            out._fusable = (logit4, obs3, batched)
-
-            def lazy():
-                mask, est, vmask = Fn.mask_head_gated(logit4, obs3)
-                return unb(mask).unsqueeze(-3), unb(est), unb(vmask).unsqueeze(-2)
-        elif "Observation" in ex:
-            def lazy():
-                mask, vmask = Fn.sigmoid_gated(logit4)
-                mask = unb(mask).unsqueeze(-3)
-                return mask, self.enhancer(mask, ex, self), unb(vmask).unsqueeze(-2)
-        else:
-            assert isinstance(self.loss, _loss.VADSigmoidBCE), type(self.loss)
-
-            def lazy():
-                mask, vmask = Fn.sigmoid_gated(logit4)
-                return unb(mask).unsqueeze(-3), None, unb(vmask).unsqueeze(-2)
-        out._lazy = out._lazy0 = lazy
-        return out
-
     # ------------------------------------------------------------------------- review
     def review(self, ex, out: "Model.ForwardOutput"):
         summary = ReviewSummary()
@@ -430,17 +411,18 @@ class Model(Configurable, torch.nn.Module):
                     tgt = tgt if batched else tgt[None]
                 else:
                     tgt = None
-                if out._gated is not None:
-                    # explicit_vad: the gated tail; with SignalAndVADSigmoidBCE the BCE of the gate column rides along
-                    # (its value on `out`, its gradient folded into the tail's d(v) store)
-                    vad = self.loss.frame_vad(ex, self) if isinstance(self.loss, _loss.SignalAndVADSigmoidBCE) else None
+                # explicit_vad with SignalAndVADSigmoidBCE: the BCE of the gate column rides along (its value on `out`, its
+                # gradient folded into the tail's d(v) store)
+                vad = None
+                if out._gated is not None and isinstance(self.loss, _loss.SignalAndVADSigmoidBCE):
+                    vad = self.loss.frame_vad(ex, self)
                     if vad is not None:
                         vad = vad if batched else vad[None]
-                    te, bce = self.fe.masked_istft(logit4, obs3, num_samples=n, target=tgt, vad=vad)
+                te = self.fe.masked_istft(logit4, obs3, num_samples=n, target=tgt, vad=vad)
+                if out._gated is not None:
+                    te, bce = te
                     if bce is not None:
                         out._gate_bce = (bce if batched else bce[0], ex[self.loss.target])
-                else:
-                    te = self.fe.masked_istft(logit4, obs3, num_samples=n, target=tgt)
                 out.time_estimate = te if batched else te[0]
             else:
                 out.time_estimate = self.fe.istft(out.stft_estimate, num_samples=n)
