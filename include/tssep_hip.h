@@ -512,6 +512,27 @@ int tssep_logmae_finalize(const float* partial, int64_t B, int64_t K, int64_t nc
                           float* loss, float* sums, void* stream);
 int tssep_logmae_bwd(const float* est, const float* tgt, const float* sums, const float* gout,
                      int64_t B, int64_t K, int64_t N, float* dest, void* stream);
+/* Pairwise costs and the permutation-invariant assignment (pit=True of tssep/train/loss.py:194-247 through
+ * pt.ops.losses.pit_loss; MSE, loss.py:183-190).  est, tgt [B,K,N], K <= 8 (TSSEP_E_SHAPE beyond).
+ * tssep_pair_cost_fwd: ONE pass over est and tgt (2 B K N floats read, whatever K is) leaves the chunk partials
+ *   part [B][nchunks][K][K] of sum_n |est[b,i,n] - tgt[b,j,n]|^p, p = 1 or 2, nchunks = tssep_pair_cost_chunks(N);
+ *   fixed-order reduction, no atomics.  diag_only != 0: only i == j is computed (pit=False), the rest is written as 0.
+ * tssep_pit_assign: cost[b,i,j] = (sum_c part[b,c,i,j]) / N (cost may be NULL), then per utterance
+ *   pit != 0: perm[b] = argmin over the K! permutations of sum_i cost[b,i,perm(i)] (float32, ascending i; among equal
+ *   sums the first in itertools.permutations(range(K)) order; a NaN sum wins, so it reaches the loss);
+ *   pit == 0: the identity.  perm [B,K] int32 (perm[b,i] = the target row matched to estimate row i),
+ *   sums[b] = the minimum, loss[b] = logarithm ? log10(sums[b]) : sums[b].  A caller-supplied cost matrix [B,K,K] is
+ *   passed as part with nchunks = 1, N = 1.
+ * tssep_pair_loss_bwd: dest[b,i,n] = c sign(e - t) (p = 1) or c 2 (e - t) (p = 2), t = tgt[b,perm[b,i],n] read in place
+ *   (perm == NULL: identity), c = gout[b] / N, divided by ln10 sums[b] when sums != NULL (LogMAE). */
+int64_t tssep_pair_cost_chunks(int64_t N);
+int64_t tssep_pair_cost_workspace_bytes(int64_t B, int64_t K, int64_t N);
+int tssep_pair_cost_fwd(const float* est, const float* tgt, int64_t B, int64_t K, int64_t N, int p, int diag_only,
+                        float* part, void* stream);
+int tssep_pit_assign(const float* part, int64_t B, int64_t K, int64_t nchunks, int64_t N, int pit, int logarithm,
+                     float* cost, int32_t* perm, float* sums, float* loss, void* stream);
+int tssep_pair_loss_bwd(const float* est, const float* tgt, const int32_t* perm, const float* sums, const float* gout,
+                        int64_t B, int64_t K, int64_t N, int p, float* dest, void* stream);
 /* VADSigmoidBCE with target 'Vad' (tssep/train/loss.py:329-345,302-310):
  * x = mean_f logit[b,k,t,:]; loss[b] = mean_{k,t} BCEWithLogits(x, vad).
  * xmean [B,K,T] is kept for bwd; ws: tssep_vadbce_workspace_bytes.

@@ -282,6 +282,228 @@ __global__ void logmae_bwd_kernel(const float* __restrict__ est, const float* __
   }
 }
 
+// ---- pairwise costs and the permutation-invariant assignment (pit=True; MSE) ----------------
+// C[b,i,j] = (1/N) sum_n |est[b,i,n] - tgt[b,j,n]|^P.  One workgroup per (utterance, chunk of PC_CHUNK samples): the K
+// est rows and the K tgt rows of the chunk are read ONCE (2 B K N floats in all, what one tssep_logmae_fwd reads) into
+// K x K accumulators per lane; wave -> workgroup in a fixed order as absdiff_partial_kernel, no atomics.
+// part [B][nchunks][K][K]; flat grid (b and the chunk share blockIdx.x: no 65535 cap on B).
+// DIAG: only the K matched pairs i == j (a pit=False loss); the other entries of `part` are written as 0.
+// Float32 roundings on the longest path into part: P == 1: 1 (e - t), P == 2: 2 (the square of the rounded difference;
+// the product is fused into the add), + PC_CHUNK / 256 adds of the lane chain + 6 (wave tree) + 2 (the four waves).
+constexpr int PC_CHUNK = 8192;
+constexpr int PIT_MAX_K = 8;
+template <int P>
+__device__ __forceinline__ float pc_term(float e, float t, float acc) {
+  const float d = e - t;
+  return P == 1 ? acc + fabsf(d) : fmaf(d, d, acc);
+}
+template <int K, int P, bool DIAG>
+__global__ __launch_bounds__(256) void pair_cost_partial_kernel(const float* __restrict__ est,
+                                                                const float* __restrict__ tgt, int64_t N,
+                                                                unsigned nchunks, int vec,
+                                                                float* __restrict__ part) {
+  constexpr int NA = DIAG ? K : K * K;
+  __shared__ float red[4][NA];
+  const int64_t b = blockIdx.x / nchunks;
+  const int64_t n0 = (int64_t)(blockIdx.x - (unsigned)b * nchunks) * PC_CHUNK;
+  const float* __restrict__ e0 = est + b * K * N;
+  const float* __restrict__ t0 = tgt + b * K * N;
+  float acc[NA];
+#pragma unroll
+  for (int a = 0; a < NA; ++a) acc[a] = 0.f;
+  if (vec) {                     // N % 4 == 0 and 16-byte aligned bases: every row starts on a 16-byte boundary
+    for (int it = 0; it < PC_CHUNK / 1024; ++it) {
+      const int64_t n = n0 + (int64_t)(it * 256 + (int)threadIdx.x) * 4;
+      if (n < N) {
+        f32x4 tv[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) tv[j] = *reinterpret_cast<const f32x4*>(t0 + j * N + n);
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+          const f32x4 ev = *reinterpret_cast<const f32x4*>(e0 + i * N + n);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            if (DIAG) {
+              acc[i] = pc_term<P>(ev[q], tv[i][q], acc[i]);
+            } else {
+#pragma unroll
+              for (int j = 0; j < K; ++j) acc[i * K + j] = pc_term<P>(ev[q], tv[j][q], acc[i * K + j]);
+            }
+          }
+        }
+      }
+    }
+  } else {
+    for (int it = 0; it < PC_CHUNK / 256; ++it) {
+      const int64_t n = n0 + it * 256 + (int)threadIdx.x;
+      if (n < N) {
+        float tv[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) tv[j] = t0[j * N + n];
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+          const float ev = e0[i * N + n];
+          if (DIAG) {
+            acc[i] = pc_term<P>(ev, tv[i], acc[i]);
+          } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) acc[i * K + j] = pc_term<P>(ev, tv[j], acc[i * K + j]);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NA; ++a) {
+    const float s = wave_sum(acc[a]);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][a] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < K * K) {
+    const int i = threadIdx.x / K, j = threadIdx.x - i * K;
+    const int a = DIAG ? i : (int)threadIdx.x;
+    const float s = (red[0][a] + red[1][a]) + (red[2][a] + red[3][a]);
+    part[(int64_t)blockIdx.x * (K * K) + threadIdx.x] = (!DIAG || i == j) ? s : 0.f;
+  }
+}
+
+// `a` before `b` in the order the assignment minimises: a NaN sum first (as torch.min, it reaches the loss), then the
+// smaller float32 sum, then -- among equal sums -- the smaller index in itertools.permutations(range(K)) order
+__device__ __forceinline__ bool pit_before(float sa, int ia, float sb, int ib) {
+  const bool na = sa != sa, nb = sb != sb;
+  if (na || nb) return na && (!nb || ia < ib);
+  return sa < sb || (sa == sb && ia < ib);
+}
+// Lexicographic enumeration of the permutations of range(K) (the order of itertools.permutations), split as
+// index = prefix * TAIL! + sub: the first K - TAIL entries are decoded from `prefix` in the factorial number system (the
+// radices are compile-time constants: no integer division is executed), the last TAIL = min(K, 3) entries run through
+// the TAIL! orders of the TAIL elements left over, ascending -- one decode and one prefix sum serve TAIL! permutations.
+template <int K>
+struct PitPlan {
+  static constexpr int TAIL = K < 3 ? K : 3;
+  static constexpr int NSUB = TAIL == 3 ? 6 : TAIL;        // TAIL!
+  static constexpr int L = K - TAIL;
+  static constexpr int fact(int n) { return n <= 1 ? 1 : n * fact(n - 1); }
+  static constexpr int NPREFIX = fact(K) / NSUB;
+};
+// -> the prefix entries (4 bits each, entry i at bits 4 i); avail: the elements left over, ascending, 4 bits each
+template <int K>
+__device__ __forceinline__ unsigned pit_prefix(int pidx, uint64_t& avail) {
+  using P = PitPlan<K>;
+  avail = 0x76543210ull;
+  unsigned perm = 0;
+#pragma unroll
+  for (int i = 0; i < P::L; ++i) {
+    const int f = P::fact(K - 1 - i) / P::NSUB;             // permutations of the prefix behind entry i
+    const int d = pidx / f;
+    pidx -= d * f;
+    perm |= (unsigned)((avail >> (4 * d)) & 15u) << (4 * i);
+    avail = (avail & ((1ull << (4 * d)) - 1ull)) | ((avail >> (4 * d + 4)) << (4 * d));
+  }
+  return perm;
+}
+// the sub-th order of TAIL elements: which of the (ascending) left-over elements goes to tail position a
+__device__ __forceinline__ int pit_sub(int tail, int sub, int a) {
+  // TAIL == 3: 012 021 102 120 201 210, two bits per position; TAIL == 2: 01 10; TAIL == 1: 0
+  const unsigned t3[6] = {0x24u, 0x18u, 0x21u, 0x09u, 0x12u, 0x06u};
+  if (tail == 3) return (int)((t3[sub] >> (2 * a)) & 3u);
+  return tail == 2 ? (a ^ sub) : 0;
+}
+// One workgroup per utterance: cost[b] = (sum over the chunks in chunk order) / N, then the assignment.  pit != 0:
+// the prefixes are dealt to the 256 lanes (lane l takes l, l + 256, ...: ascending indices within a lane), each
+// sum_i C[i, perm(i)] in float32 in ascending i out of LDS, and the best (pit_before) is reduced wave -> workgroup.
+// pit == 0: the identity.
+template <int K>
+__global__ __launch_bounds__(256) void pit_assign_kernel(const float* __restrict__ part, int nchunks, int64_t N,
+                                                         int pit, int logarithm, float* __restrict__ cost,
+                                                         int32_t* __restrict__ perm, float* __restrict__ sums,
+                                                         float* __restrict__ loss) {
+  using P = PitPlan<K>;
+  constexpr int KK = K * K, NONE = 0x7fffffff;
+  __shared__ float C[KK];
+  __shared__ float best_s[4];
+  __shared__ int best_i[4];
+  const int64_t b = blockIdx.x;
+  if ((int)threadIdx.x < KK) {
+    float s = 0.f;
+    for (int c = 0; c < nchunks; ++c) s += part[(b * nchunks + c) * KK + threadIdx.x];
+    s = s / (float)N;
+    C[threadIdx.x] = s;
+    if (cost) cost[b * KK + threadIdx.x] = s;
+  }
+  __syncthreads();
+  float bs = 0.f;
+  int bi = NONE;                                // (a lane without a permutation never wins: every real index is smaller)
+  if (pit) {
+    for (int pidx = threadIdx.x; pidx < P::NPREFIX; pidx += 256) {
+      uint64_t avail;
+      const unsigned pm = pit_prefix<K>(pidx, avail);
+      float sp = 0.f;                           // (0 + x is exact: the sum starts at C[0, perm(0)])
+#pragma unroll
+      for (int i = 0; i < P::L; ++i) sp += C[i * K + ((pm >> (4 * i)) & 15u)];
+      float c[P::TAIL][P::TAIL];                // c[a][e] = C[L + a, e-th element left over]
+#pragma unroll
+      for (int a = 0; a < P::TAIL; ++a)
+#pragma unroll
+        for (int e = 0; e < P::TAIL; ++e) c[a][e] = C[(P::L + a) * K + (int)((avail >> (4 * e)) & 15u)];
+#pragma unroll
+      for (int sub = 0; sub < P::NSUB; ++sub) {
+        float s = sp;
+#pragma unroll
+        for (int a = 0; a < P::TAIL; ++a) s += c[a][pit_sub(P::TAIL, sub, a)];
+        const int idx = pidx * P::NSUB + sub;
+        if (bi == NONE || pit_before(s, idx, bs, bi)) { bs = s; bi = idx; }
+      }
+    }
+  } else if (threadIdx.x == 0) {
+    for (int i = 0; i < K; ++i) bs += C[i * K + i];
+    bi = 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float os = __shfl_xor(bs, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (oi != NONE && (bi == NONE || pit_before(os, oi, bs, bi))) { bs = os; bi = oi; }
+  }
+  if ((threadIdx.x & 63) == 0) { best_s[threadIdx.x >> 6] = bs; best_i[threadIdx.x >> 6] = bi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w)
+      if (best_i[w] != NONE && pit_before(best_s[w], best_i[w], bs, bi)) { bs = best_s[w]; bi = best_i[w]; }
+    unsigned pm = 0x76543210u;
+    if (pit) {
+      uint64_t avail;
+      const int pidx = bi / P::NSUB, sub = bi - pidx * P::NSUB;
+      pm = pit_prefix<K>(pidx, avail);
+      for (int a = 0; a < P::TAIL; ++a)
+        pm |= (unsigned)((avail >> (4 * pit_sub(P::TAIL, sub, a))) & 15u) << (4 * (P::L + a));
+    }
+    for (int i = 0; i < K; ++i) perm[b * K + i] = (int32_t)((pm >> (4 * i)) & 15u);
+    sums[b] = bs;
+    loss[b] = logarithm ? log10f(bs) : bs;
+  }
+}
+// logmae_bwd_kernel with the target row taken through perm (NULL: the identity) and the P == 2 branch:
+// P == 1: coef sign(e - t), P == 2: coef 2 (e - t); coef = gout[b] / N, over ln10 sums[b] when sums != NULL.
+template <int P>
+__global__ void pair_loss_bwd_kernel(const float* __restrict__ est, const float* __restrict__ tgt,
+                                     const int32_t* __restrict__ perm, const float* __restrict__ sums,
+                                     const float* __restrict__ gout, int64_t K, int64_t N, int64_t total,
+                                     float* __restrict__ dest) {
+  const float ln10 = 2.30258509299404568402f;
+  const int64_t KN = K * N;
+  GRID_STRIDE(e, total) {
+    const int64_t b = e / KN, r = e - b * KN;
+    const int64_t i = r / N, n = r - i * N;
+    int64_t j = perm ? (int64_t)perm[b * K + i] : i;
+    if (j < 0 || j >= K) j = i;                 // (a corrupt perm must not turn into a read outside tgt)
+    const float g = P == 2 ? 2.0f * gout[b] : gout[b];
+    const float coef = sums ? g / ((float)N * ln10 * sums[b]) : g / (float)N;
+    const float d = est[e] - tgt[(b * K + j) * N + n];
+    dest[e] = P == 2 ? coef * d : (d > 0.f ? coef : (d < 0.f ? -coef : 0.f));
+  }
+}
+
 // ---- VAD BCE ------------------------------------------------------------------------------
 // one wave per (b,k,t) row: x = mean_f logit ; l = max(x,0) - x*y + log1p(exp(-|x|))
 __global__ __launch_bounds__(256) void vadbce_rows_kernel(const float* __restrict__ logit,
@@ -683,6 +905,69 @@ extern "C" int tssep_logmae_bwd(const float* est, const float* tgt, const float*
   if (B <= 0 || K <= 0 || N <= 0) return TSSEP_E_SHAPE;
   hipLaunchKernelGGL(logmae_bwd_kernel, dim3(grid_for(B * K * N)), dim3(256), 0, S_, est, tgt, sums,
                      gout, K * N, N, B * K * N, dest);
+  return tssep_launch_status();
+}
+extern "C" int64_t tssep_pair_cost_chunks(int64_t N) { return (N + PC_CHUNK - 1) / PC_CHUNK; }
+extern "C" int64_t tssep_pair_cost_workspace_bytes(int64_t B, int64_t K, int64_t N) {
+  return B * tssep_pair_cost_chunks(N) * K * K * (int64_t)sizeof(float);
+}
+template <int P, bool DIAG>
+static void pair_cost_launch(int K, unsigned grid, void* stream, const float* est, const float* tgt, int64_t N,
+                             unsigned nchunks, int vec, float* part) {
+  switch (K) {
+#define PC_CASE(k)                                                                                            \
+  case k:                                                                                                     \
+    hipLaunchKernelGGL((pair_cost_partial_kernel<k, P, DIAG>), dim3(grid), dim3(256), 0, S_, est, tgt, N,     \
+                       nchunks, vec, part);                                                                   \
+    break;
+    PC_CASE(1) PC_CASE(2) PC_CASE(3) PC_CASE(4) PC_CASE(5) PC_CASE(6) PC_CASE(7) PC_CASE(8)
+#undef PC_CASE
+  }
+}
+extern "C" int tssep_pair_cost_fwd(const float* est, const float* tgt, int64_t B, int64_t K, int64_t N, int p,
+                                   int diag_only, float* part, void* stream) {
+  if (!est || !tgt || !part) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || K > PIT_MAX_K || N <= 0 || (p != 1 && p != 2)) return TSSEP_E_SHAPE;
+  const int64_t nchunks = tssep_pair_cost_chunks(N);
+  if (B * nchunks > 0x7fffffffLL) return TSSEP_E_SHAPE;
+  const unsigned grid = (unsigned)(B * nchunks);
+  const int vec = (N & 3) == 0 && aligned16(est) && aligned16(tgt);
+  if (p == 1) {
+    if (diag_only) pair_cost_launch<1, true>((int)K, grid, stream, est, tgt, N, (unsigned)nchunks, vec, part);
+    else pair_cost_launch<1, false>((int)K, grid, stream, est, tgt, N, (unsigned)nchunks, vec, part);
+  } else {
+    if (diag_only) pair_cost_launch<2, true>((int)K, grid, stream, est, tgt, N, (unsigned)nchunks, vec, part);
+    else pair_cost_launch<2, false>((int)K, grid, stream, est, tgt, N, (unsigned)nchunks, vec, part);
+  }
+  return tssep_launch_status();
+}
+extern "C" int tssep_pit_assign(const float* part, int64_t B, int64_t K, int64_t nchunks, int64_t N, int pit,
+                                int logarithm, float* cost, int32_t* perm, float* sums, float* loss, void* stream) {
+  if (!part || !perm || !sums || !loss) return TSSEP_E_NULL;      // cost may be NULL (not wanted)
+  if (B <= 0 || B > 0x7fffffffLL || K <= 0 || K > PIT_MAX_K || nchunks <= 0 || nchunks > 0x7fffffffLL || N <= 0)
+    return TSSEP_E_SHAPE;
+  switch (K) {
+#define PA_CASE(k)                                                                                            \
+  case k:                                                                                                     \
+    hipLaunchKernelGGL(pit_assign_kernel<k>, dim3((unsigned)B), dim3(256), 0, S_, part, (int)nchunks, N, pit,  \
+                       logarithm, cost, perm, sums, loss);                                                    \
+    break;
+    PA_CASE(1) PA_CASE(2) PA_CASE(3) PA_CASE(4) PA_CASE(5) PA_CASE(6) PA_CASE(7) PA_CASE(8)
+#undef PA_CASE
+  }
+  return tssep_launch_status();
+}
+extern "C" int tssep_pair_loss_bwd(const float* est, const float* tgt, const int32_t* perm, const float* sums,
+                                   const float* gout, int64_t B, int64_t K, int64_t N, int p, float* dest,
+                                   void* stream) {
+  if (!est || !tgt || !gout || !dest) return TSSEP_E_NULL;        // perm may be NULL (identity), sums may be NULL (no log)
+  if (B <= 0 || K <= 0 || K > PIT_MAX_K || N <= 0 || (p != 1 && p != 2)) return TSSEP_E_SHAPE;
+  if (p == 1)
+    hipLaunchKernelGGL(pair_loss_bwd_kernel<1>, dim3(grid_for(B * K * N)), dim3(256), 0, S_, est, tgt, perm, sums,
+                       gout, K, N, B * K * N, dest);
+  else
+    hipLaunchKernelGGL(pair_loss_bwd_kernel<2>, dim3(grid_for(B * K * N)), dim3(256), 0, S_, est, tgt, perm, sums,
+                       gout, K, N, B * K * N, dest);
   return tssep_launch_status();
 }
 extern "C" int64_t tssep_vadbce_workspace_bytes(int64_t B, int64_t K, int64_t T) {

@@ -782,14 +782,52 @@ class _AbsErrorLoss(torch.autograd.Function):
         return H.logmae_bwd(est.contiguous(), tgt.contiguous(), sums, g), None, None, None, None
 
 
-def log_mae(est, tgt):
+class _PairLoss(torch.autograd.Function):
+    """f(sum_k C[k, perm(k)]) on the pairwise costs C[i, j] = mean_n |e_i - t_j|^p, f = log10 or the identity:
+    pit=True: perm = the best assignment per utterance (= the best permutation of pt.ops.losses.pit_loss, f being
+    monotone), found on the device; pit=False: the identity, on the diagonal-only pass.  One pass over est and tgt
+    either way.  -> (loss [B], perm int32 [B,K]); the permutation is a constant of the backward."""
+
+    @staticmethod
+    def forward(ctx, est, tgt, p, log, pit):
+        est, tgt = est.contiguous(), tgt.contiguous()
+        part = H.pair_cost_fwd(est, tgt, p, diag_only=not pit)
+        _, perm, sums, loss = H.pit_assign(part, est.shape[-1], pit=pit, log=log, want_cost=False)
+        ctx.save_for_backward(est, tgt, perm, sums)
+        ctx.meta = (p, log, pit)
+        ctx.mark_non_differentiable(perm)
+        return loss, perm
+
+    @staticmethod
+    def backward(ctx, g, _gperm):
+        est, tgt, perm, sums = ctx.saved_tensors
+        p, log, pit = ctx.meta
+        return H.pair_loss_bwd(est, tgt, perm if pit else None, sums if log else None, g, p), None, None, None, None
+
+
+def pair_loss(est, tgt, p=1, log=False, pit=True):
+    """est, tgt [B,K,N] (K <= 8) -> (loss [B], perm int32 [B,K]); perm[b, i] = the target row matched to estimate row i."""
+    H._check_pit_k(est.shape[-2])
+    return _PairLoss.apply(est, tgt, int(p), bool(log), bool(pit))
+
+
+def log_mae(est, tgt, pit=False):
+    if pit:
+        return pair_loss(est, tgt, 1, True, True)[0]
     part = _fused_absdiff(est, tgt)
     return _AbsErrorLoss.apply(est, tgt, True, part, _loss_link(est, part))
 
 
-def mae(est, tgt):
+def mae(est, tgt, pit=False):
+    if pit:
+        return pair_loss(est, tgt, 1, False, True)[0]
     part = _fused_absdiff(est, tgt)
     return _AbsErrorLoss.apply(est, tgt, False, part, _loss_link(est, part))
+
+
+def mse(est, tgt, pit=False):
+    """sum_k mean_n (e - t)^2 -> [B] (loss.py:183-190), with pit the minimum over the speaker permutations."""
+    return pair_loss(est, tgt, 2, False, pit)[0]
 
 
 class _VadBCE(torch.autograd.Function):

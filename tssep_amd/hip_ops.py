@@ -1640,6 +1640,61 @@ def logmae_bwd(est, tgt, sums, gout):
     return dest
 
 
+PIT_MAX_K = 8      # the assignment enumerates K! permutations (8! = 40 320); the C entry points answer TSSEP_E_SHAPE beyond
+
+
+def _check_pit_k(K):
+    if K > PIT_MAX_K:
+        raise NotImplementedError(f"pairwise-cost losses (pit=True, MSE) take at most {PIT_MAX_K} speakers, got K = {K}: "
+                                  f"the assignment enumerates K! permutations")
+
+
+def pair_cost_fwd(est, tgt, p=1, diag_only=False):
+    """est, tgt [B,K,N] -> chunk partials [B, nchunks, K, K] of sum_n |est[b,i,n] - tgt[b,j,n]|^p in ONE pass over both
+    (diag_only: only i == j, the rest 0)."""
+    L = _lib.lib()
+    B, K, N = est.shape
+    _check_pit_k(K)
+    est, tgt = _f32(est).contiguous(), _f32(tgt).contiguous()
+    part = torch.empty(B, int(L.tssep_pair_cost_chunks(N)), K, K, device=est.device, dtype=torch.float32)
+    assert part.numel() * 4 == L.tssep_pair_cost_workspace_bytes(B, K, N)
+    with _timed("pair_cost", B * K * (K if not diag_only else 1) * N * 2, 2 * B * K * N * 4):
+        check(L.tssep_pair_cost_fwd(_p(est), _p(tgt), B, K, N, int(p), int(bool(diag_only)), _p(part), _stream()),
+              "pair_cost_fwd")
+    return part
+
+
+def pit_assign(part, N, pit=True, log=False, want_cost=True):
+    """part [B, nchunks, K, K] (a cost matrix [B,K,K]: pass part = cost[:, None], N = 1) ->
+    (cost [B,K,K] or None, perm int32 [B,K], sums [B], loss [B]); all on the device, no host sync."""
+    B, nchunks, K, K2 = part.shape
+    assert K == K2, part.shape
+    _check_pit_k(K)
+    part = _f32(part).contiguous()
+    dev = part.device
+    cost = torch.empty(B, K, K, device=dev, dtype=torch.float32) if want_cost else None
+    perm = torch.empty(B, K, device=dev, dtype=torch.int32)
+    sums = torch.empty(B, device=dev, dtype=torch.float32)
+    loss = torch.empty(B, device=dev, dtype=torch.float32)
+    check(_lib.lib().tssep_pit_assign(_p(part), B, K, nchunks, int(N), int(bool(pit)), int(bool(log)), _p(cost),
+                                      _p(perm), _p(sums), _p(loss), _stream()), "pit_assign")
+    return cost, perm, sums, loss
+
+
+def pair_loss_bwd(est, tgt, perm, sums, gout, p=1):
+    """d(loss)/d(est) of a pairwise-cost loss; perm None: identity, sums None: no logarithm.  tgt is read through perm in
+    place (never gathered)."""
+    B, K, N = est.shape
+    _check_pit_k(K)
+    est, tgt = _f32(est).contiguous(), _f32(tgt).contiguous()
+    if perm is not None:
+        assert perm.dtype == torch.int32 and tuple(perm.shape) == (B, K) and perm.is_contiguous(), (perm.dtype, perm.shape)
+    dest = torch.empty_like(est)
+    check(_lib.lib().tssep_pair_loss_bwd(_p(est), _p(tgt), _p(perm), _p(sums), _p(_f32(gout).contiguous()), B, K, N,
+                                         int(p), _p(dest), _stream()), "pair_loss_bwd")
+    return dest
+
+
 def vadbce_fwd(logit, vad):
     L = _lib.lib()
     B, K, T, F = logit.shape

@@ -1,7 +1,12 @@
 """Losses -- drop-ins for tssep/train/loss.py on the HIP kernels: ``LogMAE`` (:219-247) and
-``VADSigmoidBCE`` (:272-345) with their ``from_ex_out`` glue (:89-99, :118-146), ``MAE`` (:194-216) and the joint
-TS-SEP loss ``SignalAndVADSigmoidBCE`` (:348-424) of an ``explicit_vad`` mask estimator.
-MSE / FreqMSE are not selected by any shipped config."""
+``VADSigmoidBCE`` (:272-345) with their ``from_ex_out`` glue (:89-99, :118-146), ``MAE`` (:194-216), ``MSE`` (:183-190)
+and the joint TS-SEP loss ``SignalAndVADSigmoidBCE`` (:348-424) of an ``explicit_vad`` mask estimator.
+
+``pit=True`` on the time-domain losses (LogMAE, MAE, MSE): the loss of the best speaker permutation per utterance
+(pt.ops.losses.pit_loss).  Each of them is f(sum_k C[k, perm(k)]) with f monotone on the pairwise costs
+C[i, j] = mean_n |e_i - t_j|^p, so the best permutation is the best assignment on C: one pass over both signals yields
+C, the assignment is found on the device (K <= 8), and ``.permutation`` keeps the last call's choice.
+Not built: FreqMSE, pit for the VAD losses, K > 8."""
 import torch
 
 from .. import functional as Fn
@@ -11,9 +16,7 @@ from ..configurable import Configurable
 class ABC(Configurable, torch.nn.Module):
     def __init__(self, target: str = "speaker_reverberation_early_ch0", pit: bool = False):
         super().__init__()
-        if pit:
-            raise NotImplementedError("pit=True (every shipped config uses pit: false)")
-        self.target, self.pit = target, pit
+        self.target, self.pit = target, bool(pit)
 
     def _upper(self, s):
         return s[0].upper() + s[1:]
@@ -39,13 +42,38 @@ class ABC(Configurable, torch.nn.Module):
 
 
 class TimeDomain(ABC):
+    """estimate, target [B, K, N] (or [K, N]: one utterance, the result squeezed back) -> [B].
+    pit=True: the minimum over the speaker permutations, found per utterance; ``permutation`` then holds the last call's
+    detached int32 [B, K] (or [K]) tensor, permutation[b, i] = the target row matched to estimate row i, so that
+    evaluation code can reorder estimates (``target[b, permutation[b]]`` lines up with ``estimate[b]``).  It stays on the
+    device -- no host sync, a captured step recomputes it on every replay -- and is None while pit is false."""
+    power, log = 1, False              # the pairwise cost mean_n |e - t|^power; log10 of the matched sum
+    permutation = None
+
+    @property
+    def fused_tail(self):
+        """Whether the fused tail of Model.review may form this loss's |e - t| sums and gradient itself: the L1 losses
+        with the targets in their own order only."""
+        return self.power == 1 and not self.pit
+
     def from_ex_out(self, ex, out, model, summary):      # loss.py:90-99
         return self(out.time_estimate, ex[self.target])
 
+    def _pit(self, estimate, target):
+        batched = estimate.dim() == 3
+        loss, perm = Fn.pair_loss(estimate if batched else estimate[None], target if batched else target[None],
+                                  self.power, self.log, True)
+        self.permutation = perm.detach() if batched else perm.detach()[0]
+        return loss if batched else loss[0]
+
 
 class LogMAE(TimeDomain):
+    log = True
+
     def loss_fn(self, estimate, target):
         """log10(sum_k mean_n |e - t|) -> [B]  (loss.py:244-247)"""
+        if self.pit:
+            return self._pit(estimate, target)
         if estimate.dim() == 2:
             return Fn.log_mae(estimate[None], target[None])[0]
         return Fn.log_mae(estimate, target)
@@ -54,9 +82,24 @@ class LogMAE(TimeDomain):
 class MAE(TimeDomain):
     def loss_fn(self, estimate, target):
         """sum_k mean_n |e - t| -> [B]  (loss.py:194-216)"""
+        if self.pit:
+            return self._pit(estimate, target)
         if estimate.dim() == 2:
             return Fn.mae(estimate[None], target[None])[0]
         return Fn.mae(estimate, target)
+
+
+class MSE(TimeDomain):
+    power = 2
+
+    def loss_fn(self, estimate, target):
+        """sum_k mean_n (e - t)^2  (loss.py:183-190: 0.1673 in its doctest, not the mean over all elements).  Batched
+        input gives one value per utterance, [B] -- this project's convention, the same as MAE."""
+        if self.pit:
+            return self._pit(estimate, target)
+        if estimate.dim() == 2:
+            return Fn.mse(estimate[None], target[None])[0]
+        return Fn.mse(estimate, target)
 
 
 class LogitsSTFTDomain(ABC):
@@ -90,6 +133,8 @@ class LogitsSTFTDomain(ABC):
 
 class VADSigmoidBCE(LogitsSTFTDomain):
     def __init__(self, target: str = "Vad", pit: bool = False, magnitude_threshold: float = 0.05):
+        if pit:
+            raise NotImplementedError("pit=True on a VAD loss (only the time-domain losses LogMAE, MAE, MSE take it)")
         super().__init__(target=target, pit=pit)
         assert 0 < magnitude_threshold < 1, magnitude_threshold
         self.magnitude_threshold = magnitude_threshold
@@ -122,7 +167,10 @@ class SignalAndVADSigmoidBCE(VADSigmoidBCE):
         if target != "Vad":
             raise NotImplementedError(f"target {target!r}: only the frame-level 'Vad' target (loss.py:384-393)")
         if not isinstance(signal_loss, TimeDomain):
-            raise TypeError(f"signal_loss must be a time-domain loss (LogMAE, MAE), got {type(signal_loss).__name__}")
+            raise TypeError(f"signal_loss must be a time-domain loss (LogMAE, MAE, MSE), got {type(signal_loss).__name__}")
+        if signal_loss.pit:
+            raise NotImplementedError("signal_loss with pit=True: the VAD term compares vad_logit with Vad row by row and "
+                                      "would not follow the signal loss's permutation")
         self.signal_loss = signal_loss
 
     def targets(self, lower=False, upper=False):          # loss.py:363-366

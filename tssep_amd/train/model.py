@@ -406,7 +406,9 @@ class Model(Configurable, torch.nn.Module):
                 # the |estimate - target| partial sums of a time-domain loss on the side
                 logit4, obs3, batched = fus
                 sig = self.loss.signal_loss if isinstance(self.loss, _loss.SignalAndVADSigmoidBCE) else self.loss
-                tgt = ex.get(getattr(sig, "target", None)) if isinstance(sig, _loss.TimeDomain) else None
+                # (only for an L1 loss on the targets' own order: pit=True and MSE run stand-alone on time_estimate and
+                # hand their gradient to the tail's backward as dy)
+                tgt = ex.get(getattr(sig, "target", None)) if isinstance(sig, _loss.TimeDomain) and sig.fused_tail else None
                 if isinstance(tgt, torch.Tensor):
                     tgt = tgt if batched else tgt[None]
                 else:
