@@ -462,3 +462,77 @@ def test_stft_entry_points_share_their_argument_checks():
     assert backwards(rows=(-1, -1)) == [SHAPE] * 3 and backwards(size=512) == [UNSUPPORTED] * 3
     # (only the entry points that take the argument: for the others the call would be a valid one)
     assert backwards(gout=None, only=slice(1, 3)) == [NULL] * 2 and backwards(gbce=None, only=slice(2, 3)) == [NULL]
+
+
+@pytest.mark.parametrize("bias", [True, False])
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("to_sinks", [True, False])
+def test_linear_wgrads_branch_table(monkeypatch, to_sinks, fused, bias):
+    """functional._linear_wgrads, the one emitter of dW = dY^T X and db = column sums of dY: the exact calls into hip_ops
+    of every combination of sinks / autograd return x ones-column / plain x bias / none (Nout = 3, P = 5, R = 4, CPU
+    tensors, recording fakes); with sinks every reducer accumulates and (None, None) comes back; and the fork helper
+    entered with direct=False touches nothing of torch.cuda."""
+    from tssep_amd import functional as Fn
+    Nout, P, R, S = 3, 5, 4, 2
+    dv, xv = torch.zeros(R, 4), torch.zeros(R, 8)
+    sw, sb = torch.zeros(Nout, P), (torch.zeros(Nout) if bias else None)
+    calls = []
+
+    def who(t):
+        return "sw" if t is sw else "sb" if t is sb and sb is not None else None if t is None else "new"
+
+    def wgrad(dY, ld_dy, X, ld_x, M, N, R_, b_kshift=0, kperiod=0, with_colsum=False, splitk=None):
+        assert dY is dv and X is xv and (ld_dy, ld_x, b_kshift, kperiod, splitk) == (4, 8, 0, 0, None)
+        calls.append(("wgrad", M, N, R_, bool(with_colsum)))
+        return torch.zeros(S, M * (H.round_up(N + 1, 4) if with_colsum else N)), S
+
+    def reduce_splits(part, S_, count, dst, accumulate=False):
+        calls.append(("reduce_splits", S_, count, who(dst), bool(accumulate)))
+
+    def reduce_splits_bias(part, S_, M, N, ldp, dw, db, accumulate=False):
+        calls.append(("reduce_splits_bias", S_, M, N, ldp, who(dw), who(db), bool(accumulate)))
+
+    def colsum(A, lda, M, N, out=None, accumulate=False):
+        assert A is dv and lda == 4
+        calls.append(("colsum", M, N, who(out), bool(accumulate)))
+        return out if out is not None else torch.zeros(N)
+
+    for name, fake in (("wgrad", wgrad), ("reduce_splits", reduce_splits), ("reduce_splits_bias", reduce_splits_bias),
+                       ("colsum", colsum), ("fused_colsum", lambda: calls.append(("fused_colsum",)))):
+        monkeypatch.setattr(H, name, fake)
+    got = Fn._linear_wgrads(dv, 4, xv, 8, Nout, P, R, (sw, sb) if to_sinks else None, fused, bias=bias)
+    dst_w, dst_b = ("sw", "sb") if to_sinks else ("new", "new")
+    if fused and bias:
+        want = [("wgrad", Nout, P, R, True), ("reduce_splits_bias", S, Nout, P, 8, dst_w, dst_b, to_sinks)]
+    else:
+        want = [("wgrad", Nout, P, R, False), ("reduce_splits", S, Nout * P, dst_w, to_sinks)]
+        if bias:
+            want.append(("colsum", R, Nout, "sb" if to_sinks else None, to_sinks))
+    assert calls == want
+    if to_sinks:
+        assert got == (None, None)
+        assert all(c[-1] is True for c in calls[1:])              # accumulate=True reached every reducer
+    else:
+        dw, db = got
+        assert tuple(dw.shape) == (Nout, P) and dw.dtype == torch.float32
+        assert (tuple(db.shape) == (Nout,)) if bias else db is None
+
+    def no_cuda(*a, **k):
+        raise AssertionError("torch.cuda touched with direct=False")
+    monkeypatch.setattr(torch.cuda, "current_stream", no_cuda)
+    monkeypatch.setattr(torch.cuda, "stream", no_cuda)
+    monkeypatch.setattr(H, "side_stream", no_cuda)
+    with Fn._wgrad_branch(dv.device, R, (dv, xv), False):
+        entered = True
+    assert entered
+
+
+def test_is_direct_decides_per_site():
+    """functional._is_direct: every sink present, and runtime.overlap_wgrad only for the sites that honour it"""
+    from tssep_amd import functional as Fn
+    from tssep_amd.train import runtime
+    t = torch.zeros(1)
+    for overlap in (True, False):
+        with runtime.applied(overlap_wgrad=overlap):
+            assert Fn._is_direct([t, t], True) is overlap and Fn._is_direct([t, t], False) is True
+            assert Fn._is_direct([t, None], True) is False and Fn._is_direct([t, None], False) is False

@@ -3,14 +3,13 @@
 Each Function mirrors one ATen-level operator group of the reference hot path (SURVEY.md
 section 2.2) with an explicit backward; autograd is only the glue that chains them.
 """
+import collections
+import contextlib
+
 import numpy as np
 import torch
 
 from . import hip_ops as H
-
-
-def _pad4(n):
-    return H.round_up(n, 4)
 
 
 # ---- hand-offs between neighbouring Functions of the tail --------------------------------------------------
@@ -55,224 +54,7 @@ class _Link:
         return t is not None and (bool(getattr(t, "_backward_hooks", None)) or bool(getattr(t, "retains_grad", False)))
 
 
-# ------------------------------------------------------------------------------ RNNP
-class _RNNP(torch.autograd.Function):
-    """One RNNP_packed layer (tssep/train/rnnp.py:88-96,146-168): BLSTM + Linear (+ tanh).
-
-    x: [R, ld_x] buffer view, rows (n, t) for N sequences of T frames, I valid columns.
-    Output: [R, hdim] rows (padded leading dimension), or the speaker-combined layout
-    [B, T, K*hdim] when ``combine=K`` (net.py:608-611 fused into the projection's store).
-    ``dropout_p`` > 0: the Tanh behind this layer is an ACTIVE dropout site (rnnp.py:98-100, net.py:623-625) -- the
-    projection stores plainly (act = 0) and one pass over y applies mask, 1 / (1 - p) and Tanh in place; the backward
-    regenerates the mask from the {seed, draw} pair the forward drew (hip_ops.dropout_draw)."""
-
-    @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, w_proj, b_proj,
-                N, T, act, combine, in_tanh=0, in_link=None, out_link=None, dropout_p=0.0):
-        dev = x.device
-        Hh = w_hh.shape[1]
-        I = w_ih.shape[1]
-        hdim = w_proj.shape[0]
-        xv, ld_x = H.rows_view(x)
-        R = N * T
-        assert xv.shape[0] == R and xv.shape[1] >= I, (xv.shape, R, I)
-        lstm_params = [w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r]
-        pk = H.derived("lstm_pack", lstm_params, lambda: H.lstm_pack(lstm_params, Hh, I))
-        gates = torch.empty(R, 8 * Hh, device=dev, dtype=torch.float32)
-        H.gemm(xv, ld_x, pk["wih_p"], pk["ld_i"], gates, 8 * Hh, R, 8 * Hh, I, bias=pk["bias_p"])
-        Hp = _pad4(Hh)
-        cell = torch.empty(N, T, 2, Hh, device=dev, dtype=torch.float32)
-        hout = (torch.zeros if Hp != Hh else torch.empty)(R, 2 * Hp, device=dev, dtype=torch.float32)
-        # the plan and BOTH directions' W_hh layouts are fetched here, once: the backward launches from what ctx keeps (a
-        # step captured without prepare_derived builds a layout at every ask)
-        plan = H.recurrence_plan(N, T, Hh, H.n_cus(dev))
-        whh = H.recurrence_packs(plan, w_hh, w_hh_r, Hh, pk, memo=True)
-        H.recurrence_launch(plan["fwd"], "fwd", gates, cell, hout, 2 * Hp, Hp, whh["fwd"], N, T, Hh)
-        # projection weight in the (possibly padded) [hdim, 2*Hp] column layout of hout
-        wp = H.derived("proj_layout", [w_proj], lambda: _proj_layout(w_proj, Hh, Hp))
-        drop = float(dropout_p) if dropout_p else 0.0
-        assert not drop or (act == 1 and out_link is None), "dropout_p: a site is the Tanh behind the layer, never folded"
-        store_act = 0 if drop else act
-        if combine:
-            K = combine
-            B = N // K
-            y = torch.empty(B * T, K * hdim, device=dev, dtype=torch.float32)
-            H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, 0, R, hdim, 2 * Hp, bias=b_proj.detach(), act=store_act,
-                   remap=dict(T=T, K=K, sb=T * K * hdim, sk=hdim, st=K * hdim))
-            ld_y = K * hdim
-        else:
-            y, ld_y = H.padded(R, hdim, dev, zero=True)
-            H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, ld_y, R, hdim, 2 * Hp, bias=b_proj.detach(), act=store_act)
-        used = None
-        if drop:
-            used = H.dropout_draw(dev)
-            H.dropout_tanh_fwd(y, y, R, hdim, ld_y, combine if combine else 1, T, bool(combine), drop, used)
-        ctx.drop = (drop, used)
-        ctx.save_for_backward(xv, gates, cell, hout, y, wp)
-        ctx.params = (w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, w_proj, b_proj)
-        ctx.recurrence = (plan["bwd"], whh["bwd"])
-        ctx.meta = (N, T, I, Hh, Hp, hdim, ld_x, ld_y, act, combine)
-        # Tanh-backward fold (see rnnp_layer): in_link = the link my producer hung on x, out_link = the one my
-        # consumer may answer on.  Both are decided again in backward, when it is known who else uses the tensors.
-        ctx.fold = (int(in_tanh) if in_link is not None else 0, in_link, out_link)
-        assert out_link is None or act == 1, "out_link: only behind the fused Tanh"
-        ctx.x_shape = x.shape
-        return y if combine else y[:, :hdim]
-
-    @staticmethod
-    def backward(ctx, dy):
-        xv, gates, cell, hout, y, wp = ctx.saved_tensors
-        N, T, I, Hh, Hp, hdim, ld_x, ld_y, act, combine = ctx.meta
-        dev = dy.device
-        R = N * T
-        K = combine if combine else 1
-        # d(pre-activation) of the projection, rows (n,t) x hdim, contiguous
-        in_tanh, in_link, out_link = ctx.fold
-        folded = out_link.take() if out_link is not None else None
-        if folded is not None:
-            # the consumer's d(input) GEMM already applied 1 - y^2 and wrote dense rows (n,t) x hdim; `dy` is the
-            # dummy it returned -- unless y has ANOTHER consumer (auxiliary loss): autograd then summed that
-            # consumer's plain d(y) onto the dummy's zeros, and it goes through the Tanh backward here
-            dz = folded.view(R, hdim)
-            if not _is_dummy(dy):
-                dyc = dy.contiguous() if combine else _dense_rows(dy, hdim)
-                yc = y if combine else _dense_rows(y[:, :hdim], hdim)
-                dz = dz + H.tanh_bwd(dyc, yc, R, hdim, K, T, bool(combine))
-        elif act:
-            dyc = dy.contiguous() if combine else _dense_rows(dy, hdim)
-            yc = y if combine else _dense_rows(y[:, :hdim], hdim)
-            drop, used = ctx.drop
-            if drop:
-                dz = H.dropout_tanh_bwd(dyc, yc, R, hdim, K, T, bool(combine), drop, used)
-            else:
-                dz = H.tanh_bwd(dyc, yc, R, hdim, K, T, bool(combine))
-        else:
-            if combine:   # layout change only: reuse tanh_bwd's gather with y = 0
-                dz = H.tanh_bwd(dy.contiguous(), torch.zeros_like(dy), R, hdim, K, T, True)
-            else:
-                # (a strided [R, hdim] view of a padded buffer -- what the conditioning's backward hands the pre-net --
-                # goes to the GEMMs as it is: rows_view only copies what is not 16-byte-row addressable)
-                dz = dy if dy.dim() == 2 else dy.reshape(-1, hdim)
-        dz, ld_dz = H.rows_view(dz)
-        G = 8 * Hh
-        params = ctx.params
-        sinks = [_grad_sink(p) for p in params]
-        direct = all(s_ is not None for s_ in sinks) and H.OVERLAP_WGRAD
-        main = torch.cuda.current_stream()
-        side = H.side_stream(dev, R) if direct else main
-
-        # ---- projection weight / bias gradients (side stream when direct)
-        def proj_wgrads():
-            if direct and Hp == Hh and H.fused_colsum():
-                # the bias gradient (column sums of dz) rides on the weight-gradient GEMM as a virtual ones
-                # column of hout: one pass over dz instead of two, and N = 600 -> 601 costs no extra tile
-                part, S = H.wgrad(dz, ld_dz, hout, 2 * Hp, hdim, 2 * Hp, R, with_colsum=True)
-                H.reduce_splits_bias(part, S, hdim, 2 * Hp, H.round_up(2 * Hp + 1, 4), sinks[8], sinks[9],
-                                     accumulate=True)
-                return None, None
-            part, S = H.wgrad(dz, ld_dz, hout, 2 * Hp, hdim, 2 * Hp, R)
-            if direct and Hp == Hh:
-                H.reduce_splits(part, S, hdim * 2 * Hp, sinks[8], accumulate=True)
-                H.colsum(dz, ld_dz, R, hdim, out=sinks[9], accumulate=True)
-                return None, None
-            dwp = torch.empty(hdim, 2 * Hp, device=dev, dtype=torch.float32)
-            H.reduce_splits(part, S, hdim * 2 * Hp, dwp)
-            d_w = _proj_unlayout(dwp, Hh, Hp)
-            d_b = H.colsum(dz, ld_dz, R, hdim)
-            if direct:
-                sinks[8].add_(d_w)
-                sinks[9].add_(d_b)
-                return None, None
-            return d_w, d_b
-
-        if direct:
-            side.wait_stream(main)
-            for t_ in (dz, hout):
-                t_.record_stream(side)
-            with torch.cuda.stream(side):
-                d_w_proj, d_b_proj = proj_wgrads()
-        else:
-            d_w_proj, d_b_proj = proj_wgrads()
-        # ---- critical path: dhout, BPTT (gates <- d pre-activations)
-        dhout = torch.empty(R, 2 * Hp, device=dev, dtype=torch.float32)
-        w_proj = params[8]      # (the builds read the parameters, not this step's tensors: hip_ops.prepare_derived)
-        wpT, ld_t = H.derived("proj_T", [w_proj], lambda: H.transposed(
-            H.derived("proj_layout", [w_proj], lambda: _proj_layout(w_proj, Hh, Hp)), hdim, 2 * Hp))
-        H.gemm(dz, ld_dz, wpT, ld_t, dhout, 2 * Hp, R, 2 * Hp, hdim)
-        planned, whh_bwd = ctx.recurrence
-        H.recurrence_launch(planned, "bwd", gates, cell, dhout, 2 * Hp, Hp, whh_bwd, N, T, Hh)
-
-        # ---- LSTM weight / bias gradients from dgates (side stream when direct)
-        def lstm_wgrads():
-            dwhh = torch.empty(2, 4 * Hh * Hh, device=dev, dtype=torch.float32)
-            for d in range(2):   # dgates_t paired with h_{t-1} (forward dir) / h_{t+1} (reverse)
-                part, S = H.wgrad((gates, d * 4 * Hh), G, (hout, d * Hp), 2 * Hp, 4 * Hh, Hh, R,
-                                  b_kshift=(-1 if d == 0 else 1), kperiod=T)
-                H.reduce_splits(part, S, 4 * Hh * Hh, dwhh[d])
-            # dW_ih and (split-bf16 GEMM) the bias gradient in ONE pass over dgates: a virtual ones
-            # column of x makes column I of the partials the column sums
-            fused = H.fused_colsum()
-            part, S = H.wgrad(gates, G, xv, ld_x, G, I, R, with_colsum=fused)
-            ldp = H.round_up(I + 1, 4) if fused else I
-            if fused:
-                cs, cs_ld, cs_S, cs_stride = (part, I), ldp, S, G * ldp
-            else:
-                cs, cs_ld, cs_S, cs_stride = H.colsum(gates, G, R, G), 1, 1, 0
-            if direct:
-                H.lstm_unpack(dwhh, Hh, 1, 0, Hh, Hh, sinks[1], sinks[5], accumulate=True)
-                H.lstm_unpack(part, ldp, S, G * ldp, Hh, I, sinks[0], sinks[4], accumulate=True)
-                for a_, b_ in ((2, 6), (3, 7)):      # b_ih and b_hh receive the same gradient
-                    H.lstm_unpack(cs, cs_ld, cs_S, cs_stride, Hh, 1, sinks[a_], sinks[b_], accumulate=True)
-                return (None,) * 8
-            new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)  # noqa: E731
-            d_whh, d_whh_r = new(4 * Hh, Hh), new(4 * Hh, Hh)
-            H.lstm_unpack(dwhh, Hh, 1, 0, Hh, Hh, d_whh, d_whh_r)
-            d_wih, d_wih_r = new(4 * Hh, I), new(4 * Hh, I)
-            H.lstm_unpack(part, ldp, S, G * ldp, Hh, I, d_wih, d_wih_r)
-            d_b, d_b_r = new(4 * Hh), new(4 * Hh)
-            H.lstm_unpack(cs, cs_ld, cs_S, cs_stride, Hh, 1, d_b, d_b_r)
-            return d_wih, d_whh, d_b, d_b.clone(), d_wih_r, d_whh_r, d_b_r, d_b_r.clone()
-
-        if direct:
-            side.wait_stream(main)
-            for t_ in (gates, hout, xv):
-                t_.record_stream(side)
-            with torch.cuda.stream(side):
-                lstm_grads = lstm_wgrads()
-            _notify_grads(params)                    # (10 tensors: both directions' LSTM weights + the projection)
-        else:
-            lstm_grads = lstm_wgrads()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            lstm_params = list(params[:8])
-
-            def wih_t():
-                pk_ = H.derived("lstm_pack", lstm_params, lambda: H.lstm_pack(lstm_params, Hh, I))
-                return H.transposed(pk_["wih_p"].view(G, pk_["ld_i"]), G, I)
-            wihT, ld_t = H.derived("wih_T", [params[0], params[4]], wih_t)
-            if in_tanh and not in_link.observed():
-                # my input is a Tanh output: its backward rides on this GEMM's store and the result travels on
-                # the link; x receives a dummy (its true gradient is never formed -- hence not when it is watched)
-                Kc = in_tanh
-                assert I % 4 == 0 and I % Kc == 0 and ld_x == I, (I, Kc, ld_x)
-                dxb = torch.empty(R, I, device=dev, dtype=torch.float32)
-                remap = None
-                if Kc > 1:    # rows (b,t) x (k, hdim) -> rows (b,k,t) x hdim (inverse of net.py:608-611)
-                    hd = I // Kc
-                    remap = dict(T=T, K=1, sb=Kc * T * hd, sk=0, st=hd, cm=hd, co=T * hd)
-                H.gemm(gates, G, wihT, ld_t, dxb, 0 if remap else I, R, I, G, act=2, aux=(xv, ld_x), remap=remap)
-                # (accumulated, like head_link below: the activation may feed TWO folded consumers -- ADVICE r4)
-                in_link.payload = dxb if in_link.payload is None else in_link.payload + dxb.view_as(in_link.payload)
-                dx = _dummy_grad(xv, ctx.x_shape)
-            else:
-                dxb, ld_dx = H.padded(R, I, dev, zero=True)
-                H.gemm(gates, G, wihT, ld_t, dxb, ld_dx, R, I, G)
-                dx = dxb[:, :I]
-                if tuple(ctx.x_shape) != tuple(dx.shape):
-                    dx = dx.reshape(ctx.x_shape)
-        return (dx, *lstm_grads, d_w_proj, d_b_proj, None, None, None, None, None, None, None, None)
-
-
+# --------------------------------------------------- weight gradients of y = x W^T + b: one emitter, one fork
 def _notify_grads(params):
     """The gradients of `params` are queued completely (directly into the flat bucket): a bucket with per-layer
     segments may all-reduce the layer now (distributed.GradBucket.notify; a no-op unless armed)."""
@@ -291,25 +73,260 @@ def _grad_sink(p):
     return sinks[H.ACTIVE_SINK % len(sinks)]
 
 
-def _dense_rows(t, cols):
-    t = t if t.dim() == 2 else t.reshape(-1, cols)
-    return t.contiguous()
+def _is_direct(sinks, honours_overlap_wgrad):
+    """Whether a layer accumulates its weight gradients straight into the flat bucket: every parameter offers a sink,
+    and -- for a layer that honours the switch -- runtime.overlap_wgrad is on."""
+    return all(s is not None for s in sinks) and bool(H.OVERLAP_WGRAD or not honours_overlap_wgrad)
 
 
-def _proj_layout(w_proj, Hh, Hp):
-    w = w_proj.detach()
-    if Hp == Hh and w.is_contiguous() and w.data_ptr() % 16 == 0:
-        return w
-    out = torch.zeros(w.shape[0], 2 * Hp, device=w.device, dtype=torch.float32)
-    out[:, :Hh] = w[:, :Hh]
-    out[:, Hp:Hp + Hh] = w[:, Hh:]
-    return out
+@contextlib.contextmanager
+def _wgrad_branch(dev, R, reads, direct):
+    """direct: the body runs on the weight-gradient stream of the current stream (H.side_stream: the compute stream itself
+    for layers past SIDE_STREAM_MAX_SEQS), which first waits for the compute stream; `reads` are the tensors the body reads.
+    Not direct: the body runs where it stands, and nothing of torch.cuda is touched."""
+    if direct:
+        main, side = torch.cuda.current_stream(), H.side_stream(dev, R)
+        side.wait_stream(main)
+        for t in reads:
+            t.record_stream(side)
+    with torch.cuda.stream(side) if direct else contextlib.nullcontext():
+        yield
+
+
+def _linear_wgrads(dv, ld_d, xv, ld_x, Nout, P, R, sinks, fused, bias=True):
+    """dW [Nout, P] = dv^T xv and db [Nout] = the column sums of dv, for y = x W^T + b over R rows: the one place that
+    issues this work.  sinks = (sw, sb): accumulated there, -> (None, None); sinks = None: -> (dw, db) in new tensors.
+    fused: db rides on the weight-gradient GEMM as a virtual ones column of xv -- one pass over dv instead of two, and
+    N = 600 -> 601 costs no extra tile (H.fused_colsum() says whether the GEMM arithmetic has it).  bias=False: a layer
+    without bias (sb is None; db comes back None)."""
+    acc = sinks is not None
+    fused = fused and bias
+    part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R, with_colsum=fused)
+    new = lambda *shape: torch.empty(*shape, device=dv.device, dtype=torch.float32)  # noqa: E731
+    dw, db = sinks if acc else (new(Nout, P), new(Nout) if fused else None)
+    if fused:
+        H.reduce_splits_bias(part, S, Nout, P, H.round_up(P + 1, 4), dw, db, accumulate=acc)
+    else:
+        H.reduce_splits(part, S, Nout * P, dw, accumulate=acc)
+        if bias:
+            db = H.colsum(dv, ld_d, R, Nout, out=db, accumulate=acc)
+    return (None, None) if acc else (dw, db)
+
+
+# ---- derived weight layouts: ONE builder per tag (hip_ops.derived keeps the first it sees and prepare_derived replays it;
+# a build reads the parameters, never a step's tensors)
+def _lstm_pack_of(lstm_params, Hh, I):
+    lstm_params = list(lstm_params)
+    return H.derived("lstm_pack", lstm_params, lambda: H.lstm_pack(lstm_params, Hh, I))
+
+
+def _proj_layout_of(w_proj, Hh, Hp):
+    """projection weight in the (possibly padded) [hdim, 2*Hp] column layout of hout"""
+    def build():
+        w = w_proj.detach()
+        if Hp == Hh and w.is_contiguous() and w.data_ptr() % 16 == 0:
+            return w
+        out = torch.zeros(w.shape[0], 2 * Hp, device=w.device, dtype=torch.float32)
+        out[:, :Hh] = w[:, :Hh]
+        out[:, Hp:Hp + Hh] = w[:, Hh:]
+        return out
+    return H.derived("proj_layout", [w_proj], build)
+
+
+def _proj_T_of(w_proj, Hh, Hp):
+    return H.derived("proj_T", [w_proj], lambda: H.transposed(_proj_layout_of(w_proj, Hh, Hp), w_proj.shape[0], 2 * Hp))
+
+
+def _wih_T_of(lstm_params, Hh, I):
+    def build():
+        pk = _lstm_pack_of(lstm_params, Hh, I)
+        return H.transposed(pk["wih_p"].view(8 * Hh, pk["ld_i"]), 8 * Hh, I)
+    return H.derived("wih_T", [lstm_params[0], lstm_params[4]], build)
+
+
+# ------------------------------------------------------------------------------ RNNP
+_RNNPMeta = collections.namedtuple("_RNNPMeta", "N T I Hh Hp hdim ld_x ld_y act combine")
+
+
+class _RNNP(torch.autograd.Function):
+    """One RNNP_packed layer (tssep/train/rnnp.py:88-96,146-168): BLSTM + Linear (+ tanh).
+
+    x: [R, ld_x] buffer view, rows (n, t) for N sequences of T frames, I valid columns.
+    Output: [R, hdim] rows (padded leading dimension), or the speaker-combined layout
+    [B, T, K*hdim] when ``combine=K`` (net.py:608-611 fused into the projection's store).
+    ``dropout_p`` > 0: the Tanh behind this layer is an ACTIVE dropout site (rnnp.py:98-100, net.py:623-625) -- the
+    projection stores plainly (act = 0) and one pass over y applies mask, 1 / (1 - p) and Tanh in place; the backward
+    regenerates the mask from the {seed, draw} pair the forward drew (hip_ops.dropout_draw)."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, w_proj, b_proj,
+                N, T, act, combine, in_tanh=0, in_link=None, out_link=None, dropout_p=0.0):
+        dev = x.device
+        Hh, I, hdim = w_hh.shape[1], w_ih.shape[1], w_proj.shape[0]
+        xv, ld_x = H.rows_view(x)
+        R = N * T
+        assert xv.shape[0] == R and xv.shape[1] >= I, (xv.shape, R, I)
+        pk = _lstm_pack_of([w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r], Hh, I)
+        gates = torch.empty(R, 8 * Hh, device=dev, dtype=torch.float32)
+        H.gemm(xv, ld_x, pk["wih_p"], pk["ld_i"], gates, 8 * Hh, R, 8 * Hh, I, bias=pk["bias_p"])
+        Hp = H.round_up(Hh, 4)
+        cell = torch.empty(N, T, 2, Hh, device=dev, dtype=torch.float32)
+        hout = (torch.zeros if Hp != Hh else torch.empty)(R, 2 * Hp, device=dev, dtype=torch.float32)
+        # the plan and BOTH directions' W_hh layouts are fetched here, once: the backward launches from what ctx keeps (a
+        # step captured without prepare_derived builds a layout at every ask)
+        plan = H.recurrence_plan(N, T, Hh, H.n_cus(dev))
+        whh = H.recurrence_packs(plan, w_hh, w_hh_r, Hh, pk, memo=True)
+        H.recurrence_launch(plan["fwd"], "fwd", gates, cell, hout, 2 * Hp, Hp, whh["fwd"], N, T, Hh)
+        wp = _proj_layout_of(w_proj, Hh, Hp)
+        drop = float(dropout_p) if dropout_p else 0.0
+        assert not drop or (act == 1 and out_link is None), "dropout_p: a site is the Tanh behind the layer, never folded"
+        store_act = 0 if drop else act
+        if combine:
+            K = combine
+            y = torch.empty(N // K * T, K * hdim, device=dev, dtype=torch.float32)
+            H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, 0, R, hdim, 2 * Hp, bias=b_proj.detach(), act=store_act,
+                   remap=dict(T=T, K=K, sb=T * K * hdim, sk=hdim, st=K * hdim))
+            ld_y = K * hdim
+        else:
+            y, ld_y = H.padded(R, hdim, dev, zero=True)
+            H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, ld_y, R, hdim, 2 * Hp, bias=b_proj.detach(), act=store_act)
+        used = None
+        if drop:
+            used = H.dropout_draw(dev)
+            H.dropout_tanh_fwd(y, y, R, hdim, ld_y, combine if combine else 1, T, bool(combine), drop, used)
+        ctx.drop = (drop, used)
+        ctx.save_for_backward(xv, gates, cell, hout, y, wp)
+        ctx.params = (w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, w_proj, b_proj)
+        ctx.recurrence = (plan["bwd"], whh["bwd"])
+        ctx.meta = _RNNPMeta(N, T, I, Hh, Hp, hdim, ld_x, ld_y, act, combine)
+        # Tanh-backward fold (see rnnp_layer): in_link = the link my producer hung on x, out_link = the one my
+        # consumer may answer on.  Both are decided again in backward, when it is known who else uses the tensors.
+        ctx.fold = (int(in_tanh) if in_link is not None else 0, in_link, out_link)
+        assert out_link is None or act == 1, "out_link: only behind the fused Tanh"
+        ctx.x_shape = x.shape
+        return y if combine else y[:, :hdim]
+
+    @staticmethod
+    def backward(ctx, dy):
+        xv, gates, cell, hout, y, _ = ctx.saved_tensors
+        m, params = ctx.meta, ctx.params
+        in_tanh, in_link, out_link = ctx.fold
+        dz, ld_dz = H.rows_view(_rnnp_dz(dy, y, m, ctx.drop, out_link.take() if out_link is not None else None))
+        sinks = [_grad_sink(p) for p in params]
+        direct = _is_direct(sinks, True)
+        d_w_proj, d_b_proj = _rnnp_proj_wgrads(dz, ld_dz, hout, m, sinks[8:], direct)
+        _rnnp_bptt(dz, ld_dz, gates, cell, params[8], m, ctx.recurrence)      # the critical path: gates <- d(pre-activations)
+        lstm_grads = _rnnp_lstm_wgrads(gates, hout, xv, m, sinks[:8], direct)
+        if direct:
+            _notify_grads(params)                    # (10 tensors: both directions' LSTM weights + the projection)
+        dx = _rnnp_dx(gates, xv, params[:8], m, ctx.x_shape, in_link, in_tanh) if ctx.needs_input_grad[0] else None
+        return (dx, *lstm_grads, d_w_proj, d_b_proj) + (None,) * 8
+
+
+def _rnnp_dz(dy, y, m, drop, folded):
+    """stage 1 -> d(pre-activation) of the projection, rows (n,t) x hdim.  folded: what the consumer left on the link."""
+    R, hdim, T, K, combined = m.N * m.T, m.hdim, m.T, m.combine or 1, bool(m.combine)
+
+    def tanh_args():      # (d(y), y) as the Tanh backward kernels read them -- combined as they are, dense rows otherwise -- + geometry
+        pair = (dy.contiguous(), y) if combined else (dy.reshape(-1, hdim).contiguous(), y[:, :hdim].contiguous())
+        return (*pair, R, hdim, K, T, combined)
+    if folded is not None:
+        # the consumer's d(input) GEMM already applied 1 - y^2 and wrote dense rows (n,t) x hdim; `dy` is the
+        # dummy it returned -- unless y has ANOTHER consumer (auxiliary loss): autograd then summed that
+        # consumer's plain d(y) onto the dummy's zeros, and it goes through the Tanh backward here
+        dz = folded.view(R, hdim)
+        if not _is_dummy(dy):
+            dz = dz + H.tanh_bwd(*tanh_args())
+        return dz
+    if m.act:
+        p, used = drop
+        return H.dropout_tanh_bwd(*tanh_args(), p, used) if p else H.tanh_bwd(*tanh_args())
+    if combined:   # layout change only: reuse tanh_bwd's gather with y = 0
+        return H.tanh_bwd(dy.contiguous(), torch.zeros_like(dy), R, hdim, K, T, True)
+    # (a strided [R, hdim] view of a padded buffer -- what the conditioning's backward hands the pre-net --
+    # goes to the GEMMs as it is: rows_view only copies what is not 16-byte-row addressable)
+    return dy if dy.dim() == 2 else dy.reshape(-1, hdim)
+
+
+def _rnnp_proj_wgrads(dz, ld_dz, hout, m, sinks, direct):
+    """stage 2 -> (d_w_proj, d_b_proj), or (None, None) when they went into `sinks` (side stream)"""
+    R, Hh, Hp = m.N * m.T, m.Hh, m.Hp
+    aligned = Hp == Hh           # hout's column layout is w_proj's: the emitter writes the sinks itself, fused where it can
+    with _wgrad_branch(dz.device, R, (dz, hout), direct):
+        to_sinks = direct and aligned
+        d_w, d_b = _linear_wgrads(dz, ld_dz, hout, 2 * Hp, m.hdim, 2 * Hp, R, sinks if to_sinks else None,
+                                  to_sinks and H.fused_colsum())
+        if not aligned:
+            d_w = _proj_unlayout(d_w, Hh, Hp)
+            if direct:
+                sinks[0].add_(d_w)
+                sinks[1].add_(d_b)
+                d_w = d_b = None
+    return d_w, d_b
+
+
+def _rnnp_bptt(dz, ld_dz, gates, cell, w_proj, m, recurrence):
+    """stage 3: dhout = dz W_proj, then the recurrence backwards in time: `gates` <- d(pre-activations)"""
+    R, Hp = m.N * m.T, m.Hp
+    dhout = torch.empty(R, 2 * Hp, device=dz.device, dtype=torch.float32)
+    wpT, ld_t = _proj_T_of(w_proj, m.Hh, Hp)
+    H.gemm(dz, ld_dz, wpT, ld_t, dhout, 2 * Hp, R, 2 * Hp, m.hdim)
+    H.recurrence_launch(recurrence[0], "bwd", gates, cell, dhout, 2 * Hp, Hp, recurrence[1], m.N, m.T, m.Hh)
+
+
+def _rnnp_lstm_wgrads(gates, hout, xv, m, sinks, direct):
+    """stage 4 -> the eight LSTM gradients in parameter order from dgates (in `gates`), or eight None when they went into
+    `sinks` (side stream)"""
+    R, T, I, Hh, Hp, G = m.N * m.T, m.T, m.I, m.Hh, m.Hp, 8 * m.Hh
+    with _wgrad_branch(gates.device, R, (gates, hout, xv), direct):
+        dwhh = torch.empty(2, 4 * Hh * Hh, device=gates.device, dtype=torch.float32)
+        for d in range(2):   # dgates_t paired with h_{t-1} (forward dir) / h_{t+1} (reverse)
+            part, S = H.wgrad((gates, d * 4 * Hh), G, (hout, d * Hp), 2 * Hp, 4 * Hh, Hh, R,
+                              b_kshift=(-1 if d == 0 else 1), kperiod=T)
+            H.reduce_splits(part, S, 4 * Hh * Hh, dwhh[d])
+        # dW_ih and (split-bf16 GEMM) the bias gradient in ONE pass over dgates: a virtual ones
+        # column of x makes column I of the partials the column sums
+        fused = H.fused_colsum()
+        part, S = H.wgrad(gates, G, xv, m.ld_x, G, I, R, with_colsum=fused)
+        ldp = H.round_up(I + 1, 4) if fused else I
+        bias_src = ((part, I), ldp, S, G * ldp) if fused else (H.colsum(gates, G, R, G), 1, 1, 0)
+        # (source, columns, index of the forward direction's destination: the reverse one's is 4 further)
+        unpacks = [((dwhh, Hh, 1, 0), Hh, 1), ((part, ldp, S, G * ldp), I, 0), (bias_src, 1, 2)]
+        if direct:
+            dst = sinks
+            unpacks.append((bias_src, 1, 3))      # b_ih and b_hh receive the same gradient
+        else:
+            new = lambda *shape: torch.empty(*shape, device=gates.device, dtype=torch.float32)  # noqa: E731
+            dst = [new(4 * Hh, I), new(4 * Hh, Hh), new(4 * Hh), None, new(4 * Hh, I), new(4 * Hh, Hh), new(4 * Hh), None]
+        for src, ncols, i in unpacks:
+            H.lstm_unpack(*src, Hh, ncols, dst[i], dst[i + 4], accumulate=direct)
+    if direct:
+        return (None,) * 8
+    dst[3], dst[7] = dst[2].clone(), dst[6].clone()
+    return tuple(dst)
+
+
+def _rnnp_dx(gates, xv, lstm_params, m, x_shape, in_link, Kc):
+    """stage 5 -> d(input).  Kc > 0: my input is a Tanh output whose backward rides on this GEMM's store; the result
+    travels on in_link and x receives a dummy (its true gradient is never formed -- hence not when it is watched)"""
+    R, T, I, G, dev = m.N * m.T, m.T, m.I, 8 * m.Hh, gates.device
+    wihT, ld_t = _wih_T_of(lstm_params, m.Hh, I)
+    if not Kc or in_link.observed():
+        dxb, ld_dx = H.padded(R, I, dev, zero=True)
+        H.gemm(gates, G, wihT, ld_t, dxb, ld_dx, R, I, G)
+        return dxb[:, :I].reshape(x_shape)
+    assert I % 4 == 0 and I % Kc == 0 and m.ld_x == I, (I, Kc, m.ld_x)
+    dxb = torch.empty(R, I, device=dev, dtype=torch.float32)
+    hd = I // Kc      # Kc > 1: rows (b,t) x (k, hdim) -> rows (b,k,t) x hdim (inverse of net.py:608-611)
+    remap = dict(T=T, K=1, sb=Kc * T * hd, sk=0, st=hd, cm=hd, co=T * hd) if Kc > 1 else None
+    H.gemm(gates, G, wihT, ld_t, dxb, 0 if remap else I, R, I, G, act=2, aux=(xv, m.ld_x), remap=remap)
+    # (accumulated, like head_link below: the activation may feed TWO folded consumers -- ADVICE r4)
+    in_link.payload = dxb if in_link.payload is None else in_link.payload + dxb.view_as(in_link.payload)
+    return _dummy_grad(xv, x_shape)
 
 
 def _proj_unlayout(dwp, Hh, Hp):
-    if Hp == Hh:
-        return dwp
-    return torch.cat([dwp[:, :Hh], dwp[:, Hp:Hp + Hh]], dim=1).contiguous()
+    return dwp if Hp == Hh else torch.cat([dwp[:, :Hh], dwp[:, Hp:Hp + Hh]], dim=1).contiguous()
 
 
 def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=False, dropout_p=0.0):
@@ -377,44 +394,28 @@ def condition(pre, aux, B, K, T, trials, combination):
 
 
 # ------------------------------------------------------------------------ final linear
+# geo: what the map kernels take behind (perm, iperm) -- (B, trials, K, [M,] T, F, Fr, spk_rows)
+_HeadMeta = collections.namedtuple("_HeadMeta", "geo ld_x P R Nout")
+
+
 def _head_grads(ctx, draw):
     """d(raw) [R, Nout] of the final Linear -> (dx, dw, db): the weight gradient and the bias column sums (straight into
     the optimizer's bucket on the side stream where that is set up: dw = db = None then) and the d(input) GEMM.  Shared
-    by _Head and _HeadMasks; ctx carries saved_tensors (xv, wv), params, meta and x_shape."""
-    xv, wv = ctx.saved_tensors[:2]
-    ld_x, ld_w, P, R, Nout = ctx.meta[-5:]
-    dev = draw.device
+    by _Head and _HeadMasks; ctx carries saved_tensors (xv, ...), params, meta (_HeadMeta) and x_shape."""
+    xv, m = ctx.saved_tensors[0], ctx.meta
+    weight, bias = ctx.params
     dv, ld_d = H.rows_view(draw)
-    sw, sb = _grad_sink(ctx.params[0]), _grad_sink(ctx.params[1])
-    direct = sw is not None and sb is not None and H.OVERLAP_WGRAD
+    sinks = (_grad_sink(weight), _grad_sink(bias))
+    direct = _is_direct(sinks, True)
+    with _wgrad_branch(draw.device, m.R, (dv, xv), direct):
+        dw, db = _linear_wgrads(dv, ld_d, xv, m.ld_x, m.Nout, m.P, m.R, sinks if direct else None,
+                                direct and H.fused_colsum())
     if direct:
-        main, side = torch.cuda.current_stream(), H.side_stream(dev, R)
-        side.wait_stream(main)
-        for t_ in (dv, xv):
-            t_.record_stream(side)
-        with torch.cuda.stream(side):
-            if H.fused_colsum():
-                part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R, with_colsum=True)
-                H.reduce_splits_bias(part, S, Nout, P, H.round_up(P + 1, 4), sw, sb, accumulate=True)
-            else:
-                part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R)
-                H.reduce_splits(part, S, Nout * P, sw, accumulate=True)
-                H.colsum(dv, ld_d, R, Nout, out=sb, accumulate=True)
-        dw = db = None
         _notify_grads(ctx.params)
-    else:
-        part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R)
-        dw = torch.empty(Nout, P, device=dev, dtype=torch.float32)
-        H.reduce_splits(part, S, Nout * P, dw)
-        db = H.colsum(dv, ld_d, R, Nout)
-    dxb, ld_dx = H.padded(R, P, dev, zero=True)
-    weight = ctx.params[0]
-    wvT, ld_t = H.derived("head_T", [weight], lambda: H.transposed(H.rows_view(weight.detach())[0], Nout, P))
-    H.gemm(dv, ld_d, wvT, ld_t, dxb, ld_dx, R, P, Nout)
-    dx = dxb[:, :P]
-    if tuple(ctx.x_shape) != tuple(dx.shape):
-        dx = dx.reshape(ctx.x_shape)
-    return dx, dw, db
+    dxb, ld_dx = H.padded(m.R, m.P, draw.device, zero=True)
+    wvT, ld_t = H.derived("head_T", [weight], lambda: H.transposed(H.rows_view(weight.detach())[0], m.Nout, m.P))
+    H.gemm(dv, ld_d, wvT, ld_t, dxb, ld_dx, m.R, m.P, m.Nout)
+    return dxb[:, :m.P].reshape(ctx.x_shape), dw, db
 
 
 class _Head(torch.autograd.Function):
@@ -443,19 +444,18 @@ class _Head(torch.autograd.Function):
         ctx.save_for_backward(xv, wv)
         ctx.params = (weight, bias)
         ctx.aux = (perm, iperm)
-        ctx.meta = (B, K, T, F, trials, Fr, spk_rows, ld_x, ld_w, P, R, Nout)
+        ctx.meta = _HeadMeta((B, trials, K, T, F, Fr, spk_rows), ld_x, P, R, Nout)
         ctx.x_shape = x.shape
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        perm, iperm = ctx.aux
-        B, K, T, F, trials, Fr, spk_rows, _, _, _, R, Nout = ctx.meta
+        m = ctx.meta
         draw = ctx.link.take() if ctx.link is not None else None
         if draw is None:
-            draw = H.logit_map_bwd(dout, perm, iperm, B, trials, K, T, F, Fr, spk_rows).view(R, Nout)
+            draw = H.logit_map_bwd(dout, *ctx.aux, *m.geo).view(m.R, m.Nout)
         elif not _is_dummy(dout):      # the fused tail wrote its part already laid out; someone else used logit too
-            draw = draw + H.logit_map_bwd(dout, perm, iperm, B, trials, K, T, F, Fr, spk_rows).view(R, Nout)
+            draw = draw + H.logit_map_bwd(dout, *ctx.aux, *m.geo).view(m.R, m.Nout)
         dx, dw, db = _head_grads(ctx, draw)
         return dx, dw, db, None, None, None, None, None, None, None, None, None, None
 
@@ -479,19 +479,17 @@ class _HeadMasks(torch.autograd.Function):
         ctx.save_for_backward(xv, wv, mask)
         ctx.params = (weight, bias)
         ctx.aux = (perm, iperm)
-        ctx.meta = (B, K, M, T, F, trials, Fr, spk_rows, ld_x, ld_w, P, R, Nout)
+        ctx.meta = _HeadMeta((B, trials, K, M, T, F, Fr, spk_rows), ld_x, P, R, Nout)
         ctx.x_shape = x.shape
         ctx.set_materialize_grads(False)          # d(logit) is None when nobody else used the logit
         return logit, mask
 
     @staticmethod
     def backward(ctx, dlogit, dmask):
-        perm, iperm = ctx.aux
-        B, K, M, T, F, trials, Fr, spk_rows, _, _, _, R, Nout = ctx.meta
-        mask = ctx.saved_tensors[2]
+        m, mask = ctx.meta, ctx.saved_tensors[2]
         if dmask is None:                         # only the logit was used: the same kernel with d(mask) = 0
             dmask = torch.zeros_like(mask)
-        draw = H.mask_map_bwd(dmask, mask, dlogit, perm, iperm, B, trials, K, M, T, F, Fr, spk_rows).view(R, Nout)
+        draw = H.mask_map_bwd(dmask, mask, dlogit, *ctx.aux, *m.geo).view(m.R, m.Nout)
         dx, dw, db = _head_grads(ctx, draw)
         return (dx, dw, db) + (None,) * 10
 
@@ -871,25 +869,21 @@ def instance_norm(x, axis, mode, unbiased=False):
 
 
 def _affine_wgrads(dv, ld_d, xv, ld_x, R, weight, bias):
-    """dW = dv^T xv and db = column sums of dv for y = x W^T + b: straight into the flat gradient bucket when the
-    parameters live there (-> None, None), through autograd otherwise."""
+    """dW and db of one affine layer (bias may be None): straight into the flat gradient bucket when the parameters live
+    there (-> None, None), through autograd otherwise."""
     Nout, P = weight.shape
-    sw = _grad_sink(weight)
-    sb = _grad_sink(bias) if bias is not None else None
-    direct = sw is not None and (bias is None or sb is not None)
-    part, S = H.wgrad(dv, ld_d, xv, ld_x, Nout, P, R)
+    params = [weight] if bias is None else [weight, bias]
+    sinks = [_grad_sink(p) for p in params]
+    # honours_overlap_wgrad=False, fused=False, no fork: what these layers launch today; changing it is another PR
+    direct = _is_direct(sinks, False)
+    grads = _linear_wgrads(dv, ld_d, xv, ld_x, Nout, P, R, (sinks + [None])[:2] if direct else None, False,
+                           bias=bias is not None)
     if direct:
-        H.reduce_splits(part, S, Nout * P, sw, accumulate=True)
-        if bias is not None:
-            H.colsum(dv, ld_d, R, Nout, out=sb, accumulate=True)
-        _notify_grads([weight] + ([bias] if bias is not None else []))
-        return None, None
-    dw = torch.empty(Nout, P, device=dv.device, dtype=torch.float32)
-    H.reduce_splits(part, S, Nout * P, dw)
-    return dw, (H.colsum(dv, ld_d, R, Nout) if bias is not None else None)
+        _notify_grads(params)
+    return grads
 
 
-def _affine_fwd(xv, ld_x, R, weight, bias, out=None):
+def _affine_fwd(xv, ld_x, R, weight, bias):
     """-> (y, ld_y): rows of x W^T + b in a padded buffer."""
     Nout, P = weight.shape
     wv, ld_w = H.rows_view(weight.detach())
@@ -907,6 +901,10 @@ def _affine_dgrad(dv, ld_d, R, weight):
     return dx, ld_dx
 
 
+_AffineMeta = collections.namedtuple("_AffineMeta", "R ld_x x_shape")
+_AuxMLPMeta = collections.namedtuple("_AuxMLPMeta", "N S C ld_x ld1 ld2 ldm")
+
+
 class _Affine(torch.autograd.Function):
     """net.Linear (net.py:19-43): y = x W^T + b over the rows of x [..., idim]."""
 
@@ -917,20 +915,20 @@ class _Affine(torch.autograd.Function):
         y, ld_y = _affine_fwd(xv, ld_x, R, weight, bias)
         ctx.save_for_backward(xv)
         ctx.params = (weight, bias)
-        ctx.meta = (R, ld_x, tuple(x.shape))
+        ctx.meta = _AffineMeta(R, ld_x, tuple(x.shape))
         return y[:, :weight.shape[0]].reshape(*x.shape[:-1], weight.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
         (xv,) = ctx.saved_tensors
         weight, bias = ctx.params
-        R, ld_x, x_shape = ctx.meta
+        m = ctx.meta
         dv, ld_d = H.rows_view(dy)
-        dw, db = _affine_wgrads(dv, ld_d, xv, ld_x, R, weight, bias)
+        dw, db = _affine_wgrads(dv, ld_d, xv, m.ld_x, m.R, weight, bias)
         dx = None
         if ctx.needs_input_grad[0]:
-            dxb, _ = _affine_dgrad(dv, ld_d, R, weight)
-            dx = dxb[:, :weight.shape[1]].reshape(x_shape)
+            dxb, _ = _affine_dgrad(dv, ld_d, m.R, weight)
+            dx = dxb[:, :weight.shape[1]].reshape(m.x_shape)
         return dx, dw, db
 
 
@@ -955,22 +953,22 @@ class _AuxMLP(torch.autograd.Function):
         y, ld_y = _affine_fwd(m, ldm, S, w3, b3)
         ctx.save_for_backward(xv, h1, z2, m, row0)
         ctx.params = (w1, b1, w2, b2, w3, b3)
-        ctx.meta = (N, S, C, ld_x, ld1, ld2, ldm)
+        ctx.meta = _AuxMLPMeta(N, S, C, ld_x, ld1, ld2, ldm)
         return y[:, :w3.shape[0]]
 
     @staticmethod
     def backward(ctx, dy):
         xv, h1, z2, m, row0 = ctx.saved_tensors
         w1, b1, w2, b2, w3, b3 = ctx.params
-        N, S, C, ld_x, ld1, ld2, ldm = ctx.meta
+        g = ctx.meta
         dv, ld_d = H.rows_view(dy)
-        dw3, db3 = _affine_wgrads(dv, ld_d, m, ldm, S, w3, b3)
-        dm, ld_dm = _affine_dgrad(dv, ld_d, S, w3)
-        dz2, ld_dz2 = H.segment_mean_bwd(dm, ld_dm, z2, ld2, row0, S, N, C, relu=True)
-        dw2, db2 = _affine_wgrads(dz2, ld_dz2, h1, ld1, N, w2, b2)
-        dh1, ld_dh1 = _affine_dgrad(dz2, ld_dz2, N, w2)
-        dz1, ld_dz1 = H.relu_bwd(dh1, ld_dh1, h1, ld1, N, C)
-        dw1, db1 = _affine_wgrads(dz1, ld_dz1, xv, ld_x, N, w1, b1)
+        dw3, db3 = _affine_wgrads(dv, ld_d, m, g.ldm, g.S, w3, b3)
+        dm, ld_dm = _affine_dgrad(dv, ld_d, g.S, w3)
+        dz2, ld_dz2 = H.segment_mean_bwd(dm, ld_dm, z2, g.ld2, row0, g.S, g.N, g.C, relu=True)
+        dw2, db2 = _affine_wgrads(dz2, ld_dz2, h1, g.ld1, g.N, w2, b2)
+        dh1, ld_dh1 = _affine_dgrad(dz2, ld_dz2, g.N, w2)
+        dz1, ld_dz1 = H.relu_bwd(dh1, ld_dh1, h1, g.ld1, g.N, g.C)
+        dw1, db1 = _affine_wgrads(dz1, ld_dz1, xv, g.ld_x, g.N, w1, b1)
         return None, None, None, dw1, db1, dw2, db2, dw3, db3
 
 

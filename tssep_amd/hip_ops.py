@@ -53,11 +53,22 @@ def kernel_time_summary():
     return {k: (len(v), sum(s.elapsed_time(e) for s, e in v)) for k, v in KERNEL_TIMERS.items()}
 
 
-def _p(t):
-    """Device pointer of a tensor, or of (tensor, float_offset)."""
+def _addr(t):
+    """Device address of a tensor, or of (tensor, float_offset); None stays None."""
     if isinstance(t, tuple):
-        return ctypes.c_void_p(t[0].data_ptr() + 4 * t[1])
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        return t[0].data_ptr() + 4 * t[1]
+    return t.data_ptr() if t is not None else None
+
+
+def _p(t):
+    """`_addr` as the pointer argument of a C entry point."""
+    a = _addr(t)
+    return ctypes.c_void_p(a) if a is not None else None
+
+
+def _device_of(t):
+    """Device of a tensor, or of (tensor, float_offset)."""
+    return (t[0] if isinstance(t, tuple) else t).device
 
 
 def _stream():
@@ -307,17 +318,13 @@ _PREC = {"f32": 0, "bf16x3": 1, "bf16": 3}      # "bf16": the plain-bf16 side li
 def _gemm_args(A, lda, B, ldb, C, ldc, M, N, K, a_kmajor=False, b_kmajor=False, bias=None, act=0,
                accumulate=False, b_kshift=0, kperiod=0, remap=None, splitk=1, split_stride=0,
                b_ones_col=False, aux=None):
-    def ptr(x):
-        if isinstance(x, tuple):
-            return x[0].data_ptr() + 4 * x[1]
-        return x.data_ptr()
     g = GemmArgs()
-    g.A, g.B, g.C = ptr(A), ptr(B), ptr(C)
+    g.A, g.B, g.C = _addr(A), _addr(B), _addr(C)
     g.M, g.N, g.K = M, N, K
     g.lda, g.ldb, g.ldc = lda, ldb, ldc
     g.a_kmajor, g.b_kmajor = int(a_kmajor), int(b_kmajor)
     g.b_kshift, g.kperiod = b_kshift, kperiod
-    g.bias = bias.data_ptr() if bias is not None else None
+    g.bias = _addr(bias)
     g.act, g.accumulate = act, int(accumulate)
     if remap is not None:
         g.c_remap = 2 if remap.get("narrow") else 1      # (2: the 4-byte-per-lane store, the reference of the tests)
@@ -325,14 +332,14 @@ def _gemm_args(A, lda, B, ldb, C, ldc, M, N, K, a_kmajor=False, b_kmajor=False, 
         g.c_sb, g.c_sk, g.c_st = remap["sb"], remap.get("sk", 0), remap["st"]
         g.c_cm, g.c_co = remap.get("cm", 0), remap.get("co", 0)
         perm = remap.get("perm")
-        g.c_perm = perm.data_ptr() if perm is not None else None
+        g.c_perm = _addr(perm)
         g.c_perm_ld = remap.get("perm_ld", 0)
     g.splitk, g.c_split_stride = splitk, split_stride
     g.precision = _PREC[GEMM_PRECISION]
     g.b_ones_col = int(b_ones_col)
     if act == 2:        # tanh backward folded into the store: aux = (tensor, ld) of the tanh OUTPUT, indexed like C
         assert aux is not None and splitk <= 1
-        g.aux, g.ldaux = ptr(aux[0]), aux[1]
+        g.aux, g.ldaux = _addr(aux[0]), aux[1]
     return g
 
 
@@ -418,6 +425,14 @@ def transposed(w, rows, cols):
     return out, ld
 
 
+def _wgrad_splits(g):
+    """The split count the library recommends for the weight-gradient request `g` (it follows the kernel it picks)."""
+    S = int(_lib.lib().tssep_gemm_wgrad_splits(ctypes.byref(g)))
+    if S < 1:
+        check(S, "gemm_wgrad_splits")
+    return S
+
+
 def pick_splitk(M, N, K, shifted=False, ones_col=False):
     """Split count the library recommends for the weight gradient dW[M,N] = dY[K,M]^T X[K,N] (host-only query on
     a description of the request: tools and tests; `wgrad` asks with the real arguments)."""
@@ -430,10 +445,7 @@ def pick_splitk(M, N, K, shifted=False, ones_col=False):
         g.b_kshift, g.kperiod = -1, 253
     g.b_ones_col = int(ones_col)
     g.precision = _PREC[GEMM_PRECISION]
-    S = int(_lib.lib().tssep_gemm_wgrad_splits(ctypes.byref(g)))
-    if S < 1:
-        check(S, "gemm_wgrad_splits")
-    return S
+    return _wgrad_splits(g)
 
 
 # Opt-in arithmetic of the weight gradients (bench.py's `two_product_wgrad` side line): 2 = the dY_lo * X_hi product is
@@ -452,13 +464,8 @@ def wgrad(dY, ld_dy, X, ld_x, M, N, R, b_kshift=0, kperiod=0, with_colsum=False,
                    kperiod=kperiod, splitk=8, split_stride=M * ldp, b_ones_col=with_colsum)
     if (WGRAD_PRODUCTS == 2 and GEMM_PRECISION == "bf16x3") or GEMM_PRECISION == "bf16":
         g.precision = 2      # (the plain-bf16 side line: dY as plain bf16 in the weight gradients, X keeps hi + lo)
-    S = splitk
-    if not S:
-        S = int(_lib.lib().tssep_gemm_wgrad_splits(ctypes.byref(g)))
-        if S < 1:
-            check(S, "gemm_wgrad_splits")
-    dev = dY[0].device if isinstance(dY, tuple) else dY.device
-    part = torch.empty(S, M * ldp, device=dev, dtype=torch.float32)
+    S = splitk or _wgrad_splits(g)
+    part = torch.empty(S, M * ldp, device=_device_of(dY), dtype=torch.float32)
     g.C, g.splitk = part.data_ptr(), S
     with _timed("gemm_" + GEMM_PRECISION, 2 * M * Nc * R, 4 * (M * R + N * R + S * M * ldp)):
         _launch_gemm(g)
@@ -483,13 +490,12 @@ def reduce_splits_bias(part, S, M, N, ldp, dw, db, accumulate=False):
 
 def colsum(A, lda, M, N, out=None, accumulate=False):
     L = _lib.lib()
-    dev = A[0].device if isinstance(A, tuple) else A.device
+    dev = _device_of(A)
     if out is None:
         out = torch.empty(N, device=dev, dtype=torch.float32)
     ws = torch.empty(int(L.tssep_colsum_workspace_bytes(M, N)) // 4, device=dev,
                      dtype=torch.float32)
-    a = A[0].data_ptr() + 4 * A[1] if isinstance(A, tuple) else A.data_ptr()
-    check(L.tssep_colsum_f32(ctypes.c_void_p(a), M, N, lda, _p(out), int(accumulate), _p(ws),
+    check(L.tssep_colsum_f32(_p(A), M, N, lda, _p(out), int(accumulate), _p(ws),
                              _stream()), "colsum")
     return out
 
