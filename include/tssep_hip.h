@@ -550,6 +550,28 @@ int tssep_gatebce_fwd(const float* logit, int64_t ld, const float* vad, int64_t 
                       float* loss, void* ws, void* stream);
 int tssep_gatebce_bwd(const float* logit, int64_t ld, const float* vad, const float* gout, int64_t B, int64_t K,
                       int64_t T, float* dlogit, void* stream);
+/* The targets of the VAD losses, built on the device (tssep/train/loss.py:134-146, 312-327, 381-393; tssep/util/utils.py:11-77).
+ * Frame magnitudes a [rows, T] float32, a[r,t] = sum_{f=0..F-1} |X[r,t,f]|, summed per lane (f = lane, lane + 64, ...;
+ * the last bin of the fused form by lane 0), then across the wave: a fixed order, the same bits on every run.
+ *   tssep_stft_framemag_fwd: the arguments of tssep_stft_fwd (both FFT plans) without the spectrum: X[r,t,f] is formed by
+ *     the arithmetic of tssep_stft_fwd and never written, |X| = sqrtf(re^2 + im^2), F = size / 2 + 1.
+ *   tssep_framemag_fwd: from a spectrum in memory, X [rows, T, F] complex64 (is_complex != 0) or float32 (|X| = fabsf),
+ *     any F >= 1, one wave per frame.
+ * tssep_vad_from_mag: vad[r,t] = (a[r,t] / max_t a[r,t] > (float)threshold) ? 1 : 0 with the IEEE float32 division and the
+ *   strict comparison of `target / torch.amax(target, -1, keepdim=True) > threshold` (loss.py:319-321): the same decisions
+ *   bit for bit given the same a.  A row whose maximum is 0 (an absent speaker: 0 / 0 = NaN compares false) gives zeros; a
+ *   NaN in a row makes the row's maximum NaN as torch.amax does.  One workgroup walks a row twice (the maximum, then the
+ *   decisions): any T >= 1, no workspace, no atomics.
+ * tssep_vad_frames: the frame activity of a sample activity (utils.py:11-77 is this gather): vad_samples [rows, N] uint8,
+ *   non-zero = active; Vad[r,t] = active(vad_samples[r, i]) as 1.f / 0.f, i = (t + 1) shift + window_length / 2 - lead - 1,
+ *   lead = 0 / window_length - shift / (window_length - shift) / 2 for fading = 0 (none) / 1 (full) / 2 (half); 0 where i
+ *   lies outside [0, N).  T: the caller's frame count (tssep_stft_frames with pad = 1). */
+int tssep_stft_framemag_fwd(const float* x, int64_t rows, int64_t N, int size, int shift, int fading,
+                            const float* window, const float* tw, float* a, int64_t T, void* stream);
+int tssep_framemag_fwd(const float* X, int is_complex, int64_t rows, int64_t T, int64_t F, float* a, void* stream);
+int tssep_vad_from_mag(const float* a, int64_t rows, int64_t T, double threshold, float* vad, void* stream);
+int tssep_vad_frames(const uint8_t* vad_samples, int64_t rows, int64_t N, int window_length, int shift, int fading,
+                     float* Vad, int64_t T, void* stream);
 
 /* -------------------------------------------------------- logit layout map ---
  * Tail of MaskEstimator_v2.forward: final einops rearrange / reduce-repeat

@@ -566,6 +566,65 @@ __global__ void gatebce_bwd_kernel(const float* __restrict__ logit, int64_t ld, 
   }
 }
 
+// ---- the VAD losses' targets on the device (loss.py:312-327, utils.py:11-77) -----------------------------------------
+// frame magnitudes of a spectrum in memory: one wave per frame, a[frame] = sum_f |X[frame, f]| -- per lane over
+// f = lane, lane + 64, ..., then across the wave (a fixed order)
+template <bool COMPLEX>
+__global__ __launch_bounds__(256) void framemag_kernel(const float* __restrict__ X, int64_t frames, int64_t F,
+                                                       float* __restrict__ a) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t fr = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); fr < frames; fr += (int64_t)gridDim.x * 4) {
+    float s = 0.f;
+    if (COMPLEX) {
+      const float2* xr = reinterpret_cast<const float2*>(X) + fr * F;
+      for (int64_t f = lane; f < F; f += 64) {
+        const float2 v = xr[f];
+        s += sqrtf(v.x * v.x + v.y * v.y);
+      }
+    } else {
+      const float* xr = X + fr * F;
+      for (int64_t f = lane; f < F; f += 64) s += fabsf(xr[f]);
+    }
+    s = wave_sum(s);
+    if (lane == 0) a[fr] = s;
+  }
+}
+
+// the maximum of torch.amax: a NaN wins and stays
+__device__ __forceinline__ float nanmax(float m, float v) { return (v > m || v != v) ? v : m; }
+
+// one workgroup per row of a [rows, T]: the row's maximum, then the decisions a / m > thr (IEEE division, strict
+// comparison -- torch's `target / torch.amax(target, -1, keepdim=True) > thr` on float32; NOT a > thr m, which decides
+// ties differently).  The second walk over the row reads what the first left in the cache.
+__global__ __launch_bounds__(256) void vad_from_mag_kernel(const float* __restrict__ a, int64_t rows, int64_t T, float thr,
+                                                           float* __restrict__ vad) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+    const float* ar = a + row * T;
+    float m = -INFINITY;
+    for (int64_t t = tid; t < T; t += 256) m = nanmax(m, ar[t]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = nanmax(m, __shfl_xor(m, o, 64));
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    m = nanmax(nanmax(red[0], red[1]), nanmax(red[2], red[3]));
+    for (int64_t t = tid; t < T; t += 256) vad[row * T + t] = (ar[t] / m > thr) ? 1.f : 0.f;
+    __syncthreads();          // red is rewritten by the next row
+  }
+}
+
+// sample activity -> frame activity: the sample at the end of the hop that frame t is centred on (the last sample that
+// paderbox's sample_index_to_stft_frame_index maps to t) decides the frame
+__global__ void vad_frames_kernel(const uint8_t* __restrict__ v, int64_t N, int64_t T, int64_t shift, int64_t off,
+                                  int64_t total, float* __restrict__ out) {
+  GRID_STRIDE(e, total) {
+    const int64_t row = e / T, t = e - row * T;
+    const int64_t i = (t + 1) * shift + off;
+    out[e] = (i >= 0 && i < N && v[row * N + i] != 0) ? 1.f : 0.f;
+  }
+}
+
 // ---- logit layout map: raw GEMM output -> [B, K, T, F] (+ trial mean, + 't' broadcast) ------
 // Covers the tail of MaskEstimator_v2.forward: the final einops rearrange / reduce-repeat
 // (net.py:631-659), the mean over permutation trials (net.py:928-951) and the speaker
@@ -1008,6 +1067,39 @@ extern "C" int tssep_gatebce_bwd(const float* logit, int64_t ld, const float* va
   if (B <= 0 || K <= 0 || T <= 0 || ld <= 0) return TSSEP_E_SHAPE;
   hipLaunchKernelGGL(gatebce_bwd_kernel, dim3(grid_for(B * K * T * ld)), dim3(256), 0, S_, logit, ld, vad, gout,
                      K * T, B * K * T * ld, dlogit);
+  return tssep_launch_status();
+}
+extern "C" int tssep_framemag_fwd(const float* X, int is_complex, int64_t rows, int64_t T, int64_t F, float* a,
+                                  void* stream) {
+  if (!X || !a) return TSSEP_E_NULL;
+  if (rows <= 0 || T <= 0 || F <= 0) return TSSEP_E_SHAPE;
+  if ((((uintptr_t)X) & (is_complex ? 7u : 3u)) || (((uintptr_t)a) & 3u)) return TSSEP_E_ALIGN;
+  const int64_t frames = rows * T;
+  const unsigned grid = grid_for(frames, 4, 16384);              // one wave per frame, grid-stride beyond the cap
+  if (is_complex)
+    hipLaunchKernelGGL(framemag_kernel<true>, dim3(grid), dim3(256), 0, S_, X, frames, F, a);
+  else
+    hipLaunchKernelGGL(framemag_kernel<false>, dim3(grid), dim3(256), 0, S_, X, frames, F, a);
+  return tssep_launch_status();
+}
+extern "C" int tssep_vad_from_mag(const float* a, int64_t rows, int64_t T, double threshold, float* vad, void* stream) {
+  if (!a || !vad) return TSSEP_E_NULL;
+  if (rows <= 0 || T <= 0) return TSSEP_E_SHAPE;
+  if ((((uintptr_t)a) | ((uintptr_t)vad)) & 3u) return TSSEP_E_ALIGN;
+  hipLaunchKernelGGL(vad_from_mag_kernel, dim3(grid_for(rows, 1, 65536)), dim3(256), 0, S_, a, rows, T, (float)threshold,
+                     vad);
+  return tssep_launch_status();
+}
+extern "C" int tssep_vad_frames(const uint8_t* vad_samples, int64_t rows, int64_t N, int window_length, int shift,
+                                int fading, float* Vad, int64_t T, void* stream) {
+  if (!vad_samples || !Vad) return TSSEP_E_NULL;
+  if (rows <= 0 || N <= 0 || T <= 0 || window_length <= 0 || shift <= 0) return TSSEP_E_SHAPE;
+  if (fading < 0 || fading > 2) return TSSEP_E_UNSUPPORTED;
+  if (((uintptr_t)Vad) & 3u) return TSSEP_E_ALIGN;
+  const int64_t pad = (int64_t)window_length - shift;
+  const int64_t lead = fading == 0 ? 0 : (fading == 1 ? pad : (pad >= 0 ? pad / 2 : -((1 - pad) / 2)));   // (Python's //)
+  hipLaunchKernelGGL(vad_frames_kernel, dim3(grid_for(rows * T)), dim3(256), 0, S_, vad_samples, N, T, (int64_t)shift,
+                     (int64_t)(window_length / 2) - lead - 1, rows * T, Vad);
   return tssep_launch_status();
 }
 static int map_args(MapArgs& a, const int32_t* perm, const int32_t* iperm, int64_t B, int trials,

@@ -146,7 +146,11 @@ __device__ __forceinline__ void fft512_wave(float2 (&v)[8], float2* buf, const f
 #ifndef TSSEP_RFFT_OCC
 #define TSSEP_RFFT_OCC 3
 #endif
-template <bool MASKED, bool GATED = false>
+//
+// MAG (plain only; the VAD losses' STFT-magnitude target, loss.py:312-327): no spectrum is written; the epilogue sums
+// |X[k]| = sqrtf(re^2 + im^2) of the bins it formed -- per lane over k = lane, lane + 64, ..., the Nyquist bin by lane 0,
+// then across the wave: a fixed order -- and lane 0 stores the frame's magnitude at dlogit[row * T + t].
+template <bool MASKED, bool GATED = false, bool MAG = false>
 __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     const float* __restrict__ x, int64_t rows, int64_t N, int64_t T, int shift, int pad_left,
     const float* __restrict__ window, const float2* __restrict__ tw, float2* __restrict__ X,
@@ -156,6 +160,7 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     const int32_t* __restrict__ iperm, int bt_major, const float* __restrict__ vad = nullptr,
     const float* __restrict__ gbce = nullptr, float inv_kt = 0.f) {
   static_assert(MASKED || !GATED, "the gate belongs to the mask head");
+  static_assert(!MASKED || !MAG, "the frame magnitudes are the plain STFT's");
   constexpr int LDL = NH + 1 + (GATED ? 1 : 0);   // logit / d(logit) row length
   constexpr int C0 = GATED ? 1 : 0;               // column of bin 0
   // MASKED with tgt != NULL: x is the time-domain ESTIMATE and the frame's samples are the loss gradient
@@ -266,7 +271,7 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     }
     fft512_wave(v, buf, twl, lane);
     if (valid) {
-      float2* Xo = MASKED ? nullptr : X + fidx * (NH + 1);
+      float2* Xo = (MASKED || MAG) ? nullptr : X + fidx * (NH + 1);
       float* Dr = MASKED ? dlogit + fidx * LDL : nullptr;
       if (MASKED && bt_major) {
         const int64_t b = row / Kspk, j = row - b * Kspk;
@@ -274,7 +279,7 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
         Dr = dlogit + ((b * T + t) * Kspk + kpos) * LDL;
       }
       const float gm = GATED ? sigmoidf_mask(lgate) : 1.f;
-      float gpart = 0.f;                      // GATED: this lane's sum_f dm_f sigmoid(l_f)
+      float gpart = 0.f;                      // GATED: this lane's sum_f dm_f sigmoid(l_f); MAG: this lane's sum_f |X_f|
       auto emit = [&](int k, float2 o, float lgk, float2 ob) {
         if (GATED) {
           const float s = sigmoidf_mask(lgk);
@@ -284,6 +289,8 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
         } else if (MASKED) {
           const float m = sigmoidf_mask(lgk);
           Dr[k] = (ob.x * o.x + ob.y * o.y) * m * (1.0f - m);
+        } else if (MAG) {
+          gpart += sqrtf(o.x * o.x + o.y * o.y);
         } else {
           Xo[k] = o;
         }
@@ -318,6 +325,10 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
           if (vad) dv += gbv * (sigmoidf_acc(lgate) - vadv) * inv_kt;
           Dr[0] = dv;
         }
+      }
+      if (MAG) {
+        const float tot = wave_sum(gpart);
+        if (lane == 0) dlogit[fidx] = tot;
       }
     }
     WAVE_SYNC();          // the line is rewritten by this wave's next frame
@@ -526,6 +537,8 @@ int tssep_generic_plan_supported(int size, int shift);
 int tssep_generic_twiddles(int size, float* host_out);
 int tssep_generic_rfft(const float* x, int64_t rows, int64_t N, int size, int shift, int pad_left, const float* window,
                        const float* tw, float* X, int64_t T, float s_in, float s_edge, void* stream);
+int tssep_generic_framemag(const float* x, int64_t rows, int64_t N, int size, int shift, int pad_left, const float* window,
+                           const float* tw, float* a, int64_t T, void* stream);
 int tssep_generic_istft(const float* X, int64_t rows, int64_t T, int size, int shift, int pad_left, const float* wsyn,
                         const float* tw, float* y, int64_t N, void* stream);
 
@@ -564,6 +577,7 @@ using rfft_kernel_t = decltype(&rfft_frames_kernel<false>);
 struct RfftLaunch {
   rfft_kernel_t kernel;                        // the instantiation, named by the entry point
   bool masked;                                 // its MASKED flag: which of the members below it reads
+  float* amag;                                 // its MAG flag (non-NULL): the frame magnitudes [rows, T] instead of X
   const float* x;                              // [rows, N]: the signal, dy, or with tgt != NULL the time-domain estimate
   int64_t rows, N, T;
   int size, shift, fading;
@@ -582,10 +596,12 @@ struct RfftLaunch {
 // (the checks that do not depend on the plan: the general plan of stft_generic.hip takes the same arguments)
 static int rfft_check(const RfftLaunch& a) {
   if (!a.x || !a.window || !a.tw) return TSSEP_E_NULL;
-  if (a.masked ? (!a.logit || !a.obs || !a.dlogit || (a.tgt && !a.gout) || (a.vad && !a.gbce)) : !a.X) return TSSEP_E_NULL;
+  if (a.masked ? (!a.logit || !a.obs || !a.dlogit || (a.tgt && !a.gout) || (a.vad && !a.gbce)) : (!a.X && !a.amag))
+    return TSSEP_E_NULL;
   if (a.rows <= 0 || (a.masked && a.K <= 0) || a.N <= 0 || a.T <= 0) return TSSEP_E_SHAPE;
   if (misaligned(a.tw, 8) || misaligned(a.window, 8)) return TSSEP_E_ALIGN;
-  if (a.masked ? (misaligned(a.logit, 4) || misaligned(a.dlogit, 4) || misaligned(a.obs, 8)) : misaligned(a.X, 8))
+  if (a.masked ? (misaligned(a.logit, 4) || misaligned(a.dlogit, 4) || misaligned(a.obs, 8))
+               : (a.amag ? misaligned(a.amag, 4) : misaligned(a.X, 8)))
     return TSSEP_E_ALIGN;
   return TSSEP_OK;
 }
@@ -598,7 +614,7 @@ static int rfft_launch(const RfftLaunch& a, void* stream) {
   if (blocks > 0x7fffffff) return TSSEP_E_SHAPE;
   hipLaunchKernelGGL(a.kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a.x, a.rows, a.N, a.T, a.shift,
                      a.fading ? a.size - a.shift : 0, a.window, (const float2*)a.tw, (float2*)a.X, a.s_in, a.s_edge, iters,
-                     a.logit, (const float2*)a.obs, a.dlogit, a.masked ? a.K : (int64_t)1, a.tgt, a.sums, a.gout, a.iperm,
+                     a.logit, (const float2*)a.obs, a.amag ? a.amag : a.dlogit, a.masked ? a.K : (int64_t)1, a.tgt, a.sums, a.gout, a.iperm,
                      a.bt_major, a.vad, a.gbce, a.masked ? 1.0f / ((float)a.K * (float)a.T) : 0.f);
   return tssep_launch_status();
 }
@@ -746,4 +762,18 @@ extern "C" int tssep_mask_istft_gated_bwd(const float* est, const float* tgt, co
                           T);
   a.tgt = tgt, a.sums = sums, a.gout = gout, a.iperm = iperm, a.bt_major = bt_major, a.vad = vad, a.gbce = gout_vad;
   return rfft_launch(a, stream);
+}
+
+// ---- the VAD losses' magnitude target (named last: the kernels above keep their place in the code object) --------
+// the STFT's frame magnitudes a[r,t] = sum_f |X[r,t,f]| without the spectrum (the VAD losses' magnitude target)
+extern "C" int tssep_stft_framemag_fwd(const float* x, int64_t rows, int64_t N, int size, int shift, int fading,
+                                       const float* window, const float* tw, float* a, int64_t T, void* stream) {
+  const RfftLaunch l = {.kernel = rfft_frames_kernel<false, false, true>, .amag = a, .x = x, .rows = rows, .N = N, .T = T,
+                        .size = size, .shift = shift, .fading = fading, .window = window, .tw = tw, .s_in = 1.0f,
+                        .s_edge = 1.0f};
+  if (generic_plan(size, shift)) {
+    if (int e = rfft_check(l)) return e;
+    return tssep_generic_framemag(x, rows, N, size, shift, fading ? size - shift : 0, window, tw, a, T, stream);
+  }
+  return rfft_launch(l, stream);
 }

@@ -124,6 +124,9 @@ __device__ __forceinline__ float2* stockham_wave(const GenPlan& pl, float2* a, f
 // frames -> rfft.  STFT (window = analysis window, s_in = s_edge = 1) and adjoint of the inverse STFT (window = synthesis
 // window, interior bins x 2 / size, DC / Nyquist x 1 / size), as in stft.hip.  tw: [NH] exp(-2 pi i k / NH), then
 // [NH + 1] exp(-2 pi i k / size).  Dynamic LDS: twl[NH] | per wave 2 lines of NH float2.
+// MAG: no spectrum; X is float [rows, T] and receives the frame's sum_k |X[k]| (per lane over k = lane, lane + 64, ...,
+// the Nyquist bin by lane 0, then across the wave: a fixed order), as in stft.hip.
+template <bool MAG>
 __global__ __launch_bounds__(256) void rfft_generic_kernel(const float* __restrict__ x, int64_t rows, int64_t N, int64_t T,
                                                            int shift, int pad_left, const float* __restrict__ window,
                                                            const float2* __restrict__ tw, float2* __restrict__ X,
@@ -149,7 +152,8 @@ __global__ __launch_bounds__(256) void rfft_generic_kernel(const float* __restri
     }
     GWAVE_SYNC();
     const float2* Z = stockham_wave(pl, la, lb, twl, lane);
-    float2* Xo = X + fidx * (NH + 1);
+    float2* Xo = MAG ? nullptr : X + fidx * (NH + 1);
+    float mpart = 0.f;
     const float hs_in = 0.5f * s_in;
     for (int k = lane; k < NH; k += 64) {
       const float2 zk = Z[k];
@@ -162,11 +166,18 @@ __global__ __launch_bounds__(256) void rfft_generic_kernel(const float* __restri
       } else {
         o.x *= hs_in; o.y *= hs_in;
       }
-      Xo[k] = o;
+      if (MAG) mpart += sqrtf(o.x * o.x + o.y * o.y);
+      else Xo[k] = o;
     }
     if (lane == 0) {
       const float2 z0 = Z[0];
-      Xo[NH] = make_float2((z0.x - z0.y) * s_edge, 0.f);
+      const float2 o = make_float2((z0.x - z0.y) * s_edge, 0.f);
+      if (MAG) mpart += sqrtf(o.x * o.x + o.y * o.y);
+      else Xo[NH] = o;
+    }
+    if (MAG) {
+      const float tot = wave_sum(mpart);
+      if (lane == 0) reinterpret_cast<float*>(X)[fidx] = tot;
     }
     GWAVE_SYNC();          // the lines are rewritten by this wave's next frame
   }
@@ -298,8 +309,9 @@ int tssep_generic_twiddles(int size, float* host_out) {
 
 static size_t generic_lds_bytes(const GenPlan& pl) { return (size_t)(pl.nh + 8 * pl.nh) * sizeof(float2); }
 
-int tssep_generic_rfft(const float* x, int64_t rows, int64_t N, int size, int shift, int pad_left, const float* window,
-                       const float* tw, float* X, int64_t T, float s_in, float s_edge, void* stream) {
+template <bool MAG>
+static int generic_rfft(const float* x, int64_t rows, int64_t N, int size, int shift, int pad_left, const float* window,
+                        const float* tw, float* X, int64_t T, float s_in, float s_edge, void* stream) {
   GenPlan pl;
   if (!make_plan(size, &pl) || shift < 1 || shift > size) return TSSEP_E_UNSUPPORTED;
   const int64_t total = rows * T;
@@ -307,12 +319,21 @@ int tssep_generic_rfft(const float* x, int64_t rows, int64_t N, int size, int sh
   if (blocks > 16384) blocks = 16384;
   const size_t lds = generic_lds_bytes(pl);
   if (lds > 48 * 1024) {
-    if (hipFuncSetAttribute((const void*)rfft_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)rfft_generic_kernel<MAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return TSSEP_E_UNSUPPORTED;
   }
-  hipLaunchKernelGGL(rfft_generic_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, x, rows, N, T, shift,
-                     pad_left, window, (const float2*)tw, (float2*)X, s_in, s_edge, pl);
+  hipLaunchKernelGGL(rfft_generic_kernel<MAG>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, x, rows, N, T,
+                     shift, pad_left, window, (const float2*)tw, (float2*)X, s_in, s_edge, pl);
   return tssep_launch_status();
+}
+int tssep_generic_rfft(const float* x, int64_t rows, int64_t N, int size, int shift, int pad_left, const float* window,
+                       const float* tw, float* X, int64_t T, float s_in, float s_edge, void* stream) {
+  return generic_rfft<false>(x, rows, N, size, shift, pad_left, window, tw, X, T, s_in, s_edge, stream);
+}
+// the frame magnitudes a [rows, T] of the STFT (s_in = s_edge = 1) instead of its spectrum
+int tssep_generic_framemag(const float* x, int64_t rows, int64_t N, int size, int shift, int pad_left, const float* window,
+                           const float* tw, float* a, int64_t T, void* stream) {
+  return generic_rfft<true>(x, rows, N, size, shift, pad_left, window, tw, a, T, 1.0f, 1.0f, stream);
 }
 
 int tssep_generic_istft(const float* X, int64_t rows, int64_t T, int size, int shift, int pad_left, const float* wsyn,

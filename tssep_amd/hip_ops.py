@@ -169,6 +169,70 @@ def stft_fwd(x, window, size=1024, shift=256, fading=True, T=None):
     return torch.view_as_complex(X)
 
 
+def stft_framemag(x, window, size=1024, shift=256, fading=True, T=None):
+    """x [rows, N] -> a [rows, T] float32, a[r,t] = sum_f |stft_fwd(x)[r,t,f]| without the spectrum (arguments as stft_fwd)."""
+    L = _lib.lib()
+    x = _f32(x).contiguous()
+    rows, N = x.shape
+    if T is None:
+        T = stft_frames(N, size, shift, None, True, fading)
+    a = torch.empty(rows, T, device=x.device, dtype=torch.float32)
+    with _timed("stft_framemag", 0, 4 * rows * (N + T)):
+        check(L.tssep_stft_framemag_fwd(_p(x), rows, N, size, shift, int(fading), _p(window),
+                                        _p(fft_tables(size, x.device)), _p(a), T, _stream()), "stft_framemag")
+    return a
+
+
+def framemag(X):
+    """X [rows, T, F] complex64 or float32 -> a [rows, T] float32, a[r,t] = sum_f |X[r,t,f]|."""
+    assert X.is_cuda and X.dim() == 3 and X.dtype in (torch.complex64, torch.float32), (X.device, X.shape, X.dtype)
+    X = X.contiguous()
+    rows, T, F = X.shape
+    cplx = X.is_complex()
+    a = torch.empty(rows, T, device=X.device, dtype=torch.float32)
+    with _timed("framemag", 0, 4 * rows * T * ((2 if cplx else 1) * F + 1)):
+        check(_lib.lib().tssep_framemag_fwd(_p(torch.view_as_real(X) if cplx else X), int(cplx), rows, T, F, _p(a),
+                                            _stream()), "framemag")
+    return a
+
+
+def vad_from_mag(a, threshold):
+    """a [rows, T] -> float32 [rows, T] of 0 / 1: a / amax(a, -1, keepdim=True) > threshold (loss.py:319-321), the decisions
+    of that torch expression on a float32 tensor bit for bit."""
+    a = _f32(a).contiguous()
+    rows, T = a.shape
+    vad = torch.empty_like(a)
+    with _timed("vad_from_mag", 0, 8 * rows * T):
+        check(_lib.lib().tssep_vad_from_mag(_p(a), rows, T, float(threshold), _p(vad), _stream()), "vad_from_mag")
+    return vad
+
+
+_FADING_CODE = {None: 0, False: 0, True: 1, "full": 1, "half": 2}
+
+
+def vad_frames(vad, window_length, shift, fading=True):
+    """Sample activity vad [rows, N] (bool or uint8 as they are, any other dtype through `!= 0`) -> frame activity
+    float32 [rows, T], T = the padded frame count: util.utils.stft_vad as a gather on the device."""
+    assert vad.is_cuda and vad.dim() == 2, (vad.device, vad.shape)
+    if vad.dtype == torch.bool:
+        v = vad.contiguous().view(torch.uint8)
+    elif vad.dtype == torch.uint8:
+        v = vad.contiguous()
+    else:
+        v = (vad != 0).view(torch.uint8)
+    rows, N = v.shape
+    pad = window_length - shift
+    n = N + {0: 0, 1: 2 * pad, 2: pad}[_FADING_CODE[fading]]
+    T = -(-(n - window_length + shift) // shift)               # utils.samples_to_stft_frames(pad=True)
+    out = torch.empty(rows, max(T, 0), device=v.device, dtype=torch.float32)
+    if T <= 0:
+        return out
+    with _timed("vad_frames", 0, rows * T * 5):
+        check(_lib.lib().tssep_vad_frames(_p(v), rows, N, int(window_length), int(shift), _FADING_CODE[fading], _p(out), T,
+                                          _stream()), "vad_frames")
+    return out
+
+
 def istft_fwd(X, wsyn, N, size=1024, shift=256, fading=True, tgt=None):
     """X complex64 [rows, T, F] -> y [rows, N] (+ per-chunk sums of |y - tgt| when tgt given)"""
     L = _lib.lib()

@@ -120,6 +120,39 @@ class STFT(Configurable):
             X = H.stft_fwd(x2, w, self.size, self.shift, False, T=T)
         return X.reshape(*x.shape[:-1], X.shape[-2], X.shape[-1])
 
+    def frame_activity(self, signal, threshold):
+        """[..., N] -> float32 [..., T] of 0 / 1: VADSigmoidBCE.prepare_target (loss.py:316-321) of ``self.stft(signal)`` --
+        sum_f |X| per frame, divided by its maximum over the row's frames, compared with ``threshold`` -- without the
+        spectrum: the frame kernel sums the magnitudes of the bins it formed (hip_ops.stft_framemag).  Options as in
+        ``stft``."""
+        self._check_plan()
+        x = _cuda_f32(signal)
+        w, _ = self._windows(x.device)
+        x2 = x.reshape(-1, x.shape[-1])
+        T = self.frames(x.shape[-1])
+        if self._plain():
+            a = H.stft_framemag(x2, w, self.size, self.shift, True, T=T)
+        else:
+            lead, tail = self._fade()          # (zero padding is layout, as in `stft`)
+            if lead or tail:
+                x2 = torch.nn.functional.pad(x2, (lead, tail))
+            a = H.stft_framemag(x2, w, self.size, self.shift, False, T=T)
+        return H.vad_from_mag(a, threshold).reshape(*x.shape[:-1], T)
+
+    @staticmethod
+    def stft_activity(X, threshold):
+        """A spectrum [..., T, F] (complex, or real: loss.py's doctest) on the device -> float32 [..., T] of 0 / 1, the
+        activity ``frame_activity`` derives from the signal."""
+        if X.dtype == torch.complex128:
+            X = X.to(torch.complex64)
+        elif not X.is_complex():
+            X = X.to(torch.float32)
+        if not X.is_cuda:
+            raise RuntimeError("tssep_amd runs on the GPU only: move the spectrum to cuda first (no CPU fallback)")
+        T, F = X.shape[-2:]
+        a = H.framemag(X.reshape(-1, T, F))
+        return H.vad_from_mag(a, threshold).reshape(X.shape[:-1])
+
     def _num_samples(self, T, num_samples):
         lead, tail = self._fade()
         full = (T - 1) * self.shift + self.window_length - lead - tail

@@ -89,7 +89,8 @@ class GraphedStep:
     def _host_side_targets(self, ex):
         """What the loss would compute on the HOST inside `review` (loss.py:122-146: the frame activity `Vad` from the
         sample activity `vad`, util/utils.stft_vad -- numpy, as in the reference) is computed here, in front of the graph,
-        and enters it as one more static input: a device-to-host copy cannot be captured."""
+        and enters it as one more static input: a device-to-host copy cannot be captured.  (A magnitude target needs no such
+        hoist: its kernels are nodes of the graph.)"""
         loss, fe = self.model.loss, getattr(self.model, "fe", None)
         tgt = getattr(loss, "target", None)
         if tgt == "Vad" and tgt not in ex and ex.get("vad") is not None and fe is not None:

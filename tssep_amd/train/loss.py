@@ -6,7 +6,15 @@ and the joint TS-SEP loss ``SignalAndVADSigmoidBCE`` (:348-424) of an ``explicit
 (pt.ops.losses.pit_loss).  Each of them is f(sum_k C[k, perm(k)]) with f monotone on the pairwise costs
 C[i, j] = mean_n |e_i - t_j|^p, so the best permutation is the best assignment on C: one pass over both signals yields
 C, the assignment is found on the device (K <= 8), and ``.permutation`` keeps the last call's choice.
+
+The VAD losses take two kinds of target.  ``'Vad'``: the frame activity, given by the reader or derived from the sample
+activity ``vad`` (util.utils.stft_vad, host code as in the reference; stft_vad_device is its one-kernel form).  An upper-case signal name such as
+``'Speaker_reverberation_early_ch0'`` (loss.py:312-327): a frame is active where the sum of its STFT magnitudes exceeds
+``magnitude_threshold`` times the row's largest.  That activity is built on the device too -- from the spectrum ``ex[target]``
+when the caller supplies one, otherwise from the signal ``ex[target.lower()]`` by a frame kernel that never writes the
+spectrum (STFT.frame_activity) -- and is kept in ``ex`` under a private key; ``ex[target]`` always stays a spectrum.
 Not built: FreqMSE, pit for the VAD losses, K > 8."""
+import numpy as np
 import torch
 
 from .. import functional as Fn
@@ -102,6 +110,9 @@ class MSE(TimeDomain):
         return Fn.mse(estimate, target)
 
 
+_ACTIVITY_KEY = "_tssep_amd_frame_activity:"      # ex[_ACTIVITY_KEY + target] = (the tensor it came from, the activity)
+
+
 class LogitsSTFTDomain(ABC):
     def from_ex_out(self, ex, out, model, summary):      # loss.py:122-146
         if out.logit is None:
@@ -113,18 +124,43 @@ class LogitsSTFTDomain(ABC):
                              "the squeeze of the mask axis (loss.py:122-146) is a no-op then; use nmask=1")
         estimate = torch.squeeze(out.logit, dim=-3)
         assert self.target[0].isupper(), self.target
+        if self.target != "Vad":
+            return self._bce(estimate, self.frame_activity(ex, model))
         if self.target not in ex:
-            if self.target == "Vad":
-                from ..util.utils import stft_vad
-                ex[self.target] = stft_vad(ex[self.target.lower()], model.fe.window_length,
-                                           model.fe.shift, model.fe.fading)
-            else:
-                raise NotImplementedError(self.target)
+            from ..util.utils import stft_vad
+            ex[self.target] = stft_vad(ex[self.target.lower()], model.fe.window_length,
+                                       model.fe.shift, model.fe.fading)
         return self(estimate, ex[self.target])
+
+    def frame_activity(self, ex, model):
+        """The frame activity [..., K, T] (float32 of 0 / 1, on the model's device) of a magnitude target
+        (loss.py:143-146 + 312-327): from the caller's spectrum ``ex[target]`` when there is one, otherwise from the signal
+        ``ex[target.lower()]`` without its spectrum (STFT.frame_activity).  Cached in ``ex`` under a private key, next to the
+        tensor it was derived from; ``ex[target]`` is left as it is -- other code reads that key as a spectrum."""
+        assert self.target[0].isupper() and self.target != "Vad", self.target
+        spectrum = self.target in ex
+        src = ex[self.target] if spectrum else ex[self.target.lower()]
+        cached = ex.get(_ACTIVITY_KEY + self.target)
+        if cached is not None and cached[0] is src:
+            return cached[1]
+        if not isinstance(src, torch.Tensor):
+            src = torch.stack(list(src)) if isinstance(src, (list, tuple)) else torch.as_tensor(src)
+        dev = next(model.parameters()).device
+        x = src.to(dev)
+        act = model.fe.stft_activity(x, self.magnitude_threshold) if spectrum \
+            else model.fe.frame_activity(x, self.magnitude_threshold)
+        ex[_ACTIVITY_KEY + self.target] = (ex[self.target] if spectrum else ex[self.target.lower()], act)
+        return act
+
+    def _target_activity(self, ex, model):
+        """What the summaries draw: the activity the loss was computed on."""
+        if self.target == "Vad":
+            return torch.as_tensor(ex[self.target])
+        return self.frame_activity(ex, model)
 
     def update_summary(self, summary, ex, out, model):   # loss.py:148-169: the mask image framed by the target activity
         import einops
-        target_vad = einops.repeat(self.prepare_target(torch.as_tensor(ex[self.target])).to(out.mask.device, torch.float32),
+        target_vad = einops.repeat(self._target_activity(ex, model).to(out.mask.device, torch.float32),
                                    "... spk time -> ... spk mask time freq", freq=40, mask=out.mask.shape[-3])
         masks = torch.concat([target_vad, out.mask.detach(), target_vad], dim=-1)
         summary.add_mask_image(f"{model.enhancer.name}_mask", masks,
@@ -139,20 +175,43 @@ class VADSigmoidBCE(LogitsSTFTDomain):
         assert 0 < magnitude_threshold < 1, magnitude_threshold
         self.magnitude_threshold = magnitude_threshold
 
-    def prepare_target(self, target, dtype=None):
+    def prepare_target(self, target, dtype=None):        # loss.py:312-327
+        """A spectrum [..., T, F] (complex or real) -> the activity [..., T] in ``dtype`` (default: the spectrum's real
+        dtype): sum_f |X| / max_t sum_f |X| > magnitude_threshold.  A CUDA tensor goes through the kernels
+        (STFT.stft_activity); numpy arrays and CPU tensors -- summaries, tests -- take the reference's formula as it
+        stands."""
         if self.target in ["vad", "Vad"]:
             return target
-        raise NotImplementedError("STFT-magnitude VAD targets (loss.py:316-327) are off the hot path")
+        if dtype is None:
+            dtype = target.real.dtype
+        if isinstance(target, torch.Tensor):
+            if target.is_cuda:
+                from .feature_extractor import STFT
+                return STFT.stft_activity(target, self.magnitude_threshold).type(dtype)
+            target = abs(target).sum(axis=-1)
+            target = target / torch.amax(target, dim=-1, keepdim=True)
+            return (target > self.magnitude_threshold).type(dtype)
+        target = np.abs(target).sum(axis=-1)
+        with np.errstate(invalid="ignore"):               # (a silent row: 0 / 0 = NaN compares false, as in torch)
+            target = target / np.amax(target, axis=-1, keepdims=True)
+            return (target > self.magnitude_threshold).astype(dtype)
+
+    def _bce(self, estimate, activity):
+        """estimate [..., K, T, F] (the mean over F is the kernel's), activity [..., K, T] -> mean_{k,t} BCE"""
+        assert estimate.shape[:-1] == activity.shape, (estimate.shape, activity.shape)
+        activity = activity.to(device=estimate.device, dtype=torch.float32)
+        if estimate.dim() == 3:
+            return Fn.vad_bce(estimate[None], activity[None])[0]
+        return Fn.vad_bce(estimate, activity)
 
     def forward(self, estimate, target):                 # loss.py:329-345
         if not isinstance(target, torch.Tensor):
             target = torch.stack(target)
         if self.target not in ["vad", "Vad"]:
-            raise NotImplementedError(self.target)
-        target = target.to(device=estimate.device, dtype=torch.float32)
-        if estimate.dim() == 3:
-            return Fn.vad_bce(estimate[None], target[None])[0]
-        return Fn.vad_bce(estimate, target)
+            assert estimate.shape == target.shape, (estimate.shape, target.shape)
+            assert estimate.ndim > 2, estimate.shape
+            target = self.prepare_target(target.to(estimate.device), dtype=torch.float32)
+        return self._bce(estimate, target)
 
 
 class SignalAndVADSigmoidBCE(VADSigmoidBCE):
@@ -164,8 +223,9 @@ class SignalAndVADSigmoidBCE(VADSigmoidBCE):
     def __init__(self, signal_loss: TimeDomain, target: str = "Vad", pit: bool = False,
                  magnitude_threshold: float = 0.05):
         super().__init__(target=target, pit=pit, magnitude_threshold=magnitude_threshold)
-        if target != "Vad":
-            raise NotImplementedError(f"target {target!r}: only the frame-level 'Vad' target (loss.py:384-393)")
+        if not target[:1].isupper():
+            raise NotImplementedError(f"target {target!r}: the frame-level 'Vad' or an upper-case signal name, whose STFT "
+                                      "magnitudes give the activity (loss.py:380-393 asserts the upper case)")
         if not isinstance(signal_loss, TimeDomain):
             raise TypeError(f"signal_loss must be a time-domain loss (LogMAE, MAE, MSE), got {type(signal_loss).__name__}")
         if signal_loss.pit:
@@ -178,7 +238,12 @@ class SignalAndVADSigmoidBCE(VADSigmoidBCE):
 
     def frame_vad(self, ex, model):
         """ex['Vad'] as a float32 tensor on the logits' device: from the sample activity ``vad`` when absent
-        (loss.py:381-391, util/utils.stft_vad) -- stored back, so that every user sees the same tensor."""
+        (loss.py:381-391, util/utils.stft_vad) -- stored back, so that every user sees the same tensor.  A magnitude
+        target: the cached ``frame_activity`` (the same tensor on every call for the same ``ex``)."""
+        if self.target != "Vad":
+            if ex.get(self.target) is None and ex.get(self.target.lower()) is None:
+                return None
+            return self.frame_activity(ex, model)
         v = ex.get(self.target)
         if v is None:
             if ex.get(self.target.lower()) is None:
@@ -196,9 +261,9 @@ class SignalAndVADSigmoidBCE(VADSigmoidBCE):
     def from_ex_out(self, ex, out, model, summary):       # loss.py:368-395
         signal_loss = self.signal_loss.from_ex_out(ex, out, model, summary)
         fused = getattr(out, "_gate_bce", None)
-        if fused is not None and fused[1] is ex.get(self.target):
-            return fused[0] + signal_loss
         target = self.frame_vad(ex, model)
+        if fused is not None and fused[1] is target:
+            return fused[0] + signal_loss
         gated = getattr(out, "_gated", None)
         if gated is not None:
             if target.dim() == 2:
@@ -213,7 +278,7 @@ class SignalAndVADSigmoidBCE(VADSigmoidBCE):
 
     def update_summary(self, summary, ex, out, model):    # loss.py:397-424
         import einops
-        target_vad = einops.repeat(self.prepare_target(torch.as_tensor(ex[self.target])).to(out.mask.device, torch.float32),
+        target_vad = einops.repeat(self._target_activity(ex, model).to(out.mask.device, torch.float32),
                                    "... spk time -> ... spk mask time freq", freq=40, mask=out.mask.shape[-3])
         estimate_vad = einops.repeat(out.vad_mask.detach(), "... spk mask time -> ... spk mask time freq", freq=40)
         masks = torch.concat([target_vad, estimate_vad, out.mask.detach(), estimate_vad, target_vad], dim=-1)

@@ -415,16 +415,17 @@ class Model(Configurable, torch.nn.Module):
                     tgt = None
                 # explicit_vad with SignalAndVADSigmoidBCE: the BCE of the gate column rides along (its value on `out`, its
                 # gradient folded into the tail's d(v) store)
-                vad = None
+                vad = vad_of_ex = None
                 if out._gated is not None and isinstance(self.loss, _loss.SignalAndVADSigmoidBCE):
-                    vad = self.loss.frame_vad(ex, self)
-                    if vad is not None:
-                        vad = vad if batched else vad[None]
+                    # (ex['Vad'], or the cached activity of a magnitude target: the tensor from_ex_out will ask for again)
+                    vad_of_ex = self.loss.frame_vad(ex, self)
+                    if vad_of_ex is not None:
+                        vad = vad_of_ex if batched else vad_of_ex[None]
                 te = self.fe.masked_istft(logit4, obs3, num_samples=n, target=tgt, vad=vad)
                 if out._gated is not None:
                     te, bce = te
                     if bce is not None:
-                        out._gate_bce = (bce if batched else bce[0], ex[self.loss.target])
+                        out._gate_bce = (bce if batched else bce[0], vad_of_ex)
                 out.time_estimate = te if batched else te[0]
             else:
                 out.time_estimate = self.fe.istft(out.stft_estimate, num_samples=n)

@@ -7,7 +7,10 @@ utils.py:45-47) have their start and (exclusive) end mapped through paderbox's
 fading)`` (utils.py:34-42).  paderbox 0.0.8 is absent here: both helpers are restated from the published
 package (oracle/stft_vad.py states them as plain loops; this file is the vectorised product version,
 tests/test_host_logic.py compares the two).  Host-side numpy -- target preparation, not on the GPU hot
-path (the reference bypasses it when ``ex['Vad']`` is present, loss.py:134).
+path (the reference bypasses it when ``ex['Vad']`` is present, loss.py:134).  The same mapping as ONE gather kernel on
+the device, for a caller whose ``vad`` lives there and who wants no copy to the host: ``stft_vad_device`` below
+(hip_ops.vad_frames); ``stft_vad`` itself keeps the host route for every input, so that the recorded
+launches of the shipped steps stay what they were.
 """
 import math
 
@@ -65,3 +68,14 @@ def stft_vad(vad, window_length, shift, fading=True):
     if isinstance(vad, (tuple, list)):
         return [stft_vad(v, window_length, shift, fading) for v in vad]
     raise TypeError(vad)
+
+
+def stft_vad_device(vad, window_length, shift, fading=True):
+    """``stft_vad`` of a CUDA tensor [..., N] without leaving the device: float32 [..., frames] on the same device, the
+    values ``stft_vad`` gives.  The mapping of runs above is a gather -- frame t takes the activity of the last sample
+    whose frame index is t (tests/test_boundary.py states it): one kernel, no synchronisation, capturable into a graph."""
+    from .. import hip_ops as H
+    if not (isinstance(vad, torch.Tensor) and vad.is_cuda):
+        raise TypeError("stft_vad_device takes a CUDA tensor; stft_vad serves numpy arrays, CPU tensors and lists")
+    out = H.vad_frames(vad.detach().reshape(-1, vad.shape[-1]), window_length, shift, fading)
+    return out.reshape(*vad.shape[:-1], out.shape[-1])
