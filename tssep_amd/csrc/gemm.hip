@@ -15,7 +15,7 @@
 // ds_read_b128 per 32 rows and 8 MFMA steps.  The [BK+4]-float row pitch makes
 // those reads bank-conflict free (pitch 80 B: 16-B slot index 5*row mod 16 is a
 // bijection over the 16 rows of a ds_read_b128 lane group).
-#include "gemm_common.h"
+#include "gemm_rules.h"
 
 namespace {
 
@@ -332,180 +332,62 @@ static tssep_gemm_args normalised(const tssep_gemm_args* g) {
   return a;
 }
 
-extern "C" int tssep_gemm_f32(const tssep_gemm_args* g, void* stream) {
-  if (!g) return TSSEP_E_NULL;
+// launch, forced launch, plan query (call.dry: the kernel that would run -> *kernel)
+static int gemm_entry(const tssep_gemm_args* g, GemmCall call, int32_t* kernel = nullptr) {
+  if (!g || (call.dry && !kernel)) return TSSEP_E_NULL;
+  if (call.force < TSSEP_GEMM_AUTO || call.force > TSSEP_GEMM_KERNEL_LAST) return TSSEP_E_SHAPE;
   const tssep_gemm_args a = normalised(g);
-  GemmCall call{stream, false, TSSEP_GEMM_AUTO, TSSEP_GEMM_AUTO};
-  return gemm_dispatch(&a, call);
-}
-
-extern "C" int tssep_gemm_f32_on(const tssep_gemm_args* g, int32_t kernel, void* stream) {
-  if (!g) return TSSEP_E_NULL;
-  if (kernel < TSSEP_GEMM_AUTO || kernel > TSSEP_GEMM_KERNEL_LAST) return TSSEP_E_SHAPE;
-  const tssep_gemm_args a = normalised(g);
-  GemmCall call{stream, false, kernel, TSSEP_GEMM_AUTO};
-  return gemm_dispatch(&a, call);
-}
-
-extern "C" int tssep_gemm_plan(const tssep_gemm_args* g, int32_t force, int32_t* kernel) {
-  if (!g || !kernel) return TSSEP_E_NULL;
-  if (force < TSSEP_GEMM_AUTO || force > TSSEP_GEMM_KERNEL_LAST) return TSSEP_E_SHAPE;
-  const tssep_gemm_args a = normalised(g);
-  GemmCall call{nullptr, true, force, TSSEP_GEMM_AUTO};
   const int rc = gemm_dispatch(&a, call);
-  *kernel = rc == TSSEP_OK ? call.chosen : TSSEP_GEMM_AUTO;
+  if (kernel) *kernel = rc == TSSEP_OK ? call.chosen : TSSEP_GEMM_AUTO;
   return rc;
 }
+extern "C" int tssep_gemm_f32(const tssep_gemm_args* g, void* stream) { return gemm_entry(g, GemmCall{stream, false, TSSEP_GEMM_AUTO, TSSEP_GEMM_AUTO}); }
+extern "C" int tssep_gemm_f32_on(const tssep_gemm_args* g, int32_t kernel, void* stream) { return gemm_entry(g, GemmCall{stream, false, kernel, TSSEP_GEMM_AUTO}); }
+extern "C" int tssep_gemm_plan(const tssep_gemm_args* g, int32_t force, int32_t* kernel) { return gemm_entry(g, GemmCall{nullptr, true, force, TSSEP_GEMM_AUTO}, kernel); }
 
 extern "C" const char* tssep_gemm_kernel_name(int32_t kernel) {
-  static const char* const names[] = {"auto", "f32", "pipe", "tall2", "tall4", "tall4_xcol", "big", "stream", "nt_w160",
-                                      "tn", "tn_tall", "tn_big", "tn_w160", "tn_h160", "big_p", "big_p320", "tn_p320"};
-  return kernel >= 0 && kernel <= TSSEP_GEMM_KERNEL_LAST ? names[kernel] : "?";
+  if (kernel == TSSEP_GEMM_AUTO || kernel == TSSEP_GEMM_F32) return kernel == TSSEP_GEMM_AUTO ? "auto" : "f32";
+  const GemmCandidate* c = tssep_gemm_bf16x3_candidate(kernel);      // (the other ids: rows of the split-bf16 table)
+  return c ? c->name : "?";
+}
+
+// The split count the rule of kernel `kernel_id` gives this request: the rule hangs on that kernel's row of the candidate
+// table, gemm_rules.h (tests: the kernel planned AT the returned S of tssep_gemm_wgrad_splits must be the kernel whose rule
+// produced that S).
+extern "C" int tssep_gemm_wgrad_split_rule(const tssep_gemm_args* g, int32_t kernel_id) {
+  if (!g) return TSSEP_E_NULL;
+  if (g->M <= 0 || g->N <= 0 || g->K <= 0) return TSSEP_E_SHAPE;
+  const StoreMap sm = make_store_map(g);
+  const GemmRequest q(g, sm, 1);
+  const GemmCandidate* c = tssep_gemm_bf16x3_candidate(kernel_id);
+  return c && c->splits ? c->splits(q) : splits_general(q);
 }
 
 // Split count of a weight gradient dW[M, N] = dY[K, M]^T X[K, N] (both operands k-major): `g` as for the launch,
 // splitk / c_split_stride / C ignored.  The rule follows the KERNEL the dispatcher picks (asked through the plan
-// query, never re-derived): tools/sweep_splitk.py, profiles/r2_splitk_sweep.jsonl, r3_wgrad_*_sweep.jsonl -- a model
-// that prices whole rounds of 512 resident workgroups predicts up to 20 % from other factors; measured, the large-K
-// shapes get SLOWER with more splits (the tiles of a K slab share it through one L2 only while they run together),
-// and these rules are within 0..5 % of the best S on every shape of the step.
-static int wgrad_split_rule(const tssep_gemm_args* g, int32_t kid);
+// query, never re-derived).
 extern "C" int tssep_gemm_wgrad_splits(const tssep_gemm_args* g) {
   if (!g) return TSSEP_E_NULL;
   if (g->M <= 0 || g->N <= 0 || g->K <= 0) return TSSEP_E_SHAPE;
   tssep_gemm_args a = normalised(g);
-  a.splitk = 8; a.c_split_stride = 0;
-  auto planned = [&](int splitk, int32_t* kid) {
-    a.splitk = splitk;
-    GemmCall call{nullptr, true, TSSEP_GEMM_AUTO, TSSEP_GEMM_AUTO};
-    const int rc = gemm_dispatch(&a, call);
-    *kid = call.chosen;
-    return rc;
-  };
+  a.c_split_stride = 0;
+  auto planned = [&](int splitk, int32_t* kid) { a.splitk = splitk; return tssep_gemm_plan(&a, TSSEP_GEMM_AUTO, kid); };
   int32_t kid = TSSEP_GEMM_AUTO;
-  {
-    const int rc = planned(8, &kid);
-    if (rc != TSSEP_OK) return rc;
-  }
+  if (const int rc = planned(8, &kid)) return rc;
   // The split rule is written for the kernel the dispatcher picks at splitk = 8; a launcher may refuse the S that rule
   // gives (a non-multiple of 8, the `S * 8 <= ktiles` limit of tn_p320) and the launch then falls through to ANOTHER
   // kernel than the one the rule was written for.  So: plan again with the S just chosen and, when the kernel
   // changed, apply THAT kernel's rule -- until the (kernel, S) pair is a fixed point (two rounds at most in practice).
-  int S = wgrad_split_rule(g, kid);
+  int S = tssep_gemm_wgrad_split_rule(g, kid);
   bool fixed = false;
   for (int round = 0; round < 4 && !fixed; ++round) {
     int32_t kid2 = TSSEP_GEMM_AUTO;
     if (planned(S, &kid2) != TSSEP_OK) break;
     if (kid2 == kid) { fixed = true; break; }
     kid = kid2;
-    S = wgrad_split_rule(g, kid);
+    S = tssep_gemm_wgrad_split_rule(g, kid);
   }
   // (no fixed point -- kernels whose rules keep handing the request to each other, or a refused plan: 8 splits, which
   // every weight-gradient kernel takes)
   return fixed ? S : 8;
-}
-
-// The split count the rule of kernel `kernel_id` gives this request (tests: the kernel planned AT the returned S of
-// tssep_gemm_wgrad_splits must be the kernel whose rule produced that S).
-extern "C" int tssep_gemm_wgrad_split_rule(const tssep_gemm_args* g, int32_t kernel_id) {
-  if (!g) return TSSEP_E_NULL;
-  if (g->M <= 0 || g->N <= 0 || g->K <= 0) return TSSEP_E_SHAPE;
-  return wgrad_split_rule(g, kernel_id);
-}
-
-static int wgrad_split_rule(const tssep_gemm_args* g, int32_t kid) {
-  auto cdiv = [](int64_t x, int64_t y) { return (x + y - 1) / y; };
-  auto rup = [&](int64_t x, int64_t y) { return cdiv(x, y) * y; };
-  const int64_t M = g->M, N = g->N, K = g->K, ktiles = cdiv(K, 16);
-  const int min_ktiles = 8;
-  if (kid == TSSEP_GEMM_TN_BIG && K >= 16 * 64) {
-    // 512 x 128 tiles, ONE workgroup per CU, the tiles of a K slab on one XCD (32 CUs) -> as many slabs per XCD as fill
-    // its CUs best; multiples of 8 only (N = 128 q + 1 | 2: the last columns ride on the VALU of the q-th column tile)
-    const GemmSwitches sw = gemm_switches();
-    const int ones = g->b_ones_col ? 1 : 0;
-    const int64_t rem = N % 128;
-    const bool xc = sw.tn_xc && N > 128 && rem >= 1 && rem <= 2 && rem - ones <= 1;
-    const int64_t tiles = cdiv(M, 512) * (xc ? N / 128 : cdiv(N, 128));
-    int best = 8; double waste = 1e30;
-    for (int S = 8; S <= 32; S += 8) {
-      const int64_t wg = tiles * (S / 8);
-      const double w = (double)rup(wg, 32) / (double)wg;
-      if (w < waste) { waste = w; best = S; }
-    }
-    return best;
-  }
-  if (kid == TSSEP_GEMM_TN_P320 && K >= 16 * 64) {
-    // 192 x 320 tiles, ONE workgroup per CU, the tiles of a K slab on one XCD (32 CUs): the multiple of 8 that fills whole
-    // rounds of 32 best (13 tiles: 56 splits = 91 workgroups per XCD in 3 rounds)
-    const int64_t tiles = cdiv(M, 192) * cdiv(N - (g->b_ones_col ? 1 : 0), 320);
-    int best = 8; double waste = 1e30;
-    for (int S = 8; S <= 64 && (int64_t)S * 8 <= ktiles; S += 8) {
-      const int64_t wg = tiles * (S / 8);
-      const double w = (double)rup(wg, 32) / (double)wg;
-      if (w < waste - 1e-9) { waste = w; best = S; }
-    }
-    return best;
-  }
-  if (kid == TSSEP_GEMM_TN_W160 && ktiles >= 64 * 8) {
-    if (const int wide = tn_w160_wide(g)) {
-      if (wide == 7) {
-        // swapped operands: the tiles of the transposed problem (three for 320 x 600 + 1), up to 96 splits as on the 320 x 128
-        // tile before (0.92 ms at S = 80, 1.06 at 64, 1.16 at 48; 777 216 rows)
-        const int64_t tiles = cdiv(N, 256) * cdiv(M, 320);
-        auto fill = [&](int S) { const int64_t wg = tiles * (S / 8); return (double)rup(wg, 32) / (double)wg; };
-        double waste = 1e30;
-        for (int S = 8; S <= 96 && (int64_t)S * 64 <= ktiles; S += 8) waste = fill(S) < waste ? fill(S) : waste;
-        for (int S = 8; S <= 96 && (int64_t)S * 64 <= ktiles; S += 8)
-          if (fill(S) <= waste * 1.07) return S;
-        return 8;
-      }
-      // 256 x 320 tiles, ONE workgroup per CU, the tiles of a K slab on one XCD (32 CUs): the multiple of 8 that fills whole
-      // rounds of 32 best, the smallest one among equals, >= 64 K tiles per split (tools/exp_wgrad_w320.py: dW_ih of birnn1,
-      // 10 tiles: 3.14 ms at S = 24, 3.25 at 48, 3.75 at 16; birnn2, 40 tiles: 3.00 at 32, 3.09 at 24, 3.43 at 48; dW_hh,
-      // 5 tiles: 48; tools/exp_wgrad_w320.py --sweep)
-      const int64_t tiles = (rup(M, 256) / 256) * cdiv(tn_w160_wide_cols(g, wide), wide == 5 ? 320 : 256);      // (extra columns ride on the VALU)
-      // (the smallest S within 7 % of the best fill: dW_ih of birnn0, 20 tiles, 5.54 ms at S = 24 (60 per XCD), 5.69-5.79 at 64
-      // (160 = five full rounds) -- and a third of the partial sums to reduce)
-      auto fill = [&](int S) { const int64_t wg = tiles * (S / 8); return (double)rup(wg, 32) / (double)wg; };
-      double waste = 1e30;
-      for (int S = 8; S <= 64 && (int64_t)S * 64 <= ktiles; S += 8) waste = fill(S) < waste ? fill(S) : waste;
-      for (int S = 8; S <= 64 && (int64_t)S * 64 <= ktiles; S += 8)
-        if (fill(S) <= waste * 1.07) return S;
-      return 8;
-    }
-    // 256 x 160 tile, two workgroups per CU, one round of at most 512 (tools/sweep_wgrad_splits.py: dW_hh 2.00 ms at
-    // S = 48, 2.30 at 40, 3.13 at 56)
-    const int64_t tiles = (rup(M, 256) / 256) * (rup(N, 160) / 160);
-    const int64_t a1 = 512 / tiles / 8 * 8, a2 = ktiles / 64 / 8 * 8;
-    const int64_t v = a1 < a2 ? a1 : a2;
-    return (int)(v > 8 ? v : 8);
-  }
-  if (kid == TSSEP_GEMM_TN_H160 && ktiles >= 64 * 8) {
-    // 320 x 128 tile, two workgroups per CU, one round of at most 512, at most 96 splits
-    const int64_t tiles = (rup(M, 320) / 320) * cdiv(N, 128);
-    int64_t v = 512 / tiles / 8 * 8;
-    if (v > 96) v = 96;
-    if (v > ktiles / 16 / 8 * 8) v = ktiles / 16 / 8 * 8;
-    return (int)(v > 8 ? v : 8);
-  }
-  const int64_t tiles = cdiv(M, 128) * cdiv(N, 128);
-  // the two largest dW_ih GEMMs of the step (K = 777 216 rows, 95 / 57 tiles): the sweep's best S is the smallest one --
-  // 8.37 vs 8.65 ms and 5.16 vs 5.24 ms standalone, -0.5 ms per step in an alternating A/B x3
-  if (K >= 400000 && tiles >= 48) return 8;
-  const int64_t smax = ktiles / min_ktiles;          // every split keeps >= min_ktiles K tiles
-  if (tiles <= 16 && ktiles >= 64 * 8) {
-    // few tiles (a projection weight gradient off the 320-row tile): one resident round of 512 workgroups -- 32 splits
-    // 1.38 ms, the 56 of the general rule 1.51 (tools/sweep_wgrad_small.py); never more splits than K tiles allow
-    int64_t v = 512 / tiles / 8 * 8;
-    if (v > smax / 8 * 8) v = smax / 8 * 8;
-    return (int)(v > 8 ? v : 8);
-  }
-  int64_t sp = cdiv(768, tiles);
-  if (sp > smax) sp = smax;
-  if (sp < 1) sp = 1;
-  if (sp > 1) {        // multiples of the XCD count: split z runs on XCD z % 8 (gemm_common.h)
-    const int64_t cap = smax / 8 * 8 > 8 ? smax / 8 * 8 : 8;
-    sp = rup(sp, 8) < cap ? rup(sp, 8) : cap;
-  }
-  return (int)(sp < 64 ? sp : 64);
 }

@@ -23,9 +23,8 @@
 // History (measured, profiles/r1_gemm_microbench_bf16x3.jsonl): a first version with one LDS
 // stage and two barriers per tile ran 113-267 TFLOP/s; BK = 64 and naive double buffering changed
 // nothing; the pipelined loop + row epilogue + tall tile run 190-320 TFLOP/s.
-#include <algorithm>
 #include <type_traits>
-#include "gemm_common.h"
+#include "gemm_rules.h"
 
 namespace {
 
@@ -1183,264 +1182,106 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16x3_tn_tall_kernel(
 
 }  // namespace
 
-int tssep_gemm_bf16x3_launch(const tssep_gemm_args* g, const gemm_detail::StoreMap& sm, int splitk,
-                             gemm_detail::GemmCall& call) {
-  // The candidates in the order they are tried; `gemm_try(call, kernel, rule)`: in automatic mode the rule decides,
-  // a forced call (tssep_gemm_f32_on) tries exactly the kernel it names.  A candidate's own launcher checks what
-  // the kernel REQUIRES and returns TSSEP_E_UNSUPPORTED otherwise (the next candidate is tried in automatic mode).
-  // The rules are stated in quantities of the request (padding waste of a tile shape, K stages per tile, bytes of
-  // the C stream) -- profiles/r4_gemm_shape_sweep.jsonl holds, per shape of a sweep over units / projs / speakers,
-  // the time of every candidate next to the one the rules pick.
-  hipStream_t s = (hipStream_t)call.stream;
-  const GemmSwitches sw = gemm_switches();
-  const bool shift = g->kperiod > 0;
-  const bool two = g->precision == 2;            // weight gradients only: the dY_lo * X_hi product dropped
-  if (g->b_ones_col && (!g->b_kmajor || shift || g->N < 2)) return TSSEP_E_UNSUPPORTED;
-  if (two && !(g->a_kmajor && g->b_kmajor)) return TSSEP_E_UNSUPPORTED;
-#define TAKEN(KID_) do { call.chosen = (KID_); if (call.dry) return TSSEP_OK; } while (0)
-  if (sw.tall && !g->a_kmajor && !g->b_kmajor && splitk == 1 && g->M >= 4 * TBM) {
-    const int64_t n256 = (g->N + 255) / 256 * 256;
-    const bool xcol_shape = g->N > 256 && g->N % 256 == 1 && (g->K & 3) == 0;      // N = 256 q + 1: q tiles + a VALU column
-    const bool pads_to_256 = g->N >= 1024 && n256 * 10 <= g->N * 11;               // < 10 % column padding
-    const bool pads_to_256_any = g->N >= 256 && n256 * 10 <= g->N * 11;            // ... also one or two column tiles (projs = 256)
-    const bool short_k = g->K < 448;               // a tile's life is mostly its C store below this
-    // Occupancy (round 4, the 8-utterance shard of the 8-GPU configuration: M = 2024 / 8096 rows): a kernel whose tiles do
-    // not fill three quarters of the CUs once leaves the chip idle -- 128 x 128 tiles on two workgroups per CU then run up
-    // to 2.7 x faster (profiles/r4_gemm_shape_sweep_b8.jsonl: 168 against 70 TFLOP/s at 8096 x 320 x 2400).  The
-    // persistent streaming kernel balances its own tile list: half the CUs suffice there.
-    const int64_t mt256 = (g->M + 255) / 256;
-    auto fills = [&](int64_t col_tiles, int64_t need) { return mt256 * col_tiles >= need; };
-    // ... and a one-workgroup-per-CU kernel whose last resident round is mostly empty loses it whole: 380 tiles = 1.48
-    // rounds of 256 run at 74 % (the 8-speaker pre-net, 97 152 x 256 x 512: 261 against 312 TFLOP/s on the persistent kernel)
-    auto rounds_ok = [&](int64_t col_tiles) { const int64_t t = mt256 * col_tiles; return t * 5 >= (t + 255) / 256 * 256 * 4; };
-    // (the persistent big tile against the persistent 256 x 128 tile, whose list is twice as fine: 90 %)
-    auto rounds_ok9 = [&](int64_t col_tiles) { const int64_t t = mt256 * col_tiles; return t * 10 >= (t + 255) / 256 * 256 * 9; };
-    // big-tile kernel (gemm_bf16x3_big.hip) where the 256-wide tile applies.  (K < 448: a tile's life is mostly its
-    // C store there -- the streaming kernel, which hides it, measured 4.14 against 4.56 ms at K = 320, N = 2400; from
-    // K = 513 up this kernel wins: 6.55 / 6.63, 3.10 / 3.42 at K = 1280, 2.75 / 3.29 at K = 2400, N = 1280; sw.big 2 =
-    // regardless of K)
-    // Round 4 (profiles/r4_gemm_shape_sweep.jsonl, units x projs x speakers): N = 256 / 512 (projs = 256) belong here too
-    // (302 against 244 TFLOP/s at 777 216 x 256 x 1024 with the Tanh store); the folded Tanh backward with the
-    // un-combining remap reads its aux operand in the unhidden epilogue -- below K = 1536 the eight-wave tiles win
-    // (280 against 230 at 194 304 x 1280 x 1024; at K = 2400, the default size, this kernel leads 338 to 300)
-    const bool aux_remap_short = g->act == 2 && sm.remap && g->K < 1536;
-    // 192 x 320 persistent tile (gemm_bf16x3_bigp320.hip, round 4) where 320-wide column tiles compute at least 10 % fewer
-    // columns than 256-wide ones (N = 320: the Tanh projections and d(input) of birnn1; N = 600: 640 against 768 columns)
-    {
-      const int64_t n320 = (g->N + 319) / 320 * 320, mt192 = (g->M + 191) / 192;
-      const int64_t t320 = mt192 * (n320 / 320);
-      if (gemm_try(call, TSSEP_GEMM_BIG_P320, sw.big_p320 && n320 * 11 <= n256 * 10 && n320 * 10 <= g->N * 11 && !g->accumulate && sm.remap <= 1 &&
-                                               t320 >= 192 && t320 * 10 >= (t320 + 255) / 256 * 256 * 9)) {
-        const int rc = tssep_gemm_bf16x3_bigp320_launch(g, sm, call);
-        if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_BIG_P320; return rc; }
-      }
-    }
-    // persistent big tile (gemm_bf16x3_bigp.hip, round 4): the same tile without the per-tile drain / dispatch / prologue and
-    // with a four times cheaper transposition -- plain / bias / Tanh stores, also remapped (the logit layer), any K.  profiles/r4_ab_gemm_big_p.jsonl: 5.57
-    // against 6.46 ms (big) at 777 216 x 2400 x 513, 3.53 against 4.15 (stream) at K = 320; the shorter fixed part of a tile
-    // also pays for more column padding than the tiled kernel's 10 %: N = 600 (768 columns computed) 1.05 against 1.12 ms on
-    // the streaming kernel
-    const bool pads_to_256_loosely = g->N >= 256 && n256 * 100 <= g->N * 130;
-    // (N = 256 q + 1 with M a multiple of 256: q tiles + the VALU column, as in the tiled kernel)
-    const int64_t ct_p = xcol_shape ? (g->N - 1) / 256 : n256 / 256;
-    if (gemm_try(call, TSSEP_GEMM_BIG_P, sw.big_p && (pads_to_256_loosely || (xcol_shape && g->M % 256 == 0 && !sm.remap)) && sm.remap <= 1 && !g->accumulate &&
-                                         fills(ct_p, 192) && rounds_ok9(ct_p))) {
-      const int rc = tssep_gemm_bf16x3_bigp_launch(g, sm, call);
-      if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_BIG_P; return rc; }
-    }
-    if (gemm_try(call, TSSEP_GEMM_BIG, sw.big && (!short_k || sw.big == 2) && (pads_to_256_any || xcol_shape) && !aux_remap_short &&
-                                       fills(xcol_shape ? (g->N - 1) / 256 : n256 / 256, 192) &&
-                                       rounds_ok(xcol_shape ? (g->N - 1) / 256 : n256 / 256))) {
-      const int rc = tssep_gemm_bf16x3_big_launch(g, sm, call);
-      if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_BIG; return rc; }
-    }
-    // persistent streaming kernel (gemm_bf16x3_stream.hip): plain row-major stores; the N = 256 q + 1 shapes keep
-    // the wide tile with its VALU column
-    if (gemm_try(call, TSSEP_GEMM_STREAM, sw.stream && !sm.remap && !(g->N > 256 && g->N % 256 == 1) && fills((g->N + 127) / 128, 128))) {
-      const int rc = tssep_gemm_bf16x3_stream_launch(g, sm, call);
-      if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_STREAM; return rc; }
-    }
-    // 256 x 160 tile where 160-wide column tiles waste >= 10 % fewer columns than 128-wide ones (N = 320: the Tanh
-    // projections and d(input) of birnn1, which the two kernels above do not take)
-    {
-      // (a looser rule -- 4 % fewer columns at short K, for the logit layer's N = 2052 -- looked 19 % better in the first,
-      // incumbent-first sweep and measured equal to slower in the interleaved one: not adopted)
-      const int64_t n160 = (g->N + 159) / 160 * 160, n128 = (g->N + BN - 1) / BN * BN;
-      if (gemm_try(call, TSSEP_GEMM_NT_W160, sw.nt_w160 && n160 * 11 <= n128 * 10 && fills(n160 / 160, 192))) {
-        const int rc = tssep_gemm_bf16x3_nt_w160_launch(g, sm, call);
-        if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_NT_W160; return rc; }
-      }
-    }
-    // wide (256 x 256) eight-wave tile where rounding N up to 256 wastes < 10 % of the columns
-    // (not below K = 448: 145 against 207 TFLOP/s on the four-wave tile for the 8-speaker logit layer, 97 152 x 4104 x 256;
-    // from K = 448 up the big-tile kernel above has taken the request unless it cannot address it)
-    if (gemm_try(call, TSSEP_GEMM_TALL4, sw.wide && pads_to_256 && !short_k && !aux_remap_short && fills(n256 / 256, 192))) {
-      TAKEN(TSSEP_GEMM_TALL4);
-      const TileMap tm4 = make_tile_map((g->M + TBM - 1) / TBM, n256 / 256, 1);
+// ---- launchers of this file's kernels, as the other files' (gemm_common.h): check what the kernel REQUIRES, stop in
+// front of the launch when call.dry ----  nt_takes: the row x row family -- unsplit, at least four 256-row tiles
+static bool nt_takes(const tssep_gemm_args* g) { return !g->a_kmajor && !g->b_kmajor && g->splitk <= 1 && g->M >= 4 * TBM; }
+// tall4 / tall2: 64 WN columns a tile; XCOL (tall4_xcol): N = 256 q + 1 -- q tiles + a VALU column
+template <int WN, bool XCOL = false> static int tall_launch(const tssep_gemm_args* g, const StoreMap& sm, const GemmCall& call) {
+  if (!nt_takes(g) || (XCOL && (!n_256q_plus_1(g->N) || (g->K & 3)))) return TSSEP_E_UNSUPPORTED;
+  if (call.dry) return TSSEP_OK;
+  const TileMap tm = make_tile_map(cdiv(g->M, TBM), XCOL ? (g->N - 1) / 256 : cdiv(g->N, 64 * WN), 1);
+#define TALL_LAUNCH(H_) hipLaunchKernelGGL((gemm_bf16x3_tall_kernel<WN, XCOL, H_>), dim3((unsigned)tile_map_blocks(tm)), dim3(128 * WN), 0, \
+    (hipStream_t)call.stream, g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->bias, g->act, g->accumulate, sm, tm)
 #ifdef TSSEP_GEMM_EXP
-      {
-#define HK(H_) case H_: hipLaunchKernelGGL((gemm_bf16x3_tall_kernel<4, false, H_>), dim3((unsigned)tile_map_blocks(tm4)), dim3(512), 0, s, \
-                         g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->bias, g->act, g->accumulate, sm, tm4); return tssep_launch_status();
-        switch (sw.hack) { HK(1) HK(2) HK(3) HK(4) HK(6) HK(8) HK(10) HK(12) HK(14) HK(16) HK(18) HK(32) HK(64) default: break; }
+#define HK(H_) case H_: TALL_LAUNCH(H_); return tssep_launch_status();
+  if constexpr (WN == 4 && !XCOL)
+    switch (gemm_switches().hack) { HK(1) HK(2) HK(3) HK(4) HK(6) HK(8) HK(10) HK(12) HK(14) HK(16) HK(18) HK(32) HK(64) default: break; }
 #undef HK
-      }
 #endif
-      hipLaunchKernelGGL(gemm_bf16x3_tall_kernel<4>, dim3((unsigned)tile_map_blocks(tm4)), dim3(512), 0, s,
-                         g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->bias, g->act,
-                         g->accumulate, sm, tm4);
-      return tssep_launch_status();
-    }
-    if (xcol_shape && gemm_try(call, TSSEP_GEMM_TALL4_XCOL, sw.xcol != 0 && fills((g->N - 1) / 256, 192))) {
-      TAKEN(TSSEP_GEMM_TALL4_XCOL);
-      const TileMap tmx = make_tile_map((g->M + TBM - 1) / TBM, (g->N - 1) / 256, 1);
-      hipLaunchKernelGGL((gemm_bf16x3_tall_kernel<4, true>), dim3((unsigned)tile_map_blocks(tmx)), dim3(512), 0, s,
-                         g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->bias, g->act,
-                         g->accumulate, sm, tmx);
-      return tssep_launch_status();
-    }
-    if (gemm_try(call, TSSEP_GEMM_TALL2, fills((g->N + BN - 1) / BN, 192))) {
-      TAKEN(TSSEP_GEMM_TALL2);
-      const TileMap tm2 = make_tile_map((g->M + TBM - 1) / TBM, (g->N + BN - 1) / BN, 1);
-      hipLaunchKernelGGL(gemm_bf16x3_tall_kernel<2>, dim3((unsigned)tile_map_blocks(tm2)), dim3(NTHREADS), 0, s,
-                         g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->bias, g->act,
-                         g->accumulate, sm, tm2);
-      return tssep_launch_status();
-    }
-  }
-  const TileMap tmap = make_tile_map((g->M + BM - 1) / BM, (g->N + BN - 1) / BN, splitk);
-  dim3 grid((unsigned)tile_map_blocks(tmap));
-  {
-    // weight gradients: both operands k-major, plain store, 16-byte rows (see gemm_bf16x3_tn_kernel)
-    const int64_t nreal = g->N - (g->b_ones_col ? 1 : 0);
-    const int64_t ks = g->b_kshift < 0 ? -g->b_kshift : g->b_kshift;
-    if (sw.tn && g->a_kmajor && g->b_kmajor && !sm.remap && !g->bias && g->act == 0 && (g->lda & 3) == 0 &&
-        (g->ldb & 3) == 0 && aligned16(g->A) && aligned16(g->B) && ((g->M + 3) & ~(int64_t)3) <= g->lda &&
-        nreal >= 1 && ((nreal + 3) & ~(int64_t)3) <= g->ldb && g->M >= 4 && (!shift || (ks <= 32 && ks < g->K))) {
-      // Occupancy of a weight gradient: its tiles times the splits its K allows (>= 8 K tiles of 16 rows per split, <= 64
-      // splits) must fill three quarters of the CUs, else the next smaller tile is tried (the 8-utterance shard: K = 2024
-      // rows -> 15 splits; the 256 x 160 tile of dW_hh then has 150 workgroups at most: 54 against 89 TFLOP/s on 128 x 128)
-      const int64_t max_splits = std::min<int64_t>(64, std::max<int64_t>(1, ((g->K + 15) / 16) / 8));
-      auto tn_fills = [&](int64_t tiles) { return tiles * max_splits >= 192; };
-      {   // 256 x 320 workgroups of gemm_bf16x3_tn_w160.hip (round 5) for the dW_ih GEMMs whose input width is a multiple of
-          // 320 (+ the ones column): birnn1 (N = 321) 3.14 against 3.79 ms on the 192 x 320 tile, birnn2 (N = 1281) 3.00 against
-          // 3.61 ms on the 512 x 128 tile (tools/exp_wgrad_w320.py) -- 31 % / 28 % fewer staged bytes per MFMA; M pads to 256
-          // by at most 8 % (the logit layer's M = 2052 stays on the 192-row tile)
-        const int64_t nr = g->N - (g->b_ones_col ? 1 : 0);
-        const int64_t m256w = (g->M + 255) / 256 * 256;
-        const int wide = tn_w160_wide(g);
-        // (256 x 256 workgroups, round 5: dW_ih of birnn0, N = 513 + 1 -- two column tiles + two VALU columns, 20 % fewer staged
-        // bytes per MFMA than the 512 x 128 tile)
-        const int64_t ncols = wide ? tn_w160_wide_cols(g, wide) : 0;
-        const bool takes = wide == 4 || (wide == 5 && (ncols + 319) / 320 * 320 <= (g->N + 127) / 128 * 128);
-        const int64_t tilesw = (m256w / 256) * ((ncols + (wide == 4 ? 255 : 319)) / (wide == 4 ? 256 : 320));
-        // (swapped operands, round 5: the projection weight gradients -- 320 x 600 + 1 -- 0.92 against 1.34 ms on the 320 x 128 tile)
-        // (from K = 81 920 rows: the three tiles of the swapped problem need ~80 splits of >= 64 K tiles each to fill the chip)
-        if (gemm_try(call, TSSEP_GEMM_TN_W160, sw.tn_w160 && wide == 7 && !two && g->K >= 80 * 64 * 16)) {
-          const int rc = tssep_gemm_bf16x3_tn_w160_launch(g, sm, splitk, two ? 1 : 0, call);
-          if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_TN_W160; return rc; }
-        }
-        // (M pads to 256-row tiles by at most 13 %: the logit layer's 2052 -> 2304, 0.69 against 0.83 ms on the 192 x 320 tile)
-        if (gemm_try(call, TSSEP_GEMM_TN_W160, sw.tn_w160 && !shift && takes && g->M >= 1024 && (m256w - g->M) * 100 <= 13 * g->M &&
-                                                   tn_fills(tilesw))) {
-          const int rc = tssep_gemm_bf16x3_tn_w160_launch(g, sm, splitk, two ? 1 : 0, call);
-          if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_TN_W160; return rc; }
-        }
-      }
-      {   // 192 x 320 tile (gemm_bf16x3_tn_p320.hip, round 4) where it computes at least 10 % less than the 512 x 128 tile:
-          // N = 320 (+ the ones column) -- dW_ih of birnn1: 2496 x 320 against 2560 x 384, the logit layer's weight gradient
-          // (M = 2052): 2112 x 320 against 2560 x 384
-        const int64_t nr = g->N - (g->b_ones_col ? 1 : 0);
-        const int64_t a320 = ((g->M + 191) / 192 * 192) * ((nr + 319) / 320 * 320);
-        const int64_t rem = g->N % 128, xcn = (g->N > 128 && rem >= 1 && rem <= 2 && rem - (g->b_ones_col ? 1 : 0) <= 1) ? g->N / 128 * 128 : (g->N + 127) / 128 * 128;
-        const int64_t a512 = ((g->M + 511) / 512 * 512) * xcn;
-        if (gemm_try(call, TSSEP_GEMM_TN_P320, sw.tn_p320 && !shift && !two && g->M >= 768 && a320 * 100 <= a512 * 90 &&
-                                                   tn_fills(((g->M + 191) / 192) * ((nr + 319) / 320)))) {
-          const int rc = tssep_gemm_bf16x3_tn_p320_launch(g, sm, splitk, two ? 1 : 0, call);
-          if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_TN_P320; return rc; }
-        }
-      }
-      {   // big-tile weight-gradient kernel: unshifted, M padded to 512 by at most a quarter (the dW_ih GEMMs: M = 8 units; round 4:
-          // the logit layer's M = speakers x 513 = 2052 / 4104 too -- 297 against 232 and 278 against 211 TFLOP/s on the tiles
-          // the 10 % rule of round 3 left them, profiles/r4_gemm_shape_sweep.jsonl)
-        const int64_t m512 = (g->M + 511) / 512 * 512;
-        if (gemm_try(call, TSSEP_GEMM_TN_BIG, sw.tn_big && !shift && g->M >= 1024 && m512 * 4 <= g->M * 5 &&
-                                                  tn_fills((m512 / 512) * ((g->N + 127) / 128)))) {
-          const int rc = tssep_gemm_bf16x3_tn_big_launch(g, sm, splitk, two ? 1 : 0, call);
-          if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_TN_BIG; return rc; }
-        }
-      }
-      {   // 256 x 160 tile where 160-wide column tiles waste >= 10 % fewer columns than 128-wide ones (dW_hh: N = units = 300)
-        const int64_t n160 = (g->N + 159) / 160 * 160, n128 = (g->N + BN - 1) / BN * BN;
-        if (gemm_try(call, TSSEP_GEMM_TN_W160, sw.tn_w160 && n160 * 11 <= n128 * 10 && tn_fills(((g->M + 255) / 256) * (n160 / 160)))) {
-          const int rc = tssep_gemm_bf16x3_tn_w160_launch(g, sm, splitk, two ? 1 : 0, call);
-          if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_TN_W160; return rc; }
-        }
-      }
-      {   // 320 x 128 tile where 320-row tiles waste >= 10 % fewer rows than 128-row ones (the projection weight
-          // gradients: M = projs = 320, N = 2 units + 1: 1.18 vs 1.38 ms at each kernel's best split count), four column
-          // tiles or more (one column tile: 0.13 vs 0.08 ms, profiles/r3_wgrad_h160_sweep.jsonl)
-        const int64_t m320 = (g->M + 319) / 320 * 320, m128 = (g->M + BM - 1) / BM * BM;
-        if (gemm_try(call, TSSEP_GEMM_TN_H160, sw.tn_h160 && !shift && m320 * 11 <= m128 * 10 && g->N > 3 * BN &&
-                                                   tn_fills((m320 / 320) * ((g->N + 127) / 128)))) {
-          const int rc = tssep_gemm_bf16x3_tn_h160_launch(g, sm, splitk, two ? 1 : 0, call);
-          if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = TSSEP_GEMM_TN_H160; return rc; }
-        }
-      }
-      const int64_t m256 = (g->M + TTM - 1) / TTM * TTM;
-      // rule 4: the time-shifted dW_hh GEMMs (-2.3 ms per step, alternating A/B) and, round 3, the unshifted ones
-      // with at most 3 or at least 9 column tiles (dW_ih of birnn1: N = 321, birnn2: N = 1281 -- 4.89 vs 5.27 ms and
-      // 4.28 vs 4.55 ms with the split counts tssep_gemm_wgrad_splits gives them, profiles/r3_wgrad_tile_sweep.jsonl);
-      // the 5-column-tile shapes (N = 514 / 554) stay on the 128 x 128 tile: there the larger tile measured equal or
-      // slower at every split count.  (1: all eligible, 2: shifted only, 3: unshifted only, 0: off)
-      const int tmode = sw.tn_tall;
-      const int64_t ntl = (g->N + BN - 1) / BN;
-      const bool want = tmode == 1 || (tmode == 2 && shift) || (tmode == 3 && !shift) ||
-                        (tmode == 4 && (shift || ntl <= 3 || ntl >= 9));
-      if (g->M >= 1024 && (m256 - g->M) * 100 <= 8 * g->M && (!shift || ks <= 16) &&
-          gemm_try(call, TSSEP_GEMM_TN_TALL, want && tn_fills((m256 / TTM) * ntl))) {
-        TAKEN(TSSEP_GEMM_TN_TALL);
-        const TileMap tmt = make_tile_map(m256 / TTM, (g->N + BN - 1) / BN, splitk);
-        dim3 gridt((unsigned)tile_map_blocks(tmt));
-#define TT_LAUNCH(SH, TW, KS, KP, ONES) hipLaunchKernelGGL((gemm_bf16x3_tn_tall_kernel<SH, TW>), gridt, dim3(NTHREADS), 0, s, \
-            g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, KS, KP, g->accumulate, sm.ldc, splitk, g->c_split_stride, tmt, ONES)
-        if (shift) { if (two) TT_LAUNCH(true, true, (int)g->b_kshift, (int)g->kperiod, 0); else TT_LAUNCH(true, false, (int)g->b_kshift, (int)g->kperiod, 0); }
-        else { if (two) TT_LAUNCH(false, true, 0, 1, g->b_ones_col); else TT_LAUNCH(false, false, 0, 1, g->b_ones_col); }
-#undef TT_LAUNCH
-        return tssep_launch_status();
-      }
-      if (gemm_try(call, TSSEP_GEMM_TN, true)) {
-        TAKEN(TSSEP_GEMM_TN);
-#define TN_LAUNCH(SH, TW, ...) hipLaunchKernelGGL((gemm_bf16x3_tn_kernel<SH, TW>), grid, dim3(NTHREADS), 0, s, __VA_ARGS__)
-        if (shift) {
-          if (two) TN_LAUNCH(true, true, g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, (int)g->b_kshift,
-                             (int)g->kperiod, g->accumulate, sm.ldc, splitk, g->c_split_stride, tmap, 0);
-          else TN_LAUNCH(true, false, g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, (int)g->b_kshift,
-                         (int)g->kperiod, g->accumulate, sm.ldc, splitk, g->c_split_stride, tmap, 0);
-        } else {
-          if (two) TN_LAUNCH(false, true, g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, 0, 1, g->accumulate,
-                             sm.ldc, splitk, g->c_split_stride, tmap, g->b_ones_col);
-          else TN_LAUNCH(false, false, g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, 0, 1, g->accumulate,
-                         sm.ldc, splitk, g->c_split_stride, tmap, g->b_ones_col);
-        }
+  TALL_LAUNCH(0);
+#undef TALL_LAUNCH
+  return tssep_launch_status();
+}
+// tn_tall (TALL: M >= 1024 padding to 256-row tiles by at most 8 %, |shift| <= 16) / tn: <time shift, two products> of the request
+template <bool TALL> static int tn_launch(const tssep_gemm_args* g, const StoreMap& sm, int splitk, int two, const GemmCall& call) {
+  const GemmRequest q(g, sm, splitk);
+  const int64_t mt = cdiv(g->M, TALL ? TTM : BM);
+  if (!tn_takes(q) || (TALL && (g->M < 1024 || (mt * TTM - g->M) * 100 > 8 * g->M || (q.shift && q.ks() > 16)))) return TSSEP_E_UNSUPPORTED;
+  if (call.dry) return TSSEP_OK;
+  const TileMap tm = make_tile_map(mt, cdiv(g->N, BN), splitk);
+#define TN_LAUNCH(KERNEL_, SH, TW) hipLaunchKernelGGL((KERNEL_<SH, TW>), dim3((unsigned)tile_map_blocks(tm)), dim3(NTHREADS), 0, \
+    (hipStream_t)call.stream, g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, SH ? (int)g->b_kshift : 0, SH ? (int)g->kperiod : 1, \
+    g->accumulate, sm.ldc, splitk, g->c_split_stride, tm, SH ? 0 : g->b_ones_col)
+#define TN_LAUNCH_ANY(KERNEL_) do {                                                                         \
+    if (q.shift) { if (two) TN_LAUNCH(KERNEL_, true, true); else TN_LAUNCH(KERNEL_, true, false); }         \
+    else { if (two) TN_LAUNCH(KERNEL_, false, true); else TN_LAUNCH(KERNEL_, false, false); } } while (0)
+  if constexpr (TALL) TN_LAUNCH_ANY(gemm_bf16x3_tn_tall_kernel); else TN_LAUNCH_ANY(gemm_bf16x3_tn_kernel);
+#undef TN_LAUNCH_ANY
 #undef TN_LAUNCH
-        return tssep_launch_status();
-      }
-    }
-  }
-  if (two || !gemm_try(call, TSSEP_GEMM_PIPE, true)) return TSSEP_E_UNSUPPORTED;
-  TAKEN(TSSEP_GEMM_PIPE);
-#define LAUNCH(AK, BKM, SH)                                                                      \
-  hipLaunchKernelGGL((gemm_bf16x3_pipe_kernel<32, AK, BKM, SH>), grid, dim3(NTHREADS), 0, s,     \
-                     g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->b_kshift,            \
-                     g->kperiod, g->bias, g->act, g->accumulate, sm, splitk, g->c_split_stride,  \
-                     tmap, g->b_ones_col)
-  const bool fast = shift && g->kperiod >= 32 && (g->b_kshift == 1 || g->b_kshift == -1);
+  return tssep_launch_status();
+}
+// pipe, K staged PBK at a time: every operand layout and store, not the two-product weight gradients (a template as the
+// two above: the compiler then emits this file's kernels in the order of the table, as it always has)
+template <int PBK> static int pipe_launch(const tssep_gemm_args* g, const StoreMap& sm, int splitk, int two, const GemmCall& call) {
+  if (two) return TSSEP_E_UNSUPPORTED;
+  if (call.dry) return TSSEP_OK;
+  const TileMap tmap = make_tile_map(cdiv(g->M, BM), cdiv(g->N, BN), splitk);
+#define LAUNCH(AK, BKM, SH) hipLaunchKernelGGL((gemm_bf16x3_pipe_kernel<PBK, AK, BKM, SH>), dim3((unsigned)tile_map_blocks(tmap)), dim3(NTHREADS), 0, \
+                     (hipStream_t)call.stream, g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->b_kshift,  \
+                     g->kperiod, g->bias, g->act, g->accumulate, sm, splitk, g->c_split_stride, tmap, g->b_ones_col)
+  const bool shift = g->kperiod > 0, fast = shift && g->kperiod >= 32 && (g->b_kshift == 1 || g->b_kshift == -1);
   if (!g->a_kmajor && !g->b_kmajor) LAUNCH(false, false, 0);
   else if (!g->a_kmajor && shift) { if (fast) LAUNCH(false, true, 2); else LAUNCH(false, true, 1); }
   else if (!g->a_kmajor) LAUNCH(false, true, 0);
   else if (shift) { if (fast) LAUNCH(true, true, 2); else LAUNCH(true, true, 1); }
   else LAUNCH(true, true, 0);
 #undef LAUNCH
-#undef TAKEN
   return tssep_launch_status();
+}
+
+// ---- THE candidate table: the rows in the order they are tried -- the order is the policy.  `gemm_try(call, kernel,
+// rule)`: in automatic mode the row's rule (gemm_rules.h) decides, a forced call (tssep_gemm_f32_on) tries exactly the
+// kernel it names.  A row's launcher checks what the kernel REQUIRES and returns TSSEP_E_UNSUPPORTED otherwise (the next
+// row is tried in automatic mode).  tn_w160 has three rows: its swapped, wide and 160-column forms.
+using NtLaunch = int(const tssep_gemm_args*, const StoreMap&, const GemmCall&);
+using TnLaunch = int(const tssep_gemm_args*, const StoreMap&, int, int, const GemmCall&);
+template <NtLaunch F> static int nt(const GemmRequest& q, const GemmCall& c) { return F(q.g, q.sm, c); }
+template <TnLaunch F> static int tn(const GemmRequest& q, const GemmCall& c) { return F(q.g, q.sm, q.splitk, q.two ? 1 : 0, c); }
+static const GemmCandidate kCandidates[] = {
+    {TSSEP_GEMM_BIG_P320, "big_p320", GEMM_NT, wants_big_p320, nt<tssep_gemm_bf16x3_bigp320_launch>, nullptr},
+    {TSSEP_GEMM_BIG_P, "big_p", GEMM_NT, wants_big_p, nt<tssep_gemm_bf16x3_bigp_launch>, nullptr},
+    {TSSEP_GEMM_BIG, "big", GEMM_NT, wants_big, nt<tssep_gemm_bf16x3_big_launch>, nullptr},
+    {TSSEP_GEMM_STREAM, "stream", GEMM_NT, wants_stream, nt<tssep_gemm_bf16x3_stream_launch>, nullptr},
+    {TSSEP_GEMM_NT_W160, "nt_w160", GEMM_NT, wants_nt_w160, nt<tssep_gemm_bf16x3_nt_w160_launch>, nullptr},
+    {TSSEP_GEMM_TALL4, "tall4", GEMM_NT, wants_tall4, nt<tall_launch<4>>, nullptr},
+    {TSSEP_GEMM_TALL4_XCOL, "tall4_xcol", GEMM_NT, wants_tall4_xcol, nt<tall_launch<4, true>>, nullptr},
+    {TSSEP_GEMM_TALL2, "tall2", GEMM_NT, wants_tall2, nt<tall_launch<2>>, nullptr},
+    {TSSEP_GEMM_TN_W160, "tn_w160", GEMM_TN, wants_tn_w160_swapped, tn<tssep_gemm_bf16x3_tn_w160_launch>, splits_tn_w160},
+    {TSSEP_GEMM_TN_W160, "tn_w160", GEMM_TN, wants_tn_w160_wide, tn<tssep_gemm_bf16x3_tn_w160_launch>, splits_tn_w160},
+    {TSSEP_GEMM_TN_P320, "tn_p320", GEMM_TN, wants_tn_p320, tn<tssep_gemm_bf16x3_tn_p320_launch>, splits_tn_p320},
+    {TSSEP_GEMM_TN_BIG, "tn_big", GEMM_TN, wants_tn_big, tn<tssep_gemm_bf16x3_tn_big_launch>, splits_tn_big},
+    {TSSEP_GEMM_TN_W160, "tn_w160", GEMM_TN, wants_tn_w160, tn<tssep_gemm_bf16x3_tn_w160_launch>, splits_tn_w160},
+    {TSSEP_GEMM_TN_H160, "tn_h160", GEMM_TN, wants_tn_h160, tn<tssep_gemm_bf16x3_tn_h160_launch>, splits_tn_h160},
+    {TSSEP_GEMM_TN_TALL, "tn_tall", GEMM_TN, wants_tn_tall, tn<tn_launch<true>>, nullptr},
+    {TSSEP_GEMM_TN, "tn", GEMM_TN, wants_always, tn<tn_launch<false>>, nullptr},
+    {TSSEP_GEMM_PIPE, "pipe", GEMM_ANY, wants_always, tn<pipe_launch<32>>, nullptr},
+};
+
+const GemmCandidate* tssep_gemm_bf16x3_candidate(int32_t kid) {
+  for (const GemmCandidate& c : kCandidates) if (c.kid == kid) return &c;
+  return nullptr;
+}
+
+int tssep_gemm_bf16x3_launch(const tssep_gemm_args* g, const StoreMap& sm, int splitk, GemmCall& call) {
+  const GemmRequest q(g, sm, splitk);
+  if (g->b_ones_col && (!g->b_kmajor || q.shift || g->N < 2)) return TSSEP_E_UNSUPPORTED;
+  if (q.two && !(g->a_kmajor && g->b_kmajor)) return TSSEP_E_UNSUPPORTED;
+  // the preconditions of a row's family; GEMM_ANY: every request but the two-product weight gradients
+  const bool family_open[] = {/* GEMM_ANY */ !q.two, /* GEMM_NT */ q.sw.tall && nt_takes(g), /* GEMM_TN */ q.sw.tn && tn_takes(q)};
+  for (const GemmCandidate& c : kCandidates) {
+    if (!family_open[c.family] || !gemm_try(call, c.kid, c.wants(q))) continue;
+    const int rc = c.launch(q, call);
+    if (rc != TSSEP_E_UNSUPPORTED) { call.chosen = c.kid; return rc; }
+  }
+  return TSSEP_E_UNSUPPORTED;
 }

@@ -22,7 +22,7 @@
 //  * same k order per output element and same epilogue arithmetic as the other split-bf16 kernels: bit-identical.
 #include <cstdlib>
 #include <type_traits>
-#include "gemm_common.h"
+#include "gemm_rules.h"
 
 namespace {
 
@@ -287,7 +287,7 @@ int tssep_gemm_bf16x3_big_launch(const tssep_gemm_args* g, const gemm_detail::St
   if ((int64_t)GM * g->lda * 4 + g->K * 4 >= (int64_t)1 << 31 || (int64_t)GN * g->ldb * 4 + g->K * 4 >= (int64_t)1 << 31)
     return TSSEP_E_UNSUPPORTED;
   const TileMap tm = make_tile_map((g->M + GM - 1) / GM, (g->N + GN - 1) / GN, 1);
-  if (g->N > 256 && g->N % 256 == 1) {        // 256 q + 1 columns: q tiles + one VALU column
+  if (n_256q_plus_1(g->N)) {        // 256 q + 1 columns: q tiles + one VALU column
     if (g->K & 3) return TSSEP_E_UNSUPPORTED;
     if (call.dry) return TSSEP_OK;
     const TileMap tmx = make_tile_map((g->M + GM - 1) / GM, (g->N - 1) / GN, 1);

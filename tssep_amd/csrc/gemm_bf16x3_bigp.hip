@@ -23,7 +23,7 @@
 // (gemm_bf16x3_big_schedule.inc).
 #include <cstdlib>
 #include <type_traits>
-#include "gemm_common.h"
+#include "gemm_rules.h"
 
 namespace {
 
@@ -566,7 +566,7 @@ int tssep_gemm_bf16x3_bigp_launch(const tssep_gemm_args* g, const gemm_detail::S
   }
   // bias and the Tanh only: a store that reads (accumulate, the folded Tanh backward's aux operand) keeps the tiled kernel
   // N = 256 q + 1: q tiles + one VALU column, when no row of a tile needs clamping (see the kernel)
-  const bool xcol = !remap && g->act != 2 && g->N > 256 && g->N % 256 == 1;
+  const bool xcol = !remap && g->act != 2 && n_256q_plus_1(g->N);
   if (xcol && ((g->K & 3) || g->K > XROW || g->N > XBIAS || g->M % GM)) return TSSEP_E_UNSUPPORTED;
   if (g->accumulate || g->N > PBIAS) return TSSEP_E_UNSUPPORTED;
   // the folded Tanh backward: 16-byte rows of y, a wave tile's 128 rows below 2 GB

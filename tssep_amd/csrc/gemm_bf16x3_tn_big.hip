@@ -20,7 +20,7 @@
 //  * same k order and MFMA sequence per output element as the tn kernels.
 #include <cstdlib>
 #include <type_traits>
-#include "gemm_common.h"
+#include "gemm_rules.h"
 
 namespace {
 
@@ -352,10 +352,8 @@ int tssep_gemm_bf16x3_tn_big_launch(const tssep_gemm_args* g, const gemm_detail:
   // (one real column at most; the ones column of b_ones_col is the last column)
   if (call.dry) return TSSEP_OK;
   const int rem = (int)(g->N % WN), ones = g->b_ones_col ? 1 : 0;
-  int xc = 0;
-  if (gemm_switches().tn_xc && g->N > WN && rem >= 1 && rem <= 2 && rem - ones <= 1)
-    xc = 10 * (rem - ones) + ones;
-  const TileMap tm = make_tile_map((g->M + WM - 1) / WM, xc ? g->N / WN : (g->N + WN - 1) / WN, splitk);
+  const int xc = n_128q_plus_12(g->N, ones, gemm_switches().tn_xc) ? 10 * (rem - ones) + ones : 0;
+  const TileMap tm = make_tile_map((g->M + WM - 1) / WM, tn_big_col_tiles(g->N, ones, gemm_switches().tn_xc), splitk);
   const int slow_first = splitk > 1 && tm.NT > 1 && gemm_switches().hack != 7;
 #define TNB_LAUNCH(TW, XC_) hipLaunchKernelGGL((gemm_bf16x3_tn_big_kernel<TW, XC_>), dim3((unsigned)tile_map_blocks(tm)), dim3(WNT), 0, \
       (hipStream_t)stream, g->A, g->B, g->C, g->M, g->N, g->K, g->lda, g->ldb, g->accumulate, sm.ldc, splitk, g->c_split_stride, tm, g->b_ones_col, slow_first)

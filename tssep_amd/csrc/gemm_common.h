@@ -495,7 +495,7 @@ __device__ __forceinline__ unsigned bf16_pair(float a, float b) {
 }  // namespace gemm_detail
 
 // split-bf16 (bf16x3) family, defined in gemm_bf16x3*.hip.  Every launcher checks what its kernel REQUIRES and returns
-// TSSEP_E_UNSUPPORTED otherwise; with call.dry it stops in front of the launch (plan query).  gemm_dispatch.h.
+// TSSEP_E_UNSUPPORTED otherwise; with call.dry it stops in front of the launch (plan query).  gemm_dispatch.h, gemm_rules.h.
 int tssep_gemm_bf16x3_launch(const tssep_gemm_args* g, const gemm_detail::StoreMap& sm, int splitk, gemm_detail::GemmCall& call);
 // persistent streaming variant (row x row, plain store), gemm_bf16x3_stream.hip
 int tssep_gemm_bf16x3_stream_launch(const tssep_gemm_args* g, const gemm_detail::StoreMap& sm, const gemm_detail::GemmCall& call);
@@ -521,7 +521,7 @@ namespace gemm_detail {
 // 7 -> 256 x 320 tiles with SWAPPED operands (unshifted): few output rows (192 < M <= 320: one 320-column tile of the
 //      swapped problem), many columns (N = 4 q >= 512, padding to 256-row tiles by at most 30 %) -- the projection weight
 //      gradients (320 x 600 + 1); the ones column becomes a row of ones on the MFMAs;
-// 0 -> the 256 x 160 workgroups.  The launcher, the dispatcher and the split rule (gemm.hip) all ask here.
+// 0 -> the 256 x 160 workgroups.  The launcher, the rules and the split rule (gemm_rules.h) all ask here.
 inline int tn_w160_wide(const tssep_gemm_args* g) {
   if (g->M & 3) return 0;
   const int64_t xo = g->b_ones_col ? 1 : 0, nr = g->N - xo;

@@ -1,7 +1,7 @@
-// Dispatch table of tssep_gemm_f32 (gemm.hip, gemm_bf16x3*.hip): which kernel takes which request, and the
-// split count a weight gradient should be launched with.  ONE place decides; the launcher, the plan query
-// (tssep_gemm_plan) and the split query (tssep_gemm_wgrad_splits) all walk the same candidates, and a caller may
-// name a kernel itself (tssep_gemm_f32_on: the A/B tools and the shape sweep time every candidate that way).
+// Dispatch of tssep_gemm_f32 (gemm.hip, gemm_bf16x3*.hip): which kernel takes which request, and the split count a
+// weight gradient should be launched with.  ONE place decides -- the candidate table of gemm_bf16x3.hip with the rules
+// of gemm_rules.h; the launcher, the plan query (tssep_gemm_plan) and the split query (tssep_gemm_wgrad_splits) all walk
+// it, and a caller may name a kernel itself (tssep_gemm_f32_on: the A/B tools and the shape sweep time every candidate).
 //
 // Production builds carry NO run-time switch: `gemm_switches()` is a constant, nothing in the library reads the
 // environment, nothing global is mutated (include/tssep_hip.h, conventions).  The experiment build (`make exp`,

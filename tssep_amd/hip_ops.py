@@ -410,9 +410,10 @@ def _gemm_args(A, lda, B, ldb, C, ldc, M, N, K, a_kmajor=False, b_kmajor=False, 
 # Kernel ids of include/tssep_hip.h (TSSEP_GEMM_*).  The library chooses by itself; tests, the shape sweep and the
 # A/B tools may name kernels to be tried first: GEMM_PREFER = ("stream", "tall2") launches the first one of them that
 # covers the request (asked through tssep_gemm_plan) and the library's own choice when none does.
-GEMM_KERNELS = {"auto": 0, "f32": 1, "pipe": 2, "tall2": 3, "tall4": 4, "tall4_xcol": 5, "big": 6, "stream": 7,
-                "nt_w160": 8, "tn": 9, "tn_tall": 10, "tn_big": 11, "tn_w160": 12, "tn_h160": 13, "big_p": 14, "big_p320": 15, "tn_p320": 16}
-GEMM_KERNEL_NAMES = {v: k for k, v in GEMM_KERNELS.items()}
+GEMM_KERNEL_NAMES = {}      # id -> name, as the library's candidate table names them (tssep_gemm_kernel_name; "?" past the last)
+while (_name := _lib.lib().tssep_gemm_kernel_name(len(GEMM_KERNEL_NAMES))) != b"?":
+    GEMM_KERNEL_NAMES[len(GEMM_KERNEL_NAMES)] = _name.decode()
+GEMM_KERNELS = {name: kid for kid, name in GEMM_KERNEL_NAMES.items()}
 GEMM_PREFER = ()
 GEMM_LOG = None          # a list: (kernel name, M, N, K) of every launch is appended (tests)
 RECURRENCE_LOG = None    # a list: dict(kernel, direction, N, T, H, groups) of every recurrence launch (Trainer: the kernel plan)
