@@ -427,6 +427,24 @@ int tssep_cond_cat_fwd(const float* pre, int64_t ld_pre, const float* aux, int64
                        int trials, void* stream);
 int tssep_cond_cat_bwd(const float* dxs, int64_t ld_dxs, float* dpre, int64_t ld_dpre,
                        int64_t B, int64_t K, int64_t T, int F, int trials, void* stream);
+/* The same conditioning on FRAME-WISE embeddings (net.py:866-867, aux_time = "time"): aux rows are (b, spk, ta) with
+ * leading dimension ld_aux, frame t reads row ta = t / stride, and Ta == ceil(T / stride) (anything else, or
+ * stride < 1: TSSEP_E_SHAPE before any launch).  stride = 1 is the reference's branch; stride >= T is one row per
+ * speaker.  Row decomposition, (trial, k) order and the choice between 16-byte and 4-byte accesses are those of the
+ * entry points above: a time-constant aux gives their bits.  d(pre) of cat does not read aux: tssep_cond_cat_bwd.
+ * Algorithmic HBM bytes (R = B*trials*K*T rows of xs; the aux rows are re-read `stride` times from the caches):
+ *   mul fwd  4 * (R*F + B*T*F + B*K*Ta*F)          (pre re-read trials*K times from the caches)
+ *   mul bwd  4 * (R*F + B*K*Ta*F + B*T*F)
+ *   cat fwd  4 * (R*(F+E) + B*T*F + B*K*Ta*E) */
+int tssep_cond_mul_t_fwd(const float* pre, int64_t ld_pre, const float* aux, int64_t ld_aux, float* xs,
+                         int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
+                         int64_t stride, void* stream);
+int tssep_cond_mul_t_bwd(const float* dxs, int64_t ld_dxs, const float* aux, int64_t ld_aux, float* dpre,
+                         int64_t ld_dpre, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
+                         int64_t stride, void* stream);
+int tssep_cond_cat_t_fwd(const float* pre, int64_t ld_pre, const float* aux, int64_t ld_aux, float* xs,
+                         int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int E, int trials, int64_t Ta,
+                         int64_t stride, void* stream);
 
 /* ------------------------------------------------- learned embeddings (aux.hip) ----
  * Gradient of the conditioning with respect to the embedding (aux_net / a trainable embedding, net.py:816-838):
@@ -445,6 +463,26 @@ int tssep_cond_mul_aux_bwd(const float* dxs, int64_t ld_dxs, const float* pre, i
                            void* stream);
 int tssep_cond_cat_aux_bwd(const float* dxs, int64_t ld_dxs, float* d_aux, int64_t ld_daux, void* ws,
                            int64_t B, int64_t K, int64_t T, int F, int E, int trials, void* stream);
+/* The same gradient for FRAME-WISE embeddings (rows (b, s, ta), see tssep_cond_mul_t_fwd): bucket ta holds the frames
+ * ta*stride .. min((ta+1)*stride, T) - 1 (the last bucket may be shorter; stride >= T: one bucket of all T frames)
+ *   mul: d_aux[(b,s,ta), f] = sum_tr sum_{t in bucket ta} dxs[(b,tr,(s-tr) mod K,t), f] * pre[(b,t), f]
+ *   cat: d_aux[(b,s,ta), e] = sum_tr sum_{t in bucket ta} dxs[(b,tr,(s-tr) mod K,t), F+e]
+ * One wave per (b, s, ta, chunk of 16 frames of the bucket) adds its frames in ascending (trial, frame) order into one
+ * accumulator per column; buckets of at most 16 frames are stored straight to d_aux (one launch), longer ones go
+ * through the workspace and a second launch adds the chunks in ascending order.  No atomics: bit-identical from run to
+ * run.  16-byte loads under the conditions of tssep_cond_*_aux_bwd.
+ * ws: caller-owned, tssep_cond_aux_t_bwd_workspace_bytes(B, K, T, F, E, Ta, stride) bytes (E = 0: mul; host-only;
+ * -1 = bad shape; 0 = no workspace is needed and ws may be NULL).
+ * Algorithmic HBM bytes: 4 * B*trials*K*T * C (dxs columns read, C = F or E) [+ 4 * B*T*F of pre, re-read K*trials
+ * times from the caches] + 4 * B*K*Ta*C. */
+int64_t tssep_cond_aux_t_bwd_workspace_bytes(int64_t B, int64_t K, int64_t T, int F, int E, int64_t Ta,
+                                             int64_t stride);
+int tssep_cond_mul_aux_t_bwd(const float* dxs, int64_t ld_dxs, const float* pre, int64_t ld_pre, float* d_aux,
+                             int64_t ld_daux, void* ws, int64_t B, int64_t K, int64_t T, int F, int trials,
+                             int64_t Ta, int64_t stride, void* stream);
+int tssep_cond_cat_aux_t_bwd(const float* dxs, int64_t ld_dxs, float* d_aux, int64_t ld_daux, void* ws,
+                             int64_t B, int64_t K, int64_t T, int F, int E, int trials, int64_t Ta,
+                             int64_t stride, void* stream);
 /* InstanceNorm (mode 0, net.py:250-285: (x - mean) / std, unbiased 0 / 1) and InstanceNorm_v2 (mode 1, net.py:288-330:
  * (x - mean) / (||x - mean|| / sqrt(count))) over x [R, n, C] (rows (r,t), leading dimension ld_x).  axis 0: statistics
  * along the last axis, mean / rscale [R*n]; axis 1: along the time axis, mean / rscale [R*C].  The variance is summed

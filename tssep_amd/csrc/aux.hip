@@ -95,6 +95,77 @@ __global__ void cond_aux_bwd_reduce_kernel(const float* __restrict__ part, int64
   }
 }
 
+// ---- d(conditioning) / d(frame-wise embedding) ------------------------------------------------------------------
+// aux rows are (b, s, ta); bucket ta holds the frames [ta stride, min((ta + 1) stride, T)): `stride` of them, fewer in the
+// last bucket, all T when stride >= T.  One WAVE per (b, s, ta, chunk of AUX_TFR frames of the bucket, tile of 64 lanes):
+// it adds the frames of its chunk in ascending (trial, frame) order into one accumulator per column (four loads in
+// flight per lane), so nothing is shared between waves.  A bucket of at most AUX_TFR frames is one chunk and goes
+// straight to d_aux; longer buckets go to the workspace [chunk][(b, s, ta)][ncol] and cond_aux_bwd_reduce_kernel adds
+// the chunks in ascending order.  A chunk behind the end of the last bucket stores zeros.
+constexpr int AUX_TFR = 16;
+template <bool VEC, bool MUL>
+__global__ __launch_bounds__(256) void cond_aux_t_bwd_partial_kernel(
+    const float* __restrict__ dxs, int64_t ld_dxs, const float* __restrict__ pre, int64_t ld_pre,
+    float* __restrict__ out, int64_t ld_out, int64_t BSA, int64_t K, int64_t T, int trials, int64_t Ta, int64_t stride,
+    int64_t nchunk, int64_t units, int col0, int ncol, int ntile, int off, int C) {
+  constexpr int V = VEC ? 4 : 1;
+  const int lane = threadIdx.x & 63;
+  for (int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < units; u += (int64_t)gridDim.x * 4) {
+    const int64_t q = u / ntile;
+    const int tile = (int)(u - q * ntile);
+    const int64_t bsa = q / nchunk, chunk = q - bsa * nchunk;
+    const int64_t bs = bsa / Ta, ta = bsa - bs * Ta;
+    const int64_t b = bs / K;
+    const int s = (int)(bs - b * K);
+    const int j = (tile * 64 + lane) * V;
+    const bool active = j < ncol;
+    const int64_t first = ta * stride;                                   // < T
+    const int64_t end = stride >= T - first ? T : first + stride;        // (no first + stride past T: no overflow)
+    const int64_t t0 = first + chunk * AUX_TFR, t1 = (t0 + AUX_TFR < end) ? t0 + AUX_TFR : end;
+    float acc[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) acc[i] = 0.f;
+    const float* p = MUL ? pre + b * T * ld_pre + col0 + j : nullptr;
+    for (int tr = 0; tr < trials; ++tr) {
+      int k = s - tr;
+      if (k < 0) k += (int)K;
+      const float* d = dxs + (((b * trials + tr) * K + k) * T) * ld_dxs + col0 + j;
+      for (int64_t t = t0; t < t1; t += 4) {
+        float dv[4][V], pv[4][V];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int64_t tt = t + g;
+          const bool on = active && tt < t1;
+          if (VEC) {
+            f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
+            if (on) {
+              a = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d + tt * ld_dxs));
+              if (MUL) c = *reinterpret_cast<const f32x4*>(p + tt * ld_pre);
+            }
+#pragma unroll
+            for (int i = 0; i < V; ++i) { dv[g][i] = a[i]; pv[g][i] = c[i]; }
+          } else {
+            dv[g][0] = on ? __builtin_nontemporal_load(d + tt * ld_dxs) : 0.f;
+            pv[g][0] = (on && MUL) ? p[tt * ld_pre] : 0.f;
+          }
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int i = 0; i < V; ++i) acc[i] += MUL ? dv[g][i] * pv[g][i] : dv[g][i];
+      }
+    }
+    if (active) {
+      float* o = out + (chunk * BSA + bsa) * ld_out;
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        const int c = j + i - off;
+        if (c >= 0 && c < C) o[c] = acc[i];
+      }
+    }
+  }
+}
+
 // ---- instance normalisation -----------------------------------------------------------------------------------
 // scale of a centred sum of squares over cnt values: InstanceNorm (mode 0): std with cnt - unbiased in the denominator
 // (net.py:281-285); InstanceNorm_v2 (mode 1): ||x - mean|| / sqrt(cnt) (net.py:322-330).  No epsilon, as the reference.
@@ -381,6 +452,79 @@ extern "C" int tssep_cond_cat_aux_bwd(const float* dxs, int64_t ld_dxs, float* d
                                       int64_t B, int64_t K, int64_t T, int F, int E, int trials, void* stream) {
   if (E <= 0) return TSSEP_E_SHAPE;
   return cond_aux_bwd(dxs, ld_dxs, nullptr, 0, d_aux, ld_daux, ws, B, K, T, F, E, trials, stream);
+}
+
+// chunks of AUX_TFR frames in the longest bucket
+static inline int64_t aux_t_chunks(int64_t T, int64_t stride) {
+  return ((stride < T ? stride : T) + AUX_TFR - 1) / AUX_TFR;
+}
+extern "C" int64_t tssep_cond_aux_t_bwd_workspace_bytes(int64_t B, int64_t K, int64_t T, int F, int E, int64_t Ta,
+                                                        int64_t stride) {
+  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || E < 0 || !cond_t_shape_ok(T, Ta, stride)) return -1;
+  const int64_t nchunk = aux_t_chunks(T, stride);
+  if (nchunk == 1) return 0;
+  int col0, ncol;
+  aux_window(F, E, &col0, &ncol);
+  return nchunk * B * K * Ta * (int64_t)ncol * (int64_t)sizeof(float);
+}
+
+static int cond_aux_t_bwd(const float* dxs, int64_t ld_dxs, const float* pre, int64_t ld_pre, float* d_aux,
+                          int64_t ld_daux, void* ws, int64_t B, int64_t K, int64_t T, int F, int E, int trials,
+                          int64_t Ta, int64_t stride, void* stream) {
+  const bool mul = pre != nullptr;
+  if (!dxs || !d_aux) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || E < 0 || trials <= 0 || trials > K || !cond_t_shape_ok(T, Ta, stride))
+    return TSSEP_E_SHAPE;
+  const int C = mul ? F : E, W = mul ? F : F + E;
+  if (ld_dxs < W || ld_daux < C || (mul && ld_pre < F)) return TSSEP_E_SHAPE;
+  const int64_t BSA = B * K * Ta, nchunk = aux_t_chunks(T, stride);
+  const bool direct = nchunk == 1;
+  if (!direct && !ws) return TSSEP_E_NULL;
+  int col0, ncol;
+  aux_window(F, mul ? 0 : E, &col0, &ncol);
+  const bool vec = (ld_dxs & 3) == 0 && ld_dxs >= col0 + ncol && aligned16(dxs) &&
+                   (!mul || ((ld_pre & 3) == 0 && ld_pre >= ncol && aligned16(pre)));
+  if (!vec) { col0 = mul ? 0 : F; ncol = C; }
+  // where column c of d_aux sits in the window: the partials keep the whole window (ldp columns), the reduce picks
+  const int off = (mul ? 0 : F) - col0, ldp = vec ? ncol : C;
+  const int ntile = ((vec ? ncol / 4 : ncol) + 63) / 64;
+  const int64_t units = BSA * nchunk * ntile;
+  float* out = direct ? d_aux : (float*)ws;
+  const int64_t ld_out = direct ? ld_daux : ldp;
+  const int o = direct ? off : 0, c = direct ? C : ncol;
+  const dim3 grid(grid_for(units * 64));
+  if (vec) {
+    if (mul)
+      hipLaunchKernelGGL((cond_aux_t_bwd_partial_kernel<true, true>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre, out,
+                         ld_out, BSA, K, T, trials, Ta, stride, nchunk, units, col0, ncol, ntile, o, c);
+    else
+      hipLaunchKernelGGL((cond_aux_t_bwd_partial_kernel<true, false>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre, out,
+                         ld_out, BSA, K, T, trials, Ta, stride, nchunk, units, col0, ncol, ntile, o, c);
+  } else {
+    if (mul)
+      hipLaunchKernelGGL((cond_aux_t_bwd_partial_kernel<false, true>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre, out,
+                         ld_out, BSA, K, T, trials, Ta, stride, nchunk, units, col0, ncol, ntile, o, c);
+    else
+      hipLaunchKernelGGL((cond_aux_t_bwd_partial_kernel<false, false>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre, out,
+                         ld_out, BSA, K, T, trials, Ta, stride, nchunk, units, col0, ncol, ntile, o, c);
+  }
+  if (!direct)
+    hipLaunchKernelGGL(cond_aux_bwd_reduce_kernel, dim3(grid_for(BSA * C)), dim3(256), 0, S_, (const float*)ws, BSA,
+                       (int)nchunk, ldp, off, C, d_aux, ld_daux);
+  return tssep_launch_status();
+}
+
+extern "C" int tssep_cond_mul_aux_t_bwd(const float* dxs, int64_t ld_dxs, const float* pre, int64_t ld_pre, float* d_aux,
+                                        int64_t ld_daux, void* ws, int64_t B, int64_t K, int64_t T, int F, int trials,
+                                        int64_t Ta, int64_t stride, void* stream) {
+  if (!pre) return TSSEP_E_NULL;
+  return cond_aux_t_bwd(dxs, ld_dxs, pre, ld_pre, d_aux, ld_daux, ws, B, K, T, F, 0, trials, Ta, stride, stream);
+}
+extern "C" int tssep_cond_cat_aux_t_bwd(const float* dxs, int64_t ld_dxs, float* d_aux, int64_t ld_daux, void* ws,
+                                        int64_t B, int64_t K, int64_t T, int F, int E, int trials, int64_t Ta,
+                                        int64_t stride, void* stream) {
+  if (E <= 0) return TSSEP_E_SHAPE;
+  return cond_aux_t_bwd(dxs, ld_dxs, nullptr, 0, d_aux, ld_daux, ws, B, K, T, F, E, trials, Ta, stride, stream);
 }
 
 static int instnorm_check(int64_t R, int64_t n, int C, int axis, int mode, int unbiased) {

@@ -14,6 +14,10 @@ static inline int tssep_launch_status() {
   return e == hipSuccess ? TSSEP_OK : TSSEP_E_LAUNCH;
 }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+// frame-wise embeddings: frame t reads embedding row t / stride, and there are exactly ceil(T / stride) of them
+static inline bool cond_t_shape_ok(int64_t T, int64_t Ta, int64_t stride) {
+  return T > 0 && stride >= 1 && Ta == (T - 1) / stride + 1;
+}
 
 __device__ __forceinline__ float sigmoidf_acc(float x) {
   // 1/(1+exp(-x)) with the accurate expf (parity with torch.sigmoid to ~1 ulp)

@@ -140,6 +140,107 @@ __global__ void cond_cat_bwd_kernel(const float* __restrict__ dxs, int64_t ld_dx
   }
 }
 
+// ---- speaker conditioning on frame-wise embeddings ------------------------------------------
+// aux rows are (b, spk, ta), ta = t / stride (net.py:866-894 at stride 1).  The kernels below are their utterance-level
+// neighbours above with that one row index: the same row decomposition, the same (trial, k) order and the same choice
+// between the 16-byte and the 4-byte path, so a time-constant aux gives the neighbours' bits.
+__global__ __launch_bounds__(256) void cond_mul_t_fwd_kernel(
+    const float* __restrict__ pre, int64_t ld_pre, const float* __restrict__ aux, int64_t ld_aux,
+    float* __restrict__ xs, int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
+    int64_t stride) {
+  const int lane = threadIdx.x & 63;
+  const int64_t rows = B * trials * K * T;
+  const bool vec = F <= 1024 && ((ld_pre | ld_aux | ld_xs) & 3) == 0 && ld_pre >= ((F + 3) & ~3) &&
+                   ld_aux >= ((F + 3) & ~3) && ld_xs >= ((F + 3) & ~3) &&
+                   ((((uintptr_t)pre) | ((uintptr_t)aux) | ((uintptr_t)xs)) & 15) == 0;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (int64_t)gridDim.x * 4) {
+    int64_t b, t, spk;
+    cond_row(row, K, T, trials, b, t, spk);
+    const float* p = pre + (b * T + t) * ld_pre;
+    const float* a = aux + ((b * K + spk) * Ta + t / stride) * ld_aux;
+    float* o = xs + row * ld_xs;
+    if (vec) {
+      const int nq = (F + 3) >> 2;
+      f32x4 pv[4], av[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int q = lane + 64 * r;
+        if (q < nq) {
+          pv[r] = *reinterpret_cast<const f32x4*>(p + 4 * q);
+          av[r] = *reinterpret_cast<const f32x4*>(a + 4 * q);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int q = lane + 64 * r;
+        if (q < nq) __builtin_nontemporal_store(pv[r] * av[r], reinterpret_cast<f32x4*>(o + 4 * q));
+      }
+    } else {
+      for (int f = lane; f < F; f += 64) o[f] = p[f] * a[f];
+    }
+  }
+}
+__global__ void cond_mul_t_bwd_v4_kernel(const float* __restrict__ dxs, int64_t ld_dxs,
+                                         const float* __restrict__ aux, int64_t ld_aux,
+                                         float* __restrict__ dpre, int64_t ld_dpre, int64_t B, int64_t K,
+                                         int64_t T, int F, int trials, int64_t Ta, int64_t stride) {
+  const int nq = (F + 3) >> 2;
+  const int64_t total = B * T * nq;
+  GRID_STRIDE(e, total) {
+    const int64_t row = e / nq;
+    const int q = (int)(e - row * nq);
+    const int64_t t = row % T, b = row / T;
+    const int64_t ta = t / stride;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    for (int tr = 0; tr < trials; ++tr) {
+#pragma unroll 4
+      for (int64_t k = 0; k < K; ++k) {
+        int64_t spk = k + tr;
+        if (spk >= K) spk -= K;
+        const f32x4 d = *reinterpret_cast<const f32x4*>(dxs + (((b * trials + tr) * K + k) * T + t) * ld_dxs + 4 * q);
+        const f32x4 a = *reinterpret_cast<const f32x4*>(aux + ((b * K + spk) * Ta + ta) * ld_aux + 4 * q);
+        s[0] += d[0] * a[0]; s[1] += d[1] * a[1]; s[2] += d[2] * a[2]; s[3] += d[3] * a[3];
+      }
+    }
+    *reinterpret_cast<f32x4*>(dpre + row * ld_dpre + 4 * q) = s;
+  }
+}
+__global__ void cond_mul_t_bwd_kernel(const float* __restrict__ dxs, int64_t ld_dxs,
+                                      const float* __restrict__ aux, int64_t ld_aux,
+                                      float* __restrict__ dpre, int64_t ld_dpre, int64_t B, int64_t K,
+                                      int64_t T, int F, int trials, int64_t Ta, int64_t stride) {
+  const int64_t total = B * T * F;
+  GRID_STRIDE(e, total) {
+    const int64_t row = e / F;
+    const int f = (int)(e - row * F);
+    const int64_t t = row % T, b = row / T;
+    const int64_t ta = t / stride;
+    float s = 0.f;
+    for (int tr = 0; tr < trials; ++tr)
+      for (int64_t k = 0; k < K; ++k) {
+        int64_t spk = k + tr;
+        if (spk >= K) spk -= K;
+        s += dxs[(((b * trials + tr) * K + k) * T + t) * ld_dxs + f] * aux[((b * K + spk) * Ta + ta) * ld_aux + f];
+      }
+    dpre[row * ld_dpre + f] = s;
+  }
+}
+__global__ void cond_cat_t_fwd_kernel(const float* __restrict__ pre, int64_t ld_pre,
+                                      const float* __restrict__ aux, int64_t ld_aux,
+                                      float* __restrict__ xs, int64_t ld_xs, int64_t B, int64_t K,
+                                      int64_t T, int F, int E, int trials, int64_t Ta, int64_t stride) {
+  const int W = F + E;
+  const int64_t total = B * trials * K * T * W;
+  GRID_STRIDE(e, total) {
+    const int64_t row = e / W;
+    const int c = (int)(e - row * W);
+    int64_t b, t, spk;
+    cond_row(row, K, T, trials, b, t, spk);
+    xs[row * ld_xs + c] =
+        c < F ? pre[(b * T + t) * ld_pre + c] : aux[((b * K + spk) * Ta + t / stride) * ld_aux + (c - F)];
+  }
+}
+
 // ---- tanh backward (+ optional layout change) ---------------------------------------------
 // dz rows are always (b,k,t) x P.  combined != 0: dy and y live in [B,T,K*P].
 __global__ void tanh_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
@@ -888,6 +989,44 @@ extern "C" int tssep_cond_cat_bwd(const float* dxs, int64_t ld_dxs, float* dpre,
   if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || trials <= 0 || trials > K) return TSSEP_E_SHAPE;
   hipLaunchKernelGGL(cond_cat_bwd_kernel, dim3(grid_for(B * T * F)), dim3(256), 0, S_, dxs, ld_dxs,
                      dpre, ld_dpre, B, K, T, F, trials);
+  return tssep_launch_status();
+}
+extern "C" int tssep_cond_mul_t_fwd(const float* pre, int64_t ld_pre, const float* aux, int64_t ld_aux, float* xs,
+                                    int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
+                                    int64_t stride, void* stream) {
+  if (!pre || !aux || !xs) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || trials <= 0 || trials > K || !cond_t_shape_ok(T, Ta, stride))
+    return TSSEP_E_SHAPE;
+  hipLaunchKernelGGL(cond_mul_t_fwd_kernel, dim3(grid_for(B * trials * K * T * 64)), dim3(256), 0, S_,
+                     pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, trials, Ta, stride);
+  return tssep_launch_status();
+}
+extern "C" int tssep_cond_mul_t_bwd(const float* dxs, int64_t ld_dxs, const float* aux, int64_t ld_aux, float* dpre,
+                                    int64_t ld_dpre, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
+                                    int64_t stride, void* stream) {
+  if (!dxs || !aux || !dpre) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || trials <= 0 || trials > K || !cond_t_shape_ok(T, Ta, stride))
+    return TSSEP_E_SHAPE;
+  const int64_t fp = (F + 3) & ~3;
+  if (((ld_dxs | ld_aux | ld_dpre) & 3) == 0 && ld_dxs >= fp && ld_aux >= fp && ld_dpre >= fp &&
+      ((((uintptr_t)dxs) | ((uintptr_t)aux) | ((uintptr_t)dpre)) & 15) == 0) {
+    hipLaunchKernelGGL(cond_mul_t_bwd_v4_kernel, dim3(grid_for(B * T * (fp / 4))), dim3(256), 0, S_, dxs, ld_dxs,
+                       aux, ld_aux, dpre, ld_dpre, B, K, T, F, trials, Ta, stride);
+    return tssep_launch_status();
+  }
+  hipLaunchKernelGGL(cond_mul_t_bwd_kernel, dim3(grid_for(B * T * F)), dim3(256), 0, S_, dxs, ld_dxs,
+                     aux, ld_aux, dpre, ld_dpre, B, K, T, F, trials, Ta, stride);
+  return tssep_launch_status();
+}
+extern "C" int tssep_cond_cat_t_fwd(const float* pre, int64_t ld_pre, const float* aux, int64_t ld_aux, float* xs,
+                                    int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int E, int trials,
+                                    int64_t Ta, int64_t stride, void* stream) {
+  if (!pre || !aux || !xs) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || E <= 0 || trials <= 0 || trials > K ||
+      !cond_t_shape_ok(T, Ta, stride))
+    return TSSEP_E_SHAPE;
+  hipLaunchKernelGGL(cond_cat_t_fwd_kernel, dim3(grid_for(B * trials * K * T * (F + E))), dim3(256),
+                     0, S_, pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, E, trials, Ta, stride);
   return tssep_launch_status();
 }
 extern "C" int tssep_tanh_bwd(const float* dy, const float* y, float* dz, int64_t rows, int64_t P,

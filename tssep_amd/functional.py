@@ -360,17 +360,20 @@ def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=Fals
 # ---------------------------------------------------------------------- conditioning
 class _Cond(torch.autograd.Function):
     """tssep/train/net.py:862-896 (+ trial fold :913-924).  pre rows (b,t) -> rows (b,tr,k,t).
+    aux [B, K, E] (one embedding per speaker and utterance), or frame-wise [B, K, Ta, E]: frame t reads row t // stride
+    (net.py:866-867 at stride 1), through the *_t entry points; a 3-D aux makes the calls it always made.
     An embedding that requires a gradient (aux_net, a trainable normalised embedding) gets it from one more launch over
     dxs (hip_ops.cond_aux_bwd); a fixed embedding makes exactly the calls it always made."""
 
     @staticmethod
-    def forward(ctx, pre, aux, B, K, T, trials, combination):
+    def forward(ctx, pre, aux, B, K, T, trials, combination, stride):
         F = pre.shape[-1]
+        Ta = aux.shape[-2] if aux.dim() == 4 else 0
         pv, ld_pre = H.rows_view(pre)
-        xs, ld, info = H.cond_fwd(pv, ld_pre, aux.detach(), B, K, T, F, trials, combination)
+        xs, ld, info = H.cond_fwd(pv, ld_pre, aux.detach(), B, K, T, F, trials, combination, Ta, stride)
         W = F if combination == "mul" else F + aux.shape[-1]
         ctx.info = info
-        ctx.meta = (B, K, T, F, trials, combination, ld)
+        ctx.meta = (B, K, T, F, trials, combination, ld, Ta, stride)
         ctx.aux_grad = None
         if aux.requires_grad:
             ctx.aux_grad = (tuple(aux.shape), (pv, ld_pre) if combination == "mul" else None)
@@ -378,19 +381,20 @@ class _Cond(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dxs):
-        B, K, T, F, trials, combination, ld = ctx.meta
+        B, K, T, F, trials, combination, ld, Ta, stride = ctx.meta
         dv, ld_d = H.rows_view(dxs)
-        dpre, ldp = H.cond_bwd(dv, ld_d, ctx.info, B, K, T, F, trials, combination)
+        dpre, ldp = H.cond_bwd(dv, ld_d, ctx.info, B, K, T, F, trials, combination, Ta, stride)
         d_aux = None
         if ctx.aux_grad is not None and ctx.needs_input_grad[1]:
             shape, pre = ctx.aux_grad
             pv, ld_pre = pre if pre is not None else (None, 0)
-            d_aux = H.cond_aux_bwd(dv, ld_d, pv, ld_pre, B, K, T, F, shape[-1], trials, combination).view(shape)
-        return dpre[:, :F], d_aux, None, None, None, None, None
+            d_aux = H.cond_aux_bwd(dv, ld_d, pv, ld_pre, B, K, T, F, shape[-1], trials, combination, Ta,
+                                   stride).view(shape)
+        return dpre[:, :F], d_aux, None, None, None, None, None, None
 
 
-def condition(pre, aux, B, K, T, trials, combination):
-    return _Cond.apply(pre, aux, B, K, T, trials, combination)
+def condition(pre, aux, B, K, T, trials, combination, stride=1):
+    return _Cond.apply(pre, aux, B, K, T, trials, combination, stride)
 
 
 # ------------------------------------------------------------------------ final linear

@@ -1052,6 +1052,13 @@ def side_stream(device, rows=0):
     return _SIDE[key]
 
 
+def forget_side_stream(stream):
+    """Drop the side stream paired with `stream`.  torch hands streams out of a pool, so a NEW stream can carry the handle
+    of one that was paired earlier; until it forks itself it must not join that old side stream (a captured step's waits
+    would depend on how many streams the process has made)."""
+    _SIDE.pop((str(stream.device), stream.cuda_stream), None)
+
+
 def join_side_stream(device=None):
     """Make the current stream wait for the gradient work queued on ITS side stream (the pairing is per
     compute stream, so a stream that is being captured into a hipGraph only ever joins the stream it
@@ -1155,10 +1162,26 @@ def dropout_keep_host(seed, draw, first, n, p):
     return keep
 
 
-def cond_fwd(pre, ld_pre, aux, B, K, T, F, trials, combination):
-    """-> (xs view [B*trials*K*T, W], ld)"""
+def cond_frames(T, Ta, stride):
+    """Frame-wise embeddings: frame t reads embedding row t // stride, so there are ceil(T / stride) rows.  Ta = 0 is the
+    utterance-level embedding (one row per speaker).  Raises ValueError before anything is launched."""
+    if not Ta:
+        return
+    if not isinstance(stride, int) or isinstance(stride, bool) or stride < 1:
+        raise ValueError(f"aux_stride={stride!r}: a positive number of frames per embedding row")
+    if Ta != -(-T // stride):
+        raise ValueError(f"frame-wise embeddings: {Ta} rows for {T} frames at aux_stride={stride} "
+                         f"(ceil(T / aux_stride) = {-(-T // stride)} rows are needed)")
+
+
+def cond_fwd(pre, ld_pre, aux, B, K, T, F, trials, combination, Ta=0, stride=1, auxinfo=None):
+    """-> (xs view [B*trials*K*T, W], ld, (aux rows, ld_aux)).  aux [B, K, E], or frame-wise [B, K, Ta, E] with
+    Ta = ceil(T / stride) > 0.  The kernels take aux as 16-byte addressable rows: an aux whose E is no multiple of 4 is
+    copied into padded rows first (rows_view: one pass over aux per call, layout glue); auxinfo = rows_view(aux) made by the
+    caller skips that."""
     L = _lib.lib()
-    aux2, ld_aux = rows_view(aux)
+    cond_frames(T, Ta, stride)
+    aux2, ld_aux = auxinfo if auxinfo is not None else rows_view(aux)
     E = aux.shape[-1]
     W = F if combination == "mul" else F + E
     # (the 16-byte path of cond_mul_fwd_kernel writes the pad columns itself: products of the inputs' zero pads)
@@ -1167,37 +1190,62 @@ def cond_fwd(pre, ld_pre, aux, B, K, T, F, trials, combination):
     xs, ld = padded(B * trials * K * T, W, pre.device, zero=not writes_pads)
     if combination == "mul":
         assert E == F, (E, F)
-        check(L.tssep_cond_mul_fwd(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F,
-                                   trials, _stream()), "cond_mul_fwd")
+        if Ta:
+            check(L.tssep_cond_mul_t_fwd(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F, trials, Ta, stride,
+                                         _stream()), "cond_mul_t_fwd")
+        else:
+            check(L.tssep_cond_mul_fwd(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F,
+                                       trials, _stream()), "cond_mul_fwd")
+    elif Ta:
+        check(L.tssep_cond_cat_t_fwd(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F, E, trials, Ta, stride,
+                                     _stream()), "cond_cat_t_fwd")
     else:
         check(L.tssep_cond_cat_fwd(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F, E,
                                    trials, _stream()), "cond_cat_fwd")
     return xs, ld, (aux2, ld_aux)
 
 
-def cond_bwd(dxs, ld_dxs, auxinfo, B, K, T, F, trials, combination):
+def cond_bwd(dxs, ld_dxs, auxinfo, B, K, T, F, trials, combination, Ta=0, stride=1):
     L = _lib.lib()
     aux2, ld_aux = auxinfo
     # (cond_mul_bwd_v4_kernel sums the pad columns too: zero in both inputs)
     writes_pads = combination == "mul" and ld_dxs % 4 == 0 and ld_dxs >= round_up(F, 4) and dxs.data_ptr() % 16 == 0 \
         and aux2.data_ptr() % 16 == 0
     dpre, ld = padded(B * T, F, dxs.device, zero=not writes_pads)
-    if combination == "mul":
+    if combination == "mul" and Ta:
+        check(L.tssep_cond_mul_t_bwd(_p(dxs), ld_dxs, _p(aux2), ld_aux, _p(dpre), ld, B, K, T, F, trials, Ta, stride,
+                                     _stream()), "cond_mul_t_bwd")
+    elif combination == "mul":
         check(L.tssep_cond_mul_bwd(_p(dxs), ld_dxs, _p(aux2), ld_aux, _p(dpre), ld, B, K, T, F,
                                    trials, _stream()), "cond_mul_bwd")
-    else:
+    else:                                   # (d(pre) of cat does not read the embedding: one entry point for both)
         check(L.tssep_cond_cat_bwd(_p(dxs), ld_dxs, _p(dpre), ld, B, K, T, F, trials, _stream()),
               "cond_cat_bwd")
     return dpre, ld
 
 
 # ---- learned speaker embeddings (csrc/aux.hip) --------------------------------------------------------------------
-def cond_aux_bwd(dxs, ld_dxs, pre, ld_pre, B, K, T, F, E, trials, combination):
-    """d(conditioning) / d(embedding) -> d_aux [B, K, C] (C = F for mul, E for cat).  A launch of its own, made only
-    when the embedding requires a gradient (pre: the pre-net rows the forward multiplied with; None for cat)."""
+def cond_aux_bwd(dxs, ld_dxs, pre, ld_pre, B, K, T, F, E, trials, combination, Ta=0, stride=1):
+    """d(conditioning) / d(embedding) -> d_aux [B, K, C] (C = F for mul, E for cat), or [B, K, Ta, C] for frame-wise
+    embeddings (Ta > 0).  A launch of its own, made only when the embedding requires a gradient (pre: the pre-net rows
+    the forward multiplied with; None for cat)."""
     L = _lib.lib()
     mul = combination == "mul"
     C = F if mul else E
+    if Ta:
+        nbytes = int(L.tssep_cond_aux_t_bwd_workspace_bytes(B, K, T, F, 0 if mul else E, Ta, stride))
+        if nbytes < 0:
+            check(-1, "cond_aux_t_bwd_workspace_bytes")
+        ws = torch.empty(nbytes // 4, device=dxs.device, dtype=torch.float32) if nbytes else None
+        d_aux = torch.empty(B, K, Ta, C, device=dxs.device, dtype=torch.float32)
+        with _timed("cond_aux_t_bwd", 0, 4 * (B * trials * K * T * C + (B * T * F if mul else 0) + B * K * Ta * C)):
+            if mul:
+                check(L.tssep_cond_mul_aux_t_bwd(_p(_f32(dxs)), ld_dxs, _p(_f32(pre)), ld_pre, _p(d_aux), C, _p(ws), B, K, T,
+                                                 F, trials, Ta, stride, _stream()), "cond_mul_aux_t_bwd")
+            else:
+                check(L.tssep_cond_cat_aux_t_bwd(_p(_f32(dxs)), ld_dxs, _p(d_aux), C, _p(ws), B, K, T, F, E, trials, Ta,
+                                                 stride, _stream()), "cond_cat_aux_t_bwd")
+        return d_aux
     nbytes = int(L.tssep_cond_aux_bwd_workspace_bytes(B, K, T, F, 0 if mul else E))
     if nbytes <= 0:
         check(-1, "cond_aux_bwd_workspace_bytes")

@@ -107,7 +107,16 @@ class GraphedStep:
         return (self.eager_reason is None and isinstance(ex.get("observation", ex.get("Input")), torch.Tensor)
                 and ex.get("observation", ex.get("Input")).is_cuda
                 and isinstance(ex.get("auxInput"), torch.Tensor) and ex["auxInput"].is_cuda
+                and not self._unbatched_framewise(ex)
                 and not getattr(self.model, "create_snapshot", False) and not H.KERNEL_TIMING)
+
+    @staticmethod
+    def _unbatched_framewise(ex):
+        """A 3-D auxInput beside an un-batched input (observation [C, N] / Input [T, D]) is [K, Ta, E], not [B, K, E]: its
+        leading axes are not (B, K), and nothing here sizes buffers for it."""
+        x = ex.get("observation", ex.get("Input"))
+        a = ex.get("auxInput")
+        return isinstance(a, torch.Tensor) and isinstance(x, torch.Tensor) and a.dim() == 3 and x.dim() == 2
 
     # ------------------------------------------------------------------------------ capture
     def _capture(self, ex):
@@ -115,13 +124,15 @@ class GraphedStep:
             raise RuntimeError(f"GraphedStep: {self.eager_reason}")
         if H.KERNEL_TIMING:
             raise RuntimeError("per-kernel event timing cannot be captured into a graph")
+        if self._unbatched_framewise(ex):
+            raise RuntimeError("GraphedStep: an un-batched frame-wise auxInput [K, Ta, E] takes the eager path (usable())")
         me = self.model.mask_estimator
         dev = next(self.model.parameters()).device
         st = {"keys": self._tensor_keys(ex)}
         st["static"] = {k: (ex[k].detach() if self.adopt_inputs else ex[k].detach().clone()) for k in st["keys"]}
         st["rest"] = {k: v for k, v in ex.items() if k not in st["static"]}
-        B = ex["auxInput"].shape[0] if isinstance(ex.get("auxInput"), torch.Tensor) and ex["auxInput"].dim() == 3 else 1
-        K = ex["auxInput"].shape[-2]
+        # auxInput [B, K, E] or frame-wise [B, K, Ta, E]: (B, K) are the leading axes; un-batched [K, E]: one entry
+        B, K = (1, ex["auxInput"].shape[0]) if ex["auxInput"].dim() == 2 else tuple(ex["auxInput"].shape[:2])
         shuffled = bool(getattr(me, "random_speaker_order", False))
         if shuffled:
             st["perm_dev"] = torch.zeros(2, B, K, device=dev, dtype=torch.int32)
@@ -151,6 +162,10 @@ class GraphedStep:
         drawn = H.get_state(dev)          # (also: the state tensor exists before anything is captured)
         try:
             s = torch.cuda.Stream(device=dev)
+            # torch hands streams out of a pool: a recycled handle must not inherit the side stream an earlier capture stream
+            # was paired with (the joins in front of this capture's first fork would wait for it, and the launches of a step
+            # would depend on how many streams the process has made)
+            H.forget_side_stream(s)
             s.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(s), H.record_derived() as seen:
                 for _ in range(self.warmup):       # same stream as the capture: side stream, caches, tables exist

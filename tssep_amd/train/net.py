@@ -169,8 +169,11 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
                  pre_net="RNNP", aux_net=None, aux_net_output_size=None, combination: str = "cat",
                  ts_vad=False, output_resolution: str = "tf", random_speaker_order=True,
                  num_averaged_permutations=1, input_normalizer=None, aux_normalizer=None,
-                 explicit_vad=False):
+                 explicit_vad=False, aux_stride=1):
         super().__init__()
+        if not isinstance(aux_stride, int) or isinstance(aux_stride, bool) or aux_stride < 1:
+            raise ValueError(f"aux_stride={aux_stride!r}: a positive number of frames per row of a frame-wise embedding")
+        self.aux_stride = aux_stride              # this project's keyword (frame-wise embeddings at their own frame rate)
         if odim is None:
             odim = idim
         for name, norm in (("input_normalizer", input_normalizer), ("aux_normalizer", aux_normalizer)):
@@ -291,7 +294,8 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
 
     # ----------------------------------------------------------------------------------
     def logits(self, xs, aux):
-        """-> (logit [B,K,T,F], embedding [B,K,1,E]).  explicit_vad: logit [B,K,T,F+1], the VAD logit at column 0 of
+        """-> (logit [B,K,T,F], embedding [B,K,1,E]; a frame-wise aux [B,K,Ta,E] comes back as it entered the conditioning,
+        net.py:866-867: frame t is conditioned on row t // aux_stride).  explicit_vad: logit [B,K,T,F+1], the VAD logit at column 0 of
         every row and the mask logits behind it (net.py:969-979 slices them apart).  nmask > 1: (logit [B,K,M,T,F], mask
         [B,K,M,T,F], embedding) -- the fused two-mask tail computes the sigmoid in the pass that lays the logit out."""
         if xs.dim() == 2:
@@ -305,6 +309,18 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         else:
             aux = _stack_aux(aux)
         K = len(aux[0]) if ragged else aux.shape[1]
+        if not ragged and aux.dim() == 4:               # an embedding per speaker AND frame (net.py:866-867)
+            if aux.shape[0] != B:
+                raise ValueError(f"frame-wise embeddings {tuple(aux.shape)} for a batch of {B}")
+            if self.aux_net is not None:
+                raise NotImplementedError(f"aux_net={type(self.aux_net).__name__} on frame-wise embeddings "
+                                          f"{tuple(aux.shape)}: aux_net maps one enrolment to one embedding per speaker")
+            Fn.H.cond_frames(T, aux.shape[2], self.aux_stride)       # ValueError, before anything is launched
+        elif not ragged and aux.dim() != 3:
+            raise ValueError(f"aux {tuple(aux.shape)}: [B, K, E] or frame-wise [B, K, Ta, E]")
+        elif self.aux_stride != 1:
+            raise ValueError(f"aux_stride={self.aux_stride} with one embedding per speaker and utterance "
+                             f"({'enrolment lists' if ragged else tuple(aux.shape)}): it is the frame rate of a frame-wise aux [B, K, Ta, E]")
         perm_d = iperm_d = None
         if self.random_speaker_order:                   # the RAW aux entries are shuffled (net.py:823-831)
             perm_d, iperm_d = self._speaker_permutations(B, K, dev)
@@ -313,15 +329,15 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
                 aux = [[a[i] for i in q] for a, q in zip(aux, perm_h)]
             else:
                 # shuffled aux[b, s] = aux[b, perm[b, s]]: one gather for the whole batch
-                aux = torch.gather(aux, 1, perm_d.long()[..., None].expand(-1, -1, aux.shape[-1]))
+                idx = perm_d.long().reshape(B, K, *([1] * (aux.dim() - 2))).expand(-1, -1, *aux.shape[2:])
+                aux = torch.gather(aux, 1, idx)
         if self.aux_net is not None:                    # net.py:833-838
             aux = self.aux_net(aux, xs, batched=True)
         else:
             aux = aux.to(torch.float32)
             if self.aux_normalizer is not None:         # net.py:852-853
                 aux = self.aux_normalizer(aux)
-        if aux.dim() != 3:
-            raise NotImplementedError(f"embeddings with a time axis (the attention branch, net.py:866-867): {tuple(aux.shape)}")
+        framewise = aux.dim() == 4
         aux = aux.contiguous()
         if self.input_normalizer is not None:           # net.py:858-859
             xs = self.input_normalizer(xs)
@@ -330,7 +346,7 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         trials = self.num_averaged_permutations
         F = self.odim + int(self.explicit_vad)         # the head's columns per speaker
         pre = self.pre_net.forward_rows(xs.reshape(B * T, xs.shape[-1]), B, T)       # [B*T, odim]
-        h = Fn.condition(pre, aux, B, K, T, trials, self.combination)               # rows (b,tr,k,t)
+        h = Fn.condition(pre, aux, B, K, T, trials, self.combination, self.aux_stride)     # rows (b,tr,k,t)
         nb = len(self._birnns)
         # the Tanh between two post-net modules runs forward in the producer's projection store and backward in
         # the consumer's d(input) GEMM store (functional.rnnp_layer): `fold` = both ends agree on it.  A Tanh behind an
@@ -353,10 +369,10 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         if self.nmask > 1:
             logit, mask = Fn.head_masks(h, self._linear, perm_d, iperm_d, B, K, self.nmask, T, F, trials, Fr,
                                         spk_rows=self.ts_vad is False)
-            return logit, mask, aux.unsqueeze(-2)
+            return logit, mask, aux if framewise else aux.unsqueeze(-2)
         logit = Fn.head(h, self._linear, perm_d, iperm_d, B, K, T, F, trials, Fr,
                         spk_rows=self.ts_vad is False)
-        return logit, aux.unsqueeze(-2)
+        return logit, aux if framewise else aux.unsqueeze(-2)
 
     def forward(self, xs, aux=None) -> Output:
         if self.nmask > 1:                         # [..., K, M, T, F] as they are (net.py:631-659, 983)
@@ -372,5 +388,5 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
                 mask, vad_mask, vad_logit = mask[0], vad_mask[0], vad_logit[0]
             return Output(mask=mask.unsqueeze(u), logit=None, embedding=emb, vad_mask=vad_mask.unsqueeze(-2),
                           vad_logit=vad_logit.unsqueeze(-2))
-        mask = Fn.sigmoid(logit)
+        mask = Fn.sigmoid(logit) if logit.dim() == 4 else Fn.sigmoid(logit[None])[0]      # (un-batched xs: [K, T, F])
         return Output(mask=mask.unsqueeze(u), logit=logit.unsqueeze(u), embedding=emb)
