@@ -430,8 +430,10 @@ int tssep_cond_cat_bwd(const float* dxs, int64_t ld_dxs, float* dpre, int64_t ld
 /* The same conditioning on FRAME-WISE embeddings (net.py:866-867, aux_time = "time"): aux rows are (b, spk, ta) with
  * leading dimension ld_aux, frame t reads row ta = t / stride, and Ta == ceil(T / stride) (anything else, or
  * stride < 1: TSSEP_E_SHAPE before any launch).  stride = 1 is the reference's branch; stride >= T is one row per
- * speaker.  Row decomposition, (trial, k) order and the choice between 16-byte and 4-byte accesses are those of the
- * entry points above: a time-constant aux gives their bits.  d(pre) of cat does not read aux: tssep_cond_cat_bwd.
+ * speaker.  Each entry point shares its kernel (one template, the aux row index its only branch) and its launcher with
+ * the entry point above of the same role: row decomposition, (trial, k) order and the choice between 16-byte and 4-byte
+ * accesses are the same code, and a time-constant aux gives their bits.  d(pre) of cat does not read aux:
+ * tssep_cond_cat_bwd.
  * Algorithmic HBM bytes (R = B*trials*K*T rows of xs; the aux rows are re-read `stride` times from the caches):
  *   mul fwd  4 * (R*F + B*T*F + B*K*Ta*F)          (pre re-read trials*K times from the caches)
  *   mul bwd  4 * (R*F + B*K*Ta*F + B*T*F)

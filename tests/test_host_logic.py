@@ -24,6 +24,7 @@ def test_recurrence_policy():
         L = _lib.lib()
         assert L.tssep_lstm_onchip_max_steps(300, 16) == 14913 and L.tssep_lstm_onchip_max_steps(300, 32) == 7215
         import pytest
+        H._WARNED.clear()               # (announced once per process: a test that ran before this one may have had it)
         with pytest.warns(RuntimeWarning, match="streaming fp32 kernel runs instead"):
             assert H.recurrence_kernel(32, 300, True, T=20000) == "stream"
         assert H.recurrence_kernel(33, 300, True) == "onchip"

@@ -3,18 +3,10 @@
 // Every kernel streams its operands once (bandwidth-bound), sums in a fixed order (no floating-point
 // atomics: two runs are bit-identical) and takes everything it needs from its arguments and device memory.
 #include <math.h>
+#include <type_traits>
 #include "common.h"
 
 namespace {
-
-inline unsigned grid_for(int64_t n, int per_block = 256, int64_t cap = 256 * 16) {
-  int64_t b = (n + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  return (unsigned)(b < cap ? b : cap);
-}
-#define GRID_STRIDE(i, n)                                                           \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n);         \
-       i += (int64_t)gridDim.x * blockDim.x)
 
 constexpr int AUX_TCH = 64;      // frames per time chunk of the d_aux partials
 
@@ -388,9 +380,16 @@ inline void aux_window(int F, int E, int* col0, int* ncol) {
   *ncol = ((c1 + 3) & ~3) - *col0;
 }
 
-}  // namespace
+// launch(V, M) with the integral constants of (vec, mul): the <VEC, MUL> instantiation of a d_aux partial kernel
+template <class Fn>
+inline void aux_dispatch(bool vec, bool mul, Fn launch) {
+  if (vec && mul) launch(std::true_type{}, std::true_type{});
+  else if (vec) launch(std::true_type{}, std::false_type{});
+  else if (mul) launch(std::false_type{}, std::true_type{});
+  else launch(std::false_type{}, std::false_type{});
+}
 
-#define S_ ((hipStream_t)stream)
+}  // namespace
 
 extern "C" int64_t tssep_cond_aux_bwd_workspace_bytes(int64_t B, int64_t K, int64_t T, int F, int E) {
   if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || E < 0) return 0;
@@ -415,28 +414,14 @@ static int cond_aux_bwd(const float* dxs, int64_t ld_dxs, const float* pre, int6
   float* part = (float*)ws;
   const bool vec = (ld_dxs & 3) == 0 && ld_dxs >= col0 + ncol && aligned16(dxs) &&
                    (!mul || ((ld_pre & 3) == 0 && ld_pre >= ncol && aligned16(pre)));
-  int off;
-  if (vec) {
-    const int ntile = (ncol / 4 + 63) / 64;
-    const dim3 grid((unsigned)(BS * ntile), (unsigned)nchunk);
-    if (mul)
-      hipLaunchKernelGGL((cond_aux_bwd_partial_kernel<true, true>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre,
-                         part, BS, K, T, trials, col0, ncol, ldp, ntile);
-    else
-      hipLaunchKernelGGL((cond_aux_bwd_partial_kernel<true, false>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre,
-                         part, BS, K, T, trials, col0, ncol, ldp, ntile);
-    off = (mul ? 0 : F) - col0;
-  } else {
-    const int ntile = (C + 63) / 64;
-    const dim3 grid((unsigned)(BS * ntile), (unsigned)nchunk);
-    if (mul)
-      hipLaunchKernelGGL((cond_aux_bwd_partial_kernel<false, true>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre,
-                         part, BS, K, T, trials, 0, C, ldp, ntile);
-    else
-      hipLaunchKernelGGL((cond_aux_bwd_partial_kernel<false, false>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre,
-                         part, BS, K, T, trials, F, C, ldp, ntile);
-    off = 0;
-  }
+  if (!vec) { col0 = mul ? 0 : F; ncol = C; }
+  const int off = (mul ? 0 : F) - col0;      // where column c of d_aux sits in a row of the partials
+  const int ntile = ((vec ? ncol / 4 : ncol) + 63) / 64;
+  const dim3 grid((unsigned)(BS * ntile), (unsigned)nchunk);
+  aux_dispatch(vec, mul, [&](auto V, auto M) {
+    hipLaunchKernelGGL((cond_aux_bwd_partial_kernel<decltype(V)::value, decltype(M)::value>), grid, dim3(256), 0, S_,
+                       dxs, ld_dxs, pre, ld_pre, part, BS, K, T, trials, col0, ncol, ldp, ntile);
+  });
   hipLaunchKernelGGL(cond_aux_bwd_reduce_kernel, dim3(grid_for(BS * C)), dim3(256), 0, S_, part, BS, (int)nchunk, ldp,
                      off, C, d_aux, ld_daux);
   return tssep_launch_status();
@@ -493,21 +478,11 @@ static int cond_aux_t_bwd(const float* dxs, int64_t ld_dxs, const float* pre, in
   const int64_t ld_out = direct ? ld_daux : ldp;
   const int o = direct ? off : 0, c = direct ? C : ncol;
   const dim3 grid(grid_for(units * 64));
-  if (vec) {
-    if (mul)
-      hipLaunchKernelGGL((cond_aux_t_bwd_partial_kernel<true, true>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre, out,
-                         ld_out, BSA, K, T, trials, Ta, stride, nchunk, units, col0, ncol, ntile, o, c);
-    else
-      hipLaunchKernelGGL((cond_aux_t_bwd_partial_kernel<true, false>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre, out,
-                         ld_out, BSA, K, T, trials, Ta, stride, nchunk, units, col0, ncol, ntile, o, c);
-  } else {
-    if (mul)
-      hipLaunchKernelGGL((cond_aux_t_bwd_partial_kernel<false, true>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre, out,
-                         ld_out, BSA, K, T, trials, Ta, stride, nchunk, units, col0, ncol, ntile, o, c);
-    else
-      hipLaunchKernelGGL((cond_aux_t_bwd_partial_kernel<false, false>), grid, dim3(256), 0, S_, dxs, ld_dxs, pre, ld_pre, out,
-                         ld_out, BSA, K, T, trials, Ta, stride, nchunk, units, col0, ncol, ntile, o, c);
-  }
+  aux_dispatch(vec, mul, [&](auto V, auto M) {
+    hipLaunchKernelGGL((cond_aux_t_bwd_partial_kernel<decltype(V)::value, decltype(M)::value>), grid, dim3(256), 0, S_,
+                       dxs, ld_dxs, pre, ld_pre, out, ld_out, BSA, K, T, trials, Ta, stride, nchunk, units, col0, ncol,
+                       ntile, o, c);
+  });
   if (!direct)
     hipLaunchKernelGGL(cond_aux_bwd_reduce_kernel, dim3(grid_for(BSA * C)), dim3(256), 0, S_, (const float*)ws, BSA,
                        (int)nchunk, ldp, off, C, d_aux, ld_daux);

@@ -14,6 +14,19 @@ static inline int tssep_launch_status() {
   return e == hipSuccess ? TSSEP_OK : TSSEP_E_LAUNCH;
 }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+// ---- streaming kernels (elementwise.hip, dropout.hip, aux.hip) ----
+// blocks for n work items, per_block to a block; the kernels stride over what the cap leaves
+static inline unsigned grid_for(int64_t n, int per_block = 256, int64_t cap = 256 * 16) {
+  int64_t b = (n + per_block - 1) / per_block;
+  if (b < 1) b = 1;
+  return (unsigned)(b < cap ? b : cap);
+}
+#define GRID_STRIDE(i, n)                                                           \
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n);         \
+       i += (int64_t)gridDim.x * blockDim.x)
+// the entry points' `void* stream` argument
+#define S_ ((hipStream_t)stream)
+
 // frame-wise embeddings: frame t reads embedding row t / stride, and there are exactly ceil(T / stride) of them
 static inline bool cond_t_shape_ok(int64_t T, int64_t Ta, int64_t stride) {
   return T > 0 && stride >= 1 && Ta == (T - 1) / stride + 1;

@@ -11,15 +11,6 @@ namespace {
 
 using gemm_detail::gemm_tanh;
 
-inline unsigned grid_for(int64_t n, int per_block = 256, int64_t cap = 256 * 16) {
-  int64_t b = (n + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  return (unsigned)(b < cap ? b : cap);
-}
-#define GRID_STRIDE(i, n)                                                           \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n);         \
-       i += (int64_t)gridDim.x * blockDim.x)
-
 // state = {seed, draw}: hand this site its own copy and count the draw
 __global__ void dropout_draw_kernel(int64_t* __restrict__ state, int64_t* __restrict__ used) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -133,8 +124,6 @@ __global__ void dropout_tanh_bwd_kernel(const float* __restrict__ dy, const floa
 inline bool bad_p(double p) { return !(p >= 0.0 && p <= 1.0); }
 
 }  // namespace
-
-#define S_ ((hipStream_t)stream)
 
 extern "C" int tssep_philox4x32_10_host(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
   if (!ctr || !key || !out) return TSSEP_E_NULL;

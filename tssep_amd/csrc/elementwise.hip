@@ -7,18 +7,8 @@
 
 namespace {
 
-inline unsigned grid_for(int64_t n, int per_block = 256, int64_t cap = 256 * 16) {
-  int64_t b = (n + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  return (unsigned)(b < cap ? b : cap);
-}
-#define GRID_STRIDE(i, n)                                                           \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n);         \
-       i += (int64_t)gridDim.x * blockDim.x)
-
 // ---- speaker conditioning -----------------------------------------------------------------
-// rows of xs are (b,k,t); pre rows are (b,t); aux rows are (b,k)
-// rows of xs are (b, trial, k, t); trial tr puts speaker (k + tr) % K at position k (net.py:913-924)
+// rows of xs are (b, trial, k, t); trial tr puts speaker (k + tr) % K at position k (net.py:913-924); pre rows are (b,t)
 __device__ __forceinline__ void cond_row(int64_t row, int64_t K, int64_t T, int trials, int64_t& b,
                                          int64_t& t, int64_t& spk) {
   t = row % T;
@@ -28,10 +18,22 @@ __device__ __forceinline__ void cond_row(int64_t row, int64_t K, int64_t T, int 
   spk = k + tr;
   if (spk >= K) spk -= K;
 }
-// one wave per output row: the row decomposition (3 divisions) once per row instead of per element
+// aux rows are (b, spk) for utterance-level embeddings (!TIME) and (b, spk, ta), ta = t / stride, for frame-wise ones
+// (TIME; net.py:866-894 at stride 1).  That row index is ALL the two levels differ in: every kernel below is one body
+// for both, so a time-constant frame-wise aux gives the utterance level's bits.  !TIME ignores Ta and stride and
+// carries no division for them.
+template <bool TIME>
+__device__ __forceinline__ int64_t cond_ta(int64_t t, int64_t stride) { return TIME ? t / stride : 0; }
+template <bool TIME>
+__device__ __forceinline__ int64_t cond_aux_row(int64_t b, int64_t K, int64_t spk, int64_t Ta, int64_t ta) {
+  return TIME ? (b * K + spk) * Ta + ta : b * K + spk;
+}
+// one wave per output row: the row decomposition (3 divisions, and t / stride) once per row instead of per element
+template <bool TIME>
 __global__ __launch_bounds__(256) void cond_mul_fwd_kernel(
     const float* __restrict__ pre, int64_t ld_pre, const float* __restrict__ aux, int64_t ld_aux,
-    float* __restrict__ xs, int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int trials) {
+    float* __restrict__ xs, int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
+    int64_t stride) {
   const int lane = threadIdx.x & 63;
   const int64_t rows = B * trials * K * T;
   const bool vec = F <= 1024 && ((ld_pre | ld_aux | ld_xs) & 3) == 0 && ld_pre >= ((F + 3) & ~3) &&
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(256) void cond_mul_fwd_kernel(
     int64_t b, t, spk;
     cond_row(row, K, T, trials, b, t, spk);
     const float* p = pre + (b * T + t) * ld_pre;
-    const float* a = aux + (b * K + spk) * ld_aux;
+    const float* a = aux + cond_aux_row<TIME>(b, K, spk, Ta, cond_ta<TIME>(t, stride)) * ld_aux;
     float* o = xs + row * ld_xs;
     if (vec) {
       // 16-byte accesses, all loads of the row first (F <= 1024: at most 4 quads per lane); the pad
@@ -68,16 +70,18 @@ __global__ __launch_bounds__(256) void cond_mul_fwd_kernel(
 }
 // 16-byte variant: a thread owns 4 consecutive features of one (b, t) row and sums over (trial, speaker);
 // the K * trials loads are independent of each other (no per-element index arithmetic, 4x fewer requests)
+template <bool TIME>
 __global__ void cond_mul_bwd_v4_kernel(const float* __restrict__ dxs, int64_t ld_dxs,
                                        const float* __restrict__ aux, int64_t ld_aux,
                                        float* __restrict__ dpre, int64_t ld_dpre, int64_t B, int64_t K,
-                                       int64_t T, int F, int trials) {
+                                       int64_t T, int F, int trials, int64_t Ta, int64_t stride) {
   const int nq = (F + 3) >> 2;
   const int64_t total = B * T * nq;
   GRID_STRIDE(e, total) {
     const int64_t row = e / nq;
     const int q = (int)(e - row * nq);
     const int64_t t = row % T, b = row / T;
+    const int64_t ta = cond_ta<TIME>(t, stride);
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
     for (int tr = 0; tr < trials; ++tr) {
 #pragma unroll 4
@@ -85,36 +89,40 @@ __global__ void cond_mul_bwd_v4_kernel(const float* __restrict__ dxs, int64_t ld
         int64_t spk = k + tr;
         if (spk >= K) spk -= K;
         const f32x4 d = *reinterpret_cast<const f32x4*>(dxs + (((b * trials + tr) * K + k) * T + t) * ld_dxs + 4 * q);
-        const f32x4 a = *reinterpret_cast<const f32x4*>(aux + (b * K + spk) * ld_aux + 4 * q);
+        const f32x4 a = *reinterpret_cast<const f32x4*>(aux + cond_aux_row<TIME>(b, K, spk, Ta, ta) * ld_aux + 4 * q);
         s[0] += d[0] * a[0]; s[1] += d[1] * a[1]; s[2] += d[2] * a[2]; s[3] += d[3] * a[3];
       }
     }
     *reinterpret_cast<f32x4*>(dpre + row * ld_dpre + 4 * q) = s;
   }
 }
+template <bool TIME>
 __global__ void cond_mul_bwd_kernel(const float* __restrict__ dxs, int64_t ld_dxs,
                                     const float* __restrict__ aux, int64_t ld_aux,
-                                    float* __restrict__ dpre, int64_t ld_dpre, int64_t B,
-                                    int64_t K, int64_t T, int F, int trials) {
+                                    float* __restrict__ dpre, int64_t ld_dpre, int64_t B, int64_t K,
+                                    int64_t T, int F, int trials, int64_t Ta, int64_t stride) {
   const int64_t total = B * T * F;
   GRID_STRIDE(e, total) {
     const int64_t row = e / F;
     const int f = (int)(e - row * F);
     const int64_t t = row % T, b = row / T;
+    const int64_t ta = cond_ta<TIME>(t, stride);
     float s = 0.f;
     for (int tr = 0; tr < trials; ++tr)
       for (int64_t k = 0; k < K; ++k) {
         int64_t spk = k + tr;
         if (spk >= K) spk -= K;
-        s += dxs[(((b * trials + tr) * K + k) * T + t) * ld_dxs + f] * aux[(b * K + spk) * ld_aux + f];
+        s += dxs[(((b * trials + tr) * K + k) * T + t) * ld_dxs + f] *
+             aux[cond_aux_row<TIME>(b, K, spk, Ta, ta) * ld_aux + f];
       }
     dpre[row * ld_dpre + f] = s;
   }
 }
+template <bool TIME>
 __global__ void cond_cat_fwd_kernel(const float* __restrict__ pre, int64_t ld_pre,
                                     const float* __restrict__ aux, int64_t ld_aux,
                                     float* __restrict__ xs, int64_t ld_xs, int64_t B, int64_t K,
-                                    int64_t T, int F, int E, int trials) {
+                                    int64_t T, int F, int E, int trials, int64_t Ta, int64_t stride) {
   const int W = F + E;
   const int64_t total = B * trials * K * T * W;
   GRID_STRIDE(e, total) {
@@ -123,9 +131,11 @@ __global__ void cond_cat_fwd_kernel(const float* __restrict__ pre, int64_t ld_pr
     int64_t b, t, spk;
     cond_row(row, K, T, trials, b, t, spk);
     xs[row * ld_xs + c] =
-        c < F ? pre[(b * T + t) * ld_pre + c] : aux[(b * K + spk) * ld_aux + (c - F)];
+        c < F ? pre[(b * T + t) * ld_pre + c]
+              : aux[cond_aux_row<TIME>(b, K, spk, Ta, cond_ta<TIME>(t, stride)) * ld_aux + (c - F)];
   }
 }
+// (d(pre) of cat does not read the embedding: one kernel for both levels)
 __global__ void cond_cat_bwd_kernel(const float* __restrict__ dxs, int64_t ld_dxs,
                                     float* __restrict__ dpre, int64_t ld_dpre, int64_t B,
                                     int64_t K, int64_t T, int F, int trials) {
@@ -137,107 +147,6 @@ __global__ void cond_cat_bwd_kernel(const float* __restrict__ dxs, int64_t ld_dx
     float s = 0.f;
     for (int64_t q = 0; q < (int64_t)trials * K; ++q) s += dxs[((b * trials * K + q) * T + t) * ld_dxs + f];
     dpre[row * ld_dpre + f] = s;
-  }
-}
-
-// ---- speaker conditioning on frame-wise embeddings ------------------------------------------
-// aux rows are (b, spk, ta), ta = t / stride (net.py:866-894 at stride 1).  The kernels below are their utterance-level
-// neighbours above with that one row index: the same row decomposition, the same (trial, k) order and the same choice
-// between the 16-byte and the 4-byte path, so a time-constant aux gives the neighbours' bits.
-__global__ __launch_bounds__(256) void cond_mul_t_fwd_kernel(
-    const float* __restrict__ pre, int64_t ld_pre, const float* __restrict__ aux, int64_t ld_aux,
-    float* __restrict__ xs, int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
-    int64_t stride) {
-  const int lane = threadIdx.x & 63;
-  const int64_t rows = B * trials * K * T;
-  const bool vec = F <= 1024 && ((ld_pre | ld_aux | ld_xs) & 3) == 0 && ld_pre >= ((F + 3) & ~3) &&
-                   ld_aux >= ((F + 3) & ~3) && ld_xs >= ((F + 3) & ~3) &&
-                   ((((uintptr_t)pre) | ((uintptr_t)aux) | ((uintptr_t)xs)) & 15) == 0;
-  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (int64_t)gridDim.x * 4) {
-    int64_t b, t, spk;
-    cond_row(row, K, T, trials, b, t, spk);
-    const float* p = pre + (b * T + t) * ld_pre;
-    const float* a = aux + ((b * K + spk) * Ta + t / stride) * ld_aux;
-    float* o = xs + row * ld_xs;
-    if (vec) {
-      const int nq = (F + 3) >> 2;
-      f32x4 pv[4], av[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int q = lane + 64 * r;
-        if (q < nq) {
-          pv[r] = *reinterpret_cast<const f32x4*>(p + 4 * q);
-          av[r] = *reinterpret_cast<const f32x4*>(a + 4 * q);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int q = lane + 64 * r;
-        if (q < nq) __builtin_nontemporal_store(pv[r] * av[r], reinterpret_cast<f32x4*>(o + 4 * q));
-      }
-    } else {
-      for (int f = lane; f < F; f += 64) o[f] = p[f] * a[f];
-    }
-  }
-}
-__global__ void cond_mul_t_bwd_v4_kernel(const float* __restrict__ dxs, int64_t ld_dxs,
-                                         const float* __restrict__ aux, int64_t ld_aux,
-                                         float* __restrict__ dpre, int64_t ld_dpre, int64_t B, int64_t K,
-                                         int64_t T, int F, int trials, int64_t Ta, int64_t stride) {
-  const int nq = (F + 3) >> 2;
-  const int64_t total = B * T * nq;
-  GRID_STRIDE(e, total) {
-    const int64_t row = e / nq;
-    const int q = (int)(e - row * nq);
-    const int64_t t = row % T, b = row / T;
-    const int64_t ta = t / stride;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int tr = 0; tr < trials; ++tr) {
-#pragma unroll 4
-      for (int64_t k = 0; k < K; ++k) {
-        int64_t spk = k + tr;
-        if (spk >= K) spk -= K;
-        const f32x4 d = *reinterpret_cast<const f32x4*>(dxs + (((b * trials + tr) * K + k) * T + t) * ld_dxs + 4 * q);
-        const f32x4 a = *reinterpret_cast<const f32x4*>(aux + ((b * K + spk) * Ta + ta) * ld_aux + 4 * q);
-        s[0] += d[0] * a[0]; s[1] += d[1] * a[1]; s[2] += d[2] * a[2]; s[3] += d[3] * a[3];
-      }
-    }
-    *reinterpret_cast<f32x4*>(dpre + row * ld_dpre + 4 * q) = s;
-  }
-}
-__global__ void cond_mul_t_bwd_kernel(const float* __restrict__ dxs, int64_t ld_dxs,
-                                      const float* __restrict__ aux, int64_t ld_aux,
-                                      float* __restrict__ dpre, int64_t ld_dpre, int64_t B, int64_t K,
-                                      int64_t T, int F, int trials, int64_t Ta, int64_t stride) {
-  const int64_t total = B * T * F;
-  GRID_STRIDE(e, total) {
-    const int64_t row = e / F;
-    const int f = (int)(e - row * F);
-    const int64_t t = row % T, b = row / T;
-    const int64_t ta = t / stride;
-    float s = 0.f;
-    for (int tr = 0; tr < trials; ++tr)
-      for (int64_t k = 0; k < K; ++k) {
-        int64_t spk = k + tr;
-        if (spk >= K) spk -= K;
-        s += dxs[(((b * trials + tr) * K + k) * T + t) * ld_dxs + f] * aux[((b * K + spk) * Ta + ta) * ld_aux + f];
-      }
-    dpre[row * ld_dpre + f] = s;
-  }
-}
-__global__ void cond_cat_t_fwd_kernel(const float* __restrict__ pre, int64_t ld_pre,
-                                      const float* __restrict__ aux, int64_t ld_aux,
-                                      float* __restrict__ xs, int64_t ld_xs, int64_t B, int64_t K,
-                                      int64_t T, int F, int E, int trials, int64_t Ta, int64_t stride) {
-  const int W = F + E;
-  const int64_t total = B * trials * K * T * W;
-  GRID_STRIDE(e, total) {
-    const int64_t row = e / W;
-    const int c = (int)(e - row * W);
-    int64_t b, t, spk;
-    cond_row(row, K, T, trials, b, t, spk);
-    xs[row * ld_xs + c] =
-        c < F ? pre[(b * T + t) * ld_pre + c] : aux[((b * K + spk) * Ta + t / stride) * ld_aux + (c - F)];
   }
 }
 
@@ -945,43 +854,80 @@ __global__ __launch_bounds__(256) void mask_map_bwd_t_kernel(const float* __rest
 
 }  // namespace
 
-#define S_ ((hipStream_t)stream)
+// The conditioning entry points: one launcher per role for both levels; the utterance level passes Ta = 0, stride = 1,
+// which cond_t_shape_ok is not asked about and the <false> kernels ignore.
+template <bool TIME>
+static int cond_mul_fwd(const float* pre, int64_t ld_pre, const float* aux, int64_t ld_aux, float* xs, int64_t ld_xs,
+                        int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta, int64_t stride, void* stream) {
+  if (!pre || !aux || !xs) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || trials <= 0 || trials > K || (TIME && !cond_t_shape_ok(T, Ta, stride)))
+    return TSSEP_E_SHAPE;
+  hipLaunchKernelGGL(cond_mul_fwd_kernel<TIME>, dim3(grid_for(B * trials * K * T * 64)), dim3(256), 0, S_,
+                     pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, trials, Ta, stride);
+  return tssep_launch_status();
+}
+template <bool TIME>
+static int cond_mul_bwd(const float* dxs, int64_t ld_dxs, const float* aux, int64_t ld_aux, float* dpre,
+                        int64_t ld_dpre, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta, int64_t stride,
+                        void* stream) {
+  if (!dxs || !aux || !dpre) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || trials <= 0 || trials > K || (TIME && !cond_t_shape_ok(T, Ta, stride)))
+    return TSSEP_E_SHAPE;
+  const int64_t fp = (F + 3) & ~3;
+  // 16-byte path: every row holds whole quads at 16-byte addresses (the pad columns of a row are summed too: products
+  // of the inputs' pad columns, zero in the step)
+  const bool vec = ((ld_dxs | ld_aux | ld_dpre) & 3) == 0 && ld_dxs >= fp && ld_aux >= fp && ld_dpre >= fp &&
+                   ((((uintptr_t)dxs) | ((uintptr_t)aux) | ((uintptr_t)dpre)) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(cond_mul_bwd_v4_kernel<TIME>, dim3(grid_for(B * T * (fp / 4))), dim3(256), 0, S_, dxs, ld_dxs,
+                       aux, ld_aux, dpre, ld_dpre, B, K, T, F, trials, Ta, stride);
+  else
+    hipLaunchKernelGGL(cond_mul_bwd_kernel<TIME>, dim3(grid_for(B * T * F)), dim3(256), 0, S_, dxs, ld_dxs,
+                       aux, ld_aux, dpre, ld_dpre, B, K, T, F, trials, Ta, stride);
+  return tssep_launch_status();
+}
+template <bool TIME>
+static int cond_cat_fwd(const float* pre, int64_t ld_pre, const float* aux, int64_t ld_aux, float* xs, int64_t ld_xs,
+                        int64_t B, int64_t K, int64_t T, int F, int E, int trials, int64_t Ta, int64_t stride,
+                        void* stream) {
+  if (!pre || !aux || !xs) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || E <= 0 || trials <= 0 || trials > K ||
+      (TIME && !cond_t_shape_ok(T, Ta, stride)))
+    return TSSEP_E_SHAPE;
+  hipLaunchKernelGGL(cond_cat_fwd_kernel<TIME>, dim3(grid_for(B * trials * K * T * (F + E))), dim3(256),
+                     0, S_, pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, E, trials, Ta, stride);
+  return tssep_launch_status();
+}
 
 extern "C" int tssep_cond_mul_fwd(const float* pre, int64_t ld_pre, const float* aux,
                                   int64_t ld_aux, float* xs, int64_t ld_xs, int64_t B, int64_t K,
                                   int64_t T, int F, int trials, void* stream) {
-  if (!pre || !aux || !xs) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || trials <= 0 || trials > K) return TSSEP_E_SHAPE;
-  hipLaunchKernelGGL(cond_mul_fwd_kernel, dim3(grid_for(B * trials * K * T * 64)), dim3(256), 0, S_,
-                     pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, trials);
-  return tssep_launch_status();
+  return cond_mul_fwd<false>(pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, trials, 0, 1, stream);
+}
+extern "C" int tssep_cond_mul_t_fwd(const float* pre, int64_t ld_pre, const float* aux, int64_t ld_aux, float* xs,
+                                    int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
+                                    int64_t stride, void* stream) {
+  return cond_mul_fwd<true>(pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, trials, Ta, stride, stream);
 }
 extern "C" int tssep_cond_mul_bwd(const float* dxs, int64_t ld_dxs, const float* aux,
                                   int64_t ld_aux, float* dpre, int64_t ld_dpre, int64_t B,
                                   int64_t K, int64_t T, int F, int trials, void* stream) {
-  if (!dxs || !aux || !dpre) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || trials <= 0 || trials > K) return TSSEP_E_SHAPE;
-  const int64_t fp = (F + 3) & ~3;
-  if (((ld_dxs | ld_aux | ld_dpre) & 3) == 0 && ld_dxs >= fp && ld_aux >= fp && ld_dpre >= fp &&
-      ((((uintptr_t)dxs) | ((uintptr_t)aux) | ((uintptr_t)dpre)) & 15) == 0) {
-    // (the pad columns of a row are summed too: products of the inputs' pad columns, zero in the step)
-    hipLaunchKernelGGL(cond_mul_bwd_v4_kernel, dim3(grid_for(B * T * (fp / 4))), dim3(256), 0, S_, dxs, ld_dxs,
-                       aux, ld_aux, dpre, ld_dpre, B, K, T, F, trials);
-    return tssep_launch_status();
-  }
-  hipLaunchKernelGGL(cond_mul_bwd_kernel, dim3(grid_for(B * T * F)), dim3(256), 0, S_, dxs, ld_dxs,
-                     aux, ld_aux, dpre, ld_dpre, B, K, T, F, trials);
-  return tssep_launch_status();
+  return cond_mul_bwd<false>(dxs, ld_dxs, aux, ld_aux, dpre, ld_dpre, B, K, T, F, trials, 0, 1, stream);
+}
+extern "C" int tssep_cond_mul_t_bwd(const float* dxs, int64_t ld_dxs, const float* aux, int64_t ld_aux, float* dpre,
+                                    int64_t ld_dpre, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
+                                    int64_t stride, void* stream) {
+  return cond_mul_bwd<true>(dxs, ld_dxs, aux, ld_aux, dpre, ld_dpre, B, K, T, F, trials, Ta, stride, stream);
 }
 extern "C" int tssep_cond_cat_fwd(const float* pre, int64_t ld_pre, const float* aux,
                                   int64_t ld_aux, float* xs, int64_t ld_xs, int64_t B, int64_t K,
                                   int64_t T, int F, int E, int trials, void* stream) {
-  if (!pre || !aux || !xs) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || E <= 0 || trials <= 0 || trials > K)
-    return TSSEP_E_SHAPE;
-  hipLaunchKernelGGL(cond_cat_fwd_kernel, dim3(grid_for(B * trials * K * T * (F + E))), dim3(256),
-                     0, S_, pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, E, trials);
-  return tssep_launch_status();
+  return cond_cat_fwd<false>(pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, E, trials, 0, 1, stream);
+}
+extern "C" int tssep_cond_cat_t_fwd(const float* pre, int64_t ld_pre, const float* aux, int64_t ld_aux, float* xs,
+                                    int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int E, int trials,
+                                    int64_t Ta, int64_t stride, void* stream) {
+  return cond_cat_fwd<true>(pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, E, trials, Ta, stride, stream);
 }
 extern "C" int tssep_cond_cat_bwd(const float* dxs, int64_t ld_dxs, float* dpre, int64_t ld_dpre,
                                   int64_t B, int64_t K, int64_t T, int F, int trials, void* stream) {
@@ -989,44 +935,6 @@ extern "C" int tssep_cond_cat_bwd(const float* dxs, int64_t ld_dxs, float* dpre,
   if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || trials <= 0 || trials > K) return TSSEP_E_SHAPE;
   hipLaunchKernelGGL(cond_cat_bwd_kernel, dim3(grid_for(B * T * F)), dim3(256), 0, S_, dxs, ld_dxs,
                      dpre, ld_dpre, B, K, T, F, trials);
-  return tssep_launch_status();
-}
-extern "C" int tssep_cond_mul_t_fwd(const float* pre, int64_t ld_pre, const float* aux, int64_t ld_aux, float* xs,
-                                    int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
-                                    int64_t stride, void* stream) {
-  if (!pre || !aux || !xs) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || trials <= 0 || trials > K || !cond_t_shape_ok(T, Ta, stride))
-    return TSSEP_E_SHAPE;
-  hipLaunchKernelGGL(cond_mul_t_fwd_kernel, dim3(grid_for(B * trials * K * T * 64)), dim3(256), 0, S_,
-                     pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, trials, Ta, stride);
-  return tssep_launch_status();
-}
-extern "C" int tssep_cond_mul_t_bwd(const float* dxs, int64_t ld_dxs, const float* aux, int64_t ld_aux, float* dpre,
-                                    int64_t ld_dpre, int64_t B, int64_t K, int64_t T, int F, int trials, int64_t Ta,
-                                    int64_t stride, void* stream) {
-  if (!dxs || !aux || !dpre) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || trials <= 0 || trials > K || !cond_t_shape_ok(T, Ta, stride))
-    return TSSEP_E_SHAPE;
-  const int64_t fp = (F + 3) & ~3;
-  if (((ld_dxs | ld_aux | ld_dpre) & 3) == 0 && ld_dxs >= fp && ld_aux >= fp && ld_dpre >= fp &&
-      ((((uintptr_t)dxs) | ((uintptr_t)aux) | ((uintptr_t)dpre)) & 15) == 0) {
-    hipLaunchKernelGGL(cond_mul_t_bwd_v4_kernel, dim3(grid_for(B * T * (fp / 4))), dim3(256), 0, S_, dxs, ld_dxs,
-                       aux, ld_aux, dpre, ld_dpre, B, K, T, F, trials, Ta, stride);
-    return tssep_launch_status();
-  }
-  hipLaunchKernelGGL(cond_mul_t_bwd_kernel, dim3(grid_for(B * T * F)), dim3(256), 0, S_, dxs, ld_dxs,
-                     aux, ld_aux, dpre, ld_dpre, B, K, T, F, trials, Ta, stride);
-  return tssep_launch_status();
-}
-extern "C" int tssep_cond_cat_t_fwd(const float* pre, int64_t ld_pre, const float* aux, int64_t ld_aux, float* xs,
-                                    int64_t ld_xs, int64_t B, int64_t K, int64_t T, int F, int E, int trials,
-                                    int64_t Ta, int64_t stride, void* stream) {
-  if (!pre || !aux || !xs) return TSSEP_E_NULL;
-  if (B <= 0 || K <= 0 || T <= 0 || F <= 0 || E <= 0 || trials <= 0 || trials > K ||
-      !cond_t_shape_ok(T, Ta, stride))
-    return TSSEP_E_SHAPE;
-  hipLaunchKernelGGL(cond_cat_t_fwd_kernel, dim3(grid_for(B * trials * K * T * (F + E))), dim3(256),
-                     0, S_, pre, ld_pre, aux, ld_aux, xs, ld_xs, B, K, T, F, E, trials, Ta, stride);
   return tssep_launch_status();
 }
 extern "C" int tssep_tanh_bwd(const float* dy, const float* y, float* dz, int64_t rows, int64_t P,

@@ -1174,13 +1174,25 @@ def cond_frames(T, Ta, stride):
                          f"(ceil(T / aux_stride) = {-(-T // stride)} rows are needed)")
 
 
+def _cond_level(Ta, stride):
+    """The one place that tells the two embedding levels apart: -> (t, level).  t is the infix of entry points and labels,
+    "" for utterance-level embeddings (Ta = 0) and "_t" for frame-wise ones; level holds the trailing arguments the "_t"
+    entry points take, (Ta, stride), or nothing."""
+    return ("_t", (Ta, stride)) if Ta else ("", ())
+
+
+def _entry(name):
+    """-> (the bound tssep_<name>, its check label)"""
+    return getattr(_lib.lib(), "tssep_" + name), name
+
+
 def cond_fwd(pre, ld_pre, aux, B, K, T, F, trials, combination, Ta=0, stride=1, auxinfo=None):
     """-> (xs view [B*trials*K*T, W], ld, (aux rows, ld_aux)).  aux [B, K, E], or frame-wise [B, K, Ta, E] with
     Ta = ceil(T / stride) > 0.  The kernels take aux as 16-byte addressable rows: an aux whose E is no multiple of 4 is
     copied into padded rows first (rows_view: one pass over aux per call, layout glue); auxinfo = rows_view(aux) made by the
     caller skips that."""
-    L = _lib.lib()
     cond_frames(T, Ta, stride)
+    t, level = _cond_level(Ta, stride)
     aux2, ld_aux = auxinfo if auxinfo is not None else rows_view(aux)
     E = aux.shape[-1]
     W = F if combination == "mul" else F + E
@@ -1190,18 +1202,11 @@ def cond_fwd(pre, ld_pre, aux, B, K, T, F, trials, combination, Ta=0, stride=1, 
     xs, ld = padded(B * trials * K * T, W, pre.device, zero=not writes_pads)
     if combination == "mul":
         assert E == F, (E, F)
-        if Ta:
-            check(L.tssep_cond_mul_t_fwd(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F, trials, Ta, stride,
-                                         _stream()), "cond_mul_t_fwd")
-        else:
-            check(L.tssep_cond_mul_fwd(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F,
-                                       trials, _stream()), "cond_mul_fwd")
-    elif Ta:
-        check(L.tssep_cond_cat_t_fwd(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F, E, trials, Ta, stride,
-                                     _stream()), "cond_cat_t_fwd")
+        fn, label = _entry(f"cond_mul{t}_fwd")
+        check(fn(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F, trials, *level, _stream()), label)
     else:
-        check(L.tssep_cond_cat_fwd(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F, E,
-                                   trials, _stream()), "cond_cat_fwd")
+        fn, label = _entry(f"cond_cat{t}_fwd")
+        check(fn(_p(pre), ld_pre, _p(aux2), ld_aux, _p(xs), ld, B, K, T, F, E, trials, *level, _stream()), label)
     return xs, ld, (aux2, ld_aux)
 
 
@@ -1212,12 +1217,10 @@ def cond_bwd(dxs, ld_dxs, auxinfo, B, K, T, F, trials, combination, Ta=0, stride
     writes_pads = combination == "mul" and ld_dxs % 4 == 0 and ld_dxs >= round_up(F, 4) and dxs.data_ptr() % 16 == 0 \
         and aux2.data_ptr() % 16 == 0
     dpre, ld = padded(B * T, F, dxs.device, zero=not writes_pads)
-    if combination == "mul" and Ta:
-        check(L.tssep_cond_mul_t_bwd(_p(dxs), ld_dxs, _p(aux2), ld_aux, _p(dpre), ld, B, K, T, F, trials, Ta, stride,
-                                     _stream()), "cond_mul_t_bwd")
-    elif combination == "mul":
-        check(L.tssep_cond_mul_bwd(_p(dxs), ld_dxs, _p(aux2), ld_aux, _p(dpre), ld, B, K, T, F,
-                                   trials, _stream()), "cond_mul_bwd")
+    if combination == "mul":
+        t, level = _cond_level(Ta, stride)
+        fn, label = _entry(f"cond_mul{t}_bwd")
+        check(fn(_p(dxs), ld_dxs, _p(aux2), ld_aux, _p(dpre), ld, B, K, T, F, trials, *level, _stream()), label)
     else:                                   # (d(pre) of cat does not read the embedding: one entry point for both)
         check(L.tssep_cond_cat_bwd(_p(dxs), ld_dxs, _p(dpre), ld, B, K, T, F, trials, _stream()),
               "cond_cat_bwd")
@@ -1229,35 +1232,24 @@ def cond_aux_bwd(dxs, ld_dxs, pre, ld_pre, B, K, T, F, E, trials, combination, T
     """d(conditioning) / d(embedding) -> d_aux [B, K, C] (C = F for mul, E for cat), or [B, K, Ta, C] for frame-wise
     embeddings (Ta > 0).  A launch of its own, made only when the embedding requires a gradient (pre: the pre-net rows
     the forward multiplied with; None for cat)."""
-    L = _lib.lib()
+    t, level = _cond_level(Ta, stride)
     mul = combination == "mul"
     C = F if mul else E
-    if Ta:
-        nbytes = int(L.tssep_cond_aux_t_bwd_workspace_bytes(B, K, T, F, 0 if mul else E, Ta, stride))
-        if nbytes < 0:
-            check(-1, "cond_aux_t_bwd_workspace_bytes")
-        ws = torch.empty(nbytes // 4, device=dxs.device, dtype=torch.float32) if nbytes else None
-        d_aux = torch.empty(B, K, Ta, C, device=dxs.device, dtype=torch.float32)
-        with _timed("cond_aux_t_bwd", 0, 4 * (B * trials * K * T * C + (B * T * F if mul else 0) + B * K * Ta * C)):
-            if mul:
-                check(L.tssep_cond_mul_aux_t_bwd(_p(_f32(dxs)), ld_dxs, _p(_f32(pre)), ld_pre, _p(d_aux), C, _p(ws), B, K, T,
-                                                 F, trials, Ta, stride, _stream()), "cond_mul_aux_t_bwd")
-            else:
-                check(L.tssep_cond_cat_aux_t_bwd(_p(_f32(dxs)), ld_dxs, _p(d_aux), C, _p(ws), B, K, T, F, E, trials, Ta,
-                                                 stride, _stream()), "cond_cat_aux_t_bwd")
-        return d_aux
-    nbytes = int(L.tssep_cond_aux_bwd_workspace_bytes(B, K, T, F, 0 if mul else E))
-    if nbytes <= 0:
-        check(-1, "cond_aux_bwd_workspace_bytes")
-    ws = torch.empty(nbytes // 4, device=dxs.device, dtype=torch.float32)
-    d_aux = torch.empty(B, K, C, device=dxs.device, dtype=torch.float32)
-    with _timed("cond_aux_bwd", 0, 4 * (B * trials * K * T * C + (B * T * F if mul else 0) + B * K * C)):
+    fn, label = _entry(f"cond_aux{t}_bwd_workspace_bytes")
+    nbytes = int(fn(B, K, T, F, 0 if mul else E, *level))
+    # frame-wise: -1 refuses the shapes and 0 asks for no workspace; the utterance level always needs one
+    if nbytes < 0 or (nbytes == 0 and not Ta):
+        check(-1, label)
+    ws = torch.empty(nbytes // 4, device=dxs.device, dtype=torch.float32) if nbytes else None
+    d_aux = torch.empty(B, K, *level[:1], C, device=dxs.device, dtype=torch.float32)
+    with _timed(f"cond_aux{t}_bwd", 0, 4 * (B * trials * K * T * C + (B * T * F if mul else 0) + d_aux.numel())):
         if mul:
-            check(L.tssep_cond_mul_aux_bwd(_p(_f32(dxs)), ld_dxs, _p(_f32(pre)), ld_pre, _p(d_aux), C, _p(ws), B, K, T, F,
-                                           trials, _stream()), "cond_mul_aux_bwd")
+            fn, label = _entry(f"cond_mul_aux{t}_bwd")
+            check(fn(_p(_f32(dxs)), ld_dxs, _p(_f32(pre)), ld_pre, _p(d_aux), C, _p(ws), B, K, T, F, trials, *level,
+                     _stream()), label)
         else:
-            check(L.tssep_cond_cat_aux_bwd(_p(_f32(dxs)), ld_dxs, _p(d_aux), C, _p(ws), B, K, T, F, E, trials,
-                                           _stream()), "cond_cat_aux_bwd")
+            fn, label = _entry(f"cond_cat_aux{t}_bwd")
+            check(fn(_p(_f32(dxs)), ld_dxs, _p(d_aux), C, _p(ws), B, K, T, F, E, trials, *level, _stream()), label)
     return d_aux
 
 
