@@ -755,6 +755,34 @@ int tssep_mvdr_segments_fwd_obs(const double* obs_seg, const int64_t* row0, int6
                                 double distortion_eps, double mask_power, int psd_real, double eps,
                                 int masking, double masking_eps, void* stream);
 
+/* ------------------------------------------- masks -> segment table (discretisation) ----
+ * The step between an estimated mask and the segment-wise beamformer above (the "threshold, then closing by dilation
+ * and erosion" of the TS-VAD / TS-SEP papers); the semantics are this project's own, DESIGN 4.13:
+ *   a[k,t]  = fl32(sum_f masks[k,0,t,f]) / fl32(F)       tssep_mask_activity: masks [K,M,T,F] fp32, mask index 0 read by
+ *             stride (M = 2: index 1 is never touched), activity [K,T] fp32.  The sum is fp32 in an order that depends
+ *             on F and on the row's address modulo 16 only (two calls give the same bits), the division one correctly
+ *             rounded fp32 division.  One pass, K*T*F*4 bytes read, no atomics.
+ *   b[k,t]  = a[k,t] > threshold                         strict, in fp32; a NaN is inactive
+ *   closing = binary dilation with the odd window `dilation`, then binary erosion with the odd window `erosion`, both
+ *             clipped to [0,T): frames outside the row count as inactive for the dilation and as active for the erosion
+ *             (a run that reaches the first or the last frame is not eroded from that side).  Window 1 = identity; a
+ *             window larger than 2 T is legal.
+ *   runs    = the maximal runs [s,e) of ones per row; those with e - s < min_frames are dropped
+ *   table   int32 rows (k, s, e), sorted by k then s, 0 <= s < e <= T, count[0] rows of them: the form
+ *           tssep_mvdr_segments_fwd takes.  table holds tssep_segments_capacity(K, T) = K * ceil(T / 2) rows (a row of
+ *           T frames cannot hold more runs: no overflow case); rows past count[0] are not written.
+ * tssep_segments_capacity is host-only (no launch): 0 for a shape the kernels refuse (K < 1, T < 1, T > 2^30 or
+ * K * ceil(T / 2) > 2^30).
+ * workspace: 4 * (9 * capacity + 16) bytes, 8-byte aligned.  A fixed number of launches (nine) whatever T, the content
+ * or the number of runs; the order of the table comes from prefix sums, never from atomics: the same table on every
+ * call.  No host sync.  TSSEP_E_SHAPE before any launch for K, T, F or M < 1, an even or non-positive window,
+ * min_frames < 1. */
+int64_t tssep_segments_capacity(int64_t K, int64_t T);
+int tssep_mask_activity(const float* masks, int64_t K, int M, int64_t T, int F, float* activity, void* stream);
+int tssep_activity_segments(const float* activity, int64_t K, int64_t T, float threshold, int64_t dilation,
+                            int64_t erosion, int64_t min_frames, int32_t* table, int32_t* count, void* workspace,
+                            void* stream);
+
 /* ------------------------------------------------------- WPE dereverberation ----
  * WPE / ChannelWiseWPE of the reference (tssep/train/enhancer.py:292-367; nara_wpe's wpe_v8 on the host
  * there), complex128.  Per frequency bin, K = taps * D:

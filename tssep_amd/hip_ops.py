@@ -1533,7 +1533,7 @@ def segment_psd(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1e
 
 def segment_mvdr(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1e-4, mask_power=1,
                  eps=None, masking=False, masking_eps=0.0, psd_real=True, check_singular=True,
-                 out=None, obs_seg=None, row0=None):
+                 out=None, obs_seg=None, row0=None, check_table=False):
     """ClassicBF_np('mvdr_souden', segment_bf=True), tssep/train/enhancer.py:451-590: one Souden MVDR
     per row (speaker, start, end) of `segments` from the statistics of that interval, the distortion
     mask from the other speakers' masks (mode), filtered over the interval; zero elsewhere.
@@ -1543,7 +1543,10 @@ def segment_mvdr(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1
     the (speaker, start, end) segments with a singular distortion PSD (one host read;
     check_singular=False skips it, the call is then free of host syncs and capturable).
     obs_seg [D,N,F] with row0 [S+1] (what `wpe` returns for the (s, e) columns of the same table): every row takes
-    its statistics and its filter input from its own packed frames instead of obs[:, s:e]."""
+    its statistics and its filter input from its own packed frames instead of obs[:, s:e].
+    check_table: the table travels to the host in the copy of the singular check and a row outside [0, K) x [0, T] or
+    an empty one raises ValueError: a device-born table is checked without a host read of its own (the kernels ignore
+    such rows, no access leaves the buffers)."""
     L = _lib.lib()
     masks, obs_r, tab, ws, (K, S, D, T, F) = _segment_args(masks, obs, segments)
     if (obs_seg is None) != (row0 is None):
@@ -1571,7 +1574,14 @@ def segment_mvdr(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1
                                                 _p(torch.view_as_real(out)), _p(ws), _p(info), *tail),
                   "segment_mvdr (packed observation)")
     if check_singular:
-        bad = info.cpu().numpy()
+        host = (torch.cat([info, tab.reshape(-1)]) if check_table else info).cpu().numpy()
+        bad = host[:S]
+        if check_table:
+            r = host[S:].reshape(S, 3)
+            wrong = (r[:, 0] < 0) | (r[:, 0] >= K) | (r[:, 1] < 0) | (r[:, 2] > T) | (r[:, 1] >= r[:, 2])
+            if wrong.any():
+                raise ValueError(f"segment_mvdr: rows {[tuple(int(v) for v in x) for x in r[wrong][:8]]} of the segment "
+                                 f"table lie outside speakers [0, {K}) x frames [0, {T}] or are empty")
         if bad.any():
             rows = tab.cpu().numpy()
             failed = [tuple(int(v) for v in rows[i]) for i in bad.nonzero()[0]]
@@ -1579,6 +1589,65 @@ def segment_mvdr(masks, obs, segments, mode="sum_cross_talker", distortion_eps=1
                 f"segment_mvdr: the solver failed because the distortion PSD matrix is singular in "
                 f"{len(failed)} of {S} segments (speaker, start, end): {failed}")
     return out
+
+
+# ------------------------------------------------------ masks -> segment table (csrc/segments.hip)
+def segments_capacity(K, T):
+    """Rows of the table buffer of activity_segments: K * ceil(T / 2); 0 for a shape the kernels refuse.  Host only."""
+    return int(_lib.lib().tssep_segments_capacity(int(K), int(T)))
+
+
+def mask_activity(masks):
+    """masks [K, M, T, F] -> activity float32 [K, T] = fl32(sum_f masks[k, 0, t, f]) / fl32(F): mask index 0 (the target
+    mask when M = 2), read by stride -- index 1 is never touched and nothing is copied.  One pass over K*T*F*4 bytes, the
+    sum in float32 in a fixed order (two calls give the same bits), one correctly rounded division.  float64 masks are
+    cast to float32 once, here, before the pass (mask index 0 only); any other dtype is refused."""
+    assert masks.is_cuda and masks.dim() == 4, (masks.device, masks.shape)
+    if masks.dtype == torch.float64:
+        masks = masks[:, :1].to(torch.float32)
+    m = _f32(masks.detach()).contiguous()
+    K, M, T, F = m.shape
+    act = torch.empty(K, T, device=m.device, dtype=torch.float32)
+    with _timed("mask_activity", 0, 4 * K * T * (F + 1)):
+        check(_lib.lib().tssep_mask_activity(_p(m), K, M, T, F, _p(act), _stream()), "mask_activity")
+    return act
+
+
+def check_segment_params(dilation=1, erosion=1, min_frames=1):
+    """ValueError for an even or non-positive window or min_frames < 1: on the host, before any launch."""
+    for name, w in (("dilation", dilation), ("erosion", erosion)):
+        if int(w) != w or w < 1 or w % 2 == 0:
+            raise ValueError(f"{name}={w!r}: the window is an odd number of frames >= 1")
+    if int(min_frames) != min_frames or min_frames < 1:
+        raise ValueError(f"min_frames={min_frames!r}: at least 1")
+
+
+def activity_segments(activity, threshold=0.5, dilation=1, erosion=1, min_frames=1, return_count=False):
+    """activity float32 [K, T] -> the segment table int32 [S, 3] of segment_mvdr, rows (k, s, e) sorted by k then s, on
+    the device: b = activity > threshold (strict, in float32; NaN is inactive), binary dilation then erosion with odd
+    windows clipped to the row, maximal runs, runs shorter than min_frames dropped.  Nine launches whatever
+    T, the content and the number of runs; the same table on every call.
+    The result is a view of the capacity buffer [K * ceil(T / 2), 3] cut to the count.  Reading that count is the ONE
+    host synchronisation of the route masks -> table: S is a tensor shape.  return_count=True returns
+    (buffer, count) instead, count an int32 [1] device tensor, with no synchronisation; rows past the count are
+    undefined."""
+    check_segment_params(dilation, erosion, min_frames)
+    a = _f32(activity.detach()).contiguous()
+    assert a.dim() == 2, a.shape
+    K, T = a.shape
+    cap = segments_capacity(K, T)
+    if cap <= 0:
+        raise RuntimeError(f"activity_segments: unsupported shape {tuple(a.shape)}")
+    table = torch.empty(cap, 3, device=a.device, dtype=torch.int32)
+    count = torch.empty(1, device=a.device, dtype=torch.int32)
+    ws = torch.empty(9 * cap + 16, device=a.device, dtype=torch.int32)
+    with _timed("activity_segments", 0, 12 * K * T):
+        check(_lib.lib().tssep_activity_segments(_p(a), K, T, float(threshold), int(dilation), int(erosion),
+                                                 int(min_frames), _p(table), _p(count), _p(ws), _stream()),
+              "activity_segments")
+    if return_count:
+        return table, count
+    return table[:int(count.item())]
 
 
 # ----------------------------------------------------------------------------- WPE

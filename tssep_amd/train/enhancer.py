@@ -164,6 +164,18 @@ def normalized_intervals(ai, T):
     return out
 
 
+def _table_intervals(rows, K, T):
+    """host rows (k, s, e) of a segment table -> per speaker [(s, e), ...]; a row outside [0, K) x [0, T] or an empty
+    one raises ValueError"""
+    out = [[] for _ in range(K)]
+    for k, s, e in rows:
+        if not (0 <= k < K and 0 <= s < e <= T):
+            raise ValueError(f"segment table row ({k}, {s}, {e}) lies outside speakers [0, {K}) x frames [0, {T}] or is "
+                             f"empty")
+        out[k].append((s, e))
+    return out
+
+
 class WPE(ABC):
     """WPE dereverberation -- enhancer.py:292-348, same constructor and call.  The reference hands the array to
     nara_wpe's wpe_v8 on the host; here it is one pipeline of HIP kernels (hip_ops.wpe, csrc/wpe.hip; the definition
@@ -260,8 +272,9 @@ class ClassicBF_np(ABC):
 
     def __call__(self, masks, Observation, dia, segment_bf=True, numpy_out=False):
         """masks [K, M=1, T, F], Observation [D, T, F] complex128, dia: one activity per speaker
-        (see normalized_intervals) or None.  numpy_out=True: the dense [K, T, F] device tensor;
-        False: per speaker a dict {(s, e): [e - s, F]} of views of it."""
+        (see normalized_intervals), a segment table int32 [S, 3] of rows (k, s, e) (segmenter.ActivitySegmenter; with
+        numpy_out=True and no segment_wpe it goes to the kernels as it is, without a host read of its own) or None.
+        numpy_out=True: the dense [K, T, F] device tensor; False: per speaker a dict {(s, e): [e - s, F]} of views."""
         if self.bf != "mvdr_souden":
             raise NotImplementedError(f"bf={self.bf!r}: only 'mvdr_souden' is implemented")
         for name in ("pre_wpe", "segment_wpe"):
@@ -282,20 +295,32 @@ class ClassicBF_np(ABC):
         mode, dist_eps = self._kernel_mode()
         if mode == "one_minus":
             assert K == 1, masks.shape
+        device_table = None
         if dia is None:
             assert segment_bf is False, segment_bf
             assert self.segment_wpe is None, self.segment_wpe
             assert numpy_out is True, numpy_out
             intervals = [[(0, T)]] * K
+        elif isinstance(dia, torch.Tensor) and dia.dtype == torch.int32 and dia.dim() == 2 and dia.shape[1] == 3:
+            # a segment table (segmenter.ActivitySegmenter): rows (k, s, e) with k < K inside [0, T]
+            if not segment_bf:
+                raise NotImplementedError("segment_bf=False with a diarization (the reference raises there too)")
+            if numpy_out and self.segment_wpe is None:
+                device_table, intervals = dia, None          # as it is: checked in the read of the singular check
+            else:
+                intervals = _table_intervals(dia.cpu().tolist(), K, T)      # these paths need host numbers anyway
         else:
             assert isinstance(dia, (tuple, list)), ("Expect list of ArrayInterval", type(dia), dia)
             assert len(dia) == K, (len(dia), K)
             if not segment_bf:
                 raise NotImplementedError("segment_bf=False with a diarization (the reference raises there too)")
             intervals = [normalized_intervals(ai, T) for ai in dia]
-        table = [(k, s, e) for k, iv in enumerate(intervals) for s, e in iv]
         device = masks.device if masks.is_cuda else torch.device("cuda")
-        if not table:
+        if device_table is not None:
+            table = device_table.to(device)
+        else:
+            table = [(k, s, e) for k, iv in enumerate(intervals) for s, e in iv]
+        if len(table) == 0:
             out = torch.zeros(K, T, F, dtype=torch.complex128, device=device)
         else:
             Observation = Observation.to(device)
@@ -307,7 +332,8 @@ class ClassicBF_np(ABC):
                 packed["obs_seg"], packed["row0"] = self.segment_wpe.rows(Observation, [(s, e) for _, s, e in table])
             out = H.segment_mvdr(masks.detach().to(device), Observation, table, mode=mode,
                                  distortion_eps=dist_eps, mask_power=self.mask_power, masking=self.masking,
-                                 masking_eps=self.masking_eps, psd_real=True, **packed)
+                                 masking_eps=self.masking_eps, psd_real=True, check_table=device_table is not None,
+                                 **packed)
         if numpy_out:
             return out
         return [{(s, e): out[k, s:e] for s, e in iv} for k, iv in enumerate(intervals)]
