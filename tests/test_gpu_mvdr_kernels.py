@@ -225,7 +225,7 @@ def test_info_counts_the_singular_systems_exactly(D):
     assert run_weights(partials_of(A2, X2, B, K, F), D, 16, 0, TINY)[1] == 0    # and back to zero on the next call
 
 
-@pytest.mark.parametrize("D", (2, 6, 8))
+@pytest.mark.parametrize("D", (2, 6, 7, 8))
 @pytest.mark.parametrize("poison", (NAN, float("inf")))
 def test_a_poisoned_bin_stays_alone(D, poison):
     B, K, F = 1, 3, 130

@@ -20,9 +20,12 @@
 //   3. mvdr_apply_kernel<D>   one wave per (64 bins, time chunk, up to 4 speakers): Y read once
 //                             for the speakers of a group.
 // The segment-wise pipeline of ClassicBF_np (one beamformer per activity interval of a speaker, the
-// distortion mask taken from the other speakers' masks) is at the end of this file; it shares the
-// solve kernels.
+// distortion mask taken from the other speakers' masks) and the backward of the dense pipeline
+// follow in this file; the segments share the solve kernels.  The statistics pass and the first
+// time pass of the backward run on one frame pipeline (decode_time_tile / frame_pipeline).
 #include "common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -60,6 +63,15 @@ __device__ __forceinline__ double load_mask(const void* masks, int f64, int64_t 
   return f64 ? static_cast<const double*>(masks)[i] : (double)static_cast<const float*>(masks)[i];
 }
 
+// The float / double pair of a launch whose kernel is templated on the mask's dtype: `launch` is a
+// generic lambda that gets the mask pointer typed (MT = mask_t<decltype(pointer)>)
+template <typename P> using mask_t = std::remove_cv_t<std::remove_pointer_t<P>>;
+template <typename Launch> int launch_mt(int mask_f64, const void* masks, Launch launch) {
+  if (mask_f64) launch(static_cast<const double*>(masks));
+  else launch(static_cast<const float*>(masks));
+  return tssep_launch_status();
+}
+
 // XCD-aware block -> (tile, member): consecutive block ids go round-robin over the 8 XCDs, so the
 // `members` workgroups that read the same tile get ids  8*(tile/8*members + member) + tile%8
 __device__ __forceinline__ bool xcd_tile(int64_t bid, int members, int64_t tiles, int64_t& tile,
@@ -70,43 +82,121 @@ __device__ __forceinline__ bool xcd_tile(int64_t bid, int members, int64_t tiles
   member = (int)(within % members);
   return tile < tiles;
 }
+__host__ int64_t xcd_grid(int64_t tiles, int members) { return ((tiles + 7) / 8) * 8 * members; }
 
-// One workgroup = 4 waves = 4 speakers (target AND interference statistics each) of one
-// (64 bins, time chunk) tile.  Every wave fetches one frame of Y per step and shares it with the
-// other three through LDS (double buffered, one barrier per step), so Y crosses the L2 once per 4
-// speakers instead of once per (speaker, mask): a first version with one wave per (speaker, mask)
-// reading Y straight from L2 was L2-bandwidth bound (16 x 92 MB per 30-s utterance, 1.7 TB/s of
-// algorithmic traffic).
+// ------------------------------------------------------------------ the time passes ----
+// One workgroup = 4 waves = 4 speakers of one (64 bins, time chunk) tile.  Every wave fetches one
+// frame of Y per step and shares it with the other three through LDS (double buffered, one barrier
+// per step), so Y crosses the L2 once per 4 speakers instead of once per (speaker, mask): a first
+// version with one wave per (speaker, mask) reading Y straight from L2 was L2-bandwidth bound
+// (16 x 92 MB per 30-s utterance, 1.7 TB/s of algorithmic traffic).  mvdr_psd_kernel and
+// mvdr_bwd_gw_kernel run on this pipeline; mvdr_bwd_mask_kernel keeps its own copy of it (on the shared one its
+// D = 8 float instantiation wrote the NaNs of singular bins with the other sign bit).
 constexpr int PW = 4;      // waves (= speakers) per workgroup
+__host__ int64_t time_grid(const Plan& p, int64_t B, int K) {
+  return xcd_grid(B * p.chunks * p.nf, (K + PW - 1) / PW);
+}
+
+// What a workgroup of a time pass works on: frames [t0, t1) of chunk c, wave = speaker k (kvalid:
+// k < K), lane = bin fraw (f: clamped into [0, F) for the reads)
+struct TimeTile {
+  int64_t b, t0, t1;
+  int c, lane, wave, k, fraw, f, steps;
+  bool kvalid;
+};
+__device__ __forceinline__ bool decode_time_tile(const Plan& plan, int64_t B, int K, int64_t T,
+                                                 int F, TimeTile& tt) {
+  const int groups = (K + PW - 1) / PW;
+  int64_t tile;
+  int grp;
+  if (!xcd_tile(blockIdx.x, groups, B * plan.chunks * plan.nf, tile, grp)) return false;
+  const int ft = (int)(tile % plan.nf);
+  tt.c = (int)((tile / plan.nf) % plan.chunks);
+  tt.b = tile / ((int64_t)plan.nf * plan.chunks);
+  tt.lane = threadIdx.x & 63;
+  tt.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // scalar: uniform branches
+  tt.k = grp * PW + tt.wave;
+  tt.kvalid = tt.k < K;
+  tt.fraw = ft * 64 + tt.lane;
+  tt.f = tt.fraw < F ? tt.fraw : F - 1;
+  tt.t0 = tt.c * plan.tchunk;
+  tt.t1 = tt.t0 + plan.tchunk < T ? tt.t0 + plan.tchunk : T;
+  tt.steps = (int)((tt.t1 - tt.t0 + PW - 1) / PW);
+  return true;
+}
+
+// The double-buffered loop over the steps of a chunk.  The frames arrive by asynchronous
+// global -> LDS copies (1 KB per wave instruction, lane-linear: exactly [channel][lane] of double2),
+// no staging registers; y0: the observation of the batch element at bin f.  fetch(s, regs) loads
+// what else step s needs into the caller's Regs, compute(s, regs) consumes ybuf[s & 1].
+// Written as a function of the __restrict__ y0 and the array reference, the compiler no longer takes the copies of
+// step s + 1 in flight for aliases of the LDS reads of step s: the s_waitcnt vmcnt(0) after each barrier and the
+// waits between the reads are gone (46 -> 14 s_waitcnt in mvdr_psd_kernel<6, float>), the full wait in front of
+// each barrier stays.  That is right, the two touch different halves of ybuf, and it is where the 8 % of the
+// statistics pass at 8 x cfg5 came from; it hangs on alias information that a later edit can lose again.
+template <int D, typename Regs, typename Fetch, typename Compute>
+__device__ __forceinline__ void frame_pipeline(const TimeTile& tt, double2 (&ybuf)[2][PW][D][64],
+                                               const double2* __restrict__ y0, int64_t T, int F,
+                                               Fetch fetch, Compute compute) {
+  // wave w brings frame t0 + PW s + w of step s; frames past the chunk are zero-filled
+  auto fetch_y = [&](int s_) {
+    const int64_t t = tt.t0 + (int64_t)s_ * PW + tt.wave;
+    if (t < tt.t1) {
+#pragma unroll
+      for (int d = 0; d < D; ++d)
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)(y0 + (d * T + t) * F),
+            (__attribute__((address_space(3))) void*)&ybuf[s_ & 1][tt.wave][d][0], 16, 0, 0);
+    } else {
+#pragma unroll
+      for (int d = 0; d < D; ++d) ybuf[s_ & 1][tt.wave][d][tt.lane] = double2{0.0, 0.0};
+    }
+  };
+  // one barrier per step: it drains the copies of step s (every wave waits for its own before
+  // arriving) and separates compute(s-1) from the copies of step s+1 into the same buffer
+  Regs ra, rb;
+  fetch_y(0);
+  fetch(0, ra);
+  for (int s = 0; s < tt.steps; s += 2) {
+    __syncthreads();
+    if (s + 1 < tt.steps) { fetch_y(s + 1); fetch(s + 1, rb); }
+    if (tt.kvalid) compute(s, ra);
+    if (s + 1 >= tt.steps) break;
+    __syncthreads();
+    if (s + 2 < tt.steps) { fetch_y(s + 2); fetch(s + 2, ra); }
+    if (tt.kvalid) compute(s + 1, rb);
+  }
+}
+
+// ------------------------------------------------------------------ packed Hermitian ----
+// [D diagonals, then re / im per pair i < j] x F
+// one packed Hermitian accumulator -> out (already at its matrix and bin)
+template <int D>
+__device__ __forceinline__ void store_packed_herm(double* __restrict__ out, int F, const double (&diag)[D],
+                                                  const double2 (&off)[D * (D - 1) / 2 + 1]) {
+#pragma unroll
+  for (int i = 0; i < D; ++i) out[(int64_t)i * F] = diag[i];
+#pragma unroll
+  for (int p = 0; p < D * (D - 1) / 2; ++p) {
+    out[(int64_t)(D + 2 * p) * F] = off[p].x;
+    out[(int64_t)(D + 2 * p + 1) * F] = off[p].y;
+  }
+}
+
 template <typename MT> struct MaskRegs { MT w0[PW], w1[PW]; };
 
+// Target AND interference statistics of a speaker per wave
 template <int D, typename MT>
 __global__ __launch_bounds__(64 * PW, D <= 6 ? 2 : 1) void mvdr_psd_kernel(
     const double2* __restrict__ obs, const MT* __restrict__ masks, double* __restrict__ part,
     int64_t B, int K, int M, int64_t T, int F, Plan plan) {
-  // frames arrive by asynchronous global -> LDS copies (1 KB per wave instruction, lane-linear:
-  // exactly [channel][lane] of double2), no staging registers
   __shared__ double2 ybuf[2][PW][D][64];
-  const int groups = (K + PW - 1) / PW;
-  int64_t tile;
-  int grp;
-  if (!xcd_tile(blockIdx.x, groups, B * plan.chunks * plan.nf, tile, grp)) return;
-  const int ft = (int)(tile % plan.nf);
-  const int c = (int)((tile / plan.nf) % plan.chunks);
-  const int64_t b = tile / ((int64_t)plan.nf * plan.chunks);
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // scalar: uniform branches
-  const int k = grp * PW + wave;
-  const bool kvalid = k < K;
-  const int fraw = ft * 64 + lane;
-  const int f = fraw < F ? fraw : F - 1;
-  const int64_t t0 = c * plan.tchunk;
-  const int64_t t1 = t0 + plan.tchunk < T ? t0 + plan.tchunk : T;
-  const int steps = (int)((t1 - t0 + PW - 1) / PW);
+  TimeTile tt;
+  if (!decode_time_tile(plan, B, K, T, F, tt)) return;
   // target: mask 0.  interference: mask 1 if given, else 1 - mask 0 (enhancer.py:236-250)
-  const MT* mk0 = masks + ((b * K + (kvalid ? k : 0)) * M) * T * F + f;
+  const MT* mk0 = masks + ((tt.b * K + (tt.kvalid ? tt.k : 0)) * M) * T * F + tt.f;
   const MT* mk1 = mk0 + (M == 2 ? T * (int64_t)F : 0);
-  const double2* y0 = obs + b * D * T * F + f;
+  const double2* y0 = obs + tt.b * D * T * F + tt.f;
 
   double diag[2][D];
   double2 off[2][D * (D - 1) / 2 + 1];
@@ -117,29 +207,15 @@ __global__ __launch_bounds__(64 * PW, D <= 6 ? 2 : 1) void mvdr_psd_kernel(
 #pragma unroll
     for (int i = 0; i < D * (D - 1) / 2; ++i) off[m][i] = double2{0.0, 0.0};
   }
-  // wave w brings frame t0 + PW s + w of step s; frames past the chunk are zero-filled
-  auto fetch_y = [&](int s_) {
-    const int64_t t = t0 + (int64_t)s_ * PW + wave;
-    if (t < t1) {
-#pragma unroll
-      for (int d = 0; d < D; ++d)
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(y0 + (d * T + t) * F),
-            (__attribute__((address_space(3))) void*)&ybuf[s_ & 1][wave][d][0], 16, 0, 0);
-    } else {
-#pragma unroll
-      for (int d = 0; d < D; ++d) ybuf[s_ & 1][wave][d][lane] = double2{0.0, 0.0};
-    }
-  };
   auto fetch_m = [&](int s_, MaskRegs<MT>& r) {
     // unconditional loads (a branch per load would serialise them); frames past the chunk read
     // the last frame's mask and meet zero-filled Y
 #pragma unroll
     for (int fr = 0; fr < PW; ++fr) {
-      int64_t tt = t0 + (int64_t)s_ * PW + fr;
-      tt = tt < t1 ? tt : t1 - 1;
-      r.w0[fr] = mk0[tt * F];
-      r.w1[fr] = mk1[tt * F];
+      int64_t t = tt.t0 + (int64_t)s_ * PW + fr;
+      t = t < tt.t1 ? t : tt.t1 - 1;
+      r.w0[fr] = mk0[t * F];
+      r.w1[fr] = mk1[t * F];
     }
   };
   auto compute = [&](int s_, const MaskRegs<MT>& r) {
@@ -147,7 +223,7 @@ __global__ __launch_bounds__(64 * PW, D <= 6 ? 2 : 1) void mvdr_psd_kernel(
     for (int fr = 0; fr < PW; ++fr) {
       double2 y[D];
 #pragma unroll
-      for (int d = 0; d < D; ++d) y[d] = ybuf[s_ & 1][fr][d][lane];
+      for (int d = 0; d < D; ++d) y[d] = ybuf[s_ & 1][fr][d][tt.lane];
       const double w0 = (double)r.w0[fr];
       const double w1 = M == 2 ? (double)r.w1[fr] : 1.0 - w0;
       // y_i conj(y_j) once, weighted into both accumulators
@@ -169,32 +245,12 @@ __global__ __launch_bounds__(64 * PW, D <= 6 ? 2 : 1) void mvdr_psd_kernel(
       }
     }
   };
-  // one barrier per step: it drains the copies of step s (every wave waits for its own before
-  // arriving) and separates compute(s-1) from the copies of step s+1 into the same buffer
-  MaskRegs<MT> ra, rb;
-  fetch_y(0);
-  fetch_m(0, ra);
-  for (int s = 0; s < steps; s += 2) {
-    __syncthreads();
-    if (s + 1 < steps) { fetch_y(s + 1); fetch_m(s + 1, rb); }
-    if (kvalid) compute(s, ra);
-    if (s + 1 >= steps) break;
-    __syncthreads();
-    if (s + 2 < steps) { fetch_y(s + 2); fetch_m(s + 2, ra); }
-    if (kvalid) compute(s + 1, rb);
-  }
-  if (!kvalid || fraw >= F) return;
+  frame_pipeline<D, MaskRegs<MT>>(tt, ybuf, y0, T, F, fetch_m, compute);
+  if (!tt.kvalid || tt.fraw >= F) return;
 #pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    double* out = part + ((((b * plan.chunks + c) * K + k) * 2 + m) * (int64_t)(D * D)) * F + f;
-#pragma unroll
-    for (int i = 0; i < D; ++i) out[(int64_t)i * F] = diag[m][i];
-#pragma unroll
-    for (int p = 0; p < D * (D - 1) / 2; ++p) {
-      out[(int64_t)(D + 2 * p) * F] = off[m][p].x;
-      out[(int64_t)(D + 2 * p + 1) * F] = off[m][p].y;
-    }
-  }
+  for (int m = 0; m < 2; ++m)
+    store_packed_herm<D>(
+        part + ((((tt.b * plan.chunks + tt.c) * K + tt.k) * 2 + m) * (int64_t)(D * D)) * F + tt.f, F, diag[m], off[m]);
 }
 
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
@@ -471,17 +527,21 @@ __global__ __launch_bounds__(64) void mvdr_apply_kernel(
 template <int D>
 int launch_psd(const double* obs, const void* masks, int mask_f64, double* part, int64_t B, int K,
                int M, int64_t T, int F, const Plan& p, hipStream_t s) {
-  const int64_t tiles = B * p.chunks * p.nf;
-  const int64_t grid = ((tiles + 7) / 8) * 8 * ((K + PW - 1) / PW);
-  if (mask_f64)
-    hipLaunchKernelGGL((mvdr_psd_kernel<D, double>), dim3((unsigned)grid), dim3(64 * PW), 0, s,
-                       reinterpret_cast<const double2*>(obs), static_cast<const double*>(masks), part,
-                       B, K, M, T, F, p);
-  else
-    hipLaunchKernelGGL((mvdr_psd_kernel<D, float>), dim3((unsigned)grid), dim3(64 * PW), 0, s,
-                       reinterpret_cast<const double2*>(obs), static_cast<const float*>(masks), part,
-                       B, K, M, T, F, p);
-  return tssep_launch_status();
+  return launch_mt(mask_f64, masks, [&](auto* mk) {
+    hipLaunchKernelGGL((mvdr_psd_kernel<D, mask_t<decltype(mk)>>), dim3((unsigned)time_grid(p, B, K)),
+                       dim3(64 * PW), 0, s, reinterpret_cast<const double2*>(obs), mk, part, B, K, M, T, F, p);
+  });
+}
+
+// Time chunks of an apply pass: about 4096 waves in all, 16 frames per chunk at the least
+struct ApplyChunks { int64_t tchunk; int achunks; };
+__host__ ApplyChunks apply_chunks(int64_t waves, int64_t T) {
+  int64_t c = (4096 + waves - 1) / waves;
+  const int64_t cmax = (T + 15) / 16;
+  if (c > cmax) c = cmax;
+  if (c < 1) c = 1;
+  const int64_t tchunk = (T + c - 1) / c;
+  return ApplyChunks{tchunk, (int)((T + tchunk - 1) / tchunk)};
 }
 
 template <int D>
@@ -490,18 +550,12 @@ int launch_apply(const double* obs, const double* wconj, const void* masks, int 
                  double masking_eps, hipStream_t s) {
   const int nf = (F + 63) / 64;
   const int groups = (K + KG - 1) / KG;
-  int64_t c = (4096 + B * nf * groups - 1) / (B * nf * groups);
-  const int64_t cmax = (T + 15) / 16;
-  if (c > cmax) c = cmax;
-  if (c < 1) c = 1;
-  const int64_t tchunk = (T + c - 1) / c;
-  const int achunks = (int)((T + tchunk - 1) / tchunk);
-  const int64_t tiles = B * achunks * nf;
-  const int64_t grid = ((tiles + 7) / 8) * 8 * groups;
+  const ApplyChunks a = apply_chunks(B * nf * groups, T);
+  const int64_t grid = xcd_grid(B * a.achunks * nf, groups);
   hipLaunchKernelGGL(mvdr_apply_kernel<D>, dim3((unsigned)grid), dim3(64), 0, s,
                      reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(wconj),
-                     masks, mask_f64, reinterpret_cast<double2*>(enh), B, K, M, T, F, nf, achunks,
-                     tchunk, masking, masking_eps);
+                     masks, mask_f64, reinterpret_cast<double2*>(enh), B, K, M, T, F, nf, a.achunks,
+                     a.tchunk, masking, masking_eps);
   return tssep_launch_status();
 }
 
@@ -775,16 +829,8 @@ __global__ __launch_bounds__(64, D <= 6 ? 2 : 1) void seg_psd_kernel(
   }
   if (fraw >= F) return;
 #pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    double* out = part + ((((int64_t)c * S + sg) * 2 + m) * (int64_t)(D * D)) * F + f;
-#pragma unroll
-    for (int i = 0; i < D; ++i) out[(int64_t)i * F] = diag[m][i];
-#pragma unroll
-    for (int p = 0; p < D * (D - 1) / 2; ++p) {
-      out[(int64_t)(D + 2 * p) * F] = off[m][p].x;
-      out[(int64_t)(D + 2 * p + 1) * F] = off[m][p].y;
-    }
-  }
+  for (int m = 0; m < 2; ++m)
+    store_packed_herm<D>(part + ((((int64_t)c * S + sg) * 2 + m) * (int64_t)(D * D)) * F + f, F, diag[m], off[m]);
 }
 
 // slice partials -> slice 0, scaled by 1 / (e - s) the way numpy divides complex by real; with
@@ -871,15 +917,11 @@ int launch_seg_psd(const double* obs, const void* masks, int mask_f64, const int
   const int nf = (F + 63) / 64, C = seg_chunks(S, F);
   const int ipow = mask_power == 1.0 ? 1 : mask_power == 2.0 ? 2 : 0;
   const dim3 grid((unsigned)((int64_t)S * C * nf));
-  if (mask_f64)
-    hipLaunchKernelGGL((seg_psd_kernel<D, double, PACKED>), grid, dim3(64), 0, s,
-                       reinterpret_cast<const double2*>(obs), static_cast<const double*>(masks), tab,
-                       part, K, S, T, F, nf, C, mode, dist_eps, ipow, mask_power, row0, N);
-  else
-    hipLaunchKernelGGL((seg_psd_kernel<D, float, PACKED>), grid, dim3(64), 0, s,
-                       reinterpret_cast<const double2*>(obs), static_cast<const float*>(masks), tab,
-                       part, K, S, T, F, nf, C, mode, dist_eps, ipow, mask_power, row0, N);
-  return tssep_launch_status();
+  return launch_mt(mask_f64, masks, [&](auto* mk) {
+    hipLaunchKernelGGL((seg_psd_kernel<D, mask_t<decltype(mk)>, PACKED>), grid, dim3(64), 0, s,
+                       reinterpret_cast<const double2*>(obs), mk, tab, part, K, S, T, F, nf, C, mode,
+                       dist_eps, ipow, mask_power, row0, N);
+  });
 }
 
 template <int D, bool PACKED = false>
@@ -888,24 +930,14 @@ int launch_seg_apply(const double* obs, const double* wconj, const int32_t* map,
                      double masking_eps, hipStream_t s, const int32_t* tab = nullptr,
                      const int64_t* row0 = nullptr, int64_t N = 0) {
   const int nf = (F + 63) / 64;
-  int64_t c = (4096 + (int64_t)nf * K - 1) / ((int64_t)nf * K);
-  const int64_t cmax = (T + 15) / 16;
-  if (c > cmax) c = cmax;
-  if (c < 1) c = 1;
-  const int tchunk = (int)((T + c - 1) / c);
-  const int achunks = (int)((T + tchunk - 1) / tchunk);
-  const dim3 grid((unsigned)((int64_t)achunks * nf * K));
-  if (mask_f64)
-    hipLaunchKernelGGL((seg_apply_kernel<D, double, PACKED>), grid, dim3(64), 0, s,
+  const ApplyChunks a = apply_chunks((int64_t)nf * K, T);
+  const dim3 grid((unsigned)((int64_t)a.achunks * nf * K));
+  return launch_mt(mask_f64, masks, [&](auto* mk) {
+    hipLaunchKernelGGL((seg_apply_kernel<D, mask_t<decltype(mk)>, PACKED>), grid, dim3(64), 0, s,
                        reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(wconj),
-                       map, static_cast<const double*>(masks), reinterpret_cast<double2*>(enh), K, T,
-                       F, nf, achunks, tchunk, masking, masking_eps, tab, row0, N);
-  else
-    hipLaunchKernelGGL((seg_apply_kernel<D, float, PACKED>), grid, dim3(64), 0, s,
-                       reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(wconj),
-                       map, static_cast<const float*>(masks), reinterpret_cast<double2*>(enh), K, T,
-                       F, nf, achunks, tchunk, masking, masking_eps, tab, row0, N);
-  return tssep_launch_status();
+                       map, mk, reinterpret_cast<double2*>(enh), K, T, F, nf, a.achunks, (int)a.tchunk,
+                       masking, masking_eps, tab, row0, N);
+  });
 }
 
 }  // namespace
@@ -933,17 +965,7 @@ int seg_psd_stage(const double* obs, const void* masks, int mask_f64, const int3
   (row0 ? launch_seg_psd<DD, true>(obs, masks, mask_f64, segments, part, K, S, T, F, mode, distortion_eps,     \
                                    mask_power, s, row0, N)                                                     \
         : launch_seg_psd<DD>(obs, masks, mask_f64, segments, part, K, S, T, F, mode, distortion_eps, mask_power, s))
-  int st;
-  switch (D) {
-    case 1: st = CALL(1); break;
-    case 2: st = CALL(2); break;
-    case 3: st = CALL(3); break;
-    case 4: st = CALL(4); break;
-    case 5: st = CALL(5); break;
-    case 6: st = CALL(6); break;
-    case 7: st = CALL(7); break;
-    default: st = CALL(8); break;
-  }
+  const int st = [&]() -> int { DISPATCH_D(D, CALL) }();
 #undef CALL
   if (st != TSSEP_OK) return st;
   const int64_t n = (int64_t)S * 2 * D * D * F;
@@ -1032,7 +1054,12 @@ extern "C" int tssep_mvdr_segments_fwd_obs(const double* obs_seg, const int64_t*
 // term is formed there, from the forward's wconj): no atomics, run-to-run identical.
 // Saved between forward and backward: nothing but the forward's workspace -- the reduced statistics (chunk 0 of
 // the partials) and wconj.  P and lam are NOT saved: the solve repeats the forward's elimination, the same
-// operations in the same order, so it sees the P and the clamp decision the forward saw, bit for bit.
+// operations in the same order.  That gives the forward's P to rounding, NOT bit for bit: which product of an
+// a*b +- c*d the compiler contracts into an FMA is decided per kernel, not by the expression (at D = 2 the sum of two products in
+// the back substitution's cmul(s, r) is fma(c, d, a * b) in mvdr_solve_kernel and fma(a, b, c * d) in
+// mvdr_bwd_solve_kernel: profiles/mvdr_solve_contraction.txt; a body shared by both kernels still came out with
+// one choice each).  A pivot or the clamp can therefore be decided the
+// other way where two candidates, or lam and eps, lie within a rounding of each other.
 namespace {
 
 template <typename MT> struct GradRegs { double2 g[PW]; MT m[PW]; };
@@ -1043,52 +1070,24 @@ __global__ __launch_bounds__(64 * PW, 2) void mvdr_bwd_gw_kernel(
     double* __restrict__ part, int64_t B, int K, int M, int64_t T, int F, Plan plan, int masking,
     double masking_eps) {
   __shared__ double2 ybuf[2][PW][D][64];
-  const int groups = (K + PW - 1) / PW;
-  int64_t tile;
-  int grp;
-  if (!xcd_tile(blockIdx.x, groups, B * plan.chunks * plan.nf, tile, grp)) return;
-  const int ft = (int)(tile % plan.nf);
-  const int c = (int)((tile / plan.nf) % plan.chunks);
-  const int64_t b = tile / ((int64_t)plan.nf * plan.chunks);
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int k = grp * PW + wave;
-  const bool kvalid = k < K;
-  const int fraw = ft * 64 + lane;
-  const int f = fraw < F ? fraw : F - 1;
-  const int64_t t0 = c * plan.tchunk;
-  const int64_t t1 = t0 + plan.tchunk < T ? t0 + plan.tchunk : T;
-  const int steps = (int)((t1 - t0 + PW - 1) / PW);
-  const int64_t bk = b * K + (kvalid ? k : 0);
-  const MT* mk0 = masks + (bk * M) * T * F + f;              // only read with masking
-  const double2* g0 = genh + bk * T * F + f;
-  const double2* y0 = obs + b * D * T * F + f;
+  TimeTile tt;
+  if (!decode_time_tile(plan, B, K, T, F, tt)) return;
+  const int64_t bk = tt.b * K + (tt.kvalid ? tt.k : 0);
+  const MT* mk0 = masks + (bk * M) * T * F + tt.f;           // only read with masking
+  const double2* g0 = genh + bk * T * F + tt.f;
+  const double2* y0 = obs + tt.b * D * T * F + tt.f;
 
   double2 acc[D];
 #pragma unroll
   for (int d = 0; d < D; ++d) acc[d] = double2{0.0, 0.0};
-  // the forward's frame pipeline (mvdr_psd_kernel): wave w brings frame t0 + PW s + w of step s
-  auto fetch_y = [&](int s_) {
-    const int64_t t = t0 + (int64_t)s_ * PW + wave;
-    if (t < t1) {
-#pragma unroll
-      for (int d = 0; d < D; ++d)
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(y0 + (d * T + t) * F),
-            (__attribute__((address_space(3))) void*)&ybuf[s_ & 1][wave][d][0], 16, 0, 0);
-    } else {
-#pragma unroll
-      for (int d = 0; d < D; ++d) ybuf[s_ & 1][wave][d][lane] = double2{0.0, 0.0};
-    }
-  };
   auto fetch_g = [&](int s_, GradRegs<MT>& r) {
     // frames past the chunk read the last frame's G and meet zero-filled Y
 #pragma unroll
     for (int fr = 0; fr < PW; ++fr) {
-      int64_t tt = t0 + (int64_t)s_ * PW + fr;
-      tt = tt < t1 ? tt : t1 - 1;
-      r.g[fr] = g0[tt * F];
-      r.m[fr] = masking ? mk0[tt * F] : (MT)1;
+      int64_t t = tt.t0 + (int64_t)s_ * PW + fr;
+      t = t < tt.t1 ? t : tt.t1 - 1;
+      r.g[fr] = g0[t * F];
+      r.m[fr] = masking ? mk0[t * F] : (MT)1;
     }
   };
   auto compute = [&](int s_, const GradRegs<MT>& r) {
@@ -1103,26 +1102,15 @@ __global__ __launch_bounds__(64 * PW, 2) void mvdr_bwd_gw_kernel(
       }
 #pragma unroll
       for (int d = 0; d < D; ++d) {                           // conj(Ge) y_d
-        const double2 y = ybuf[s_ & 1][fr][d][lane];
+        const double2 y = ybuf[s_ & 1][fr][d][tt.lane];
         acc[d].x += g.x * y.x + g.y * y.y;
         acc[d].y += g.x * y.y - g.y * y.x;
       }
     }
   };
-  GradRegs<MT> ra, rb;
-  fetch_y(0);
-  fetch_g(0, ra);
-  for (int s = 0; s < steps; s += 2) {
-    __syncthreads();
-    if (s + 1 < steps) { fetch_y(s + 1); fetch_g(s + 1, rb); }
-    if (kvalid) compute(s, ra);
-    if (s + 1 >= steps) break;
-    __syncthreads();
-    if (s + 2 < steps) { fetch_y(s + 2); fetch_g(s + 2, ra); }
-    if (kvalid) compute(s + 1, rb);
-  }
-  if (!kvalid || fraw >= F) return;
-  double* out = part + (((b * plan.chunks + c) * K + k) * (int64_t)(2 * D)) * F + f;
+  frame_pipeline<D, GradRegs<MT>>(tt, ybuf, y0, T, F, fetch_g, compute);
+  if (!tt.kvalid || tt.fraw >= F) return;
+  double* out = part + (((tt.b * plan.chunks + tt.c) * K + tt.k) * (int64_t)(2 * D)) * F + tt.f;
 #pragma unroll
   for (int d = 0; d < D; ++d) {
     out[(int64_t)(2 * d) * F] = acc[d].x;
@@ -1484,17 +1472,11 @@ int64_t bwd_gw_bytes(int64_t B, int K, int D, const Plan& p, int F) {
 template <int D>
 int launch_bwd_gw(const double* obs, const double* genh, const void* masks, int mask_f64, double* part, int64_t B,
                   int K, int M, int64_t T, int F, const Plan& p, int masking, double masking_eps, hipStream_t s) {
-  const int64_t tiles = B * p.chunks * p.nf;
-  const int64_t grid = ((tiles + 7) / 8) * 8 * ((K + PW - 1) / PW);
-  if (mask_f64)
-    hipLaunchKernelGGL((mvdr_bwd_gw_kernel<D, double>), dim3((unsigned)grid), dim3(64 * PW), 0, s,
-                       reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(genh),
-                       static_cast<const double*>(masks), part, B, K, M, T, F, p, masking, masking_eps);
-  else
-    hipLaunchKernelGGL((mvdr_bwd_gw_kernel<D, float>), dim3((unsigned)grid), dim3(64 * PW), 0, s,
-                       reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(genh),
-                       static_cast<const float*>(masks), part, B, K, M, T, F, p, masking, masking_eps);
-  return tssep_launch_status();
+  return launch_mt(mask_f64, masks, [&](auto* mk) {
+    hipLaunchKernelGGL((mvdr_bwd_gw_kernel<D, mask_t<decltype(mk)>>), dim3((unsigned)time_grid(p, B, K)),
+                       dim3(64 * PW), 0, s, reinterpret_cast<const double2*>(obs),
+                       reinterpret_cast<const double2*>(genh), mk, part, B, K, M, T, F, p, masking, masking_eps);
+  });
 }
 
 template <int D>
@@ -1521,19 +1503,13 @@ template <int D>
 int launch_bwd_mask(const double* obs, const double* genh, const double* wconj, const double* herm, const void* masks,
                     int mask_f64, void* dmask, int64_t B, int K, int M, int64_t T, int F, const Plan& p, int masking,
                     double masking_eps, hipStream_t s) {
-  const int64_t tiles = B * p.chunks * p.nf;
-  const int64_t grid = ((tiles + 7) / 8) * 8 * ((K + PW - 1) / PW);
-  if (mask_f64)
-    hipLaunchKernelGGL((mvdr_bwd_mask_kernel<D, double>), dim3((unsigned)grid), dim3(64 * PW), 0, s,
+  return launch_mt(mask_f64, masks, [&](auto* mk) {
+    using MT = mask_t<decltype(mk)>;
+    hipLaunchKernelGGL((mvdr_bwd_mask_kernel<D, MT>), dim3((unsigned)time_grid(p, B, K)), dim3(64 * PW), 0, s,
                        reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(genh),
-                       reinterpret_cast<const double2*>(wconj), herm, static_cast<const double*>(masks),
-                       static_cast<double*>(dmask), B, K, M, T, F, p, masking, masking_eps);
-  else
-    hipLaunchKernelGGL((mvdr_bwd_mask_kernel<D, float>), dim3((unsigned)grid), dim3(64 * PW), 0, s,
-                       reinterpret_cast<const double2*>(obs), reinterpret_cast<const double2*>(genh),
-                       reinterpret_cast<const double2*>(wconj), herm, static_cast<const float*>(masks),
-                       static_cast<float*>(dmask), B, K, M, T, F, p, masking, masking_eps);
-  return tssep_launch_status();
+                       reinterpret_cast<const double2*>(wconj), herm, mk, static_cast<MT*>(dmask), B, K, M, T, F, p,
+                       masking, masking_eps);
+  });
 }
 
 }  // namespace
