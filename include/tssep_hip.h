@@ -573,6 +573,35 @@ int tssep_pit_assign(const float* part, int64_t B, int64_t K, int64_t nchunks, i
                      float* cost, int32_t* perm, float* sums, float* loss, void* stream);
 int tssep_pair_loss_bwd(const float* est, const float* tgt, const int32_t* perm, const float* sums, const float* gout,
                         int64_t B, int64_t K, int64_t N, int p, float* dest, void* stream);
+/* FreqMSE (tssep/train/loss.py:250-269 on STFTDomain, :102-115): the squared error of two spectra,
+ *   cost[b,i,j] = sum_t (1/F) sum_f |E[b,i,t,f] - S[b,j,t,f]|^2,   E, S [B,K,T,F], K <= 8, any F >= 1
+ * (TSSEP_E_SHAPE for K > 8 or an empty dimension; int64 element offsets throughout).  tgt is complex64.
+ * Forward: chunk partials part [B][nchunks][K][K] of sum_{t in chunk} sum_f |E_i - S_j|^2, the layout of
+ *   tssep_pair_cost_fwd with the chunks over T, nchunks = tssep_specmse_chunks(T); fixed-order two-stage reduction, no
+ *   atomics: two runs agree bit for bit.  diag_only != 0: only i == j is computed (pit=False), the rest is written as 0.
+ *   Finished by tssep_pit_assign(part, B, K, nchunks, N = F, pit, logarithm = 0, ...): its / N is the mean over F.
+ *   tssep_specmse_workspace_bytes: the bytes of part rounded up to 16; 0 for a shape the kernels refuse.
+ * tssep_mask_specmse_*: E = sigmoid(logit) * obs formed on the fly (net.py:983, enhancer.py:98-100; logit [B,K,T,F]
+ *   fp32, obs [B,T,F] complex64), neither mask nor estimate is written.  Backward, with t = S[b, perm[b,k]] (perm ==
+ *   NULL: identity), m = sigmoid(l), d = m Y - t:
+ *     dlogit = gout[b] (2/F) Re(conj(d) Y) m (1 - m);
+ *   bt_major / iperm as tssep_mask_istft_bwd_loss: bt_major = 1 stores rows (b, t) x (iperm[b*K + k] (NULL: k), f), the
+ *   same values bit for bit as bt_major = 0's [B,K,T,F].
+ * tssep_specmse_*: an estimate in memory, complex64 (est_f64 == 0) or complex128 (est_f64 != 0).  A complex128
+ *   estimate is differenced with the target in double; the forward rounds that difference to float32 before it is
+ *   squared and summed (the partials are float32 either way), the backward stays in double throughout.
+ *   Backward: dest = gout[b] (2/F) (E - t) in the estimate's dtype (torch's complex-gradient convention). */
+int64_t tssep_specmse_chunks(int64_t T);
+int64_t tssep_specmse_workspace_bytes(int64_t B, int64_t K, int64_t T, int64_t F);
+int tssep_mask_specmse_fwd(const float* logit, const float* obs, const float* tgt, int64_t B, int64_t K, int64_t T,
+                           int64_t F, int diag_only, float* part, void* stream);
+int tssep_mask_specmse_bwd(const float* logit, const float* obs, const float* tgt, const int32_t* perm,
+                           const float* gout, int64_t B, int64_t K, int64_t T, int64_t F, const int32_t* iperm,
+                           int bt_major, float* dlogit, void* stream);
+int tssep_specmse_fwd(const void* est, int est_f64, const float* tgt, int64_t B, int64_t K, int64_t T, int64_t F,
+                      int diag_only, float* part, void* stream);
+int tssep_specmse_bwd(const void* est, int est_f64, const float* tgt, const int32_t* perm, const float* gout,
+                      int64_t B, int64_t K, int64_t T, int64_t F, void* dest, void* stream);
 /* VADSigmoidBCE with target 'Vad' (tssep/train/loss.py:329-345,302-310):
  * x = mean_f logit[b,k,t,:]; loss[b] = mean_{k,t} BCEWithLogits(x, vad).
  * xmean [B,K,T] is kept for bwd; ws: tssep_vadbce_workspace_bytes.

@@ -832,6 +832,69 @@ def mse(est, tgt, pit=False):
     return pair_loss(est, tgt, 2, False, pit)[0]
 
 
+class _SpecMSE(torch.autograd.Function):
+    """FreqMSE on an estimate in memory: sum_k C[k, perm(k)] on C[i, j] = sum_t mean_f |E_i - S_j|^2, est [B,K,T,F]
+    complex64 | complex128, tgt complex64; pit as _PairLoss (the same assignment kernel).  -> (loss [B], perm)."""
+
+    @staticmethod
+    def forward(ctx, est, tgt, pit):
+        est, tgt = est.contiguous(), tgt.contiguous()
+        part = H.specmse_fwd(est, tgt, diag_only=not pit)
+        _, perm, _, loss = H.pit_assign(part, est.shape[-1], pit=pit, log=False, want_cost=False)
+        ctx.save_for_backward(est, tgt, perm)
+        ctx.pit = pit
+        ctx.mark_non_differentiable(perm)
+        return loss, perm
+
+    @staticmethod
+    def backward(ctx, g, _gperm):
+        est, tgt, perm = ctx.saved_tensors
+        return H.specmse_bwd(est, tgt, perm if ctx.pit else None, g), None, None
+
+
+def spec_mse(est, tgt, pit=False):
+    """est, tgt [B,K,T,F] complex (K <= 8) -> (loss [B], perm int32 [B,K]), differentiable in est."""
+    H._check_pit_k(est.shape[-3])
+    return _SpecMSE.apply(est, tgt, bool(pit))
+
+
+class _MaskSpecMSE(torch.autograd.Function):
+    """sigmoid (net.py:983) -> Masking (enhancer.py:98-100) -> FreqMSE as ONE kernel each way: logit, Observation and
+    target are read once, mask and estimate never written, no inverse STFT.  The head link as in _MaskISTFT: d(logit)
+    is stored where the final Linear's backward reads it."""
+
+    @staticmethod
+    def forward(ctx, logit, obs, tgt, pit, head_link=None):
+        logit, obs, tgt = logit.contiguous(), obs.contiguous(), tgt.contiguous()
+        part = H.mask_specmse_fwd(logit, obs, tgt, diag_only=not pit)
+        _, perm, _, loss = H.pit_assign(part, logit.shape[-1], pit=pit, log=False, want_cost=False)
+        ctx.save_for_backward(logit, obs, tgt, perm)
+        ctx.pit, ctx.link = pit, head_link
+        ctx.mark_non_differentiable(perm)
+        return loss, perm
+
+    @staticmethod
+    def backward(ctx, g, _gperm):
+        logit, obs, tgt, perm = ctx.saved_tensors
+        head_link = ctx.link
+        to_head = head_link is not None and tuple(head_link.shape) == tuple(logit.shape)
+        d = H.mask_specmse_bwd(logit, obs, tgt, perm if ctx.pit else None, g,
+                               iperm=head_link.iperm if to_head else None, bt_major=to_head)
+        if to_head:                                     # written where the Linear's backward reads it
+            head_link.payload = d if head_link.payload is None else head_link.payload + d
+            d = _dummy_grad(logit)
+        return d, None, None, None, None
+
+
+def mask_spec_mse(logit, obs, tgt, pit=False):
+    """logit [B,K,T,F], obs complex64 [B,T,F], tgt complex64 [B,K,T,F] (K <= 8) -> (loss [B], perm int32 [B,K]) of
+    FreqMSE on sigmoid(logit) * obs, differentiable in logit only."""
+    H._check_pit_k(logit.shape[-3])
+    fold = H.FOLD_TAIL and logit.requires_grad
+    head_link = getattr(logit, "_tssep_head_link", None) if fold and H.FOLD_TAIL != 2 else None
+    return _MaskSpecMSE.apply(logit, obs, tgt, bool(pit), head_link)
+
+
 class _VadBCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logit, vad):

@@ -1875,6 +1875,91 @@ def pair_loss_bwd(est, tgt, perm, sums, gout, p=1):
     return dest
 
 
+# FreqMSE (specloss.hip): cost[b,i,j] = sum_t mean_f |E_i - S_j|^2 as chunk partials over T; pit_assign(part, N=F) finishes
+def _spec_target(tgt, shape):
+    assert tgt.is_cuda and tgt.dtype == torch.complex64 and tuple(tgt.shape) == tuple(shape), \
+        (tgt.device, tgt.dtype, tuple(tgt.shape), tuple(shape))
+    return torch.view_as_real(tgt.contiguous())
+
+
+def _spec_part(B, K, T, F, device):
+    L = _lib.lib()
+    part = torch.empty(B, int(L.tssep_specmse_chunks(T)), K, K, device=device, dtype=torch.float32)
+    assert 0 < part.numel() * 4 <= L.tssep_specmse_workspace_bytes(B, K, T, F)
+    return part
+
+
+def _spec_perm(perm, B, K):
+    if perm is not None:
+        assert perm.dtype == torch.int32 and tuple(perm.shape) == (B, K) and perm.is_contiguous(), (perm.dtype, perm.shape)
+    return perm
+
+
+def mask_specmse_fwd(logit, obs, tgt, diag_only=False):
+    """logit [B,K,T,F] fp32, obs [B,T,F] complex64, tgt [B,K,T,F] complex64 -> chunk partials [B, nchunks, K, K] of
+    sum_{t,f} |sigmoid(logit_i) obs - tgt_j|^2 in one pass over the three (diag_only: only i == j, the rest 0); neither
+    the mask nor the estimate is written."""
+    B, K, T, F = logit.shape
+    _check_pit_k(K)
+    assert tuple(obs.shape) == (B, T, F) and obs.dtype == torch.complex64, (tuple(obs.shape), obs.dtype, (B, T, F))
+    logit, obs_r, tgt_r = _f32(logit).contiguous(), torch.view_as_real(obs.contiguous()), _spec_target(tgt, logit.shape)
+    part = _spec_part(B, K, T, F, logit.device)
+    with _timed("mask_specmse_fwd", 0, B * T * F * (12 * K + 8)):
+        check(_lib.lib().tssep_mask_specmse_fwd(_p(logit), _p(obs_r), _p(tgt_r), B, K, T, F, int(bool(diag_only)),
+                                                _p(part), _stream()), "mask_specmse_fwd")
+    return part
+
+
+def mask_specmse_bwd(logit, obs, tgt, perm, gout, iperm=None, bt_major=False):
+    """-> d(loss)/d(logit) = gout[b] (2/F) Re(conj(m Y - t) Y) m (1 - m), t = tgt[b, perm[b,k]] read in place (perm None:
+    identity).  bt_major: laid out [B*T, K*F] with speaker k at position iperm[b, k] -- what the final Linear's backward
+    reads (as mask_istft_bwd)."""
+    B, K, T, F = logit.shape
+    _check_pit_k(K)
+    assert tuple(obs.shape) == (B, T, F) and obs.dtype == torch.complex64, (tuple(obs.shape), obs.dtype, (B, T, F))
+    logit, obs_r, tgt_r = _f32(logit).contiguous(), torch.view_as_real(obs.contiguous()), _spec_target(tgt, logit.shape)
+    gout = _f32(gout).contiguous()
+    assert gout.numel() == B, (gout.shape, B)
+    dlogit = torch.empty(B * T, K * F, device=logit.device, dtype=torch.float32) if bt_major else torch.empty_like(logit)
+    with _timed("mask_specmse_bwd", 0, B * T * F * (16 * K + 8)):
+        check(_lib.lib().tssep_mask_specmse_bwd(_p(logit), _p(obs_r), _p(tgt_r), _p(_spec_perm(perm, B, K)), _p(gout),
+                                                B, K, T, F, _p(iperm), int(bool(bt_major)), _p(dlogit), _stream()),
+              "mask_specmse_bwd")
+    return dlogit
+
+
+def _spec_est(est):
+    assert est.is_cuda and est.dtype in (torch.complex64, torch.complex128) and est.dim() == 4, (est.device, est.dtype, est.shape)
+    return torch.view_as_real(est.contiguous()), int(est.dtype == torch.complex128)
+
+
+def specmse_fwd(est, tgt, diag_only=False):
+    """est [B,K,T,F] complex64 | complex128, tgt [B,K,T,F] complex64 -> chunk partials [B, nchunks, K, K]"""
+    B, K, T, F = est.shape
+    _check_pit_k(K)
+    est_r, f64 = _spec_est(est)
+    tgt_r = _spec_target(tgt, est.shape)
+    part = _spec_part(B, K, T, F, est.device)
+    with _timed("specmse_fwd", 0, B * K * T * F * (16 + 8 * f64)):
+        check(_lib.lib().tssep_specmse_fwd(_p(est_r), f64, _p(tgt_r), B, K, T, F, int(bool(diag_only)), _p(part),
+                                           _stream()), "specmse_fwd")
+    return part
+
+
+def specmse_bwd(est, tgt, perm, gout):
+    """-> d(loss)/d(est) = gout[b] (2/F) (est - tgt[b, perm[b,k]]) in est's dtype (perm None: identity)"""
+    B, K, T, F = est.shape
+    _check_pit_k(K)
+    est_r, f64 = _spec_est(est)
+    tgt_r = _spec_target(tgt, est.shape)
+    gout = _f32(gout).contiguous()
+    assert gout.numel() == B, (gout.shape, B)
+    dest = torch.empty_like(est_r)
+    check(_lib.lib().tssep_specmse_bwd(_p(est_r), f64, _p(tgt_r), _p(_spec_perm(perm, B, K)), _p(gout), B, K, T, F,
+                                       _p(dest), _stream()), "specmse_bwd")
+    return torch.view_as_complex(dest)
+
+
 def vadbce_fwd(logit, vad):
     L = _lib.lib()
     B, K, T, F = logit.shape

@@ -13,7 +13,12 @@ activity ``vad`` (util.utils.stft_vad, host code as in the reference; stft_vad_d
 ``magnitude_threshold`` times the row's largest.  That activity is built on the device too -- from the spectrum ``ex[target]``
 when the caller supplies one, otherwise from the signal ``ex[target.lower()]`` by a frame kernel that never writes the
 spectrum (STFT.frame_activity) -- and is kept in ``ex`` under a private key; ``ex[target]`` always stays a spectrum.
-Not built: FreqMSE, pit for the VAD losses, K > 8."""
+
+``FreqMSE`` (:250-269, on ``STFTDomain``, :102-115) compares spectra: sum_k sum_t mean_f |E - S|^2 per utterance, with pit
+the best speaker permutation on the K x K costs.  On the training step of a Masking enhancer Model.review forms it from
+the logits, the Observation and the target spectrum in one pass each way -- no mask, no estimate, no inverse STFT
+(functional.mask_spec_mse); anywhere else it reads ``out.stft_estimate`` (functional.spec_mse; complex128 from TorchBF).
+Not built: FreqMSE as ``signal_loss`` of the joint loss, pit for the VAD losses, K > 8."""
 import numpy as np
 import torch
 
@@ -108,6 +113,50 @@ class MSE(TimeDomain):
         if estimate.dim() == 2:
             return Fn.mse(estimate[None], target[None])[0]
         return Fn.mse(estimate, target)
+
+
+class STFTDomain(ABC):
+    """estimate, target [B, K, T, F] complex (or [K, T, F]: one utterance, the result squeezed back) -> [B].
+    pit=True permutes SPEAKERS, per utterance, and ``permutation`` is kept as on TimeDomain.  (The reference's
+    ``pit_loss(axis=-2)`` would permute the frames of a [K, T, F] estimate; that reading is not reproduced.)"""
+    permutation = None
+
+    def target_spectrum(self, ex, model):
+        """ex[target], computed from the signal ``ex[target.lower()]`` when absent (loss.py:111-114) and stored back.
+        The reference writes ``self.fe`` there, which no loss has: ``model.fe`` is used, as in LogitsSTFTDomain."""
+        assert self.target[0].isupper(), self.target
+        if self.target not in ex:
+            ex[self.target] = model.fe.stft(ex[self.target.lower()])
+        return ex[self.target]
+
+    def from_ex_out(self, ex, out, model, summary):      # loss.py:103-115
+        target = self.target_spectrum(ex, model)
+        fused = getattr(out, "_spec_loss", None)         # Model.review's fused tail: (loss, permutation, the target it used)
+        if fused is not None and fused[2] is target:
+            self.permutation = fused[1]
+            return fused[0]
+        return self(out.stft_estimate, target)
+
+
+class FreqMSE(STFTDomain):
+    def __init__(self, target: str = "Speaker_reverberation_early", pit: bool = False):
+        super().__init__(target=target, pit=pit)
+
+    def loss_fn(self, estimate, target):
+        """sum_k sum_t mean_f |e - t|^2 -> [B]  (loss.py:258-269: its doctest's 0.1673 is MSE's, the mean over the last
+        axis and the sum over the others; the batch axis is kept, this project's convention).  With pit the minimum over
+        the speaker permutations."""
+        batched = estimate.dim() == 4
+        assert estimate.dim() in (3, 4), estimate.shape
+        if not isinstance(target, torch.Tensor):
+            target = torch.stack(list(target))
+        e, t = (estimate, target) if batched else (estimate[None], target[None])
+        Fn.H._check_pit_k(e.shape[1])
+        if t.dtype != torch.complex64:
+            t = t.to(torch.complex64)
+        loss, perm = Fn.spec_mse(e, t.to(e.device), self.pit)
+        self.permutation = (perm.detach() if batched else perm.detach()[0]) if self.pit else None
+        return loss if batched else loss[0]
 
 
 _ACTIVITY_KEY = "_tssep_amd_frame_activity:"      # ex[_ACTIVITY_KEY + target] = (the tensor it came from, the activity)

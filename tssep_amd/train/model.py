@@ -242,7 +242,8 @@ class Model(Configurable, torch.nn.Module):
         def __init__(self, mask=None, logit=None, embedding=None, stft_estimate=None, time_estimate=None,
                      vad_mask=None, vad_logit=None, _lazy=None):
             self._mask, self._stft_estimate, self._lazy, self._lazy0 = mask, stft_estimate, _lazy, _lazy
-            self.logit, self.embedding, self.time_estimate = logit, embedding, time_estimate
+            self.logit, self.embedding, self._time_estimate = logit, embedding, time_estimate
+            self._lazy_time = self._lazy_time0 = None      # review's spectral tail: time_estimate on first read
             self._vad_mask, self.vad_logit = vad_mask, vad_logit
             self._gated = None          # explicit_vad: the head's [B,K,T,F+1] logit rows (VAD logit at column 0)
 
@@ -288,6 +289,19 @@ class Model(Configurable, torch.nn.Module):
             self._stft_estimate = value
 
         @property
+        def time_estimate(self):
+            """Set by ``Model.review``.  After the spectral tail (an STFT-domain loss formed from the logits, no inverse
+            STFT in the step) it is computed on first read, by the unfused ``fe.istft(self.stft_estimate, ...)``."""
+            if self._time_estimate is None and self._lazy_time is not None:
+                lazy, self._lazy_time = self._lazy_time, None
+                self._time_estimate = lazy(self)
+            return self._time_estimate
+
+        @time_estimate.setter
+        def time_estimate(self, value):
+            self._time_estimate = value
+
+        @property
         def materialised(self):
             return self._lazy is None
 
@@ -301,6 +315,8 @@ class Model(Configurable, torch.nn.Module):
                 if other._gated is not None:
                     other._vad_mask = None
                 other._lazy = other._lazy0
+            if other._lazy_time0 is not None:
+                other._time_estimate, other._lazy_time = None, other._lazy_time0
             return other
 
         def __repr__(self):
@@ -309,7 +325,7 @@ class Model(Configurable, torch.nn.Module):
             return (f"ForwardOutput(mask={'<lazy>' if self._mask is None and self._lazy else sh(self._mask)}, "
                     f"logit={sh(self.logit)}, embedding={sh(self.embedding)}, "
                     f"stft_estimate={'<lazy>' if self._stft_estimate is None and self._lazy else sh(self._stft_estimate)}, "
-                    f"time_estimate={sh(self.time_estimate)})")
+                    f"time_estimate={'<lazy>' if self._time_estimate is None and self._lazy_time else sh(self._time_estimate)})")
 
     def forward(self, ex, feature_transform=None) -> "Model.ForwardOutput":
         ex["AuxInput"] = [a for a in ex["auxInput"]]
@@ -396,9 +412,37 @@ class Model(Configurable, torch.nn.Module):
         return ex
 
     # ------------------------------------------------------------------------- review
+    def _spectral_tail(self, ex, out):
+        """An STFT-domain loss (FreqMSE) on a Masking enhancer's plain logit rows whose mask / stft_estimate nobody has
+        looked at: sigmoid -> masking -> |estimate - Target|^2 -> sums as one kernel each way (functional.mask_spec_mse),
+        no inverse STFT in the step.  The loss is left on ``out`` for ``from_ex_out``, keyed on the target tensor;
+        ``out.time_estimate`` is computed on first read.  -> whether it ran (any other case takes the routes it always took)."""
+        fus = getattr(out, "_fusable", None)
+        if not isinstance(self.loss, _loss.STFTDomain) or fus is None or out.materialised or out._gated is not None \
+                or not hasattr(self.fe, "stft"):
+            return False
+        logit4, obs3, batched = fus
+        if self.loss.target not in ex and self.loss.target.lower() not in ex:
+            return False
+        target = self.loss.target_spectrum(ex, self)
+        tgt = target if batched or not isinstance(target, torch.Tensor) else target[None]
+        if not (isinstance(tgt, torch.Tensor) and tgt.dtype == torch.complex64 and tgt.device == logit4.device
+                and tgt.shape == logit4.shape and tgt.is_contiguous() and obs3.dtype == torch.complex64):
+            return False
+        value, perm = Fn.mask_spec_mse(logit4, obs3, tgt, self.loss.pit)
+        perm = perm.detach() if self.loss.pit else None
+        out._spec_loss = (value, perm, target) if batched else (value[0], None if perm is None else perm[0], target)
+        if hasattr(self.fe, "istft") and "observation" in ex:
+            n = ex["observation"].shape[-1]
+            out._time_estimate = None
+            out._lazy_time = out._lazy_time0 = lambda o: self.fe.istft(o.stft_estimate, num_samples=n)
+        return True
+
     def review(self, ex, out: "Model.ForwardOutput"):
         summary = ReviewSummary()
-        if hasattr(self.fe, "istft") and "observation" in ex:          # model.py:661-664
+        if self._spectral_tail(ex, out):
+            pass
+        elif hasattr(self.fe, "istft") and "observation" in ex:        # model.py:661-664
             n = ex["observation"].shape[-1]
             fus = getattr(out, "_fusable", None)
             if fus is not None and not out.materialised and hasattr(self.fe, "masked_istft"):
