@@ -602,6 +602,31 @@ int tssep_specmse_fwd(const void* est, int est_f64, const float* tgt, int64_t B,
                       int diag_only, float* part, void* stream);
 int tssep_specmse_bwd(const void* est, int est_f64, const float* tgt, const int32_t* perm, const float* gout,
                       int64_t B, int64_t K, int64_t T, int64_t F, void* dest, void* stream);
+/* SDR / SI-SDR (this project's own loss; the reference has none).  est, tgt [B,K,N], K <= 8 (TSSEP_E_SHAPE beyond).
+ * With a_i = sum_n e_i^2, b_j = sum_n t_j^2, c_ij = sum_n e_i t_j:
+ *   scale_invariant != 0: alpha = c / (b + eps), s = alpha c, n = a - s;   else: s = b, n = a - 2 c + b;   n < 0 -> 0
+ *   D = n + tau s + eps,  value[b,i,j] = 10 log10((s + eps) / D) dB,  cost = -value / K;  tau = 10^(-sdr_max / 10) or 0.
+ * tssep_sdr_stats_fwd: ONE pass over est and tgt leaves the float64 chunk partials part [B][nchunks][K*K + 2K]
+ *   (c_ij at i*K + j, a_i at K*K + i, b_j at K*K + K + j), nchunks = tssep_sdr_chunks(N).  Float32 only in the per-lane
+ *   chain of at most 32 fused multiply-adds, float64 behind it; fixed order, no atomics: two runs agree bit for bit.
+ *   diag_only != 0: only c_ii is computed (pit=False), the other c entries are written as 0.
+ *   tssep_sdr_workspace_bytes: the bytes of part; 0 for a shape the kernels refuse.
+ * tssep_sdr_cost: stat [B][K*K + 2K] float64 = the partials summed in chunk order (kept for the backward), value and
+ *   cost [B,K,K] float32, formed in float64 and rounded once; diag_only != 0: both 0 off the diagonal.  The assignment
+ *   and the loss follow from tssep_pit_assign(cost, B, K, nchunks = 1, N = 1, pit, logarithm = 0, ...).
+ *   eps > 0 and tau >= 0, otherwise TSSEP_E_UNSUPPORTED.
+ * tssep_sdr_bwd: dest[b,i,:] = P e_i + Q t, t = tgt[b, perm[b,i]] read in place (perm == NULL: identity), with
+ *   g = gout[b] 20 / (K ln 10):  scale-invariant P = g / D, Q = -g alpha (1 / (s + eps) + (1 - tau) / D);
+ *   plain P = g / D = -Q, both 0 where n was clamped.  P, Q are formed from stat in float64 and rounded once. */
+int64_t tssep_sdr_chunks(int64_t N);
+int64_t tssep_sdr_workspace_bytes(int64_t B, int64_t K, int64_t N);
+int tssep_sdr_stats_fwd(const float* est, const float* tgt, int64_t B, int64_t K, int64_t N, int diag_only,
+                        double* part, void* stream);
+int tssep_sdr_cost(const double* part, int64_t B, int64_t K, int64_t nchunks, int scale_invariant, double tau,
+                   double eps, int diag_only, double* stat, float* value, float* cost, void* stream);
+int tssep_sdr_bwd(const float* est, const float* tgt, const int32_t* perm, const double* stat, const float* gout,
+                  int64_t B, int64_t K, int64_t N, int scale_invariant, double tau, double eps, float* dest,
+                  void* stream);
 /* VADSigmoidBCE with target 'Vad' (tssep/train/loss.py:329-345,302-310):
  * x = mean_f logit[b,k,t,:]; loss[b] = mean_{k,t} BCEWithLogits(x, vad).
  * xmean [B,K,T] is kept for bwd; ws: tssep_vadbce_workspace_bytes.

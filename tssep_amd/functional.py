@@ -832,6 +832,39 @@ def mse(est, tgt, pit=False):
     return pair_loss(est, tgt, 2, False, pit)[0]
 
 
+class _SDRLoss(torch.autograd.Function):
+    """-(1/K) sum_i value[i, perm(i)], value the SDR or SI-SDR in dB: one pass over est and tgt leaves the
+    float64 statistics, a small launch maps them to the K x K costs, tssep_pit_assign matches (pit=False: the identity
+    on the diagonal-only pass), and the backward is linear in est and tgt with two coefficients per row.
+    -> (loss [B], perm int32 [B,K], values dB [B,K]); perm and values are constants of the backward."""
+
+    @staticmethod
+    def forward(ctx, est, tgt, scale_invariant, sdr_max, eps, pit):
+        est, tgt = est.contiguous(), tgt.contiguous()
+        loss, perm, values, stat = H.sdr_forward(est, tgt, scale_invariant, sdr_max, eps, pit)
+        ctx.save_for_backward(est, tgt, perm, stat)
+        ctx.meta = (scale_invariant, sdr_max, eps, pit)
+        ctx.mark_non_differentiable(perm, values)
+        return loss, perm, values
+
+    @staticmethod
+    def backward(ctx, g, _gperm, _gvalues):
+        est, tgt, perm, stat = ctx.saved_tensors
+        scale_invariant, sdr_max, eps, pit = ctx.meta
+        return H.sdr_bwd(est, tgt, perm if pit else None, stat, g, scale_invariant, sdr_max, eps), None, None, None, \
+            None, None
+
+
+def sdr_loss(est, tgt, scale_invariant=True, sdr_max=None, eps=1e-8, pit=False):
+    """est, tgt [B,K,N] or [K,N] (K <= 8) -> (loss [B] = the negated mean over speakers of the matched SDR / SI-SDR in dB,
+    perm int32 [B,K], values dB [B,K]); a [K,N] input gives the same without the batch axis.  Differentiable in est."""
+    H._check_pit_k(est.shape[-2])
+    if est.dim() == 2:
+        loss, perm, values = _SDRLoss.apply(est[None], tgt[None], bool(scale_invariant), sdr_max, float(eps), bool(pit))
+        return loss[0], perm[0], values[0]
+    return _SDRLoss.apply(est, tgt, bool(scale_invariant), sdr_max, float(eps), bool(pit))
+
+
 class _SpecMSE(torch.autograd.Function):
     """FreqMSE on an estimate in memory: sum_k C[k, perm(k)] on C[i, j] = sum_t mean_f |E_i - S_j|^2, est [B,K,T,F]
     complex64 | complex128, tgt complex64; pit as _PairLoss (the same assignment kernel).  -> (loss [B], perm)."""

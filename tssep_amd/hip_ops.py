@@ -1875,6 +1875,84 @@ def pair_loss_bwd(est, tgt, perm, sums, gout, p=1):
     return dest
 
 
+# SDR / SI-SDR (sdrloss.hip): statistics as float64 chunk partials -> value / cost -> pit_assign -> backward
+def sdr_tau(sdr_max):
+    """The soft threshold tau = 10^(-sdr_max / 10) (0: none)."""
+    return 0.0 if sdr_max is None else 10.0 ** (-float(sdr_max) / 10.0)
+
+
+def _sdr_nstat(K):
+    return K * K + 2 * K
+
+
+def sdr_stats_fwd(est, tgt, diag_only=False):
+    """est, tgt [B,K,N] -> float64 chunk partials [B, nchunks, K*K + 2K] of c_ij = sum e_i t_j, a_i = sum e_i^2,
+    b_j = sum t_j^2 in ONE pass over both (diag_only: only c_ii, the other c entries 0)."""
+    L = _lib.lib()
+    B, K, N = est.shape
+    _check_pit_k(K)
+    assert tuple(tgt.shape) == (B, K, N), (tuple(tgt.shape), (B, K, N))
+    est, tgt = _f32(est).contiguous(), _f32(tgt).contiguous()
+    part = torch.empty(B, int(L.tssep_sdr_chunks(N)), _sdr_nstat(K), device=est.device, dtype=torch.float64)
+    assert 0 < part.numel() * 8 == L.tssep_sdr_workspace_bytes(B, K, N)
+    with _timed("sdr_stats", B * N * 2 * ((K if diag_only else K * K) + 2 * K), 2 * B * K * N * 4):
+        check(L.tssep_sdr_stats_fwd(_p(est), _p(tgt), B, K, N, int(bool(diag_only)), _p(part), _stream()),
+              "sdr_stats_fwd")
+    return part
+
+
+def sdr_cost(part, K, scale_invariant=True, sdr_max=None, eps=1e-8, diag_only=False):
+    """part [B, nchunks, K*K + 2K] float64 -> (stat float64 [B, K*K + 2K], value dB [B,K,K], cost = -value / K [B,K,K]);
+    cost[:, None] is what pit_assign takes with N = 1."""
+    B, nchunks, ns = part.shape
+    _check_pit_k(K)
+    assert ns == _sdr_nstat(K) and part.dtype == torch.float64 and part.is_cuda, (part.shape, part.dtype, K)
+    part = part.contiguous()
+    stat = torch.empty(B, ns, device=part.device, dtype=torch.float64)
+    value = torch.empty(B, K, K, device=part.device, dtype=torch.float32)
+    cost = torch.empty_like(value)
+    with _timed("sdr_cost", 0, part.numel() * 8 + stat.numel() * 8 + 2 * value.numel() * 4):
+        check(_lib.lib().tssep_sdr_cost(_p(part), B, K, nchunks, int(bool(scale_invariant)), sdr_tau(sdr_max), float(eps),
+                                        int(bool(diag_only)), _p(stat), _p(value), _p(cost), _stream()), "sdr_cost")
+    return stat, value, cost
+
+
+def sdr_bwd(est, tgt, perm, stat, gout, scale_invariant=True, sdr_max=None, eps=1e-8):
+    """d(loss)/d(est) = gout[b] (P e_i + Q tgt[b, perm[b,i]]) with P, Q from stat (sdr_cost's); perm None: identity.
+    tgt is read through perm in place."""
+    B, K, N = est.shape
+    _check_pit_k(K)
+    est, tgt = _f32(est).contiguous(), _f32(tgt).contiguous()
+    assert tuple(stat.shape) == (B, _sdr_nstat(K)) and stat.dtype == torch.float64 and stat.is_contiguous(), \
+        (stat.shape, stat.dtype)
+    gout = _f32(gout).contiguous()
+    assert gout.numel() == B, (gout.shape, B)
+    dest = torch.empty_like(est)
+    with _timed("sdr_bwd", 3 * B * K * N, 3 * B * K * N * 4):
+        check(_lib.lib().tssep_sdr_bwd(_p(est), _p(tgt), _p(_spec_perm(perm, B, K)), _p(stat), _p(gout), B, K, N,
+                                       int(bool(scale_invariant)), sdr_tau(sdr_max), float(eps), _p(dest), _stream()),
+              "sdr_bwd")
+    return dest
+
+
+def sdr_forward(est, tgt, scale_invariant=True, sdr_max=None, eps=1e-8, pit=False):
+    """The three forward launches -> (loss [B], perm int32 [B,K], values dB [B,K] of the matched pairs, stat)."""
+    K = est.shape[-2]
+    part = sdr_stats_fwd(est, tgt, diag_only=not pit)
+    stat, value, cost = sdr_cost(part, K, scale_invariant, sdr_max, eps, diag_only=not pit)
+    _, perm, _, loss = pit_assign(cost[:, None], 1, pit=pit, log=False, want_cost=False)
+    values = torch.gather(value, 2, perm.long()[..., None])[..., 0]
+    return loss, perm, values, stat
+
+
+def sdr(est, tgt, scale_invariant=True, sdr_max=None, eps=1e-8, pit=False):
+    """The metric: est, tgt [B,K,N] -> (values dB [B,K], values[b, i] = estimate row i against target row perm[b, i];
+    perm int32 [B,K], the best assignment with pit, else the identity).  No gradient, no host sync."""
+    with torch.no_grad():
+        _, perm, values, _ = sdr_forward(est, tgt, scale_invariant, sdr_max, eps, pit)
+    return values, perm
+
+
 # FreqMSE (specloss.hip): cost[b,i,j] = sum_t mean_f |E_i - S_j|^2 as chunk partials over T; pit_assign(part, N=F) finishes
 def _spec_target(tgt, shape):
     assert tgt.is_cuda and tgt.dtype == torch.complex64 and tuple(tgt.shape) == tuple(shape), \

@@ -18,6 +18,10 @@ spectrum (STFT.frame_activity) -- and is kept in ``ex`` under a private key; ``e
 the best speaker permutation on the K x K costs.  On the training step of a Masking enhancer Model.review forms it from
 the logits, the Observation and the target spectrum in one pass each way -- no mask, no estimate, no inverse STFT
 (functional.mask_spec_mse); anywhere else it reads ``out.stft_estimate`` (functional.spec_mse; complex128 from TorchBF).
+
+``SDR`` has no counterpart in the reference: the negated mean over speakers of the SI-SDR or SDR in dB, on float64
+dot-product sums from one pass over estimate and target, with pit and a soft threshold; usable as
+``signal_loss`` of the joint loss, and ``.values`` keeps the last call's dB per speaker.
 Not built: FreqMSE as ``signal_loss`` of the joint loss, pit for the VAD losses, K > 8."""
 import numpy as np
 import torch
@@ -113,6 +117,40 @@ class MSE(TimeDomain):
         if estimate.dim() == 2:
             return Fn.mse(estimate[None], target[None])[0]
         return Fn.mse(estimate, target)
+
+
+class SDR(TimeDomain):
+    """The negated mean over speakers of the SI-SDR (``scale_invariant=True``) or SDR in dB -- this project's own loss,
+    the reference has none.  Per estimate row e and matched target row t, sums over the samples:
+    a = sum e^2, b = sum t^2, c = sum e t;  scale-invariant: alpha = c / (b + eps), s = alpha c, n = a - s;  plain: s = b,
+    n = max(a - 2 c + b, 0);  value = 10 log10((s + eps) / (n + tau s + eps)), tau = 10^(-sdr_max / 10) (``sdr_max=None``:
+    0) the soft threshold that keeps a value below ``sdr_max``.  ``eps`` is an absolute energy (a sum, not a mean).
+    ``pit=True`` takes the best assignment on the K x K values; ``.permutation`` as on the other time-domain losses.
+    ``.values`` keeps the last call's detached dB per speaker, [B, K] (or [K]), on the device."""
+    values = None
+
+    def __init__(self, target: str = "speaker_reverberation_early_ch0", pit: bool = False, scale_invariant: bool = True,
+                 sdr_max=None, eps: float = 1e-8):
+        super().__init__(target=target, pit=pit)
+        if not (isinstance(eps, (int, float)) and np.isfinite(eps) and eps > 0):
+            raise ValueError(f"eps must be a positive finite energy, got {eps!r}")
+        if sdr_max is not None and not (isinstance(sdr_max, (int, float)) and np.isfinite(sdr_max)):
+            raise ValueError(f"sdr_max must be None or a finite level in dB, got {sdr_max!r}")
+        self.scale_invariant = bool(scale_invariant)
+        self.sdr_max = None if sdr_max is None else float(sdr_max)
+        self.eps = float(eps)
+
+    @property
+    def fused_tail(self):
+        return False
+
+    def loss_fn(self, estimate, target):
+        """-(1/K) sum_k value[k, perm(k)] -> [B]"""
+        Fn.H._check_pit_k(estimate.shape[-2])
+        loss, perm, values = Fn.sdr_loss(estimate, target, self.scale_invariant, self.sdr_max, self.eps, self.pit)
+        self.permutation = perm.detach() if self.pit else None
+        self.values = values.detach()
+        return loss
 
 
 class STFTDomain(ABC):
