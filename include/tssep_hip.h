@@ -297,6 +297,27 @@ int tssep_blstm_bwd(float* gates, const float* cell, const float* dhout, int64_t
 int tssep_lstm_unpack(const float* src, int64_t ld, int nsplit, int64_t split_stride,
                       int H, int ncols, float* dst_f, float* dst_r, int accumulate, void* stream);
 
+/* ONE direction of time (torch.nn.LSTM(bidirectional=False), tssep/train/rnnp.py:80-96 typ='lstm'): the streaming
+ * kernels above instantiated for one direction -- 8 sequences per workgroup, no exchange between workgroups, no spin,
+ * no error flag, no concurrency contract (capturable, safe beside anything).  Layouts are the [dir = 0] half of the
+ * two-direction ones: gate columns [unit][gate], wih_p [4H, ld_i], bias_p [4H]; gates [N,T,H,4], cell [N,T,H],
+ * hout / dhout [N,T,ldo] with columns 0..H-1 (H..ldo-1 are never written and never read).  H <= 512.
+ * h0 / c0 [N,H]: the state the recurrence starts from -- both or neither (one alone: TSSEP_E_NULL); null = zeros.
+ * hT / cT [N,H], each nullable: the state after the last frame, the bits of hout[:, T-1, :H] / cell[:, T-1].
+ * tssep_lstm1_bwd assumes a ZERO initial state: a carried state exists without gradients only. */
+int tssep_lstm1_pack_sizes(int H, int I, int64_t ld_i, tssep_lstm_sizes* out);
+int tssep_lstm1_pack(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                     int H, int I, int64_t ld_i, float* wih_p, float* bias_p, float* whh_f,
+                     float* whh_b, void* stream);
+int tssep_lstm1_fwd(float* gates, float* cell, float* hout, int64_t ldo, const float* whh_f,
+                    const float* h0, const float* c0, float* hT, float* cT,
+                    int64_t N, int64_t T, int H, void* stream);
+int tssep_lstm1_bwd(float* gates, const float* cell, const float* dhout, int64_t ldo,
+                    const float* whh_b, int64_t N, int64_t T, int H, void* stream);
+/* dst[(g*H + u)*ncols + k] (+)= sum_{s<nsplit} src[s*split_stride + (4u + g)*ld + k] */
+int tssep_lstm1_unpack(const float* src, int64_t ld, int nsplit, int64_t split_stride,
+                       int H, int ncols, float* dst, int accumulate, void* stream);
+
 /* Cluster (W-stationary) recurrence -- latency-optimised alternative to tssep_blstm_fwd/bwd for
  * batches that do not fill the chip (same math, same tensor layouts; see lstm_cluster.hip).
  * A cluster of ceil(H/32) co-resident workgroups keeps W_hh in registers and exchanges h / dh

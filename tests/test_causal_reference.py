@@ -1,0 +1,455 @@
+"""The causal RNNP layer (typ='lstm': an LSTM in ONE direction of time + projection (+ Tanh), functional._RNNP1) in plain
+torch, tested without a GPU; tests/test_gpu_causal_layer.py and tests/test_gpu_causal_estimator.py import it.
+
+The restatement.  No new formulas: a one-direction layer IS the two-direction restatement of
+tests/test_rnnp_layer_reference.py (`layer`, `two_layers`) with the reverse half of the projection zeroed
+(w_proj[:, H:] = 0) -- the reverse direction then reaches neither y nor any gradient of the forward direction's tensors,
+whose values are the causal layer's.  `causal_layer` / `causal_two_layers` build that ten-tensor case from the SIX causal
+tensors (w_ih, w_hh, b_ih, b_hh, w_proj [hdim, H], b_proj), run the restatement and hand back the causal tensors.  It is
+pinned against torch.nn.LSTM(bidirectional=False).double() + Linear + Tanh under autograd (<= 1e-11 normwise).
+
+The measure and the margin are that file's (`errors`, `bounds`, `assert_within`, MARGIN = 8, SPLIT_RATIO, FLOOR).  That
+MARGIN holds here as well is shown for an independent fp32 implementation -- torch.nn.LSTM fp32 under autograd against
+the fp32 restatement -- over seeds 0-4, act 0 / 1 and MARGIN_SHAPES.  Measured for this file: pin 1.4e-15 at worst (bound 1e-11);
+worst ratio 4.43, at (6, 5, 7, 5, 6) on b_ih / b_hh.
+
+The state.  `lstm1_loop` is the float64 time loop of one direction with an initial state (the idea of
+test_recurrence_reference.lstm_forward_loop); chunks (T), (1 x T) and (5, 1, T - 6), each started from the previous
+chunk's final state, reproduce the whole sequence to <= 1e-12, and the final state is the last frame.
+
+The teeth.  CAUSAL_DEFECTS plants what the causal route could get wrong (time reversed; c not carried while h is; the
+state of sequence n handed to n + 1; the boundary row of the neighbouring sequence in dW_hh; b_hh left zero; a pad column
+of hout leaking into dW_proj; the projection reading 2H columns): each is rejected under the WIDER (split-bf16) bound at
+the GPU file's shapes.
+
+Host logic: key lists and repr of RNNP_packed(typ='lstm') / MaskEstimator_v2(rnn_typ='lstm') against the modules the
+reference's constructor describes, the refusals (raised before anything touches a device), the toy overlay."""
+import os
+
+import pytest
+import torch
+
+from test_recurrence_reference import _w_fwd
+from test_rnnp_layer_reference import (MARGIN, NAMES, U, assert_within, combine_rows, corrupt, errors, failures, layer,
+                                       layer_forward, report, round_up, two_layers)
+
+CNAMES = ("w_ih", "w_hh", "b_ih", "b_hh", "w_proj", "b_proj")
+CATTRS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+SEEDS = (0, 1, 2, 3, 4)
+EXP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tssep_amd", "exp")
+
+# (N, T, I, H, hdim, combine)
+MARGIN_SHAPES = [(6, 5, 7, 5, 6, 0), (8, 5, 7, 5, 6, 4), (6, 7, 8, 8, 8, 0), (1, 1, 7, 5, 6, 0), (9, 7, 8, 12, 8, 0),
+                 (32, 7, 321, 300, 320, 0), (8, 23, 321, 300, 320, 4)]
+# the shapes of tests/test_gpu_causal_layer.py
+LAYER_SHAPES = [(6, 5, 7, 5, 6, 0), (8, 5, 7, 5, 6, 4), (6, 7, 8, 8, 8, 0), (32, 7, 321, 300, 320, 0), (768, 7, 321, 300, 320, 4)]
+STATE_SHAPE = (8, 23, 321, 300, 320, 0)
+
+
+def chunkings(T):
+    return [[T], [1] * T, [5, 1, T - 6]]
+
+
+# ---- the restatement ---------------------------------------------------------------------------------------------------
+def make_causal_params(I, H, hdim, gen, device="cpu"):
+    """the six tensors with torch.nn.LSTM's / Linear's initial ranges"""
+    def uni(bound, *shape):
+        return (torch.rand(*shape, generator=gen, device=device) * 2 - 1) * bound
+    b = H ** -0.5
+    return [uni(b, 4 * H, I), uni(b, 4 * H, H), uni(b, 4 * H), uni(b, 4 * H), uni(b, hdim, H), uni(b, hdim)]
+
+
+def make_causal_case(N, T, I, H, hdim, seed, combine=0, device="cpu"):
+    """-> x rows (n, t) [N T, I], the six parameters, dy in the output's layout: fp32 values, fixed seed"""
+    gen = torch.Generator(device=device).manual_seed(2000 + seed)
+    params = make_causal_params(I, H, hdim, gen, device)
+    x = torch.randn(N * T, I, generator=gen, device=device)
+    K = combine or 1
+    return x, params, torch.randn(N // K * T, K * hdim, generator=gen, device=device)
+
+
+def two_directions(params):
+    """six causal tensors -> the ten of the two-direction restatement: a reverse direction with the forward one's LSTM
+    tensors (any would do) whose half of the projection is zero"""
+    w_proj = torch.cat([params[4], torch.zeros_like(params[4])], 1)
+    return list(params[:4]) + list(params[:4]) + [w_proj, params[5]]
+
+
+def _causal_of(out, H, prefix=""):
+    got = {k: out[prefix + k] for k in ("w_ih", "w_hh", "b_ih", "b_hh", "b_proj")}
+    got["w_proj"] = out[prefix + "w_proj"][:, :H]
+    return got
+
+
+def causal_layer(x, params, dy, N, T, dtype, act=0, combine=0):
+    """-> {"y", "x", the six parameter names} of the causal layer in `dtype`"""
+    out = layer(x, two_directions(params), dy, N, T, dtype, act, combine)
+    got = _causal_of(out, params[1].shape[1])
+    got.update(y=out["y"], x=out["x"])
+    return got
+
+
+def causal_two_layers(x, p0, p1, dy, N, T, K, dtype):
+    """causal layer 0 (act = 1, combine = K or 0) feeding causal layer 1 -> {"y", "h", "dh", "x", "0.<name>", "1.<name>"}"""
+    out = two_layers(x, two_directions(p0), two_directions(p1), dy, N, T, K, dtype)
+    got = {k: out[k] for k in ("y", "h", "dh", "x")}
+    for i, p in (("0.", p0), ("1.", p1)):
+        got.update({i + k: v for k, v in _causal_of(out, p[1].shape[1], i).items()})
+    return got
+
+
+def causal_modules(params, device="cpu", dtype=torch.float32):
+    """the six tensors in torch.nn.LSTM(bidirectional=False) / Linear containers"""
+    I, H, hdim = params[0].shape[1], params[1].shape[1], params[4].shape[0]
+    lstm, lin = torch.nn.LSTM(I, H, bidirectional=False, batch_first=True), torch.nn.Linear(H, hdim)
+    with torch.no_grad():
+        for a, t in zip(CATTRS, params[:4]):
+            getattr(lstm, a).copy_(t)
+        lin.weight.copy_(params[4])
+        lin.bias.copy_(params[5])
+    return lstm.to(device=device, dtype=dtype), lin.to(device=device, dtype=dtype)
+
+
+def causal_module_params(lstm, lin):
+    return [getattr(lstm, a) for a in CATTRS] + [lin.weight, lin.bias]
+
+
+def torch_causal_layer(x, params, dy, N, T, dtype, act=0, combine=0):
+    """the same layer by torch.nn.LSTM(bidirectional=False) + Linear (+ Tanh) under autograd"""
+    lstm, lin = causal_modules(params, dtype=dtype)
+    xr = x.to(dtype).view(N, T, -1).clone().requires_grad_()
+    z = lin(lstm(xr)[0]).reshape(N * T, -1)
+    y = torch.tanh(z) if act else z
+    y = combine_rows(y, N, T, combine) if combine else y
+    (y * dy.to(dtype)).sum().backward()
+    out = {k: t.grad for k, t in zip(CNAMES, causal_module_params(lstm, lin))}
+    out.update(y=y.detach(), x=xr.grad.reshape(N * T, -1))
+    return out
+
+
+_CACHE = {}
+
+
+def causal_reference(shape, seed, act):
+    """-> (x, params, dy, {dtype: causal layer outputs}), computed once per process and left unchanged"""
+    key = (tuple(shape), seed, act)
+    if key not in _CACHE:
+        N, T, I, H, hdim, combine = shape
+        x, params, dy = make_causal_case(N, T, I, H, hdim, seed, combine)
+        _CACHE[key] = (x, params, dy, {dt: causal_layer(x, params, dy, N, T, dt, act, combine)
+                                       for dt in (torch.float64, torch.float32)})
+    return _CACHE[key]
+
+
+# ---- the state ---------------------------------------------------------------------------------------------------------
+def lstm1_loop(gin, whh, H, dtype, state=None):
+    """gin [n, T, H, 4] pre-activations, whh [4H, H] (torch's layout) -> A [n, T, H, 4], c, h [n, T, H] and the final
+    state (h, c) of ONE direction of time in `dtype`, from `state` = (h0, c0) [n, H] (None: zeros)"""
+    g = gin.to(dtype)
+    n, T = g.shape[:2]
+    wk = _w_fwd([whh], H, dtype)[0]
+    A, C, Hs = torch.empty_like(g), torch.empty_like(g[..., 0]), torch.empty_like(g[..., 0])
+    h, c = (torch.zeros(n, H, dtype=dtype, device=g.device) for _ in range(2)) if state is None else (s.to(dtype) for s in state)
+    for t in range(T):
+        a = g[:, t] + (h @ wk).view(n, H, 4)
+        act = torch.sigmoid(a)
+        act[..., 2] = torch.tanh(a[..., 2])
+        c = act[..., 1] * c + act[..., 0] * act[..., 2]
+        h = act[..., 3] * torch.tanh(c)
+        A[:, t], C[:, t], Hs[:, t] = act, c, h
+    return A, C, Hs, (h, c)
+
+
+def chunked_forward(x, params, N, T, chunks, dtype, act=0, hand_over=lambda h, c: (h, c)):
+    """The causal layer's forward over consecutive chunks of frames, each started from the state the previous one ended
+    in (through `hand_over`: the identity, or a planted defect) -> (y rows (n, t) [N T, hdim], the final (h, c))."""
+    p = [t.to(dtype) for t in params]
+    H = p[1].shape[1]
+    x3 = x.to(dtype).view(N, T, -1)
+    ys, state, t0 = [], None, 0
+    for n in chunks:
+        xc = x3[:, t0:t0 + n]
+        gin = (xc @ p[0].t() + (p[2] + p[3])).view(N, n, 4, H).transpose(2, 3)
+        _, _, h, last = lstm1_loop(gin, p[1], H, dtype, state)
+        z = h @ p[4].t() + p[5]
+        ys.append(torch.tanh(z) if act else z)
+        state = hand_over(*last)
+        t0 += n
+    assert t0 == T, (chunks, T)
+    return torch.cat(ys, 1).reshape(N * T, -1), last
+
+
+# ---- tests: the restatement is the layer -------------------------------------------------------------------------------
+@pytest.mark.parametrize("act", [0, 1])
+@pytest.mark.parametrize("shape", MARGIN_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_restatement_equals_a_one_direction_torch_lstm_in_float64(shape, act):
+    N, T, I, H, hdim, combine = shape
+    x, params, dy, ref = causal_reference(shape, 0, act)
+    want = torch_causal_layer(x, params, dy, N, T, torch.float64, act, combine)
+    for k in ("y", "x") + CNAMES:
+        e = errors(ref[torch.float64][k], want[k])[0]
+        print(k, e)
+        assert ref[torch.float64][k].shape == want[k].shape and e <= 1e-11, (k, e)
+
+
+def test_two_causal_layers_equal_autograd_through_tanh():
+    N, T, I, H, hdim, K = 4, 3, 8, 4, 8, 2
+    gen = torch.Generator().manual_seed(5)
+    p0, p1 = make_causal_params(I, H, hdim, gen), make_causal_params(K * hdim, H, hdim, gen)
+    x = torch.randn(N * T, I, generator=gen)
+    dy = torch.randn(N // K * T, hdim, generator=gen)
+    mine = causal_two_layers(x, p0, p1, dy, N, T, K, torch.float64)
+    (l0, q0), (l1, q1) = causal_modules(p0, dtype=torch.float64), causal_modules(p1, dtype=torch.float64)
+    xr = x.double().view(N, T, I).requires_grad_()
+    h = combine_rows(torch.tanh(q0(l0(xr)[0])).reshape(N * T, hdim), N, T, K)
+    h.retain_grad()
+    y = q1(l1(h.view(N // K, T, K * hdim))[0]).reshape(-1, hdim)
+    (y * dy.double()).sum().backward()
+    want = {"y": y.detach(), "h": h.detach(), "dh": h.grad, "x": xr.grad.reshape(N * T, I)}
+    want.update({"0." + k: t.grad for k, t in zip(CNAMES, causal_module_params(l0, q0))})
+    want.update({"1." + k: t.grad for k, t in zip(CNAMES, causal_module_params(l1, q1))})
+    assert set(want) == set(mine)
+    for k, w in want.items():
+        assert errors(mine[k], w)[0] <= 1e-11, k
+
+
+@pytest.mark.parametrize("shape", MARGIN_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_margin_covers_an_independent_fp32_implementation(shape):
+    """torch.nn.LSTM(bidirectional=False) + Linear + Tanh in fp32 under autograd against the fp32 restatement's own error:
+    inside MARGIN for every tensor, seed and activation"""
+    N, T, I, H, hdim, combine = shape
+    worst = {}
+    for seed in SEEDS:
+        for act in (0, 1):
+            x, params, dy, ref = causal_reference(shape, seed, act)
+            got = torch_causal_layer(x, params, dy, N, T, torch.float32, act, combine)
+            for k, v in report(got, ref[torch.float64], ref[torch.float32], split=False).items():
+                worst[k] = max(worst.get(k, 0.0), v["ratio"])
+    print(shape, " ".join(f"{k}={v:.2f}" for k, v in worst.items()))
+    assert max(worst.values()) <= MARGIN, worst
+
+
+# ---- tests: the state --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(3, 23, 7, 5, 6, 0), STATE_SHAPE], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("act", [0, 1])
+def test_chunks_with_a_carried_state_reproduce_the_whole_sequence(shape, act):
+    N, T, I, H, hdim, _ = shape
+    x, params, dy, ref = causal_reference(shape, 0, act)
+    for chunks in chunkings(T):
+        y, (hT, cT) = chunked_forward(x, params, N, T, chunks, torch.float64, act)
+        e = errors(y, ref[torch.float64]["y"])[0]
+        print(chunks[:4], e)
+        assert e <= 1e-12, (chunks, e)
+    # the final state is the last frame (of the whole-sequence loop, and of the last chunk: the same thing)
+    p = [t.double() for t in params]
+    gin = (x.double() @ p[0].t() + (p[2] + p[3])).view(N, T, 4, H).transpose(2, 3)
+    _, c, h, (hl, cl) = lstm1_loop(gin, p[1], H, torch.float64)
+    assert torch.equal(hl, h[:, -1]) and torch.equal(cl, c[:, -1])
+    assert errors(hT, hl)[0] <= 1e-12 and errors(cT, cl)[0] <= 1e-12
+
+
+# ---- tests: the teeth --------------------------------------------------------------------------------------------------
+def _reverse_time(x, dy, N, T, combine):
+    K = combine or 1
+    return (x.view(N, T, -1).flip(1).reshape(N * T, -1), dy.view(N // K, T, -1).flip(1).reshape(N // K * T, -1))
+
+
+def plant(name, shape, x, params, dy, ref64, act):
+    """-> (the float64 outputs with defect `name` planted, the tensors it must show in)"""
+    N, T, I, H, hdim, combine = shape
+    g = dict(ref64)
+    if name == "time_reversed":               # the recurrence walks the frames backwards
+        xr, dyr = _reverse_time(x, dy, N, T, combine)
+        bad = causal_layer(xr, params, dyr, N, T, torch.float64, act, combine)
+        K = combine or 1
+        bad["y"] = bad["y"].view(N // K, T, -1).flip(1).reshape(ref64["y"].shape)
+        bad["x"] = bad["x"].view(N, T, -1).flip(1).reshape(N * T, -1)
+        return bad, ["y", "x", *CNAMES]
+    if name in ("c_not_carried", "state_of_the_neighbour"):
+        hand = (lambda h, c: (h, torch.zeros_like(c))) if name == "c_not_carried" else (lambda h, c: (h.roll(1, 0), c.roll(1, 0)))
+        y, _ = chunked_forward(x, params, N, T, [2, T - 2], torch.float64, act, hand)
+        g["y"] = combine_rows(y, N, T, combine) if combine else y
+        return g, ["y"]
+    fw = layer_forward(x, two_directions(params), N, T, torch.float64, act, combine)
+    if name == "boundary_row_of_the_neighbour":
+        bad, _ = corrupt(name, fw, dy, dict(ref64))
+        g["w_hh"] = bad["w_hh"]
+        return g, ["w_hh"]
+    if name == "b_hh_zero":
+        g["b_hh"] = torch.zeros_like(ref64["b_hh"])
+        return g, ["b_hh"]
+    if name == "pad_column_leaks":            # hout [R, Hp] read with the leading dimension H: the pad columns walk into dW_proj
+        Hp = round_up(H, 4)
+        assert Hp != H, "only where the hidden width is padded"
+        R = N * T
+        hpad = torch.zeros(R, Hp, dtype=torch.float64)
+        hpad[:, :H] = fw["h"][:, :, 0].reshape(R, H)
+        dz = corrupt_terms(fw, dy)
+        g["w_proj"] = torch.einsum("rj,rc->jc", dz, hpad.reshape(-1)[:R * H].view(R, H))
+        return g, ["w_proj"]
+    if name == "projection_reads_2H_columns":      # the reverse half of the two-direction projection is NOT zero
+        ten = two_directions(params)
+        ten[8] = torch.cat([params[4], params[4]], 1)
+        out = layer(x, ten, dy, N, T, torch.float64, act, combine)
+        bad = {k: out[k] for k in ("y", "x", "w_ih", "w_hh", "b_ih", "b_hh", "b_proj")}
+        bad["w_proj"] = out["w_proj"][:, :H]
+        return bad, ["y", "x", *CNAMES]
+    raise KeyError(name)
+
+
+def corrupt_terms(fw, dy):
+    from test_rnnp_layer_reference import layer_terms
+    return layer_terms(fw, dy)["dz"]
+
+
+CAUSAL_DEFECTS = ("time_reversed", "c_not_carried", "state_of_the_neighbour", "boundary_row_of_the_neighbour", "b_hh_zero",
+                  "pad_column_leaks", "projection_reads_2H_columns")
+DEFECT_CASES = [(s, d) for s in LAYER_SHAPES for d in CAUSAL_DEFECTS if d != "pad_column_leaks" or s[3] % 4]
+
+
+@pytest.mark.parametrize("shape,name", DEFECT_CASES, ids=lambda v: v if isinstance(v, str) else "x".join(map(str, v)))
+def test_planted_defects_are_rejected(shape, name):
+    """each defect fails the measure under the WIDER (split-bf16) bound in every tensor it must show in"""
+    x, params, dy, ref = causal_reference(shape, 0, 1)
+    bad, touched = plant(name, shape, x, params, dy, ref[torch.float64], 1)
+    rep = report(bad, ref[torch.float64], ref[torch.float32], split=True)
+    failed = failures(rep)
+    print(name, shape, {k: (f"{rep[k]['norm']:.3g}", f"{rep[k]['bound_norm']:.3g}") for k in touched})
+    assert set(touched) <= set(failed), (name, touched, failed, {k: rep[k] for k in touched})
+
+
+@pytest.mark.parametrize("shape", LAYER_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_fp32_restatement_is_inside_the_narrow_bound(shape):
+    x, params, dy, ref = causal_reference(shape, 0, 1)
+    rep = assert_within(ref[torch.float32], ref[torch.float64], ref[torch.float32], split=False)
+    assert all(v["bound_norm"] < 1e-4 for v in rep.values()), rep      # fp32-sized at every shape: not vacuous
+
+
+# ---- tests: host logic -------------------------------------------------------------------------------------------------
+def described_rnnp(idim, elayers, cdim, hdim, dropout, typ):
+    """The ModuleList the reference's RNNP_packed constructor describes (tssep/train/rnnp.py:80-103): per layer an LSTM in
+    one or two directions and a Linear from its width, a Dropout and a Tanh between two layers."""
+    bidir = typ[0] == "b"
+    net = []
+    for i in range(elayers):
+        net += [torch.nn.LSTM(idim if i == 0 else hdim, cdim, num_layers=1, bidirectional=bidir, batch_first=True),
+                torch.nn.Linear(2 * cdim if bidir else cdim, hdim)]
+        if i < elayers - 1:
+            net += [torch.nn.Dropout(p=dropout), torch.nn.Tanh()]
+    return torch.nn.ModuleList(net)
+
+
+def test_rnnp_packed_lstm_is_the_described_module():
+    from tssep_amd.train.rnnp import RNNP_packed
+    m = RNNP_packed(7, 3, 5, 6, 0.3, typ="lstm")
+    want = described_rnnp(7, 3, 5, 6, 0.3, "lstm")
+    assert list(m.state_dict()) == ["net." + k for k in want.state_dict()]
+    assert [tuple(v.shape) for v in m.state_dict().values()] == [tuple(v.shape) for v in want.state_dict().values()]
+    assert repr(m.net) == repr(want) and repr(m).startswith("RNNP_packed(\n  (net): ModuleList(")
+    assert list(m.state_dict())[:6] == ["net.0.weight_ih_l0", "net.0.weight_hh_l0", "net.0.bias_ih_l0", "net.0.bias_hh_l0",
+                                        "net.1.weight", "net.1.bias"]
+    assert not any("_reverse" in k for k in m.state_dict())
+    assert (m.typ, m.bidir, m.elayers, m.cdim, m.dropout, m.return_states) == ("lstm", False, 3, 5, 0.3, False)
+    # 'blstm' is what it was
+    b = RNNP_packed(7, 3, 5, 6, 0.3)
+    assert repr(b.net) == repr(described_rnnp(7, 3, 5, 6, 0.3, "blstm")) and b.bidir
+
+
+def test_rnnp_packed_refusals():
+    from tssep_amd.train.rnnp import RNNP_packed
+    for typ in ("bgru", "gru"):
+        with pytest.raises(NotImplementedError):
+            RNNP_packed(7, 3, 5, 6, 0.3, typ=typ)
+    for typ in ("rnn", "", "LSTM", "blstmp"):
+        with pytest.raises(ValueError):
+            RNNP_packed(7, 3, 5, 6, 0.3, typ=typ)
+    with pytest.raises(NotImplementedError):
+        RNNP_packed(7, 1, 5, 6, 0, typ="blstm", return_states=True)
+    m = RNNP_packed(7, 2, 5, 6, 0, typ="lstm", return_states=True)
+    x = torch.zeros(2, 3, 7)
+    state = [(torch.zeros(1, 2, 5), torch.zeros(1, 2, 5))] * 2
+    with pytest.raises(RuntimeError, match="without gradients"):      # gradients are enabled here
+        m(x, prev_state=state)
+    with torch.no_grad(), pytest.raises(ValueError, match="one .h, c. per layer"):
+        m(x, prev_state=state[:1])
+    with pytest.raises(ValueError, match="return_states"):
+        RNNP_packed(7, 2, 5, 6, 0, typ="lstm")(x, prev_state=state)
+    with pytest.raises(NotImplementedError):
+        m(torch.nn.utils.rnn.pack_sequence([torch.zeros(3, 7)]))
+
+
+ESTIMATORS = [dict(ts_vad=4, combination="cat", aux_net_output_size=9), dict(ts_vad=False, combination="cat", aux_net_output_size=9),
+              dict(ts_vad=4, combination="mul"), dict(ts_vad=False, combination="mul")]
+
+
+@pytest.mark.parametrize("kw", ESTIMATORS, ids=lambda kw: f"{kw['combination']}-{kw['ts_vad']}")
+def test_mask_estimator_lstm_is_the_blstm_model_in_one_direction(kw):
+    from tssep_amd.train.net import MaskEstimator_v2
+    units, projs = 5, 12
+    base = dict(idim=8, layers=3, units=units, projs=projs, **kw)
+    two, one = MaskEstimator_v2(**base), MaskEstimator_v2(rnn_typ="lstm", **base)
+    assert MaskEstimator_v2(rnn_typ="blstm", **base).rnn_typ == two.rnn_typ == "blstm" and one.rnn_typ == "lstm"
+    assert list(one.state_dict()) == [k for k in two.state_dict() if not k.endswith("_reverse")]
+    for k, v in one.state_dict().items():
+        w = two.state_dict()[k]
+        if k.endswith("net.1.weight"):        # the projection behind an LSTM: from units, not 2 units
+            assert tuple(v.shape) == (w.shape[0], units) and w.shape[1] == 2 * units, k
+        else:
+            assert v.shape == w.shape, k
+    want = repr(two).replace(", bidirectional=True", "").replace(f"Linear(in_features={2 * units},", f"Linear(in_features={units},")
+    assert repr(one) == want
+    for rnn in [one.pre_net, *one._birnns]:
+        assert rnn.typ == "lstm" and repr(rnn.net) == repr(described_rnnp(rnn.net[0].input_size, 1, units, rnn.hdim, 0, "lstm"))
+    with pytest.raises(ValueError, match="rnn_typ"):
+        MaskEstimator_v2(rnn_typ="gru", **base)
+
+
+def test_forward_chunk_refusals():
+    """raised on the arguments alone: CPU tensors, nothing is launched"""
+    from tssep_amd.train.net import InstanceNorm, MaskEstimator_v2
+    base = dict(idim=8, layers=2, units=5, projs=12, combination="mul")
+    xs, aux = torch.zeros(2, 3, 8), torch.zeros(2, 4, 8)
+    with pytest.raises(ValueError, match="reads the future"):
+        MaskEstimator_v2(**base).forward_chunk(xs, aux)
+    with pytest.raises(NotImplementedError, match="span the utterance"):
+        MaskEstimator_v2(rnn_typ="lstm", input_normalizer=InstanceNorm(), **base).forward_chunk(xs, aux)
+    m = MaskEstimator_v2(rnn_typ="lstm", **base)
+    with pytest.raises(NotImplementedError, match="frame-wise"):
+        m.forward_chunk(xs, torch.zeros(2, 4, 3, 8))
+    with pytest.raises(NotImplementedError, match="frame-wise"):
+        m.forward_chunk(xs[0], torch.zeros(4, 3, 8))
+    with pytest.raises(ValueError, match="Tc >= 1"):
+        m.forward_chunk(torch.zeros(2, 0, 8), aux)
+    with pytest.raises(TypeError):
+        m.forward_chunk(xs, aux, state=object())
+
+
+def test_rnnp_layer_refuses_a_state_with_gradients_and_on_two_directions():
+    from tssep_amd import functional as Fn
+    lstm, lin = causal_modules(make_causal_params(7, 5, 6, torch.Generator().manual_seed(0)))
+    x = torch.zeros(6, 7)
+    state = (torch.zeros(2, 5), torch.zeros(2, 5))
+    with pytest.raises(RuntimeError, match="without gradients"):
+        Fn.rnnp_layer(x, lstm, lin, 2, 3, state=state)
+    two = torch.nn.LSTM(7, 5, bidirectional=True, batch_first=True)
+    with torch.no_grad(), pytest.raises(NotImplementedError):
+        Fn.rnnp_layer(x, two, torch.nn.Linear(10, 6), 2, 3, state=state)
+
+
+def test_toy_causal_overlay_resolves():
+    from tssep_amd import configurable
+    from tssep_amd.train import run
+    from tssep_amd.train.experiment import Experiment
+    from tssep_amd.train.net import MaskEstimator_v2
+    yamls = ("toy_common.yaml", "toy_tssep.yaml")
+    cfg = run.build_config([os.path.join(EXP, y) for y in (*yamls, "toy_tssep_causal.yaml")] + ["eg.trainer.storage_dir=/tmp/unused"])
+    assert cfg["eg"]["trainer"]["model"]["mask_estimator"]["rnn_typ"] == "lstm"
+    assert Experiment.get_config(cfg["eg"])["trainer"]["model"]["mask_estimator"]["rnn_typ"] == "lstm"
+    assert configurable.resolve(cfg["eg"]["trainer"]["model"]["mask_estimator"]["factory"]) is MaskEstimator_v2
+    model = Experiment.from_config(cfg["eg"]).trainer.model
+    me = model.mask_estimator
+    assert me.rnn_typ == "lstm" and all(not r.bidir for r in [me.pre_net, *me._birnns])
+    plain = run.build_config([os.path.join(EXP, y) for y in yamls] + ["eg.trainer.storage_dir=/tmp/unused"])
+    ref = Experiment.from_config(plain["eg"]).trainer.model
+    assert ref.mask_estimator.rnn_typ == "blstm"
+    assert list(model.state_dict()) == [k for k in ref.state_dict() if not k.endswith("_reverse")]

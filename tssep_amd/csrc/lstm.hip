@@ -23,6 +23,11 @@
 //   whh_b : [dir][gate 4][kq KQ3][ubb NBB][lane 64][4] = W_hh[g*H + 4kq + e][ubb*64 + lane]
 //                                                      (BPTT: dh_prev = dgates x W_hh)
 // with NB = ceil(ceil(H/16)/4), NBB = ceil(H/64), KQ3 = ceil(ceil(H/4)/3)*3; zero padded.
+//
+// One direction of time (torch.nn.LSTM(bidirectional=False), rnnp.py:80-96 typ='lstm'; tssep_lstm1_*): the same kernels
+// with the direction count ND = 1 -- every [dir] axis above has one entry, gates are [N,T,H,4] -- plus an optional
+// initial state (h0 into the LDS copy of h, c0 into the cell registers) and final state (the last step's h, c).  The
+// ND = 2 instantiation carries none of it: its step is the instruction sequence it was.
 #include "common.h"
 
 namespace {
@@ -38,12 +43,14 @@ __global__ void lstm_pack_kernel(const float* w_ih_f, const float* w_hh_f, const
                                  const float* b_hh_f, const float* w_ih_r, const float* w_hh_r,
                                  const float* b_ih_r, const float* b_hh_r, int H, int I,
                                  int64_t ld_i, float* wih_p, float* bias_p, float* whh_f,
-                                 float* whh_b) {
+                                 float* whh_b, int ND) {
+  // ND directions (1: the *_r pointers are null and never read -- every d below is 0)
   const int NB = lstm_nb(H), NBB = lstm_nbb(H), KQ3 = lstm_kq3(H);
-  const int64_t n_wih = (int64_t)8 * H * ld_i;
-  const int64_t n_f = (int64_t)2 * 4 * KQ3 * NB * 256;
-  const int64_t n_b = (int64_t)2 * 4 * KQ3 * NBB * 256;
-  const int64_t total = n_wih + 8 * H + n_f + n_b;
+  const int n_bias = ND * 4 * H;
+  const int64_t n_wih = (int64_t)n_bias * ld_i;
+  const int64_t n_f = (int64_t)ND * 4 * KQ3 * NB * 256;
+  const int64_t n_b = (int64_t)ND * 4 * KQ3 * NBB * 256;
+  const int64_t total = n_wih + n_bias + n_f + n_b;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (int64_t)gridDim.x * blockDim.x) {
     if (e < n_wih) {
@@ -52,13 +59,13 @@ __global__ void lstm_pack_kernel(const float* w_ih_f, const float* w_hh_f, const
       const int u = ug >> 2, g = ug & 3;
       const float* w = d ? w_ih_r : w_ih_f;
       wih_p[e] = k < I ? w[(int64_t)(g * H + u) * I + k] : 0.f;
-    } else if (e < n_wih + 8 * H) {
+    } else if (e < n_wih + n_bias) {
       const int row = (int)(e - n_wih);
       const int d = row / (4 * H), ug = row % (4 * H);
       const int u = ug >> 2, g = ug & 3;
       bias_p[row] = (d ? b_ih_r : b_ih_f)[g * H + u] + (d ? b_hh_r : b_hh_f)[g * H + u];
-    } else if (e < n_wih + 8 * H + n_f) {
-      int64_t r = e - n_wih - 8 * H;
+    } else if (e < n_wih + n_bias + n_f) {
+      int64_t r = e - n_wih - n_bias;
       const int el = (int)(r & 3); r >>= 2;
       const int lane = (int)(r & 63); r >>= 6;
       const int i = (int)(r % NB); r /= NB;
@@ -67,9 +74,9 @@ __global__ void lstm_pack_kernel(const float* w_ih_f, const float* w_hh_f, const
       const int d = (int)(r >> 2);
       const int u = (wave * NB + i) * 16 + (lane >> 2), g = lane & 3, k = 4 * kq + el;
       const float* w = d ? w_hh_r : w_hh_f;
-      whh_f[e - n_wih - 8 * H] = (u < H && k < H) ? w[(int64_t)(g * H + u) * H + k] : 0.f;
+      whh_f[e - n_wih - n_bias] = (u < H && k < H) ? w[(int64_t)(g * H + u) * H + k] : 0.f;
     } else {
-      int64_t r = e - n_wih - 8 * H - n_f;
+      int64_t r = e - n_wih - n_bias - n_f;
       const int el = (int)(r & 3); r >>= 2;
       const int lane = (int)(r & 63); r >>= 6;
       const int ubb = (int)(r % NBB); r /= NBB;
@@ -78,7 +85,7 @@ __global__ void lstm_pack_kernel(const float* w_ih_f, const float* w_hh_f, const
       const int d = (int)(r >> 2);
       const int unit = ubb * 64 + lane, kk = 4 * kq + el;
       const float* w = d ? w_hh_r : w_hh_f;
-      whh_b[e - n_wih - 8 * H - n_f] =
+      whh_b[e - n_wih - n_bias - n_f] =
           (unit < H && kk < H) ? w[(int64_t)(g * H + kk) * H + unit] : 0.f;
     }
   }
@@ -87,8 +94,8 @@ __global__ void lstm_pack_kernel(const float* w_ih_f, const float* w_hh_f, const
 // dst_d[(g*H + u)*ncols + k] = sum_s src[s*split_stride + (d*4H + 4u + g)*ld + k]
 __global__ void lstm_unpack_kernel(const float* __restrict__ src, int64_t ld, int nsplit,
                                    int64_t split_stride, int H, int ncols, float* dst_f,
-                                   float* dst_r, int accumulate) {
-  const int64_t per = (int64_t)4 * H * ncols, total = 2 * per;
+                                   float* dst_r, int accumulate, int ND) {
+  const int64_t per = (int64_t)4 * H * ncols, total = ND * per;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (int64_t)gridDim.x * blockDim.x) {
     const int d = e >= per;
@@ -107,18 +114,32 @@ __global__ void lstm_unpack_kernel(const float* __restrict__ src, int64_t ld, in
 // --------------------------------------------------------------------- forward
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 0, 0, 0)
 
-template <int NB>
+// ND = 2: the bidirectional layer, blockIdx.y = direction of time, zero initial state.  ND = 1: ONE direction, forward in
+// time (gates [N,T,H,4], cell [N,T,H], hout columns 0..H-1), with an optional initial state h0 / c0 [N,H] and an optional
+// final state hT / cT [N,H]; everything about the state is compiled out of the ND = 2 instantiation.
+template <int NB, int ND>
 __global__ __launch_bounds__(256, 1) void blstm_fwd_kernel(
     float* __restrict__ gates, float* __restrict__ cell, float* __restrict__ hout, int64_t ldo,
-    int64_t dstride, const float* __restrict__ whh_f, int64_t N, int64_t T, int H, int KQ3) {
+    int64_t dstride, const float* __restrict__ whh_f, int64_t N, int64_t T, int H, int KQ3,
+    const float* __restrict__ h0, const float* __restrict__ c0, float* __restrict__ hT,
+    float* __restrict__ cT) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int KROW = 4 * KQ3 + 12;
   float* hs = smem;  // [2][8][KROW]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int dir = blockIdx.y;
+  const int dir = ND == 2 ? blockIdx.y : 0;
   const int64_t seq0 = (int64_t)blockIdx.x * 8;
   const int ub = lane >> 2, j = lane & 3;
   for (int i = tid; i < 2 * 8 * KROW; i += 256) hs[i] = 0.f;
+  if constexpr (ND == 1) {
+    if (h0) {      // (uniform) the previous chunk's last h, behind the zero fill; the barrier below publishes it
+      __syncthreads();
+      for (int i = tid; i < 8 * H; i += 256) {
+        const int s = i / H, k = i - s * H;
+        if (seq0 + s < N) hs[s * KROW + k] = h0[(seq0 + s) * H + k];
+      }
+    }
+  }
 
   const f32x4* W = reinterpret_cast<const f32x4*>(whh_f) +
                    ((int64_t)(dir * 4 + wave) * KQ3) * NB * 64 + lane;
@@ -140,6 +161,15 @@ __global__ __launch_bounds__(256, 1) void blstm_fwd_kernel(
   float c[NB][2];
 #pragma unroll
   for (int i = 0; i < NB; ++i) { c[i][0] = 0.f; c[i][1] = 0.f; }
+  if constexpr (ND == 1) {
+    if (c0) {
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg)
+          if (nvalid[sg] && uvalid[i]) c[i][sg] = c0[nrow[sg] * H + u[i]];
+    }
+  }
 
   f32x4 w0[NB], w1[NB], w2[NB];
 #define LOADW(dst, kq_)                                              \
@@ -178,7 +208,7 @@ __global__ __launch_bounds__(256, 1) void blstm_fwd_kernel(
         // streamed once: non-temporal so these lines do not push W_hh out of the XCD's L2
         if (nvalid[sg] && uvalid[i])
           v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(
-              gates + (((nrow[sg] * T + t) * 2 + dir) * (int64_t)H + u[i]) * 4));
+              gates + (((nrow[sg] * T + t) * ND + dir) * (int64_t)H + u[i]) * 4));
         gx[i][sg] = v;
       }
     f32x4 acc[NB][2];
@@ -216,11 +246,17 @@ __global__ __launch_bounds__(256, 1) void blstm_fwd_kernel(
         if (uvalid[i]) {
           hnext[(sg * 4 + j) * KROW + u[i]] = h;
           if (nvalid[sg]) {
-            const int64_t cellidx = ((nrow[sg] * T + t) * 2 + dir) * (int64_t)H + u[i];
+            const int64_t cellidx = ((nrow[sg] * T + t) * ND + dir) * (int64_t)H + u[i];
             __builtin_nontemporal_store(f32x4{ig, fg, gg, og},
                                         reinterpret_cast<f32x4*>(gates + cellidx * 4));
             __builtin_nontemporal_store(cn, cell + cellidx);
             __builtin_nontemporal_store(h, hout + (nrow[sg] * T + t) * ldo + dir * dstride + u[i]);
+            if constexpr (ND == 1) {
+              if (step == T - 1) {      // the state a next chunk starts from: the last frame's bits
+                if (hT) hT[nrow[sg] * H + u[i]] = h;
+                if (cT) cT[nrow[sg] * H + u[i]] = cn;
+              }
+            }
           }
         }
       }
@@ -231,7 +267,7 @@ __global__ __launch_bounds__(256, 1) void blstm_fwd_kernel(
 }
 
 // -------------------------------------------------------------------- backward
-template <int NB, int NBB>
+template <int NB, int NBB, int ND>
 __global__ __launch_bounds__(256, 1) void blstm_bwd_kernel(
     float* __restrict__ gates, const float* __restrict__ cell, const float* __restrict__ dhout,
     int64_t ldo, int64_t dstride, const float* __restrict__ whh_b, int64_t N, int64_t T, int H, int KQ3) {
@@ -241,7 +277,7 @@ __global__ __launch_bounds__(256, 1) void blstm_bwd_kernel(
   float* dgs = smem;                     // [4 gates][8 seqs][KROW]
   float* part = smem + 4 * 8 * KROW;     // [4 waves][8 seqs][PROW]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int dir = blockIdx.y;
+  const int dir = ND == 2 ? blockIdx.y : 0;
   const int64_t seq0 = (int64_t)blockIdx.x * 8;
   const int ub = lane >> 2, j = lane & 3;
   for (int i = tid; i < 4 * 8 * KROW + 4 * 8 * PROW; i += 256) smem[i] = 0.f;
@@ -302,12 +338,12 @@ __global__ __launch_bounds__(256, 1) void blstm_bwd_kernel(
           float dh = part[(0 * 8 + s) * PROW + u[i]] + part[(1 * 8 + s) * PROW + u[i]] +
                      part[(2 * 8 + s) * PROW + u[i]] + part[(3 * 8 + s) * PROW + u[i]];
           if (nvalid[sg]) {
-            const int64_t cellidx = ((nrow[sg] * T + t) * 2 + dir) * (int64_t)H + u[i];
+            const int64_t cellidx = ((nrow[sg] * T + t) * ND + dir) * (int64_t)H + u[i];
             const f32x4 g4 =
                 __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(gates + cellidx * 4));
             const float ct = __builtin_nontemporal_load(cell + cellidx);
             const float cp = has_prev ? __builtin_nontemporal_load(
-                                            cell + ((nrow[sg] * T + tp) * 2 + dir) * (int64_t)H + u[i])
+                                            cell + ((nrow[sg] * T + tp) * ND + dir) * (int64_t)H + u[i])
                                       : 0.f;
             dh += __builtin_nontemporal_load(dhout + (nrow[sg] * T + t) * ldo + dir * dstride + u[i]);
             const float tc = tanhf_acc(ct);
@@ -361,66 +397,59 @@ __global__ __launch_bounds__(256, 1) void blstm_bwd_kernel(
 #undef SB
 }
 
-}  // namespace
-
-extern "C" int tssep_lstm_pack_sizes(int H, int I, int64_t ld_i, tssep_lstm_sizes* out) {
+// ------------------------------------------------------------------- launchers
+// ND = 2: tssep_lstm_* / tssep_blstm_*; ND = 1: tssep_lstm1_* (one direction of time, optional state)
+int pack_sizes(int ND, int H, int I, int64_t ld_i, tssep_lstm_sizes* out) {
   if (!out) return TSSEP_E_NULL;
   if (H <= 0 || I <= 0 || ld_i < I || (ld_i & 3)) return TSSEP_E_SHAPE;
   if (lstm_nb(H) > 8) return TSSEP_E_UNSUPPORTED;      // H <= 512
-  out->wih_p = (int64_t)8 * H * ld_i;
-  out->bias_p = (int64_t)8 * H;
-  out->whh_f = (int64_t)2 * 4 * lstm_kq3(H) * lstm_nb(H) * 256;
-  out->whh_b = (int64_t)2 * 4 * lstm_kq3(H) * lstm_nbb(H) * 256;
+  out->wih_p = (int64_t)ND * 4 * H * ld_i;
+  out->bias_p = (int64_t)ND * 4 * H;
+  out->whh_f = (int64_t)ND * 4 * lstm_kq3(H) * lstm_nb(H) * 256;
+  out->whh_b = (int64_t)ND * 4 * lstm_kq3(H) * lstm_nbb(H) * 256;
   return TSSEP_OK;
 }
 
-extern "C" int tssep_lstm_pack(const float* w_ih_f, const float* w_hh_f, const float* b_ih_f,
-                               const float* b_hh_f, const float* w_ih_r, const float* w_hh_r,
-                               const float* b_ih_r, const float* b_hh_r, int H, int I,
-                               int64_t ld_i, float* wih_p, float* bias_p, float* whh_f,
-                               float* whh_b, void* stream) {
-  if (!w_ih_f || !w_hh_f || !b_ih_f || !b_hh_f || !w_ih_r || !w_hh_r || !b_ih_r || !b_hh_r ||
-      !wih_p || !bias_p || !whh_f || !whh_b)
-    return TSSEP_E_NULL;
+int launch_pack(int ND, const float* w_ih_f, const float* w_hh_f, const float* b_ih_f,
+                const float* b_hh_f, const float* w_ih_r, const float* w_hh_r, const float* b_ih_r,
+                const float* b_hh_r, int H, int I, int64_t ld_i, float* wih_p, float* bias_p,
+                float* whh_f, float* whh_b, void* stream) {
   tssep_lstm_sizes sz;
-  if (int e = tssep_lstm_pack_sizes(H, I, ld_i, &sz)) return e;
+  if (int e = pack_sizes(ND, H, I, ld_i, &sz)) return e;
   if (!aligned16(wih_p) || !aligned16(whh_f) || !aligned16(whh_b)) return TSSEP_E_ALIGN;
   const int64_t total = sz.wih_p + sz.bias_p + sz.whh_f + sz.whh_b;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(lstm_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                      w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r, H, I, ld_i,
-                     wih_p, bias_p, whh_f, whh_b);
+                     wih_p, bias_p, whh_f, whh_b, ND);
   return tssep_launch_status();
 }
 
-extern "C" int tssep_lstm_unpack(const float* src, int64_t ld, int nsplit, int64_t split_stride,
-                                 int H, int ncols, float* dst_f, float* dst_r, int accumulate,
-                                 void* stream) {
-  if (!src || !dst_f || !dst_r) return TSSEP_E_NULL;
+int launch_unpack(int ND, const float* src, int64_t ld, int nsplit, int64_t split_stride, int H,
+                  int ncols, float* dst_f, float* dst_r, int accumulate, void* stream) {
   if (H <= 0 || ncols <= 0 || nsplit <= 0) return TSSEP_E_SHAPE;
-  const int64_t total = (int64_t)8 * H * ncols;
+  const int64_t total = (int64_t)ND * 4 * H * ncols;
   int64_t blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(lstm_unpack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     src, ld, nsplit, split_stride, H, ncols, dst_f, dst_r, accumulate);
+                     src, ld, nsplit, split_stride, H, ncols, dst_f, dst_r, accumulate, ND);
   return tssep_launch_status();
 }
 
-extern "C" int tssep_blstm_fwd(float* gates, float* cell, float* hout, int64_t ldo,
-                               int64_t dstride, const float* whh_f, int64_t N, int64_t T, int H,
-                               void* stream) {
-  if (!gates || !cell || !hout || !whh_f) return TSSEP_E_NULL;
-  if (N <= 0 || T <= 0 || H <= 0 || dstride < H || ldo < dstride + H) return TSSEP_E_SHAPE;
+template <int ND>
+int launch_fwd(float* gates, float* cell, float* hout, int64_t ldo, int64_t dstride,
+               const float* whh_f, const float* h0, const float* c0, float* hT, float* cT, int64_t N,
+               int64_t T, int H, void* stream) {
   if (!aligned16(gates) || !aligned16(whh_f)) return TSSEP_E_ALIGN;
   const int NB = lstm_nb(H), KQ3 = lstm_kq3(H);
   if (NB > 8) return TSSEP_E_UNSUPPORTED;
-  dim3 grid((unsigned)((N + 7) / 8), 2);
+  dim3 grid((unsigned)((N + 7) / 8), ND);
   const size_t lds = (size_t)2 * 8 * (4 * KQ3 + 12) * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-#define L(NB_)                                                                                 \
-  hipLaunchKernelGGL((blstm_fwd_kernel<NB_>), grid, dim3(256), lds, s, gates, cell, hout, ldo, \
-                     dstride, whh_f, N, T, H, KQ3)
+#define L(NB_)                                                                                   \
+  hipLaunchKernelGGL((blstm_fwd_kernel<NB_, ND>), grid, dim3(256), lds, s, gates, cell, hout,    \
+                     ldo, dstride, whh_f, N, T, H, KQ3, h0, c0, hT, cT)
   switch (NB) {
     case 1: L(1); break;
     case 2: L(2); break;
@@ -435,19 +464,17 @@ extern "C" int tssep_blstm_fwd(float* gates, float* cell, float* hout, int64_t l
   return tssep_launch_status();
 }
 
-extern "C" int tssep_blstm_bwd(float* gates, const float* cell, const float* dhout, int64_t ldo,
-                               int64_t dstride, const float* whh_b, int64_t N, int64_t T, int H,
-                               void* stream) {
-  if (!gates || !cell || !dhout || !whh_b) return TSSEP_E_NULL;
-  if (N <= 0 || T <= 0 || H <= 0 || dstride < H || ldo < dstride + H) return TSSEP_E_SHAPE;
+template <int ND>
+int launch_bwd(float* gates, const float* cell, const float* dhout, int64_t ldo, int64_t dstride,
+               const float* whh_b, int64_t N, int64_t T, int H, void* stream) {
   if (!aligned16(gates) || !aligned16(whh_b)) return TSSEP_E_ALIGN;
   const int NB = lstm_nb(H), NBB = lstm_nbb(H), KQ3 = lstm_kq3(H);
   if (NB > 8) return TSSEP_E_UNSUPPORTED;
-  dim3 grid((unsigned)((N + 7) / 8), 2);
+  dim3 grid((unsigned)((N + 7) / 8), ND);
   const size_t lds = (size_t)(4 * 8 * (4 * KQ3 + 12) + 4 * 8 * (NBB * 64 + 4)) * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
 #define L(NB_, NBB_)                                                                          \
-  hipLaunchKernelGGL((blstm_bwd_kernel<NB_, NBB_>), grid, dim3(256), lds, s, gates, cell,      \
+  hipLaunchKernelGGL((blstm_bwd_kernel<NB_, NBB_, ND>), grid, dim3(256), lds, s, gates, cell,  \
                      dhout, ldo, dstride, whh_b, N, T, H, KQ3)
   // NB = ceil(ceil(H/16)/4), NBB = ceil(H/64): NBB is NB or NB-... enumerate the reachable pairs
   if (NB == 1) L(1, 1);
@@ -460,4 +487,81 @@ extern "C" int tssep_blstm_bwd(float* gates, const float* cell, const float* dho
   else L(8, 8);
 #undef L
   return tssep_launch_status();
+}
+
+}  // namespace
+
+extern "C" int tssep_lstm_pack_sizes(int H, int I, int64_t ld_i, tssep_lstm_sizes* out) {
+  return pack_sizes(2, H, I, ld_i, out);
+}
+
+extern "C" int tssep_lstm_pack(const float* w_ih_f, const float* w_hh_f, const float* b_ih_f,
+                               const float* b_hh_f, const float* w_ih_r, const float* w_hh_r,
+                               const float* b_ih_r, const float* b_hh_r, int H, int I,
+                               int64_t ld_i, float* wih_p, float* bias_p, float* whh_f,
+                               float* whh_b, void* stream) {
+  if (!w_ih_f || !w_hh_f || !b_ih_f || !b_hh_f || !w_ih_r || !w_hh_r || !b_ih_r || !b_hh_r ||
+      !wih_p || !bias_p || !whh_f || !whh_b)
+    return TSSEP_E_NULL;
+  return launch_pack(2, w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r, H, I, ld_i,
+                     wih_p, bias_p, whh_f, whh_b, stream);
+}
+
+extern "C" int tssep_lstm_unpack(const float* src, int64_t ld, int nsplit, int64_t split_stride,
+                                 int H, int ncols, float* dst_f, float* dst_r, int accumulate,
+                                 void* stream) {
+  if (!src || !dst_f || !dst_r) return TSSEP_E_NULL;
+  return launch_unpack(2, src, ld, nsplit, split_stride, H, ncols, dst_f, dst_r, accumulate, stream);
+}
+
+extern "C" int tssep_blstm_fwd(float* gates, float* cell, float* hout, int64_t ldo,
+                               int64_t dstride, const float* whh_f, int64_t N, int64_t T, int H,
+                               void* stream) {
+  if (!gates || !cell || !hout || !whh_f) return TSSEP_E_NULL;
+  if (N <= 0 || T <= 0 || H <= 0 || dstride < H || ldo < dstride + H) return TSSEP_E_SHAPE;
+  return launch_fwd<2>(gates, cell, hout, ldo, dstride, whh_f, nullptr, nullptr, nullptr, nullptr,
+                       N, T, H, stream);
+}
+
+extern "C" int tssep_blstm_bwd(float* gates, const float* cell, const float* dhout, int64_t ldo,
+                               int64_t dstride, const float* whh_b, int64_t N, int64_t T, int H,
+                               void* stream) {
+  if (!gates || !cell || !dhout || !whh_b) return TSSEP_E_NULL;
+  if (N <= 0 || T <= 0 || H <= 0 || dstride < H || ldo < dstride + H) return TSSEP_E_SHAPE;
+  return launch_bwd<2>(gates, cell, dhout, ldo, dstride, whh_b, N, T, H, stream);
+}
+
+// ---- one direction of time (typ = 'lstm'): the same kernels with ND = 1 ----
+extern "C" int tssep_lstm1_pack_sizes(int H, int I, int64_t ld_i, tssep_lstm_sizes* out) {
+  return pack_sizes(1, H, I, ld_i, out);
+}
+
+extern "C" int tssep_lstm1_pack(const float* w_ih, const float* w_hh, const float* b_ih,
+                                const float* b_hh, int H, int I, int64_t ld_i, float* wih_p,
+                                float* bias_p, float* whh_f, float* whh_b, void* stream) {
+  if (!w_ih || !w_hh || !b_ih || !b_hh || !wih_p || !bias_p || !whh_f || !whh_b) return TSSEP_E_NULL;
+  return launch_pack(1, w_ih, w_hh, b_ih, b_hh, nullptr, nullptr, nullptr, nullptr, H, I, ld_i,
+                     wih_p, bias_p, whh_f, whh_b, stream);
+}
+
+extern "C" int tssep_lstm1_unpack(const float* src, int64_t ld, int nsplit, int64_t split_stride,
+                                  int H, int ncols, float* dst, int accumulate, void* stream) {
+  if (!src || !dst) return TSSEP_E_NULL;
+  return launch_unpack(1, src, ld, nsplit, split_stride, H, ncols, dst, nullptr, accumulate, stream);
+}
+
+extern "C" int tssep_lstm1_fwd(float* gates, float* cell, float* hout, int64_t ldo,
+                               const float* whh_f, const float* h0, const float* c0, float* hT,
+                               float* cT, int64_t N, int64_t T, int H, void* stream) {
+  if (!gates || !cell || !hout || !whh_f) return TSSEP_E_NULL;
+  if ((h0 == nullptr) != (c0 == nullptr)) return TSSEP_E_NULL;      // a state is both halves or neither
+  if (N <= 0 || T <= 0 || H <= 0 || ldo < H) return TSSEP_E_SHAPE;
+  return launch_fwd<1>(gates, cell, hout, ldo, 0, whh_f, h0, c0, hT, cT, N, T, H, stream);
+}
+
+extern "C" int tssep_lstm1_bwd(float* gates, const float* cell, const float* dhout, int64_t ldo,
+                               const float* whh_b, int64_t N, int64_t T, int H, void* stream) {
+  if (!gates || !cell || !dhout || !whh_b) return TSSEP_E_NULL;
+  if (N <= 0 || T <= 0 || H <= 0 || ldo < H) return TSSEP_E_SHAPE;
+  return launch_bwd<1>(gates, cell, dhout, ldo, 0, whh_b, N, T, H, stream);
 }

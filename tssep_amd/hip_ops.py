@@ -713,6 +713,48 @@ def lstm_pack(params, H, I):
     return dict(wih_p=wih_p, bias_p=bias_p, whh_f=whh_f, whh_b=whh_b, ld_i=ld_i, _keep=(buf, ps))
 
 
+# ---- one direction of time (typ = 'lstm'): the streaming kernels instantiated for one direction, with a state
+def lstm1_pack(params, H, I):
+    """params: 4 tensors (w_ih, w_hh, b_ih, b_hh), torch layout -> the [dir = 0] half of lstm_pack's layouts."""
+    L = _lib.lib()
+    ld_i = round_up(I, 4)
+    sz = LstmSizes()
+    check(L.tssep_lstm1_pack_sizes(H, I, ld_i, ctypes.byref(sz)), "lstm1_pack_sizes")
+    buf = torch.empty(sz.wih_p + round_up(sz.bias_p, 4) + sz.whh_f + sz.whh_b, device=params[0].device,
+                      dtype=torch.float32)
+    o1 = sz.wih_p
+    o2 = o1 + round_up(sz.bias_p, 4)
+    o3 = o2 + sz.whh_f
+    wih_p, bias_p, whh_f, whh_b = buf[:o1], buf[o1:o1 + sz.bias_p], buf[o2:o3], buf[o3:]
+    ps = [_f32(p.detach()).contiguous() for p in params]
+    check(L.tssep_lstm1_pack(*[_p(p) for p in ps], H, I, ld_i, _p(wih_p), _p(bias_p), _p(whh_f), _p(whh_b),
+                             _stream()), "lstm1_pack")
+    return dict(wih_p=wih_p, bias_p=bias_p, whh_f=whh_f, whh_b=whh_b, ld_i=ld_i, _keep=(buf, ps))
+
+
+def lstm1_fwd(gates, cell, hout, ldo, whh_f, N, T, H, h0=None, c0=None, hT=None, cT=None):
+    """gates [N,T,H,4] pre-activations -> activated gates; cell [N,T,H]; hout [N,T,ldo] columns 0..H-1.  h0 / c0 [N,H]:
+    the initial state (both or neither; None = zeros); hT / cT [N,H]: receive the state after the last frame."""
+    for s in (h0, c0, hT, cT):
+        assert s is None or (s.is_contiguous() and tuple(s.shape) == (N, H) and _f32(s) is s), (N, H)
+    _log_recurrence("stream1_f32", "fwd", N, T, H)
+    with _timed("lstm1_fwd", 2 * N * T * 4 * H * H, 0):
+        check(_lib.lib().tssep_lstm1_fwd(_p(gates), _p(cell), _p(hout), ldo, _p(whh_f), _p(h0), _p(c0), _p(hT), _p(cT),
+                                         N, T, H, _stream()), "lstm1_fwd")
+
+
+def lstm1_bwd(gates, cell, dhout, ldo, whh_b, N, T, H):
+    """dhout [N,T,ldo] -> `gates` is overwritten with d(pre-activation); zero initial state."""
+    _log_recurrence("stream1_f32", "bwd", N, T, H)
+    with _timed("lstm1_bwd", 2 * N * T * 4 * H * H, 0):
+        check(_lib.lib().tssep_lstm1_bwd(_p(gates), _p(cell), _p(dhout), ldo, _p(whh_b), N, T, H, _stream()), "lstm1_bwd")
+
+
+def lstm1_unpack(src, ld, nsplit, split_stride, H, ncols, dst, accumulate=False):
+    check(_lib.lib().tssep_lstm1_unpack(_p(src), ld, nsplit, split_stride, H, ncols, _p(dst), int(accumulate),
+                                        _stream()), "lstm1_unpack")
+
+
 _ERR = {}
 
 

@@ -67,6 +67,14 @@ def _stack_aux(aux):
     return aux
 
 
+def _aux_ndim(aux):
+    """dimensions of what _stack_aux would return, without building it"""
+    n = 0
+    while isinstance(aux, (tuple, list)):
+        aux, n = aux[0], n + 1
+    return n + aux.dim()
+
+
 class Linear(Configurable, torch.nn.Module):           # net.py:19-43: how i-vectors enter a `mul` model
     def __init__(self, idim, odim, bias=True):
         super().__init__()
@@ -134,6 +142,17 @@ class Output:                      # net.py:240-247
     vad_logit: torch.Tensor = None
 
 
+@dataclasses.dataclass
+class ChunkState:
+    """What MaskEstimator_v2.forward_chunk carries from one chunk to the next (opaque to its callers)."""
+    layers: list             # per recurrent layer, pre-net first: (h, c), each [1, N, units]
+    perm: torch.Tensor       # speaker permutation and its inverse, device int32 [B, K] (None: speakers in their order)
+    iperm: torch.Tensor
+    embedding: torch.Tensor  # [B, K, E], as the conditioning reads it
+    K: int
+    frames: int              # consumed so far
+
+
 class Sequential(torch.nn.Sequential):        # net.py:190-237 (container role only)
     pass
 
@@ -169,8 +188,11 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
                  pre_net="RNNP", aux_net=None, aux_net_output_size=None, combination: str = "cat",
                  ts_vad=False, output_resolution: str = "tf", random_speaker_order=True,
                  num_averaged_permutations=1, input_normalizer=None, aux_normalizer=None,
-                 explicit_vad=False, aux_stride=1):
+                 explicit_vad=False, aux_stride=1, rnn_typ="blstm"):
         super().__init__()
+        if rnn_typ not in ("blstm", "lstm"):
+            raise ValueError(f"rnn_typ={rnn_typ!r}: 'blstm' | 'lstm'")
+        self.rnn_typ = rnn_typ                    # this project's keyword: 'lstm' = every recurrent layer causal (forward_chunk)
         if not isinstance(aux_stride, int) or isinstance(aux_stride, bool) or aux_stride < 1:
             raise ValueError(f"aux_stride={aux_stride!r}: a positive number of frames per row of a frame-wise embedding")
         self.aux_stride = aux_stride              # this project's keyword (frame-wise embeddings at their own frame rate)
@@ -201,7 +223,7 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
             assert self.num_averaged_permutations == 1, (self.ts_vad, self.num_averaged_permutations)
         if pre_net == "RNNP":
             self.pre_net = RNNP_packed(idim=idim, elayers=1, cdim=units, hdim=odim, dropout=dropout,
-                                       typ="blstm")
+                                       typ=rnn_typ)
         elif pre_net in [None, False]:
             raise NotImplementedError("pre_net=None (every shipped config uses 'RNNP')")
         else:
@@ -239,7 +261,7 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
                 put("rearrange", _Marker("... spk time feature -> ... 1 time (spk feature)"))
                 ts_factor = ts_vad
             put("birnn", RNNP_packed(idim=(first_birnn_idim if l == 0 else projs) * ts_factor,
-                                     elayers=1, cdim=units, hdim=projs, dropout=dropout, typ="blstm"))
+                                     elayers=1, cdim=units, hdim=projs, dropout=dropout, typ=rnn_typ))
             if l < layers - 1:
                 put("dropout", torch.nn.Dropout(p=dropout))
                 put("activation", torch.nn.Tanh())
@@ -301,8 +323,12 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         if xs.dim() == 2:
             return tuple(r[0] for r in self.logits(xs[None], [aux]))
         assert xs.dim() == 3, xs.shape
-        B, T = xs.shape[0], xs.shape[1]
-        dev = xs.device
+        aux, perm_d, iperm_d, K = self._embedding(aux, xs.shape[0], xs.shape[1], xs.device)
+        return self._trunk(xs, aux, perm_d, iperm_d, K)
+
+    def _embedding(self, aux, B, T, dev):
+        """aux as the caller gave it -> (the embedding the conditioning reads, [B,K,E] or frame-wise [B,K,Ta,E]; perm,
+        iperm device int32 [B,K] or None; K): the speaker permutation (net.py:823-831), aux_net / aux_normalizer."""
         ragged = isinstance(self.aux_net, AuxNet)       # enrolment sequences [T_i, idim]: lists, shuffled on the host
         if ragged:
             aux = [list(a) for a in aux]
@@ -332,20 +358,31 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
                 idx = perm_d.long().reshape(B, K, *([1] * (aux.dim() - 2))).expand(-1, -1, *aux.shape[2:])
                 aux = torch.gather(aux, 1, idx)
         if self.aux_net is not None:                    # net.py:833-838
-            aux = self.aux_net(aux, xs, batched=True)
+            aux = self.aux_net(aux, None, batched=True)
         else:
             aux = aux.to(torch.float32)
             if self.aux_normalizer is not None:         # net.py:852-853
                 aux = self.aux_normalizer(aux)
+        return aux.contiguous(), perm_d, iperm_d, K
+
+    def _trunk(self, xs, aux, perm_d, iperm_d, K, prev=None, states=None):
+        """xs [B,T,idim] and what _embedding returned -> `logits`' result.  prev / states: the per-layer (h, c) lists of
+        RNNP_packed.forward_rows, pre-net first (forward_chunk; without gradients)."""
+        B, T = xs.shape[0], xs.shape[1]
         framewise = aux.dim() == 4
-        aux = aux.contiguous()
+        carry = prev is not None or states is not None
+
+        def st(i):      # keywords of layer i's forward_rows: its own slice of the state lists
+            if not carry:
+                return {}
+            return dict(prev_state=None if prev is None else prev[i:i + 1], states=states)
         if self.input_normalizer is not None:           # net.py:858-859
             xs = self.input_normalizer(xs)
         if self.ts_vad is not False:
             assert K == self.ts_vad, (K, self.ts_vad)
         trials = self.num_averaged_permutations
         F = self.odim + int(self.explicit_vad)         # the head's columns per speaker
-        pre = self.pre_net.forward_rows(xs.reshape(B * T, xs.shape[-1]), B, T)       # [B*T, odim]
+        pre = self.pre_net.forward_rows(xs.reshape(B * T, xs.shape[-1]), B, T, **st(0))       # [B*T, odim]
         h = Fn.condition(pre, aux, B, K, T, trials, self.combination, self.aux_stride)     # rows (b,tr,k,t)
         nb = len(self._birnns)
         # the Tanh between two post-net modules runs forward in the producer's projection store and backward in
@@ -358,12 +395,12 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
             site = None if last else dropouts[l]
             fold = (not last) and birnn.hdim % 4 == 0 and Fn.H.FOLD_TANH and not birnn.site_p(site)
             if last and self.ts_vad is not False:
-                h = birnn.forward_rows(h, B * trials, T, in_tanh=prev_tanh)        # combined input
+                h = birnn.forward_rows(h, B * trials, T, in_tanh=prev_tanh, **st(l + 1))        # combined input
             else:
                 nxt_combined = (l == nb - 2) and self.ts_vad is not False
                 h = birnn.forward_rows(h, B * trials * K, T, final_act=0 if last else 1,
                                        combine=K if nxt_combined else 0, in_tanh=prev_tanh, next_folds=fold,
-                                       final_dropout=site)
+                                       final_dropout=site, **st(l + 1))
                 prev_tanh = (K if nxt_combined else 1) if fold else 0
         Fr = F if self.output_resolution == "tf" else 1
         if self.nmask > 1:
@@ -375,10 +412,46 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         return logit, aux if framewise else aux.unsqueeze(-2)
 
     def forward(self, xs, aux=None) -> Output:
+        return self._output(self.logits(xs, aux))
+
+    def forward_chunk(self, xs, aux, state=None):
+        """Online inference of a causal model (rnn_typ='lstm'), without gradients: xs [B, Tc, idim] or [Tc, idim] are the
+        NEXT Tc >= 1 feature frames of the utterance(s), `state` what the previous call returned (None: the utterance
+        starts here) -> (Output for exactly these frames, the new state).  The state is opaque: the (h, c) of every
+        recurrent layer, the speaker permutation (drawn ONCE, at the first chunk, when random_speaker_order) and the
+        embedding (computed ONCE, aux_net / aux_normalizer included; `aux` is not read again), and the frames consumed.
+        Chunks of any lengths give what `forward` gives on their concatenation within the layers' error bounds: the
+        recurrence continues from the very bits it stopped at; a GEMM over another number of rows may round differently."""
+        if self.rnn_typ != "lstm":
+            raise ValueError(f"forward_chunk needs rnn_typ='lstm': {self.rnn_typ!r} reads the future of every frame")
+        if self.input_normalizer is not None:
+            raise NotImplementedError("forward_chunk with input_normalizer: its statistics span the utterance")
+        unbatched = xs.dim() == 2
+        if unbatched:
+            xs, aux = xs[None], ([aux] if state is None else aux)
+        if xs.dim() != 3 or xs.shape[1] < 1:
+            raise ValueError(f"xs {tuple(xs.shape)}: [B, Tc, idim] or [Tc, idim] with Tc >= 1")
+        B, T = xs.shape[0], xs.shape[1]
+        with torch.no_grad():
+            if state is None:
+                if not isinstance(self.aux_net, AuxNet) and _aux_ndim(aux) == 4:
+                    raise NotImplementedError("forward_chunk with a frame-wise aux [B, K, Ta, E]: an embedding per frame "
+                                              "would have to arrive with the frames (not built)")
+                emb, perm_d, iperm_d, K = self._embedding(aux, B, T, xs.device)
+                state = ChunkState(layers=None, perm=perm_d, iperm=iperm_d, embedding=emb, K=K, frames=0)
+            elif not isinstance(state, ChunkState):
+                raise TypeError(f"state: what forward_chunk returned, not {type(state).__name__}")
+            layers = []
+            res = self._trunk(xs, state.embedding, state.perm, state.iperm, state.K, prev=state.layers, states=layers)
+            out = self._output(tuple(r[0] for r in res) if unbatched else res)
+        return out, ChunkState(layers=layers, perm=state.perm, iperm=state.iperm, embedding=state.embedding, K=state.K,
+                               frames=state.frames + T)
+
+    def _output(self, res) -> Output:
         if self.nmask > 1:                         # [..., K, M, T, F] as they are (net.py:631-659, 983)
-            logit, mask, emb = self.logits(xs, aux)
+            logit, mask, emb = res
             return Output(mask=mask, logit=logit, embedding=emb)
-        logit, emb = self.logits(xs, aux)
+        logit, emb = res
         u = -3
         if self.explicit_vad:                      # net.py:969-979
             lg = logit if logit.dim() == 4 else logit[None]
