@@ -1,4 +1,4 @@
-"""The causal RNNP layer (typ='lstm': an LSTM in ONE direction of time + projection (+ Tanh), functional._RNNP1) in plain
+"""The causal RNNP layer (typ='lstm': an LSTM in ONE direction of time + projection (+ Tanh), functional._RNNP at D = 1) in plain
 torch, tested without a GPU; tests/test_gpu_causal_layer.py and tests/test_gpu_causal_estimator.py import it.
 
 The restatement.  No new formulas: a one-direction layer IS the two-direction restatement of

@@ -1,4 +1,4 @@
-"""functional.rnnp_layer on ONE-direction containers (typ='lstm': functional._RNNP1, the sibling of _RNNP) on a real MI355X
+"""functional.rnnp_layer on ONE-direction containers (typ='lstm': functional._RNNP over one direction of time) on a real MI355X
 against the float64 restatement of tests/test_causal_reference.py -- the two-direction restatement with the reverse half of
 the projection zeroed.  Measure and bound are tests/test_rnnp_layer_reference.py's (`assert_within`): per tensor the
 normwise and the element-wise error against float64, each within MARGIN x the same figure of the fp32 restatement of the

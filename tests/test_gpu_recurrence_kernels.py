@@ -414,6 +414,44 @@ def test_through_the_plan(N, T, H, settings):
         assert plan["bwd"] == ("onchip32_bf16x3", 0) and plan["fwd"][0] == "onchip16_bf16x3"
 
 
+def test_through_the_plan_in_one_direction():
+    """directions=1 (typ='lstm'): plan -> packs -> launch is the one-direction streaming kernel with its state, and leaves
+    the bits of the by-name wrappers lstm1_fwd / lstm1_bwd on copies of the same buffers"""
+    N, T, H = 6, 5, 5
+    ld = Hop.round_up(H, 4)
+    gen = torch.Generator().manual_seed(12)
+    whh = ((torch.rand(4 * H, H, generator=gen) * 2 - 1) * H ** -0.5).to(DEV)
+    gates0, dh0 = torch.randn(N * T, 4 * H, generator=gen).to(DEV), torch.randn(N * T, ld, generator=gen).to(DEV)
+    h0, c0 = (0.5 * torch.randn(N, H, generator=gen).to(DEV) for _ in range(2))
+    pk = Hop.lstm1_pack([torch.zeros(4 * H, 4, device=DEV), whh, torch.zeros(4 * H, device=DEV), torch.zeros(4 * H, device=DEV)], H, 4)
+    plan = Hop.recurrence_plan(N, T, H, Hop.n_cus(torch.device("cuda", 0)), directions=1)
+    assert plan == {"fwd": ("stream1_f32", 0), "bwd": ("stream1_f32", 0)}
+    whh_of = Hop.recurrence_packs(plan, whh, whh, H, pk)
+    assert whh_of["fwd"] is pk["whh_f"] and whh_of["bwd"] is pk["whh_b"]
+
+    def run(fwd, bwd):
+        g, cell, hout, dh = gates0.clone(), torch.zeros(N, T, H, device=DEV), torch.zeros(N * T, ld, device=DEV), dh0.clone()
+        hT, cT = (torch.zeros(N, H, device=DEV) for _ in range(2))
+        fwd(g, cell, hout, (h0, c0, hT, cT))
+        act = g.clone()
+        bwd(g, cell, dh)
+        torch.cuda.synchronize()
+        return dict(act=act, cell=cell, hout=hout, hT=hT, cT=cT, dgates=g)
+
+    log = Hop.RECURRENCE_LOG = []
+    try:
+        got = run(lambda g, c, h, st: Hop.recurrence_launch(plan["fwd"], "fwd", g, c, h, ld, ld, whh_of["fwd"], N, T, H, state=st),
+                  lambda g, c, dh: Hop.recurrence_launch(plan["bwd"], "bwd", g, c, dh, ld, ld, whh_of["bwd"], N, T, H))
+    finally:
+        Hop.RECURRENCE_LOG = None
+    want = run(lambda g, c, h, st: Hop.lstm1_fwd(g, c, h, ld, pk["whh_f"], N, T, H, *st),
+               lambda g, c, dh: Hop.lstm1_bwd(g, c, dh, ld, pk["whh_b"], N, T, H))
+    assert [(e["kernel"], e["direction"], e["groups"]) for e in log] == [("stream1_f32", "fwd", 0), ("stream1_f32", "bwd", 0)], log
+    for k in got:
+        assert bool(torch.isfinite(got[k]).all()) and torch.equal(got[k], want[k]), k
+    assert float(got["hT"].abs().max()) > 0 and float(got["dgates"].abs().max()) > 0      # (the launches wrote)
+
+
 def test_zz_report():
     """the largest error / bound of every family, direction and output this run saw (pytest -rP)"""
     for (fam, direction, name), v in sorted(WORST.items()):

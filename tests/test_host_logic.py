@@ -1,6 +1,7 @@
 """Host-side logic that needs no GPU: kernel selection policy, split-K choice, workspace sizes,
 argument validation of the C ABI (status codes instead of launches)."""
 import ctypes
+import warnings
 
 import numpy as np
 import pytest
@@ -78,6 +79,18 @@ def test_recurrence_plan():
         assert plan(8, 256) == dict(fwd=(O16, 1), bwd=(O32, 0))
         assert plan(40, 260) == dict(fwd=(O16, 1), bwd=(O16, 1))
         assert plan(8, 130) == dict(fwd=(O32, 0), bwd=(O32, 0))
+        # one direction of time (typ = 'lstm'): the one-direction streaming kernel both ways, whatever the policy says and
+        # however long the sequence -- there is no other, so nothing is announced
+        STREAM1 = dict(fwd=("stream1_f32", 0), bwd=("stream1_f32", 0))
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            H._WARNED.clear()
+            for N, Hh, T in ((8, 300, 253), (768, 300, 253), (64, 12, 5), (32, 300, 20000)):
+                assert H.recurrence_plan(N, T, Hh, 256, directions=1) == STREAM1, (N, Hh, T)
+                for policy in ("cluster", "onchip", "stream"):
+                    with runtime.applied(recurrence=policy):
+                        assert H.recurrence_plan(N, T, Hh, 256, directions=1) == STREAM1, (N, Hh, T, policy)
+        assert H.recurrence_plan(8, 253, 300, 256, directions=2) == plan(8, 300)
         # small or unsupported hidden sizes fall back to the streaming kernels
         assert plan(64, 12)["fwd"] == STREAM
         assert plan(64, 512)["fwd"] == STREAM

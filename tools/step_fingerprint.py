@@ -17,7 +17,8 @@ what its predecessor in the process left there, and must not pass for reproducib
 written when all runs agree, otherwise the case goes to "unstable" with the digests seen.  Cases A - C run fixed-order, atomic-free kernels: one of
 them under "unstable" is a finding (exit status 1), not something to commit.
 tests/test_gpu_step_fingerprint.py re-runs the cases against the committed file; a change that moves launches or kernels
-on purpose records again with this tool.
+on purpose records again with this tool.  --cases PREFIX[,PREFIX...] records the chosen cases only and leaves the other
+entries of an existing file as they are (new cases beside a record that must not move).
 
 The parent's Python beside the library of this tree: put the parent's `tssep_amd/` (and `include/`) first on PYTHONPATH
 and name the library in TSSEP_HIP_LIB -- this file only appends its own tree to sys.path."""
@@ -95,8 +96,22 @@ def _bucket(params, sinks):
 
 
 # ---- A: one RNNP layer ---------------------------------------------------------------------------------------------------
-def rnnp(shape, act, prec, sinks, frozen=None, x_grad=True, dropout_p=0.0):
-    from test_rnnp_layer_reference import NAMES, SHAPES, make_case, module_params, modules
+Builders = collections.namedtuple("Builders", "NAMES SHAPES make_case make_params modules module_params")
+
+
+def builders(causal):
+    """the case builders of the two-direction layer (tests/test_rnnp_layer_reference.py) or of the causal one
+    (tests/test_causal_reference.py: the first four of its LAYER_SHAPES, by name)"""
+    if causal:
+        import test_causal_reference as R
+        shapes = dict(zip(("pad", "pad_combined", "align", "w32"), R.LAYER_SHAPES))
+        return Builders(R.CNAMES, shapes, R.make_causal_case, R.make_causal_params, R.causal_modules, R.causal_module_params)
+    import test_rnnp_layer_reference as R
+    return Builders(R.NAMES, R.SHAPES, R.make_case, R.make_params, R.modules, R.module_params)
+
+
+def rnnp(shape, act, prec, sinks, frozen=None, x_grad=True, dropout_p=0.0, causal=False):
+    NAMES, SHAPES, make_case, _, modules, module_params = builders(causal)
     N, T, I, Hh, hdim, combine = SHAPES[shape]
     x, params, dy = make_case(N, T, I, Hh, hdim, 0, combine)
     lstm, lin = modules(params, device=DEV)
@@ -116,9 +131,9 @@ def rnnp(shape, act, prec, sinks, frozen=None, x_grad=True, dropout_p=0.0):
     return dict(_grads(NAMES, ps), y=y.detach(), x=xg.grad)
 
 
-def chain(K):
+def chain(K, causal=False):
     """two stacked layers with the Tanh backward folded into the consumer's d(input) GEMM (K: the producer combines)"""
-    from test_rnnp_layer_reference import NAMES, make_params, module_params, modules
+    NAMES, _, _, make_params, modules, module_params = builders(causal)
     N, T, I, Hh, hdim = 8, 5, 7, 5, 8
     Kc = K or 1
     gen = torch.Generator().manual_seed(77)
@@ -134,6 +149,26 @@ def chain(K):
     out = {"0." + k: v for k, v in _grads(NAMES, module_params(l0, q0)).items()}
     out.update({"1." + k: v for k, v in _grads(NAMES, module_params(l1, q1)).items()})
     return dict(out, y=y.detach(), h=h.detach(), x=xg.grad)
+
+
+def state(shape, chunks, act):
+    """The causal layer without gradients: the whole utterance with return_state, then the same frames in `chunks`, each
+    started from the previous chunk's (hT, cT)."""
+    _, SHAPES, make_case, _, modules, _ = builders(True)
+    N, T, I, Hh, hdim, combine = SHAPES[shape]
+    x, params, _ = make_case(N, T, I, Hh, hdim, 0, combine)
+    lstm, lin = modules(params, device=DEV)
+    x3 = x.to(DEV).view(N, T, I)
+    with torch.no_grad():
+        y, (hT, cT) = Fn.rnnp_layer(x3.reshape(N * T, I), lstm, lin, N, T, act=act, combine=combine, return_state=True)
+        ys, last, t0 = [], None, 0
+        for n in chunks:
+            yc, last = Fn.rnnp_layer(x3[:, t0:t0 + n].reshape(N * n, I), lstm, lin, N, n, act=act, combine=combine,
+                                     state=last, return_state=True)
+            ys.append(yc.reshape(N // (combine or 1), n, -1))
+            t0 += n
+    assert t0 == T, (chunks, T)
+    return dict(y=y, hT=hT, cT=cT, y_chunks=torch.cat(ys, 1), hT_chunks=last[0], cT_chunks=last[1])
 
 
 # ---- B: the final Linear ---------------------------------------------------------------------------------------------------
@@ -275,6 +310,19 @@ def _cases():
     c["A/two_layers/K0"] = (chain, (0,))
     c["A/two_layers/K4"] = (chain, (4,))
     c["A/align/act1/bf16x3/dropout"] = (rnnp, ("align", 1, "bf16x3", False, None, True, 0.5))
+    for shape in ("pad", "pad_combined", "align", "w32"):
+        for act in (0, 1) if shape != "w32" else (1,):
+            for prec in ("f32", "bf16x3") if shape != "w32" else ("bf16x3",):
+                for sinks in (False, True):
+                    c[f"A/causal/{shape}/act{act}/{prec}/{'sinks' if sinks else 'autograd'}"] = (
+                        rnnp, (shape, act, prec, sinks, None, True, 0.0, True))
+    c["A/causal/pad/act1/bf16x3/frozen"] = (rnnp, ("pad", 1, "bf16x3", True, "bias_hh_l0", True, 0.0, True))
+    c["A/causal/pad/act1/bf16x3/no_dx"] = (rnnp, ("pad", 1, "bf16x3", False, None, False, 0.0, True))
+    c["A/causal/align/act1/bf16x3/dropout"] = (rnnp, ("align", 1, "bf16x3", False, None, True, 0.5, True))
+    c["A/causal/two_layers/K0"] = (chain, (0, True))
+    c["A/causal/two_layers/K4"] = (chain, (4, True))
+    c["A/causal/state/plain"] = (state, ("align", [5, 1, 1], 0))
+    c["A/causal/state/combined"] = (state, ("pad_combined", [3, 1, 1], 1))
     for sinks in (False, True):
         tag = "sinks" if sinks else "autograd"
         c[f"B/head_fast/{tag}"] = (head, (False, 1, sinks))
@@ -283,7 +331,7 @@ def _cases():
         c[f"C/affine_bias/{tag}"] = (affine, (True, sinks))
         c[f"C/affine_nobias/{tag}"] = (affine, (False, sinks))
         c[f"C/aux_mlp/{tag}"] = (aux_mlp, (sinks,))
-    for overlay in (None, "explicit_vad", "auxnet", "two_mask", "dropout", "pit"):
+    for overlay in (None, "explicit_vad", "auxnet", "two_mask", "dropout", "pit", "causal"):
         for graph in ("off", "on"):
             c[f"D/{overlay or 'plain'}/{'graph' if graph == 'on' else 'eager'}"] = (
                 toy, (f"toy_tssep_{overlay}.yaml" if overlay else None, graph))
@@ -322,6 +370,10 @@ def main():
     args = ap.parse_args()
     pick = [p for p in args.cases.split(",") if p]
     out, unstable, moved = {}, {}, []
+    if pick and os.path.exists(args.record):      # chosen cases only: the file's other entries stay as they are
+        with open(args.record) as f:
+            old = json.load(f)
+        out, unstable = old["cases"], old["unstable"]
     names = [n for n in CASES if not pick or any(n.startswith(p) for p in pick)]
     seen = {n: [] for n in names}                      # name -> [(trace, tensor hashes)]
     for name in names:
@@ -340,6 +392,7 @@ def main():
             continue
         if all(h == h1 for h in hs):
             out[name] = dict(fp1, tensors=h1)
+            unstable.pop(name, None)
         else:
             out[name] = fp1
             unstable[name] = sorted({hashlib.sha256(json.dumps(h).encode()).hexdigest() for h in hs})

@@ -114,113 +114,145 @@ def _linear_wgrads(dv, ld_d, xv, ld_x, Nout, P, R, sinks, fused, bias=True):
 
 
 # ---- derived weight layouts: ONE builder per tag (hip_ops.derived keeps the first it sees and prepare_derived replays it;
-# a build reads the parameters, never a step's tensors)
+# a build reads the parameters, never a step's tensors).  D directions of time -- 2: BLSTM, 1: typ = 'lstm', the causal
+# route -- are 4 D LSTM tensors and D column blocks of the projection; memo and builder live on the parameter object, and a
+# parameter belongs to one LSTM, so both kinds share the tags.
 def _lstm_pack_of(lstm_params, Hh, I):
     lstm_params = list(lstm_params)
-    return H.derived("lstm_pack", lstm_params, lambda: H.lstm_pack(lstm_params, Hh, I))
+    # (the library has an entry point per direction count; looked up when the build runs)
+    return H.derived("lstm_pack", lstm_params,
+                     lambda: (H.lstm1_pack if len(lstm_params) == 4 else H.lstm_pack)(lstm_params, Hh, I))
 
 
 def _proj_layout_of(w_proj, Hh, Hp):
-    """projection weight in the (possibly padded) [hdim, 2*Hp] column layout of hout"""
+    """projection weight [hdim, D*Hh] in the (possibly padded) [hdim, D*Hp] column layout of hout"""
     def build():
         w = w_proj.detach()
         if Hp == Hh and w.is_contiguous() and w.data_ptr() % 16 == 0:
             return w
-        out = torch.zeros(w.shape[0], 2 * Hp, device=w.device, dtype=torch.float32)
-        out[:, :Hh] = w[:, :Hh]
-        out[:, Hp:Hp + Hh] = w[:, Hh:]
+        D = w.shape[1] // Hh
+        out = torch.zeros(w.shape[0], D * Hp, device=w.device, dtype=torch.float32)
+        for d in range(D):
+            out[:, d * Hp:d * Hp + Hh] = w[:, d * Hh:(d + 1) * Hh]
         return out
     return H.derived("proj_layout", [w_proj], build)
 
 
 def _proj_T_of(w_proj, Hh, Hp):
-    return H.derived("proj_T", [w_proj], lambda: H.transposed(_proj_layout_of(w_proj, Hh, Hp), w_proj.shape[0], 2 * Hp))
+    return H.derived("proj_T", [w_proj], lambda: H.transposed(_proj_layout_of(w_proj, Hh, Hp), w_proj.shape[0],
+                                                              w_proj.shape[1] // Hh * Hp))
 
 
 def _wih_T_of(lstm_params, Hh, I):
+    G = len(lstm_params) * Hh      # 4 D Hh gate rows
+
     def build():
         pk = _lstm_pack_of(lstm_params, Hh, I)
-        return H.transposed(pk["wih_p"].view(8 * Hh, pk["ld_i"]), 8 * Hh, I)
-    return H.derived("wih_T", [lstm_params[0], lstm_params[4]], build)
+        return H.transposed(pk["wih_p"].view(G, pk["ld_i"]), G, I)
+    return H.derived("wih_T", list(lstm_params[0::4]), build)
 
 
 # ------------------------------------------------------------------------------ RNNP
-_RNNPMeta = collections.namedtuple("_RNNPMeta", "N T I Hh Hp hdim ld_x ld_y act combine")
+_RNNPMeta = collections.namedtuple("_RNNPMeta", "N T I D Hh Hp hdim ld_x ld_y act combine")
+
+
+def _rnnp_forward(x, lstm_params, w_proj, b_proj, N, T, act, combine, dropout_p, state=None, want_state=False):
+    """The forward stages of one layer over D = len(lstm_params) // 4 directions of time: input GEMM with bias into gates
+    [R, 4 D Hh], the recurrence (D = 1: from `state` = (h0, c0) [N, Hh] when given), the projection [hdim, D Hh] with
+    act / combine / the dropout site.  Run inside _RNNP, and as they are under no_grad with a carried state (rnnp_layer).
+    -> (y, saved tensors, (drop, used), meta, the backward's (plan, W_hh layout), (hT, cT) or None)"""
+    D = len(lstm_params) // 4
+    w_ih, w_hh = lstm_params[0], lstm_params[1::4]
+    dev = x.device
+    Hh, I, hdim = w_hh[0].shape[1], w_ih.shape[1], w_proj.shape[0]
+    assert w_proj.shape[1] == D * Hh, (tuple(w_proj.shape), D, Hh)
+    xv, ld_x = H.rows_view(x)
+    R, G = N * T, 4 * D * Hh
+    assert xv.shape[0] == R and xv.shape[1] >= I, (xv.shape, R, I)
+    pk = _lstm_pack_of(lstm_params, Hh, I)
+    gates = torch.empty(R, G, device=dev, dtype=torch.float32)
+    H.gemm(xv, ld_x, pk["wih_p"], pk["ld_i"], gates, G, R, G, I, bias=pk["bias_p"])
+    Hp = H.round_up(Hh, 4)
+    cell = torch.empty(N, T, D, Hh, device=dev, dtype=torch.float32)
+    hout = (torch.zeros if Hp != Hh else torch.empty)(R, D * Hp, device=dev, dtype=torch.float32)
+    h0 = c0 = hT = cT = None
+    if state is not None:
+        h0, c0 = (H._f32(s).reshape(N, Hh).contiguous() for s in state)
+    if want_state:
+        hT, cT = (torch.empty(N, Hh, device=dev, dtype=torch.float32) for _ in range(2))
+    # the plan and BOTH directions' W_hh layouts are fetched here, once: the backward launches from what ctx keeps (a
+    # step captured without prepare_derived builds a layout at every ask)
+    plan = H.recurrence_plan(N, T, Hh, H.n_cus(dev), directions=D)
+    whh = H.recurrence_packs(plan, w_hh[0], w_hh[-1], Hh, pk, memo=True)
+    H.recurrence_launch(plan["fwd"], "fwd", gates, cell, hout, D * Hp, Hp, whh["fwd"], N, T, Hh, state=(h0, c0, hT, cT))
+    wp = _proj_layout_of(w_proj, Hh, Hp)
+    drop = float(dropout_p) if dropout_p else 0.0
+    store_act = 0 if drop else act
+    if combine:
+        K = combine
+        y = torch.empty(N // K * T, K * hdim, device=dev, dtype=torch.float32)
+        H.gemm(hout, D * Hp, wp, D * Hp, y, 0, R, hdim, D * Hp, bias=b_proj.detach(), act=store_act,
+               remap=dict(T=T, K=K, sb=T * K * hdim, sk=hdim, st=K * hdim))
+        ld_y = K * hdim
+    else:
+        y, ld_y = H.padded(R, hdim, dev, zero=True)
+        H.gemm(hout, D * Hp, wp, D * Hp, y, ld_y, R, hdim, D * Hp, bias=b_proj.detach(), act=store_act)
+    used = None
+    if drop:
+        used = H.dropout_draw(dev)
+        H.dropout_tanh_fwd(y, y, R, hdim, ld_y, combine if combine else 1, T, bool(combine), drop, used)
+    meta = _RNNPMeta(N, T, I, D, Hh, Hp, hdim, ld_x, ld_y, act, combine)
+    return (y, (xv, gates, cell, hout, y, wp), (drop, used), meta, (plan["bwd"], whh["bwd"]),
+            (hT, cT) if want_state else None)
 
 
 class _RNNP(torch.autograd.Function):
-    """One RNNP_packed layer (tssep/train/rnnp.py:88-96,146-168): BLSTM + Linear (+ tanh).
+    """One RNNP_packed layer (tssep/train/rnnp.py:80-96,146-168): LSTM in both directions of time (BLSTM), or in ONE
+    (typ='lstm') + Linear (+ tanh).  params: the 4 D LSTM tensors (w_ih, w_hh, b_ih, b_hh forward, then reverse), w_proj
+    [hdim, D Hh], b_proj.
 
     x: [R, ld_x] buffer view, rows (n, t) for N sequences of T frames, I valid columns.
     Output: [R, hdim] rows (padded leading dimension), or the speaker-combined layout
     [B, T, K*hdim] when ``combine=K`` (net.py:608-611 fused into the projection's store).
     ``dropout_p`` > 0: the Tanh behind this layer is an ACTIVE dropout site (rnnp.py:98-100, net.py:623-625) -- the
     projection stores plainly (act = 0) and one pass over y applies mask, 1 / (1 - p) and Tanh in place; the backward
-    regenerates the mask from the {seed, draw} pair the forward drew (hip_ops.dropout_draw)."""
+    regenerates the mask from the {seed, draw} pair the forward drew (hip_ops.dropout_draw).
+    ``want_state`` (D = 1): the state after the last frame leaves as two more outputs.  Zero initial state: a carried state
+    exists without gradients only (rnnp_layer)."""
 
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, w_proj, b_proj,
-                N, T, act, combine, in_tanh=0, in_link=None, out_link=None, dropout_p=0.0):
-        dev = x.device
-        Hh, I, hdim = w_hh.shape[1], w_ih.shape[1], w_proj.shape[0]
-        xv, ld_x = H.rows_view(x)
-        R = N * T
-        assert xv.shape[0] == R and xv.shape[1] >= I, (xv.shape, R, I)
-        pk = _lstm_pack_of([w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r], Hh, I)
-        gates = torch.empty(R, 8 * Hh, device=dev, dtype=torch.float32)
-        H.gemm(xv, ld_x, pk["wih_p"], pk["ld_i"], gates, 8 * Hh, R, 8 * Hh, I, bias=pk["bias_p"])
-        Hp = H.round_up(Hh, 4)
-        cell = torch.empty(N, T, 2, Hh, device=dev, dtype=torch.float32)
-        hout = (torch.zeros if Hp != Hh else torch.empty)(R, 2 * Hp, device=dev, dtype=torch.float32)
-        # the plan and BOTH directions' W_hh layouts are fetched here, once: the backward launches from what ctx keeps (a
-        # step captured without prepare_derived builds a layout at every ask)
-        plan = H.recurrence_plan(N, T, Hh, H.n_cus(dev))
-        whh = H.recurrence_packs(plan, w_hh, w_hh_r, Hh, pk, memo=True)
-        H.recurrence_launch(plan["fwd"], "fwd", gates, cell, hout, 2 * Hp, Hp, whh["fwd"], N, T, Hh)
-        wp = _proj_layout_of(w_proj, Hh, Hp)
-        drop = float(dropout_p) if dropout_p else 0.0
-        assert not drop or (act == 1 and out_link is None), "dropout_p: a site is the Tanh behind the layer, never folded"
-        store_act = 0 if drop else act
-        if combine:
-            K = combine
-            y = torch.empty(N // K * T, K * hdim, device=dev, dtype=torch.float32)
-            H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, 0, R, hdim, 2 * Hp, bias=b_proj.detach(), act=store_act,
-                   remap=dict(T=T, K=K, sb=T * K * hdim, sk=hdim, st=K * hdim))
-            ld_y = K * hdim
-        else:
-            y, ld_y = H.padded(R, hdim, dev, zero=True)
-            H.gemm(hout, 2 * Hp, wp, 2 * Hp, y, ld_y, R, hdim, 2 * Hp, bias=b_proj.detach(), act=store_act)
-        used = None
-        if drop:
-            used = H.dropout_draw(dev)
-            H.dropout_tanh_fwd(y, y, R, hdim, ld_y, combine if combine else 1, T, bool(combine), drop, used)
-        ctx.drop = (drop, used)
-        ctx.save_for_backward(xv, gates, cell, hout, y, wp)
-        ctx.params = (w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, w_proj, b_proj)
-        ctx.recurrence = (plan["bwd"], whh["bwd"])
-        ctx.meta = _RNNPMeta(N, T, I, Hh, Hp, hdim, ld_x, ld_y, act, combine)
+    def forward(ctx, x, N, T, act, combine, in_tanh, in_link, out_link, dropout_p, want_state, *params):
+        assert not dropout_p or (act == 1 and out_link is None), "dropout_p: a site is the Tanh behind the layer, never folded"
+        y, saved, ctx.drop, ctx.meta, ctx.recurrence, last = _rnnp_forward(x, params[:-2], *params[-2:], N, T, act, combine,
+                                                                           dropout_p, want_state=want_state)
+        ctx.save_for_backward(*saved)
+        ctx.params = params
         # Tanh-backward fold (see rnnp_layer): in_link = the link my producer hung on x, out_link = the one my
         # consumer may answer on.  Both are decided again in backward, when it is known who else uses the tensors.
         ctx.fold = (int(in_tanh) if in_link is not None else 0, in_link, out_link)
         assert out_link is None or act == 1, "out_link: only behind the fused Tanh"
         ctx.x_shape = x.shape
-        return y if combine else y[:, :hdim]
+        y = y if combine else y[:, :ctx.meta.hdim]
+        if not want_state:
+            return y
+        ctx.mark_non_differentiable(*last)      # (the last frame's state leaves without a gradient: no truncated BPTT)
+        return (y, *last)
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, *_):
         xv, gates, cell, hout, y, _ = ctx.saved_tensors
         m, params = ctx.meta, ctx.params
         in_tanh, in_link, out_link = ctx.fold
         dz, ld_dz = H.rows_view(_rnnp_dz(dy, y, m, ctx.drop, out_link.take() if out_link is not None else None))
         sinks = [_grad_sink(p) for p in params]
         direct = _is_direct(sinks, True)
-        d_w_proj, d_b_proj = _rnnp_proj_wgrads(dz, ld_dz, hout, m, sinks[8:], direct)
-        _rnnp_bptt(dz, ld_dz, gates, cell, params[8], m, ctx.recurrence)      # the critical path: gates <- d(pre-activations)
-        lstm_grads = _rnnp_lstm_wgrads(gates, hout, xv, m, sinks[:8], direct)
+        d_w_proj, d_b_proj = _rnnp_proj_wgrads(dz, ld_dz, hout, m, sinks[-2:], direct)
+        _rnnp_bptt(dz, ld_dz, gates, cell, params[-2], m, ctx.recurrence)     # the critical path: gates <- d(pre-activations)
+        lstm_grads = _rnnp_lstm_wgrads(gates, hout, xv, m, sinks[:-2], direct)
         if direct:
-            _notify_grads(params)                    # (10 tensors: both directions' LSTM weights + the projection)
-        dx = _rnnp_dx(gates, xv, params[:8], m, ctx.x_shape, in_link, in_tanh) if ctx.needs_input_grad[0] else None
-        return (dx, *lstm_grads, d_w_proj, d_b_proj) + (None,) * 8
+            _notify_grads(params)                    # (4 D + 2 tensors: every direction's LSTM weights + the projection)
+        dx = _rnnp_dx(gates, xv, params[:-2], m, ctx.x_shape, in_link, in_tanh) if ctx.needs_input_grad[0] else None
+        return (dx,) + (None,) * 9 + (*lstm_grads, d_w_proj, d_b_proj)
 
 
 def _rnnp_dz(dy, y, m, drop, folded):
@@ -249,12 +281,12 @@ def _rnnp_dz(dy, y, m, drop, folded):
 
 
 def _rnnp_proj_wgrads(dz, ld_dz, hout, m, sinks, direct):
-    """stage 2 -> (d_w_proj, d_b_proj), or (None, None) when they went into `sinks` (side stream)"""
-    R, Hh, Hp = m.N * m.T, m.Hh, m.Hp
+    """stage 2 -> (d_w_proj [hdim, D Hh], d_b_proj), or (None, None) when they went into `sinks` (side stream)"""
+    R, Hh, Hp, ld_h = m.N * m.T, m.Hh, m.Hp, m.D * m.Hp
     aligned = Hp == Hh           # hout's column layout is w_proj's: the emitter writes the sinks itself, fused where it can
     with _wgrad_branch(dz.device, R, (dz, hout), direct):
         to_sinks = direct and aligned
-        d_w, d_b = _linear_wgrads(dz, ld_dz, hout, 2 * Hp, m.hdim, 2 * Hp, R, sinks if to_sinks else None,
+        d_w, d_b = _linear_wgrads(dz, ld_dz, hout, ld_h, m.hdim, ld_h, R, sinks if to_sinks else None,
                                   to_sinks and H.fused_colsum())
         if not aligned:
             d_w = _proj_unlayout(d_w, Hh, Hp)
@@ -267,21 +299,21 @@ def _rnnp_proj_wgrads(dz, ld_dz, hout, m, sinks, direct):
 
 def _rnnp_bptt(dz, ld_dz, gates, cell, w_proj, m, recurrence):
     """stage 3: dhout = dz W_proj, then the recurrence backwards in time: `gates` <- d(pre-activations)"""
-    R, Hp = m.N * m.T, m.Hp
-    dhout = torch.empty(R, 2 * Hp, device=dz.device, dtype=torch.float32)
+    R, Hp, ld_h = m.N * m.T, m.Hp, m.D * m.Hp
+    dhout = torch.empty(R, ld_h, device=dz.device, dtype=torch.float32)
     wpT, ld_t = _proj_T_of(w_proj, m.Hh, Hp)
-    H.gemm(dz, ld_dz, wpT, ld_t, dhout, 2 * Hp, R, 2 * Hp, m.hdim)
-    H.recurrence_launch(recurrence[0], "bwd", gates, cell, dhout, 2 * Hp, Hp, recurrence[1], m.N, m.T, m.Hh)
+    H.gemm(dz, ld_dz, wpT, ld_t, dhout, ld_h, R, ld_h, m.hdim)
+    H.recurrence_launch(recurrence[0], "bwd", gates, cell, dhout, ld_h, Hp, recurrence[1], m.N, m.T, m.Hh)
 
 
 def _rnnp_lstm_wgrads(gates, hout, xv, m, sinks, direct):
-    """stage 4 -> the eight LSTM gradients in parameter order from dgates (in `gates`), or eight None when they went into
+    """stage 4 -> the 4 D LSTM gradients in parameter order from dgates (in `gates`), or 4 D None when they went into
     `sinks` (side stream)"""
-    R, T, I, Hh, Hp, G = m.N * m.T, m.T, m.I, m.Hh, m.Hp, 8 * m.Hh
+    R, T, I, D, Hh, Hp, G = m.N * m.T, m.T, m.I, m.D, m.Hh, m.Hp, 4 * m.D * m.Hh
     with _wgrad_branch(gates.device, R, (gates, hout, xv), direct):
-        dwhh = torch.empty(2, 4 * Hh * Hh, device=gates.device, dtype=torch.float32)
-        for d in range(2):   # dgates_t paired with h_{t-1} (forward dir) / h_{t+1} (reverse)
-            part, S = H.wgrad((gates, d * 4 * Hh), G, (hout, d * Hp), 2 * Hp, 4 * Hh, Hh, R,
+        dwhh = torch.empty(D, 4 * Hh * Hh, device=gates.device, dtype=torch.float32)
+        for d in range(D):   # dgates_t paired with h_{t-1} (forward dir) / h_{t+1} (reverse)
+            part, S = H.wgrad((gates, d * 4 * Hh), G, (hout, d * Hp), D * Hp, 4 * Hh, Hh, R,
                               b_kshift=(-1 if d == 0 else 1), kperiod=T)
             H.reduce_splits(part, S, 4 * Hh * Hh, dwhh[d])
         # dW_ih and (split-bf16 GEMM) the bias gradient in ONE pass over dgates: a virtual ones
@@ -297,19 +329,21 @@ def _rnnp_lstm_wgrads(gates, hout, xv, m, sinks, direct):
             unpacks.append((bias_src, 1, 3))      # b_ih and b_hh receive the same gradient
         else:
             new = lambda *shape: torch.empty(*shape, device=gates.device, dtype=torch.float32)  # noqa: E731
-            dst = [new(4 * Hh, I), new(4 * Hh, Hh), new(4 * Hh), None, new(4 * Hh, I), new(4 * Hh, Hh), new(4 * Hh), None]
+            dst = [t for _ in range(D) for t in (new(4 * Hh, I), new(4 * Hh, Hh), new(4 * Hh), None)]
+        unpack = H.lstm1_unpack if D == 1 else H.lstm_unpack      # (the library's entry point per direction count)
         for src, ncols, i in unpacks:
-            H.lstm_unpack(*src, Hh, ncols, dst[i], dst[i + 4], accumulate=direct)
+            unpack(*src, Hh, ncols, *dst[i::4], accumulate=direct)
     if direct:
-        return (None,) * 8
-    dst[3], dst[7] = dst[2].clone(), dst[6].clone()
+        return (None,) * (4 * D)
+    for d in range(D):
+        dst[4 * d + 3] = dst[4 * d + 2].clone()
     return tuple(dst)
 
 
 def _rnnp_dx(gates, xv, lstm_params, m, x_shape, in_link, Kc):
     """stage 5 -> d(input).  Kc > 0: my input is a Tanh output whose backward rides on this GEMM's store; the result
     travels on in_link and x receives a dummy (its true gradient is never formed -- hence not when it is watched)"""
-    R, T, I, G, dev = m.N * m.T, m.T, m.I, 8 * m.Hh, gates.device
+    R, T, I, G, dev = m.N * m.T, m.T, m.I, 4 * m.D * m.Hh, gates.device
     wihT, ld_t = _wih_T_of(lstm_params, m.Hh, I)
     if not Kc or in_link.observed():
         dxb, ld_dx = H.padded(R, I, dev, zero=True)
@@ -326,223 +360,17 @@ def _rnnp_dx(gates, xv, lstm_params, m, x_shape, in_link, Kc):
 
 
 def _proj_unlayout(dwp, Hh, Hp):
-    return dwp if Hp == Hh else torch.cat([dwp[:, :Hh], dwp[:, Hp:Hp + Hh]], dim=1).contiguous()
-
-
-# ------------------------------------------------------------------------------ RNNP, one direction of time
-def _lstm1_pack_of(lstm_params, Hh, I):
-    lstm_params = list(lstm_params)
-    return H.derived("lstm1_pack", lstm_params, lambda: H.lstm1_pack(lstm_params, Hh, I))
-
-
-def _proj1_layout_of(w_proj, Hh, Hp):
-    """projection weight [hdim, Hh] in the (possibly padded) [hdim, Hp] column layout of the one-direction hout"""
-    def build():
-        w = w_proj.detach()
-        if Hp == Hh and w.is_contiguous() and w.data_ptr() % 16 == 0:
-            return w
-        out = torch.zeros(w.shape[0], Hp, device=w.device, dtype=torch.float32)
-        out[:, :Hh] = w
-        return out
-    return H.derived("proj1_layout", [w_proj], build)
-
-
-def _proj1_T_of(w_proj, Hh, Hp):
-    return H.derived("proj1_T", [w_proj], lambda: H.transposed(_proj1_layout_of(w_proj, Hh, Hp), w_proj.shape[0], Hp))
-
-
-def _wih1_T_of(lstm_params, Hh, I):
-    def build():
-        pk = _lstm1_pack_of(lstm_params, Hh, I)
-        return H.transposed(pk["wih_p"].view(4 * Hh, pk["ld_i"]), 4 * Hh, I)
-    return H.derived("wih1_T", [lstm_params[0]], build)
-
-
-def _rnn1_forward(x, lstm_params, w_proj, b_proj, N, T, act, combine, dropout_p, state=None, want_state=False):
-    """The forward stages of one causal layer: input GEMM with bias into gates [R, 4H], the one-direction recurrence
-    (from `state` = (h0, c0) [N, Hh] when given), the projection [hdim, Hh] with act / combine / the dropout site.
-    -> (y, ld_y, saved tensors, drop, meta, (hT, cT) or None)"""
-    w_ih, w_hh = lstm_params[0], lstm_params[1]
-    dev = x.device
-    Hh, I, hdim = w_hh.shape[1], w_ih.shape[1], w_proj.shape[0]
-    assert w_proj.shape[1] == Hh, (tuple(w_proj.shape), Hh)
-    xv, ld_x = H.rows_view(x)
-    R = N * T
-    assert xv.shape[0] == R and xv.shape[1] >= I, (xv.shape, R, I)
-    pk = _lstm1_pack_of(lstm_params, Hh, I)
-    gates = torch.empty(R, 4 * Hh, device=dev, dtype=torch.float32)
-    H.gemm(xv, ld_x, pk["wih_p"], pk["ld_i"], gates, 4 * Hh, R, 4 * Hh, I, bias=pk["bias_p"])
-    Hp = H.round_up(Hh, 4)
-    cell = torch.empty(N, T, Hh, device=dev, dtype=torch.float32)
-    hout = (torch.zeros if Hp != Hh else torch.empty)(R, Hp, device=dev, dtype=torch.float32)
-    h0 = c0 = hT = cT = None
-    if state is not None:
-        h0, c0 = (H._f32(s).reshape(N, Hh).contiguous() for s in state)
-    if want_state:
-        hT, cT = (torch.empty(N, Hh, device=dev, dtype=torch.float32) for _ in range(2))
-    H.lstm1_fwd(gates, cell, hout, Hp, pk["whh_f"], N, T, Hh, h0, c0, hT, cT)
-    wp = _proj1_layout_of(w_proj, Hh, Hp)
-    drop = float(dropout_p) if dropout_p else 0.0
-    store_act = 0 if drop else act
-    if combine:
-        K = combine
-        y = torch.empty(N // K * T, K * hdim, device=dev, dtype=torch.float32)
-        H.gemm(hout, Hp, wp, Hp, y, 0, R, hdim, Hp, bias=b_proj.detach(), act=store_act,
-               remap=dict(T=T, K=K, sb=T * K * hdim, sk=hdim, st=K * hdim))
-        ld_y = K * hdim
-    else:
-        y, ld_y = H.padded(R, hdim, dev, zero=True)
-        H.gemm(hout, Hp, wp, Hp, y, ld_y, R, hdim, Hp, bias=b_proj.detach(), act=store_act)
-    used = None
-    if drop:
-        used = H.dropout_draw(dev)
-        H.dropout_tanh_fwd(y, y, R, hdim, ld_y, combine if combine else 1, T, bool(combine), drop, used)
-    meta = _RNNPMeta(N, T, I, Hh, Hp, hdim, ld_x, ld_y, act, combine)
-    return y, (xv, gates, cell, hout, y, wp), (drop, used), meta, pk, ((hT, cT) if want_state else None)
-
-
-class _RNNP1(torch.autograd.Function):
-    """One RNNP_packed layer of typ='lstm' (tssep/train/rnnp.py:80-96,146-168): LSTM in ONE direction of time + Linear
-    (+ tanh).  The sibling of _RNNP, stage by stage; gates are [R, 4H], hout is [R, Hp], the projection [hdim, H].  Zero
-    initial state: a carried state exists without gradients only (rnnp_layer)."""
-
-    @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, w_proj, b_proj, N, T, act, combine, in_tanh=0, in_link=None,
-                out_link=None, dropout_p=0.0, want_state=False):
-        assert not dropout_p or (act == 1 and out_link is None), "dropout_p: a site is the Tanh behind the layer, never folded"
-        y, saved, ctx.drop, ctx.meta, pk, last = _rnn1_forward(x, [w_ih, w_hh, b_ih, b_hh], w_proj, b_proj, N, T, act,
-                                                               combine, dropout_p, want_state=want_state)
-        ctx.save_for_backward(*saved)
-        ctx.params = (w_ih, w_hh, b_ih, b_hh, w_proj, b_proj)
-        ctx.whh_b = pk["whh_b"]
-        ctx.fold = (int(in_tanh) if in_link is not None else 0, in_link, out_link)
-        assert out_link is None or act == 1, "out_link: only behind the fused Tanh"
-        ctx.x_shape = x.shape
-        y = y if combine else y[:, :ctx.meta.hdim]
-        if not want_state:
-            return y
-        ctx.mark_non_differentiable(*last)      # (the last frame's state leaves without a gradient: no truncated BPTT)
-        return (y, *last)
-
-    @staticmethod
-    def backward(ctx, dy, *_):
-        xv, gates, cell, hout, y, _ = ctx.saved_tensors
-        m, params = ctx.meta, ctx.params
-        in_tanh, in_link, out_link = ctx.fold
-        dz, ld_dz = H.rows_view(_rnnp_dz(dy, y, m, ctx.drop, out_link.take() if out_link is not None else None))
-        sinks = [_grad_sink(p) for p in params]
-        direct = _is_direct(sinks, True)
-        d_w_proj, d_b_proj = _rnn1_proj_wgrads(dz, ld_dz, hout, m, sinks[4:], direct)
-        _rnn1_bptt(dz, ld_dz, gates, cell, params[4], m, ctx.whh_b)
-        lstm_grads = _rnn1_lstm_wgrads(gates, hout, xv, m, sinks[:4], direct)
-        if direct:
-            _notify_grads(params)
-        dx = _rnn1_dx(gates, xv, params[:4], m, ctx.x_shape, in_link, in_tanh) if ctx.needs_input_grad[0] else None
-        return (dx, *lstm_grads, d_w_proj, d_b_proj) + (None,) * 9
-
-
-def _rnn1_proj_wgrads(dz, ld_dz, hout, m, sinks, direct):
-    """stage 2 -> (d_w_proj [hdim, Hh], d_b_proj), or (None, None) when they went into `sinks` (side stream)"""
-    R, Hh, Hp = m.N * m.T, m.Hh, m.Hp
-    aligned = Hp == Hh
-    with _wgrad_branch(dz.device, R, (dz, hout), direct):
-        to_sinks = direct and aligned
-        d_w, d_b = _linear_wgrads(dz, ld_dz, hout, Hp, m.hdim, Hp, R, sinks if to_sinks else None,
-                                  to_sinks and H.fused_colsum())
-        if not aligned:
-            d_w = d_w[:, :Hh].contiguous()      # (the pad columns of hout are zero: nothing of them reaches dW_proj)
-            if direct:
-                sinks[0].add_(d_w)
-                sinks[1].add_(d_b)
-                d_w = d_b = None
-    return d_w, d_b
-
-
-def _rnn1_bptt(dz, ld_dz, gates, cell, w_proj, m, whh_b):
-    """stage 3: dhout = dz W_proj, then the recurrence backwards in time: `gates` <- d(pre-activations)"""
-    R, Hp = m.N * m.T, m.Hp
-    dhout = torch.empty(R, Hp, device=dz.device, dtype=torch.float32)
-    wpT, ld_t = _proj1_T_of(w_proj, m.Hh, Hp)
-    H.gemm(dz, ld_dz, wpT, ld_t, dhout, Hp, R, Hp, m.hdim)
-    H.lstm1_bwd(gates, cell, dhout, Hp, whh_b, m.N, m.T, m.Hh)
-
-
-def _rnn1_lstm_wgrads(gates, hout, xv, m, sinks, direct):
-    """stage 4 -> the four LSTM gradients in parameter order from dgates (in `gates`), or four None when they went into
-    `sinks` (side stream)"""
-    R, T, I, Hh, Hp, G = m.N * m.T, m.T, m.I, m.Hh, m.Hp, 4 * m.Hh
-    with _wgrad_branch(gates.device, R, (gates, hout, xv), direct):
-        dwhh = torch.empty(G * Hh, device=gates.device, dtype=torch.float32)
-        part, S = H.wgrad(gates, G, hout, Hp, G, Hh, R, b_kshift=-1, kperiod=T)      # dgates_t paired with h_{t-1}
-        H.reduce_splits(part, S, G * Hh, dwhh)
-        fused = H.fused_colsum()
-        part, S = H.wgrad(gates, G, xv, m.ld_x, G, I, R, with_colsum=fused)
-        ldp = H.round_up(I + 1, 4) if fused else I
-        bias_src = ((part, I), ldp, S, G * ldp) if fused else (H.colsum(gates, G, R, G), 1, 1, 0)
-        unpacks = [((dwhh, Hh, 1, 0), Hh, 1), ((part, ldp, S, G * ldp), I, 0), (bias_src, 1, 2)]
-        if direct:
-            dst = sinks
-            unpacks.append((bias_src, 1, 3))      # b_ih and b_hh receive the same gradient
-        else:
-            new = lambda *shape: torch.empty(*shape, device=gates.device, dtype=torch.float32)  # noqa: E731
-            dst = [new(G, I), new(G, Hh), new(G), None]
-        for src, ncols, i in unpacks:
-            H.lstm1_unpack(*src, Hh, ncols, dst[i], accumulate=direct)
-    if direct:
-        return (None,) * 4
-    dst[3] = dst[2].clone()
-    return tuple(dst)
-
-
-def _rnn1_dx(gates, xv, lstm_params, m, x_shape, in_link, Kc):
-    """stage 5 -> d(input); Kc > 0: the Tanh backward of my input rides on this GEMM's store (see _rnnp_dx)"""
-    R, T, I, G, dev = m.N * m.T, m.T, m.I, 4 * m.Hh, gates.device
-    wihT, ld_t = _wih1_T_of(lstm_params, m.Hh, I)
-    if not Kc or in_link.observed():
-        dxb, ld_dx = H.padded(R, I, dev, zero=True)
-        H.gemm(gates, G, wihT, ld_t, dxb, ld_dx, R, I, G)
-        return dxb[:, :I].reshape(x_shape)
-    assert I % 4 == 0 and I % Kc == 0 and m.ld_x == I, (I, Kc, m.ld_x)
-    dxb = torch.empty(R, I, device=dev, dtype=torch.float32)
-    hd = I // Kc
-    remap = dict(T=T, K=1, sb=Kc * T * hd, sk=0, st=hd, cm=hd, co=T * hd) if Kc > 1 else None
-    H.gemm(gates, G, wihT, ld_t, dxb, 0 if remap else I, R, I, G, act=2, aux=(xv, m.ld_x), remap=remap)
-    in_link.payload = dxb if in_link.payload is None else in_link.payload + dxb.view_as(in_link.payload)
-    return _dummy_grad(xv, x_shape)
-
-
-def _rnn1_layer(x, lstm, linear, N, T, act, combine, in_tanh, dz_given, dropout_p, state, return_state):
-    import weakref
-    lstm_params = [lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0]
-    dropout_p = float(dropout_p) if (dropout_p and act == 1) else 0.0
-    if state is not None:
-        if torch.is_grad_enabled():
-            raise RuntimeError("rnnp_layer: a carried state (state=(h0, c0)) exists without gradients only -- call it under "
-                               "torch.no_grad() (a gradient through the state, truncated BPTT, is not implemented)")
-        if len(state) != 2:
-            raise ValueError("state: (h0, c0)")
-        y, _, _, m, _, last = _rnn1_forward(x, lstm_params, linear.weight, linear.bias, N, T, act, combine, dropout_p,
-                                            state=state, want_state=True)
-        return (y if combine else y[:, :m.hdim]), last
-    in_link = getattr(x, "_tssep_tanh_link", None) if in_tanh else None
-    if in_link is not None and not (x.requires_grad and torch.is_grad_enabled()):
-        in_link = None
-    out_link = _Link() if (dz_given and act == 1 and not dropout_p and torch.is_grad_enabled()) else None
-    out = _RNNP1.apply(x, *lstm_params, linear.weight, linear.bias, N, T, act, combine, in_tanh, in_link, out_link,
-                       dropout_p, bool(return_state))
-    last = None
-    if return_state:
-        out, last = out[0], (out[1], out[2])
-    if out_link is not None and out.requires_grad:
-        out_link.out = weakref.ref(out)
-        out._tssep_tanh_link = out_link
-    return (out, last) if return_state else out
+    """the D column blocks of w_proj out of hout's padded layout (the pad columns of hout are zero: nothing of them
+    reaches dW_proj)"""
+    if Hp == Hh:
+        return dwp
+    return torch.cat([dwp[:, d * Hp:d * Hp + Hh] for d in range(dwp.shape[1] // Hp)], dim=1).contiguous()
 
 
 def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=False, dropout_p=0.0, state=None,
                return_state=False):
     """x rows (n,t); lstm = torch.nn.LSTM parameter container, linear = nn.Linear container.
-    lstm.bidirectional False: the causal route (_RNNP1) -- same stages, one direction of time.  There, and only without
+    lstm.bidirectional False: the causal route -- the same _RNNP over one direction of time.  There, and only without
     gradients, state = (h0, c0) [N, H] starts the recurrence from a carried state and / or return_state asks for the last
     frame's: the result is then (output, (hT, cT)).
     The Tanh between two layers (net.py:623-625) runs forward in the producer's projection epilogue (act = 1);
@@ -556,23 +384,35 @@ def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=Fals
     dropout_p > 0 (with act = 1): that Tanh is an active dropout site, y = keep ? tanh(z / (1 - p)) : 0 (_RNNP); such a
     site is never folded -- the caller passes in_tanh = 0 to the consumer, and dz_given is ignored here."""
     import weakref
-    if not lstm.bidirectional:
-        return _rnn1_layer(x, lstm, linear, N, T, act, combine, in_tanh, dz_given, dropout_p, state, return_state)
-    if state is not None or return_state:
+    if lstm.bidirectional and (state is not None or return_state):
         raise NotImplementedError("rnnp_layer: a state on a bidirectional layer (it reads the whole utterance)")
+    names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+    lstm_params = [getattr(lstm, n) for n in names]
+    if lstm.bidirectional:
+        lstm_params += [getattr(lstm, n + "_reverse") for n in names]
+    dropout_p = float(dropout_p) if (dropout_p and act == 1) else 0.0
+    if state is not None:
+        if torch.is_grad_enabled():
+            raise RuntimeError("rnnp_layer: a carried state (state=(h0, c0)) exists without gradients only -- call it under "
+                               "torch.no_grad() (a gradient through the state, truncated BPTT, is not implemented)")
+        if len(state) != 2:
+            raise ValueError("state: (h0, c0)")
+        y, _, _, m, _, last = _rnnp_forward(x, lstm_params, linear.weight, linear.bias, N, T, act, combine, dropout_p,
+                                            state=state, want_state=True)
+        return (y if combine else y[:, :m.hdim]), last
     in_link = getattr(x, "_tssep_tanh_link", None) if in_tanh else None
     if in_link is not None and not (x.requires_grad and torch.is_grad_enabled()):
         in_link = None
-    dropout_p = float(dropout_p) if (dropout_p and act == 1) else 0.0
     out_link = _Link() if (dz_given and act == 1 and not dropout_p and torch.is_grad_enabled()) else None
-    out = _RNNP.apply(x, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0,
-                      lstm.weight_ih_l0_reverse, lstm.weight_hh_l0_reverse,
-                      lstm.bias_ih_l0_reverse, lstm.bias_hh_l0_reverse,
-                      linear.weight, linear.bias, N, T, act, combine, in_tanh, in_link, out_link, dropout_p)
+    out = _RNNP.apply(x, N, T, act, combine, in_tanh, in_link, out_link, dropout_p, bool(return_state), *lstm_params,
+                      linear.weight, linear.bias)
+    last = None
+    if return_state:
+        out, last = out[0], (out[1], out[2])
     if out_link is not None and out.requires_grad:
         out_link.out = weakref.ref(out)
         out._tssep_tanh_link = out_link
-    return out
+    return (out, last) if return_state else out
 
 
 # ---------------------------------------------------------------------- conditioning

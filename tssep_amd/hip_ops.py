@@ -4,6 +4,7 @@ PyTorch is used for device memory and the current HIP stream only; every computa
 is a call into libtssep_hip.so.  Nothing here falls back to ATen math.
 """
 import ctypes
+import functools
 import itertools
 import math
 
@@ -689,17 +690,14 @@ class prepare_derived:
 
 
 # ------------------------------------------------------------------------------ BLSTM
-def lstm_sizes(H, I, ld_i):
-    sz = LstmSizes()
-    check(_lib.lib().tssep_lstm_pack_sizes(H, I, ld_i, ctypes.byref(sz)), "lstm_pack_sizes")
-    return sz
-
-
 def lstm_pack(params, H, I):
-    """params: 8 tensors (w_ih, w_hh, b_ih, b_hh forward, then reverse), torch layout."""
+    """params: 8 tensors (w_ih, w_hh, b_ih, b_hh forward, then reverse), torch layout; or the 4 of one direction of time
+    (typ = 'lstm') -> the [dir = 0] half of the same layouts, through the library's one-direction entry points."""
     L = _lib.lib()
+    sizes, pack = ("lstm1_pack_sizes", "lstm1_pack") if len(params) // 4 == 1 else ("lstm_pack_sizes", "lstm_pack")
     ld_i = round_up(I, 4)
-    sz = lstm_sizes(H, I, ld_i)
+    sz = LstmSizes()
+    check(getattr(L, "tssep_" + sizes)(H, I, ld_i, ctypes.byref(sz)), sizes)
     dev = params[0].device
     buf = torch.empty(sz.wih_p + round_up(sz.bias_p, 4) + sz.whh_f + sz.whh_b, device=dev,
                       dtype=torch.float32)
@@ -708,51 +706,12 @@ def lstm_pack(params, H, I):
     o3 = o2 + sz.whh_f
     wih_p, bias_p, whh_f, whh_b = buf[:o1], buf[o1:o1 + sz.bias_p], buf[o2:o3], buf[o3:]
     ps = [_f32(p.detach()).contiguous() for p in params]
-    check(L.tssep_lstm_pack(*[_p(p) for p in ps], H, I, ld_i, _p(wih_p), _p(bias_p), _p(whh_f),
-                            _p(whh_b), _stream()), "lstm_pack")
+    check(getattr(L, "tssep_" + pack)(*[_p(p) for p in ps], H, I, ld_i, _p(wih_p), _p(bias_p), _p(whh_f),
+                                      _p(whh_b), _stream()), pack)
     return dict(wih_p=wih_p, bias_p=bias_p, whh_f=whh_f, whh_b=whh_b, ld_i=ld_i, _keep=(buf, ps))
 
 
-# ---- one direction of time (typ = 'lstm'): the streaming kernels instantiated for one direction, with a state
-def lstm1_pack(params, H, I):
-    """params: 4 tensors (w_ih, w_hh, b_ih, b_hh), torch layout -> the [dir = 0] half of lstm_pack's layouts."""
-    L = _lib.lib()
-    ld_i = round_up(I, 4)
-    sz = LstmSizes()
-    check(L.tssep_lstm1_pack_sizes(H, I, ld_i, ctypes.byref(sz)), "lstm1_pack_sizes")
-    buf = torch.empty(sz.wih_p + round_up(sz.bias_p, 4) + sz.whh_f + sz.whh_b, device=params[0].device,
-                      dtype=torch.float32)
-    o1 = sz.wih_p
-    o2 = o1 + round_up(sz.bias_p, 4)
-    o3 = o2 + sz.whh_f
-    wih_p, bias_p, whh_f, whh_b = buf[:o1], buf[o1:o1 + sz.bias_p], buf[o2:o3], buf[o3:]
-    ps = [_f32(p.detach()).contiguous() for p in params]
-    check(L.tssep_lstm1_pack(*[_p(p) for p in ps], H, I, ld_i, _p(wih_p), _p(bias_p), _p(whh_f), _p(whh_b),
-                             _stream()), "lstm1_pack")
-    return dict(wih_p=wih_p, bias_p=bias_p, whh_f=whh_f, whh_b=whh_b, ld_i=ld_i, _keep=(buf, ps))
-
-
-def lstm1_fwd(gates, cell, hout, ldo, whh_f, N, T, H, h0=None, c0=None, hT=None, cT=None):
-    """gates [N,T,H,4] pre-activations -> activated gates; cell [N,T,H]; hout [N,T,ldo] columns 0..H-1.  h0 / c0 [N,H]:
-    the initial state (both or neither; None = zeros); hT / cT [N,H]: receive the state after the last frame."""
-    for s in (h0, c0, hT, cT):
-        assert s is None or (s.is_contiguous() and tuple(s.shape) == (N, H) and _f32(s) is s), (N, H)
-    _log_recurrence("stream1_f32", "fwd", N, T, H)
-    with _timed("lstm1_fwd", 2 * N * T * 4 * H * H, 0):
-        check(_lib.lib().tssep_lstm1_fwd(_p(gates), _p(cell), _p(hout), ldo, _p(whh_f), _p(h0), _p(c0), _p(hT), _p(cT),
-                                         N, T, H, _stream()), "lstm1_fwd")
-
-
-def lstm1_bwd(gates, cell, dhout, ldo, whh_b, N, T, H):
-    """dhout [N,T,ldo] -> `gates` is overwritten with d(pre-activation); zero initial state."""
-    _log_recurrence("stream1_f32", "bwd", N, T, H)
-    with _timed("lstm1_bwd", 2 * N * T * 4 * H * H, 0):
-        check(_lib.lib().tssep_lstm1_bwd(_p(gates), _p(cell), _p(dhout), ldo, _p(whh_b), N, T, H, _stream()), "lstm1_bwd")
-
-
-def lstm1_unpack(src, ld, nsplit, split_stride, H, ncols, dst, accumulate=False):
-    check(_lib.lib().tssep_lstm1_unpack(_p(src), ld, nsplit, split_stride, H, ncols, _p(dst), int(accumulate),
-                                        _stream()), "lstm1_unpack")
+lstm1_pack = lstm_pack      # (a name of its own: the callers of one direction ask for it, and the tests watch each name)
 
 
 _ERR = {}
@@ -785,6 +744,7 @@ def check_cluster_errors(device="cuda"):
         raise RuntimeError(f"cluster recurrence kernel timed out waiting for a peer (code {v})")
 
 
+@functools.lru_cache(maxsize=None)      # (asked once per layer and step, by both layer types)
 def n_cus(device):
     return torch.cuda.get_device_properties(device).multi_processor_count
 
@@ -812,9 +772,11 @@ ONCHIP16_BWD_GROUPS = 2  # at most: a backward phase is paced by its three barri
 KEEP_XBUF = None         # a list: the exchange buffers of the interleaved launches are appended (trace builds, tools)
 
 
-def recurrence_plan(N, T, H, cus):
+def recurrence_plan(N, T, H, cus, directions=2):
     """-> {"fwd": (kernel, groups), "bwd": (kernel, groups)}: the kernel of each direction of time of a BLSTM layer over
-    N sequences of T frames with H units, on a device of `cus` compute units.  kernel: "stream_f32" (lstm.hip),
+    N sequences of T frames with H units, on a device of `cus` compute units.  directions = 1 (typ = 'lstm'): the
+    streaming kernels instantiated for one direction, with a state, ("stream1_f32", 0) both ways -- the only recurrence
+    of one direction there is, so no policy switch is read and nothing is announced.  kernel: "stream_f32" (lstm.hip),
     "cluster_f32" (lstm_cluster.hip), "onchip32_bf16x3" or "onchip16_bf16x3" (lstm_onchip.hip); groups: 16-sequence groups
     in rotation per cluster of the interleaved kernels, 0 for the others.  ms per launch on MI355X at H=300, T=253
     (profiles/r2_recurrence_microbench.jsonl, forward / backward):
@@ -830,6 +792,8 @@ def recurrence_plan(N, T, H, cus):
     W-stationary (cluster) and streaming kernels remain selectable (RECURRENCE) as the exact-fp32 recurrences, and
     streaming is the path for H the W-stationary kernels do not support -- a fallback for a SUPPORTED H (sequence too
     long) is announced, never silent."""
+    if directions == 1:
+        return dict.fromkeys(("fwd", "bwd"), ("stream1_f32", 0))
     return {direction: _plan_direction(N, T, H, cus, direction == "bwd") for direction in ("fwd", "bwd")}
 
 
@@ -914,7 +878,7 @@ def recurrence_packs(plan, w_hh_f, w_hh_r, H, lstm_pk=None, memo=False, waves=8)
 
     built, out = {}, {}
     for direction, (kernel, _) in plan.items():
-        if kernel == "stream_f32":
+        if kernel in ("stream_f32", "stream1_f32"):
             out[direction] = lstm_pk["whh_b" if direction == "bwd" else "whh_f"]
             continue
         tag, build, which = layout(kernel, direction == "bwd")
@@ -928,17 +892,22 @@ def recurrence_packs(plan, w_hh_f, w_hh_r, H, lstm_pk=None, memo=False, waves=8)
 # activations out 16 + 16, c 4, h 4; activations 16, c 4 + 4, dh 4 in, d(gates) 16 out)
 _RECURRENCE_KERNELS = {
     "stream_f32": (("tssep_blstm_fwd", "tssep_blstm_bwd"), "blstm", (0, 0)),
+    "stream1_f32": (("tssep_lstm1_fwd", "tssep_lstm1_bwd"), "lstm1", (0, 0)),
     "cluster_f32": (("tssep_blstm_cluster_fwd", "tssep_blstm_cluster_bwd"), "blstm_cluster", (0, 0)),
     "onchip32_bf16x3": (("tssep_blstm_onchip_fwd", "tssep_blstm_onchip_bwd"), "blstm_onchip", (40, 44)),
     "onchip16_bf16x3": (("tssep_blstm_onchip16_fwd", "tssep_blstm_onchip16_bwd"), "blstm_onchip", (40, 44)),
 }
 
 
-def recurrence_launch(planned, direction, gates, cell, h, ldo, dstride, whh, N, T, H, ms=2, layout=0, waves=8):
+def recurrence_launch(planned, direction, gates, cell, h, ldo, dstride, whh, N, T, H, ms=2, layout=0, waves=8,
+                      state=(None,) * 4):
     """One direction of time ("fwd" | "bwd") of a BLSTM layer on planned = (kernel, groups), recurrence_plan's: h is hout
     (written forward) or dhout (read backward; d(gates) replace the gates in place), whh the layout recurrence_packs gave
     for the same kernel and direction.  ms (cluster), layout (on-chip kernels) and waves = 4 (the interleaved forward's
-    four-wave workgroups, experiment build: `_w16`) go to the kernel as they are."""
+    four-wave workgroups, experiment build: `_w16`) go to the kernel as they are.
+    "stream1_f32" (one direction: gates [N,T,H,4], cell [N,T,H], h columns 0..H-1 of [N,T,ldo]; no dstride) takes
+    state = (h0, c0, hT, cT) forward: h0 / c0 [N,H] the initial state (both or neither; None = zeros), hT / cT [N,H]
+    receive the state after the last frame.  Backward it starts from a zero state."""
     kernel, groups = planned
     bwd = direction == "bwd"
     entry, timed, cell_bytes = _RECURRENCE_KERNELS[kernel]
@@ -946,9 +915,15 @@ def recurrence_launch(planned, direction, gates, cell, h, ldo, dstride, whh, N, 
     w4 = kernel == "onchip16_bf16x3" and not bwd and waves == 4
     _log_recurrence(kernel + ("_w4" if w4 else ""), direction, N, T, H, groups)
     L = _lib.lib()
-    args = (_p(gates), _p(cell), _p(h), ldo, dstride, _p(whh))
-    flops, nbytes = 2 * 2 * N * T * 4 * H * H, N * T * 2 * H * cell_bytes[bwd]
-    if kernel == "stream_f32":
+    D = 1 if kernel == "stream1_f32" else 2
+    flops, nbytes = 2 * D * N * T * 4 * H * H, N * T * D * H * cell_bytes[bwd]
+    if D == 1:
+        for s in state:
+            assert s is None or (s.is_contiguous() and tuple(s.shape) == (N, H) and _f32(s) is s), (N, H)
+        args = (_p(gates), _p(cell), _p(h), ldo, _p(whh), *(() if bwd else map(_p, state)))
+    else:
+        args = (_p(gates), _p(cell), _p(h), ldo, dstride, _p(whh))
+    if kernel in ("stream_f32", "stream1_f32"):
         with _timed(f"{timed}_{direction}", flops, nbytes):
             check(getattr(L, entry)(*args, N, T, H, _stream()), entry[6:])
         return
@@ -1022,6 +997,14 @@ def blstm_bwd(gates, cell, dhout, ldo, dstride, whh_b, N, T, H):
     recurrence_launch(("stream_f32", 0), "bwd", gates, cell, dhout, ldo, dstride, whh_b, N, T, H)
 
 
+def lstm1_fwd(gates, cell, hout, ldo, whh_f, N, T, H, h0=None, c0=None, hT=None, cT=None):
+    recurrence_launch(("stream1_f32", 0), "fwd", gates, cell, hout, ldo, 0, whh_f, N, T, H, state=(h0, c0, hT, cT))
+
+
+def lstm1_bwd(gates, cell, dhout, ldo, whh_b, N, T, H):
+    recurrence_launch(("stream1_f32", 0), "bwd", gates, cell, dhout, ldo, 0, whh_b, N, T, H)
+
+
 def blstm_cluster_fwd(gates, cell, hout, ldo, dstride, whh_cf, N, T, H, ms=2):
     recurrence_launch(("cluster_f32", 0), "fwd", gates, cell, hout, ldo, dstride, whh_cf, N, T, H, ms=ms)
 
@@ -1051,6 +1034,11 @@ def blstm_onchip16_bwd(gates, cell, dhout, ldo, dstride, wb16, N, T, H, groups, 
 def lstm_unpack(src, ld, nsplit, split_stride, H, ncols, dst_f, dst_r, accumulate=False):
     check(_lib.lib().tssep_lstm_unpack(_p(src), ld, nsplit, split_stride, H, ncols, _p(dst_f),
                                        _p(dst_r), int(accumulate), _stream()), "lstm_unpack")
+
+
+def lstm1_unpack(src, ld, nsplit, split_stride, H, ncols, dst, accumulate=False):
+    check(_lib.lib().tssep_lstm1_unpack(_p(src), ld, nsplit, split_stride, H, ncols, _p(dst), int(accumulate),
+                                        _stream()), "lstm1_unpack")
 
 
 # ---- side stream for weight gradients ---------------------------------------------------------
