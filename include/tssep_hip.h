@@ -925,6 +925,50 @@ int tssep_reduce_splits_bias(const float* src, int nsplit, int64_t stride, int64
                              int64_t ldp, float* dw, int64_t ld_w, float* db, int accumulate,
                              void* stream);
 
+/* ------------------------------------------------------------------ online ---
+ * A live signal in pushes: causal feature statistics and state-carrying STFT / inverse STFT (this project's own; the
+ * reference has no online path).  The caller owns every state buffer; a state's successor is ANOTHER buffer (the caller
+ * ping-pongs two): one that overlaps its predecessor is TSSEP_E_SHAPE.  A fixed number of launches whatever the chunk
+ * length, no allocation, no host sync.  The stream kernels are built for FFT plan 1 (size 1024, shift 256, full fading, a
+ * full-size window); any other plan: TSSEP_E_UNSUPPORTED.
+ *
+ * tssep_feat_causal_fwd: tssep_feat_fwd with the statistics over the frames t' <= t of the utterance (the current frame
+ *   included) instead of the whole utterance / batch:
+ *     norm[b,t]  = max_{t' <= t, f} |X[b,t',f]|,            log1p(|X| (e - 1) / norm[b,t]);  norm == 0 (silence so far): 0
+ *     floor[b,t] = max_{t' <= t, m} dB[b,t',m] - top_db,    PER UTTERANCE, never over the batch (top_db < 0: log_mels, no floor)
+ *   X is a chunk of T frames per utterance; state_in / state_out [B, 2] = {running max |X|, running max dB} in front of /
+ *   behind the chunk (state_in NULL: {0, -inf}, a fresh stream; state_out NULL: not written).  max is exact: any split of
+ *   an utterance into calls gives the bits of one call.  The frame's own arithmetic is tssep_feat_fwd's: frame t equals
+ *   tssep_feat_fwd(stat_axis 0) of X[:, :t+1] at t.  Four launches (init, pass 1, scan, pass 2).
+ *   ws: tssep_feat_causal_workspace_bytes(B, T, n_mels, F) bytes, 16-byte aligned.
+ * tssep_stft_stream_fwd: the Tc frames a push of n_new = Tc * shift samples completes, read from [tail_in | x_new]
+ *   (tail_in [rows, size - shift]: the samples in front of the push; NULL: zeros = the leading fade of a fresh stream),
+ *   X [rows, Tc, size/2+1] with the bits tssep_stft_fwd gives those frames; tail_out = the last size - shift samples of
+ *   [tail_in | x_new].  The trailing fade is a push of zeros by the caller.  Two launches.
+ *   n_new != Tc * shift or Tc < 1: TSSEP_E_SHAPE.  x_new, tail_*, X 8-byte aligned.
+ * tssep_istft_stream_fwd (X [rows, Tc, F] complex64) / tssep_mask_istft_stream_fwd (logit [B*K, Tc, F] or, gated != 0,
+ *   [B*K, Tc, F + 1] with the VAD logit at column 0; obs [B, Tc, F] complex64): the hops the stream's next Tc frames
+ *   complete.  A hop sums four frames oldest first; ola_in / ola_out [rows, 3, shift] hold the oldest-first partial sums
+ *   of the three hops pending in front of / behind the call (ola_in NULL: zeros), added FIRST, so the concatenated
+ *   output equals tssep_istft_fwd / tssep_mask_istft_fwd / tssep_mask_istft_gated_fwd of all frames bit for bit (a -0
+ *   may come out as +0).  skip in 0..3: the call's first `skip` hops lie before the utterance's first sample and are not
+ *   stored -- max(0, 3 - frames of the earlier calls): 3 for the first call.  y [rows, N], N = max(Tc - skip, 0) * shift;
+ *   last != 0: the final hop may end early, (hops - 1) * shift < N <= hops * shift (the utterance's length); anything else
+ *   TSSEP_E_SHAPE.  y may be NULL when N == 0.  One launch, Tc beyond one workgroup's 64 hops included. */
+int64_t tssep_feat_causal_workspace_bytes(int64_t B, int64_t T, int n_mels, int F);
+int tssep_feat_causal_fwd(const float* X, int64_t B, int64_t T, int F, const float* fb, const float* dct,
+                          int n_mels, int n_mfcc, float top_db, const float* state_in, float* state_out,
+                          float* out, int64_t ld_out, void* ws, void* stream);
+int tssep_stft_stream_fwd(const float* x_new, int64_t rows, int64_t n_new, const float* tail_in, float* tail_out,
+                          int size, int shift, const float* window, const float* tw, float* X, int64_t Tc,
+                          void* stream);
+int tssep_istft_stream_fwd(const float* X, int64_t rows, int64_t Tc, int size, int shift, const float* wsyn,
+                           const float* tw, const float* ola_in, float* ola_out, int skip, int last, float* y,
+                           int64_t N, void* stream);
+int tssep_mask_istft_stream_fwd(const float* logit, int gated, const float* obs, int64_t B, int64_t K, int64_t Tc,
+                                int size, int shift, const float* wsyn, const float* tw, const float* ola_in,
+                                float* ola_out, int skip, int last, float* y, int64_t N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,10 +80,14 @@ constexpr int FPW = 4;            // frames per wave and block
 constexpr int CWMAX = 2 * MAXF;   // packed filter weights
 constexpr int LMELS = 128;        // filters whose table fits in LDS (40 in every shipped config)
 
+// CAUSAL (tssep_feat_causal_fwd): no maximum is collected by atomics; each frame leaves its own max |X| in fa[frame] and
+// its own max dB in fd[frame] (-inf without the MFCC block) for the scan below.  The frame's arithmetic is untouched.
+template <bool CAUSAL = false>
 __global__ __launch_bounds__(256) void feat_pass1_kernel(const float2* __restrict__ X, int64_t B,
                                                          int64_t T, int F,
                                                          const float* __restrict__ fb, int n_mels,
-                                                         int n_mfcc, void* ws, int stat, int log_mels) {
+                                                         int n_mfcc, void* ws, int stat, int log_mels,
+                                                         float* __restrict__ fa = nullptr, float* __restrict__ fd = nullptr) {
   __shared__ float pw[4][MAXF];
   __shared__ float cw[CWMAX];
   __shared__ int clo[LMELS], chi[LMELS], coff[LMELS + 1];
@@ -148,7 +152,10 @@ __global__ __launch_bounds__(256) void feat_pass1_kernel(const float2* __restric
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     amax = wave_max(amax);
-    if (lane == 0 && stat == STAT_TF) atomicMax(w.umax + frame / T, ord(amax));
+    if (CAUSAL) {
+      if (lane == 0) fa[frame] = amax;
+    } else if (lane == 0 && stat == STAT_TF) atomicMax(w.umax + frame / T, ord(amax));
+    float dbframe = -INFINITY;        // CAUSAL: this frame's max dB (lanes m < n_mels)
     if (n_mfcc > 0) {
       // one lane per filter walks its own band front to back (<= 64 bins for the widest filters): ~3 instructions per
       // bin on 40 lanes.  (Rounds 1-2: all 64 lanes shared each band and a butterfly summed them -- ~25 instructions
@@ -181,25 +188,34 @@ __global__ __launch_bounds__(256) void feat_pass1_kernel(const float2* __restric
           const float db = log_mels ? logf(mine + 1e-6f) : 10.0f * log10f(fmaxf(mine, 1e-10f));
           w.db[frame * n_mels + m0 + lane] = db;
           dbmax = fmaxf(dbmax, db);
+          if (CAUSAL) dbframe = fmaxf(dbframe, db);
         }
       }
+    }
+    if (CAUSAL) {
+      dbframe = wave_max(dbframe);
+      if (lane == 0) fd[frame] = dbframe;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // band reads done before the next frame's row
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
-  if (n_mfcc > 0) {
+  if (!CAUSAL && n_mfcc > 0) {
     dbmax = wave_max(dbmax);
     if (lane == 0 && dbmax > -INFINITY) atomicMax(w.gmax + (blockIdx.x & (GSLOTS - 1)), ord(dbmax));
   }
 }
 
+// CAUSAL: the frame reads its own floor (running max dB fd[frame] - top_db) and its own norm (running max |X| fa[frame],
+// the 'tf' arithmetic with it; 0 = digital silence so far: the feature is 0, not 0 / 0).
+template <bool CAUSAL = false>
 __global__ __launch_bounds__(256) void feat_pass2_kernel(const float2* __restrict__ X, int64_t B,
                                                          int64_t T, int F,
                                                          const float* __restrict__ dct, int n_mels,
                                                          int n_mfcc, float top_db,
                                                          float* __restrict__ out, int64_t ld_out,
-                                                         const void* ws, int stat) {
+                                                         const void* ws, int stat, const float* __restrict__ fa = nullptr,
+                                                         const float* __restrict__ fd = nullptr) {
   __shared__ float dbl[4][64];
   FeatWs w = feat_ws(const_cast<void*>(ws), feat_nmax(B, F, stat), n_mels);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -208,7 +224,8 @@ __global__ __launch_bounds__(256) void feat_pass2_kernel(const float2* __restric
   float* o = out + (valid ? frame : 0) * ld_out;
   if (n_mfcc > 0) {
     // (top_db < 0 = log_mels: no floor)
-    const float floor_db = top_db < 0.f ? -INFINITY : wave_max(unord(w.gmax[lane])) - top_db;      // merge the 64 slots
+    // (not CAUSAL: merge the 64 slots)
+    const float floor_db = top_db < 0.f ? -INFINITY : (CAUSAL ? fd[valid ? frame : 0] : wave_max(unord(w.gmax[lane]))) - top_db;
     for (int m0 = 0; m0 < n_mels; m0 += 64) {   // n_mels <= 64 in every config; loop kept general
       if (valid && m0 + lane < n_mels)
         dbl[wave][lane] = fmaxf(w.db[frame * n_mels + m0 + lane], floor_db);
@@ -233,11 +250,15 @@ __global__ __launch_bounds__(256) void feat_pass2_kernel(const float2* __restric
     xv[r] = f < F ? x[f] : make_float2(0.f, 0.f);
   }
   if (stat == STAT_TF) {
-    const float scale = (float)(M_E - 1.0) / unord(w.umax[frame / T]);
+    const float norm = CAUSAL ? fa[frame] : unord(w.umax[frame / T]);
+    const float scale = (float)(M_E - 1.0) / norm;
 #pragma unroll
     for (int r = 0; r < 17; ++r) {
       const int f = lane + 64 * r;
-      if (f < F) o[n_mfcc + f] = log1pf(sqrtf(xv[r].x * xv[r].x + xv[r].y * xv[r].y) * scale);
+      if (f < F) {
+        const float v = log1pf(sqrtf(xv[r].x * xv[r].x + xv[r].y * xv[r].y) * scale);
+        o[n_mfcc + f] = (CAUSAL && !(norm > 0.f)) ? 0.f : v;
+      }
     }
     return;
   }
@@ -257,6 +278,33 @@ __global__ __launch_bounds__(256) void feat_pass2_kernel(const float2* __restric
       o[n_mfcc + f] = log1pf(sqrtf(xv[r].x * xv[r].x + xv[r].y * xv[r].y) * ((float)(M_E - 1.0) / norm));
     }
   }
+}
+
+// The scan between the causal passes: one wave per utterance turns the per-frame maxima into RUNNING maxima over the frames
+// t' <= t, in place, seeded by the carried state (state_in [B, 2] = {max |X|, max dB}; NULL: {0, -inf}, a fresh stream), and
+// leaves the state after the last frame in state_out.  max is exact and associative: the result does not depend on how the
+// frames were split into calls, nor on the order of the scan.
+__global__ __launch_bounds__(256) void feat_scan_kernel(float* __restrict__ fa, float* __restrict__ fd, int64_t B, int64_t T,
+                                                        const float* __restrict__ state_in, float* __restrict__ state_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  float ca = state_in ? state_in[2 * b] : 0.f, cd = state_in ? state_in[2 * b + 1] : -INFINITY;
+  for (int64_t t0 = 0; t0 < T; t0 += 64) {
+    const int64_t t = t0 + lane;
+    float a = t < T ? fa[b * T + t] : 0.f, d = t < T ? fd[b * T + t] : -INFINITY;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const float ua = __shfl_up(a, o, 64), ud = __shfl_up(d, o, 64);
+      if (lane >= o) { a = fmaxf(a, ua); d = fmaxf(d, ud); }
+    }
+    a = fmaxf(a, ca);
+    d = fmaxf(d, cd);
+    if (t < T) { fa[b * T + t] = a; fd[b * T + t] = d; }
+    ca = __shfl(a, 63, 64);
+    cd = __shfl(d, 63, 64);
+  }
+  if (state_out && lane == 0) { state_out[2 * b] = ca; state_out[2 * b + 1] = cd; }
 }
 
 }  // namespace
@@ -284,9 +332,49 @@ extern "C" int tssep_feat_fwd(const float* X, int64_t B, int64_t T, int F, const
   hipLaunchKernelGGL(feat_init_kernel, dim3((unsigned)(nb0 > nm ? (nb0 > 4096 ? 4096 : nb0) : nm)), dim3(64), 0, s, ws, nmax, fb, F, n_mels);
   const unsigned blocks = (unsigned)((B * T + 3) / 4);
   const unsigned blocks1 = (unsigned)((B * T + 4 * FPW - 1) / (4 * FPW));
-  hipLaunchKernelGGL(feat_pass1_kernel, dim3(blocks1), dim3(256), 0, s, (const float2*)X, B, T, F,
-                     fb, n_mels, n_mfcc, ws, stat_axis, top_db < 0.f ? 1 : 0);
-  hipLaunchKernelGGL(feat_pass2_kernel, dim3(blocks), dim3(256), 0, s, (const float2*)X, B, T, F,
-                     dct, n_mels, n_mfcc, top_db, out, ld_out, ws, stat_axis);
+  hipLaunchKernelGGL(feat_pass1_kernel<false>, dim3(blocks1), dim3(256), 0, s, (const float2*)X, B, T, F,
+                     fb, n_mels, n_mfcc, ws, stat_axis, top_db < 0.f ? 1 : 0, (float*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL(feat_pass2_kernel<false>, dim3(blocks), dim3(256), 0, s, (const float2*)X, B, T, F,
+                     dct, n_mels, n_mfcc, top_db, out, ld_out, ws, stat_axis, (const float*)nullptr, (const float*)nullptr);
+  return tssep_launch_status();
+}
+
+// ---- causal statistics (this project's own): the maxima span the frames t' <= t of the utterance ---------
+// workspace: the layout of tssep_feat_fwd('tf') followed by the per-frame maxima fa, fd [B * T]
+static int64_t feat_causal_frame_off(int64_t B, int64_t T, int n_mels) {
+  FeatWs w = feat_ws(nullptr, B, n_mels);
+  return (((int64_t)((char*)w.db - (char*)nullptr) + B * T * (int64_t)n_mels * 4 + 15) / 16) * 16;
+}
+
+extern "C" int64_t tssep_feat_causal_workspace_bytes(int64_t B, int64_t T, int n_mels, int F) {
+  if (B <= 0 || T <= 0 || F <= 0 || n_mels < 0) return 0;
+  return feat_causal_frame_off(B, T, n_mels) + 2 * B * T * 4 + 16;
+}
+
+extern "C" int tssep_feat_causal_fwd(const float* X, int64_t B, int64_t T, int F, const float* fb, const float* dct,
+                                     int n_mels, int n_mfcc, float top_db, const float* state_in, float* state_out,
+                                     float* out, int64_t ld_out, void* ws, void* stream) {
+  if (!X || !out || !ws) return TSSEP_E_NULL;
+  if (n_mfcc > 0 && (!fb || !dct)) return TSSEP_E_NULL;
+  if (B <= 0 || T <= 0 || F <= 0 || F > MAXF || ld_out < n_mfcc + F) return TSSEP_E_SHAPE;
+  if (n_mfcc > 0 && (n_mels <= 0 || n_mels > 1024)) return TSSEP_E_SHAPE;
+  if (state_in && state_in == state_out) return TSSEP_E_SHAPE;
+  if (n_mfcc == 0) n_mels = 0;
+  if ((((uintptr_t)X) & 7u) || (((uintptr_t)ws) & 15u) || (((uintptr_t)state_in) & 3u) || (((uintptr_t)state_out) & 3u))
+    return TSSEP_E_ALIGN;
+  if ((B + 3) / 4 > 0x7fffffff || (B * T + 3) / 4 > 0x7fffffff) return TSSEP_E_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  const int nm = n_mels > 0 ? n_mels : 1;
+  float* fa = (float*)((char*)ws + feat_causal_frame_off(B, T, n_mels));
+  float* fd = fa + B * T;
+  const int64_t nb0 = (B + 64 * 16 - 1) / (64 * 16);
+  hipLaunchKernelGGL(feat_init_kernel, dim3((unsigned)(nb0 > nm ? (nb0 > 4096 ? 4096 : nb0) : nm)), dim3(64), 0, s, ws, B, fb, F, n_mels);
+  const unsigned blocks = (unsigned)((B * T + 3) / 4);
+  const unsigned blocks1 = (unsigned)((B * T + 4 * FPW - 1) / (4 * FPW));
+  hipLaunchKernelGGL(feat_pass1_kernel<true>, dim3(blocks1), dim3(256), 0, s, (const float2*)X, B, T, F, fb, n_mels, n_mfcc,
+                     ws, STAT_TF, top_db < 0.f ? 1 : 0, fa, fd);
+  hipLaunchKernelGGL(feat_scan_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, fa, fd, B, T, state_in, state_out);
+  hipLaunchKernelGGL(feat_pass2_kernel<true>, dim3(blocks), dim3(256), 0, s, (const float2*)X, B, T, F, dct, n_mels, n_mfcc,
+                     top_db, out, ld_out, ws, STAT_TF, (const float*)fa, (const float*)fd);
   return tssep_launch_status();
 }

@@ -150,7 +150,13 @@ __device__ __forceinline__ void fft512_wave(float2 (&v)[8], float2* buf, const f
 // MAG (plain only; the VAD losses' STFT-magnitude target, loss.py:312-327): no spectrum is written; the epilogue sums
 // |X[k]| = sqrtf(re^2 + im^2) of the bins it formed -- per lane over k = lane, lane + 64, ..., the Nyquist bin by lane 0,
 // then across the wave: a fixed order -- and lane 0 stores the frame's magnitude at dlogit[row * T + t].
-template <bool MASKED, bool GATED = false, bool MAG = false>
+//
+// STREAM (plain only; tssep_stft_stream_fwd): x is the NEW samples of a live signal, [rows, T * 256], and `tail` the 768
+// samples in front of them ([rows, 768]; NULL: zeros, the leading fade).  Frame t reads the virtual concatenation
+// [tail | x] at 256 t: sample pair lane + 64 r lies in the tail while 2 t + r < 6 -- for all lanes of the wave at once, so
+// each of the eight loads picks one of two descriptors by a scalar condition.  Everything behind the loads is the code of
+// the whole-signal transform: the frames carry its bits.
+template <bool MASKED, bool GATED = false, bool MAG = false, bool STREAM = false>
 __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     const float* __restrict__ x, int64_t rows, int64_t N, int64_t T, int shift, int pad_left,
     const float* __restrict__ window, const float2* __restrict__ tw, float2* __restrict__ X,
@@ -158,9 +164,10 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     const float2* __restrict__ obs, float* __restrict__ dlogit, int64_t Kspk,
     const float* __restrict__ tgt, const float* __restrict__ sums, const float* __restrict__ gout,
     const int32_t* __restrict__ iperm, int bt_major, const float* __restrict__ vad = nullptr,
-    const float* __restrict__ gbce = nullptr, float inv_kt = 0.f) {
+    const float* __restrict__ gbce = nullptr, float inv_kt = 0.f, const float* __restrict__ tail = nullptr) {
   static_assert(MASKED || !GATED, "the gate belongs to the mask head");
   static_assert(!MASKED || !MAG, "the frame magnitudes are the plain STFT's");
+  static_assert(!STREAM || (!MASKED && !MAG), "the stream form is the plain STFT's");
   constexpr int LDL = NH + 1 + (GATED ? 1 : 0);   // logit / d(logit) row length
   constexpr int C0 = GATED ? 1 : 0;               // column of bin 0
   // MASKED with tgt != NULL: x is the time-domain ESTIMATE and the frame's samples are the loss gradient
@@ -206,6 +213,20 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     if (!valid) {
 #pragma unroll
       for (int r = 0; r < 8; ++r) v[r] = make_float2(0.f, 0.f);
+    } else if constexpr (STREAM) {
+      const srd_t sx = make_srd(xr, N * 4), st = make_srd(tail ? tail + row * 768 : xr, tail ? 768 * 4 : 0);
+      const unsigned vo = (unsigned)((t * 256 + 2 * lane) * 4);
+      float2 xv[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const bool in_tail = 2 * t + r < 6;                    // (wave-uniform)
+        xv[r] = bload2(in_tail ? st : sx, vo + 512u * r - (in_tail ? 0u : 768u * 4u));
+      }
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const float2 wv = wl[lane + 64 * r];
+        v[r] = make_float2(xv[r].x * wv.x, xv[r].y * wv.y);
+      }
     } else if (fast) {
       // (base + 2 lane + 128 r) may be negative or beyond the row: as an unsigned byte offset it then lies outside
       // the descriptor's range and the pair reads as (0, 0)
@@ -360,12 +381,22 @@ constexpr int HCB_MAX = 64;              // hops per workgroup (upper bound; the
 #ifndef TSSEP_ISTFT_OCC
 #define TSSEP_ISTFT_OCC 3            // waves per SIMD the register allocation aims at (A/B: build with -D...=2)
 #endif
-template <bool MASKED, bool GATED = false>
+//
+// STREAM (tssep_istft_stream_fwd / tssep_mask_istft_stream_fwd): the T frames are the NEXT frames of a live stream and
+// y [rows, N] the hops they complete.  Hop j = 0 .. T - 1 of the call sums ring frames j .. j + 3 as above, where ring
+// frame l stands for frame l - 3 of the call: ring frames 0, 1, 2 are not transformed -- their last quarter holds the
+// carry ola_in [rows, 3, 256], the oldest-first partial sums of the three hops the stream's earlier frames left pending
+// (NULL: zeros), and the quarters a later hop reads hold 0 -- so a hop adds the carry first and then the call's frames in
+// order: the sum of the whole-utterance kernel, bit for bit (x + 0 = x; only a -0 may become +0).  The first `skip` hops
+// (3 at the start of a stream) lie before the utterance's first sample and are not stored.  The workgroup of the last
+// chunk leaves the partial sums of the three hops still pending in ola_out.
+template <bool MASKED, bool GATED = false, bool STREAM = false>
 __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
     const float2* __restrict__ X, int64_t T, int shift_, int64_t N,
     const float* __restrict__ wsyn, const float2* __restrict__ tw, float* __restrict__ y,
     const float* __restrict__ tgt, float* __restrict__ abs_partial, int nchunks, int hcb,
-    const float* __restrict__ logit, const float2* __restrict__ obs, int64_t Kspk) {
+    const float* __restrict__ logit, const float2* __restrict__ obs, int64_t Kspk,
+    const float* __restrict__ ola_in = nullptr, float* __restrict__ ola_out = nullptr, int skip = 0) {
   __shared__ float2 twl[NH];
   __shared__ float2 line[4][LINE];
   __shared__ __attribute__((aligned(16))) float fr[RING][1024];       // (51 KB with the rest: three workgroups per CU --
@@ -385,15 +416,27 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
   const float2 tw2_lane = tw[NH + lane];
   const int64_t t_lo = (int64_t)c * hcb;   // hop h of this chunk sums frames t_lo + h .. t_lo + h + 3
   const int64_t n0 = t_lo * 256;
-  const int64_t total_hops = (N + 255) / 256;
+  const int64_t total_hops = STREAM ? T : (N + 255) / 256;
   const int hops = (int)(total_hops - t_lo < hcb ? total_hops - t_lo : hcb);
   const int iters = (hops + 3 + 3) / 4;    // frames 0 .. hops + 2
   const float hinv = 0.5f / 512.0f;
   float* yr = y + row * N;
   const float* tr = tgt ? tgt + row * N : nullptr;
-  // the chunk's samples [n0, min(N, n0 + 256 hops)) of this row
-  const int64_t chunk_bytes = ((N - n0 < (int64_t)hops * 256 ? N - n0 : (int64_t)hops * 256)) * 4;
-  const srd_t sy = make_srd(yr + n0, chunk_bytes), str_ = make_srd(tr ? tr + n0 : yr + n0, chunk_bytes);
+  constexpr int TOFF = STREAM ? 3 : 0;     // ring frame l of the chunk is frame t_lo + l - TOFF
+  // the chunk's samples [n0, min(N, n0 + 256 hops)) of this row; STREAM: y begins `skip` hops into the call, so the chunk's
+  // samples lie at [n0 - 256 skip, ...) of the row and the first `yadj` of them in front of it (chunk 0 only: a further
+  // chunk begins at least 33 hops in)
+  int64_t chunk_bytes = ((N - n0 < (int64_t)hops * 256 ? N - n0 : (int64_t)hops * 256)) * 4;
+  int64_t ylo = n0;
+  int yadj = 0;
+  if constexpr (STREAM) {
+    const int64_t ybeg = n0 - 256 * (int64_t)skip;
+    const int64_t yhi = ybeg + (int64_t)hops * 256 < N ? ybeg + (int64_t)hops * 256 : N;
+    ylo = ybeg > 0 ? ybeg : 0;
+    yadj = (int)(ylo - ybeg);
+    chunk_bytes = (yhi > ylo ? yhi - ylo : 0) * 4;
+  }
+  const srd_t sy = make_srd(yr + ylo, chunk_bytes), str_ = make_srd(tr ? tr + n0 : yr + n0, chunk_bytes);
   float asum = 0.f;
   float2* buf = line[wave];
   // MASKED: the logits and observation bins of a frame are requested one iteration ahead (27 registers), right after
@@ -404,8 +447,8 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
   const int64_t urow = MASKED ? row / Kspk : 0;        // the utterance of this (utterance, speaker) row
   auto request = [&](int it_) __attribute__((always_inline)) {
     const int lf_ = it_ * 4 + wave;
-    const int64_t t_ = t_lo + lf_;
-    const bool ok = it_ < iters && t_ < T && lf_ < hops + 3;
+    const int64_t t_ = t_lo + lf_ - TOFF;
+    const bool ok = it_ < iters && (!STREAM || t_ >= 0) && t_ < T && lf_ < hops + 3;
     const int64_t tt = ok ? t_ : 0;
     const srd_t sl = make_srd(logit + (row * T + tt) * LDL, ok ? LDL * 4 : 0);
     const srd_t so = make_srd(obs + (urow * T + tt) * (NH + 1), ok ? (NH + 1) * 8 : 0);
@@ -421,8 +464,8 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
   if (MASKED) request(0);
   for (int it = 0; it < iters; ++it) {
     const int lf = it * 4 + wave;
-    const int64_t t = t_lo + lf;
-    const bool valid = t < T && lf < hops + 3;
+    const int64_t t = t_lo + lf - TOFF;
+    const bool valid = (!STREAM || t >= 0) && t < T && lf < hops + 3;
     float* slot = fr[lf % RING];
     float2 xnyq = make_float2(0.f, 0.f);              // MASKED: X[512], needed by lane 0 only
     if (MASKED) {
@@ -473,8 +516,14 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
       WAVE_SYNC();          // the wave's line is reused by its next frame; ring slots are disjoint
     } else {
 #pragma unroll
-      for (int r = 0; r < 8; ++r)
-        *reinterpret_cast<float2*>(&slot[2 * (lane + 64 * r)]) = make_float2(0.f, 0.f);
+      for (int r = 0; r < 8; ++r) {
+        float2 z = make_float2(0.f, 0.f);
+        if constexpr (STREAM) {       // ring frame lf < 3 of the call: the carry of pending hop lf in the last quarter
+          if (t < 0 && r >= 6 && ola_in)
+            z = *reinterpret_cast<const float2*>(ola_in + (row * 3 + lf) * 256 + 2 * (lane + 64 * (r - 6)));
+        }
+        *reinterpret_cast<float2*>(&slot[2 * (lane + 64 * r)]) = z;
+      }
     }
     __syncthreads();        // frames <= 4 it + 3 are in the ring
     // emit the hops completed by this iteration: h in [4 it - 3, 4 it] (4 x 256 samples, 4 per thread).
@@ -503,7 +552,7 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        bstore1(sy, (unsigned)(((4 * it - 3 + q) * 256 + tid) * 4), sv[q]);
+        bstore1(sy, (unsigned)(((4 * it - 3 + q) * 256 + tid - yadj) * 4), sv[q]);
         if (tr && em[q]) asum += fabsf(sv[q] - tv[q]);
       }
     }
@@ -515,6 +564,32 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
     __syncthreads();
     if (tid == 0) abs_partial[row * nchunks + c] = (red[0] + red[1]) + (red[2] + red[3]);
   }
+  if constexpr (STREAM) {
+    // the last chunk holds the call's last frame at ring index hops + 2 (the ring keeps the six frames in front of the
+    // last iteration's newest): the partial sums of the three pending hops, oldest frame first as in the emission above
+    if (c == nchunks - 1) {
+      const float *f0 = fr[hops % RING], *f1 = fr[(hops + 1) % RING], *f2 = fr[(hops + 2) % RING];
+      float* o = ola_out + row * 768;
+      float s0 = f0[tid + 768];
+      s0 += f1[tid + 512];
+      s0 += f2[tid + 256];
+      float s1 = f1[tid + 768];
+      s1 += f2[tid + 512];
+      o[tid] = s0;
+      o[256 + tid] = s1;
+      o[512 + tid] = f2[tid + 768];
+    }
+  }
+}
+
+// the sample tail a push leaves: the last 768 samples of [tail_in | x_new] (tail_in NULL: zeros)
+__global__ __launch_bounds__(256) void stream_tail_kernel(const float* __restrict__ x_new, const float* __restrict__ tail_in,
+                                                          float* __restrict__ tail_out, int64_t rows, int64_t n_new) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;      // (768 = 3 x 256: a block lies inside one row)
+  const int64_t row = idx / 768;
+  if (row >= rows) return;
+  const int64_t v = n_new + (idx - row * 768);                      // position in [tail_in | x_new]
+  tail_out[idx] = v < 768 ? (tail_in ? tail_in[row * 768 + v] : 0.f) : x_new[row * n_new + v - 768];
 }
 
 }  // namespace
@@ -591,6 +666,7 @@ struct RfftLaunch {
   const int32_t* iperm;                        // the layout fold
   int bt_major;
   const float *vad, *gbce;                     // gated: the BCE fold on the gate column (vad == NULL: none)
+  const float* tail;                           // the STREAM instantiation: the samples in front of x (NULL: zeros)
 };
 
 // (the checks that do not depend on the plan: the general plan of stft_generic.hip takes the same arguments)
@@ -615,7 +691,7 @@ static int rfft_launch(const RfftLaunch& a, void* stream) {
   hipLaunchKernelGGL(a.kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a.x, a.rows, a.N, a.T, a.shift,
                      a.fading ? a.size - a.shift : 0, a.window, (const float2*)a.tw, (float2*)a.X, a.s_in, a.s_edge, iters,
                      a.logit, (const float2*)a.obs, a.amag ? a.amag : a.dlogit, a.masked ? a.K : (int64_t)1, a.tgt, a.sums, a.gout, a.iperm,
-                     a.bt_major, a.vad, a.gbce, a.masked ? 1.0f / ((float)a.K * (float)a.T) : 0.f);
+                     a.bt_major, a.vad, a.gbce, a.masked ? 1.0f / ((float)a.K * (float)a.T) : 0.f, a.tail);
   return tssep_launch_status();
 }
 
@@ -653,7 +729,7 @@ static int istft_launch(const IstftLaunch& a, void* stream) {
   const int hcb = (int)(((a.N + 255) / 256 + nchunks - 1) / nchunks);          // hops per chunk
   hipLaunchKernelGGL(a.kernel, dim3((unsigned)nchunks, (unsigned)a.rows), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)a.X, a.T, a.shift, a.N, a.wsyn, (const float2*)a.tw, a.y, a.tgt, a.abs_partial, nchunks,
-                     hcb, a.logit, (const float2*)a.obs, a.masked ? a.K : (int64_t)1);
+                     hcb, a.logit, (const float2*)a.obs, a.masked ? a.K : (int64_t)1, (const float*)nullptr, (float*)nullptr, 0);
   return tssep_launch_status();
 }
 
@@ -776,4 +852,73 @@ extern "C" int tssep_stft_framemag_fwd(const float* x, int64_t rows, int64_t N, 
     return tssep_generic_framemag(x, rows, N, size, shift, fading ? size - shift : 0, window, tw, a, T, stream);
   }
   return rfft_launch(l, stream);
+}
+
+// ---- the online forms (plan 1 only): a live signal in pushes of whole hops, the state carried by the caller ---------
+static bool overlap(const void* a, const void* b, int64_t bytes) {
+  const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+  return p < q + (uintptr_t)bytes && q < p + (uintptr_t)bytes;
+}
+
+extern "C" int tssep_stft_stream_fwd(const float* x_new, int64_t rows, int64_t n_new, const float* tail_in, float* tail_out,
+                                     int size, int shift, const float* window, const float* tw, float* X, int64_t Tc,
+                                     void* stream) {
+  if (!x_new || !tail_out || !window || !tw || !X) return TSSEP_E_NULL;
+  if (int e = check_plan(size, shift)) return e;
+  if (rows <= 0 || Tc < 1 || n_new != Tc * shift) return TSSEP_E_SHAPE;
+  const int64_t tail_bytes = rows * (size - shift) * 4;
+  if (tail_in && overlap(tail_in, tail_out, tail_bytes)) return TSSEP_E_SHAPE;
+  if (misaligned(x_new, 8) || misaligned(tail_out, 8) || misaligned(tail_in, 8) || misaligned(tw, 8) || misaligned(window, 8) ||
+      misaligned(X, 8))
+    return TSSEP_E_ALIGN;
+  if (rows * 3 > 0x7fffffff) return TSSEP_E_SHAPE;
+  // (the whole-signal launcher: no fade in front, the rows are the new samples)
+  const RfftLaunch a = {.kernel = rfft_frames_kernel<false, false, false, true>, .x = x_new, .rows = rows, .N = n_new, .T = Tc,
+                        .size = size, .shift = shift, .fading = 0, .window = window, .tw = tw, .s_in = 1.0f, .s_edge = 1.0f,
+                        .X = X, .tail = tail_in};
+  if (int e = rfft_launch(a, stream)) return e;
+  hipLaunchKernelGGL(stream_tail_kernel, dim3((unsigned)(rows * 3)), dim3(256), 0, (hipStream_t)stream, x_new, tail_in,
+                     tail_out, rows, n_new);
+  return tssep_launch_status();
+}
+
+// One launch of the STREAM instantiations of istft_kernel.  y holds the Tc - skip hops the call completes (none: y may be NULL and N is 0);
+// `last` lets the final hop end early, at the utterance's last sample.
+static int istft_stream_launch(int variant, const float* X, const float* logit, const float* obs, int64_t rows, int64_t K,
+                               int64_t Tc, int size, int shift, const float* wsyn, const float* tw, const float* ola_in,
+                               float* ola_out, int skip, int last, float* y, int64_t N, void* stream) {
+  const bool masked = variant != 0;
+  if ((masked ? (!logit || !obs) : !X) || !wsyn || !tw || !ola_out) return TSSEP_E_NULL;
+  if (int e = check_plan(size, shift)) return e;
+  if (rows <= 0 || (masked && (K <= 0 || rows % K)) || Tc < 1 || skip < 0 || skip > 3 || rows > 65535) return TSSEP_E_SHAPE;
+  const int64_t hops = Tc > skip ? Tc - skip : 0;
+  if (N < 0 || N > hops * shift || (last ? N <= (hops - 1) * shift && hops > 0 : N != hops * shift)) return TSSEP_E_SHAPE;
+  if (N > 0 && !y) return TSSEP_E_NULL;
+  if (ola_in && overlap(ola_in, ola_out, rows * (size - shift) * 4)) return TSSEP_E_SHAPE;
+  if (misaligned(tw, 8) || misaligned(wsyn, 8) || misaligned(ola_in, 8) || misaligned(ola_out, 4) || misaligned(y, 4))
+    return TSSEP_E_ALIGN;
+  if (masked ? (misaligned(logit, 4) || misaligned(obs, 8)) : misaligned(X, 8)) return TSSEP_E_ALIGN;
+  const int nchunks = (int)((Tc + HCB_MAX - 1) / HCB_MAX);
+  const int hcb = (int)((Tc + nchunks - 1) / nchunks);
+  const istft_kernel_t kernel = variant == 0 ? istft_kernel<false, false, true>
+                                              : (variant == 1 ? istft_kernel<true, false, true> : istft_kernel<true, true, true>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nchunks, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const float2*)X, Tc,
+                     shift, N, wsyn, (const float2*)tw, y, (const float*)nullptr, (float*)nullptr, nchunks, hcb, logit,
+                     (const float2*)obs, masked ? K : (int64_t)1, ola_in, ola_out, skip);
+  return tssep_launch_status();
+}
+
+extern "C" int tssep_istft_stream_fwd(const float* X, int64_t rows, int64_t Tc, int size, int shift, const float* wsyn,
+                                      const float* tw, const float* ola_in, float* ola_out, int skip, int last, float* y,
+                                      int64_t N, void* stream) {
+  return istft_stream_launch(0, X, nullptr, nullptr, rows, 1, Tc, size, shift, wsyn, tw, ola_in, ola_out, skip, last, y, N,
+                             stream);
+}
+
+extern "C" int tssep_mask_istft_stream_fwd(const float* logit, int gated, const float* obs, int64_t B, int64_t K, int64_t Tc,
+                                           int size, int shift, const float* wsyn, const float* tw, const float* ola_in,
+                                           float* ola_out, int skip, int last, float* y, int64_t N, void* stream) {
+  if (B <= 0 || K <= 0) return (!logit || !obs || !wsyn || !tw || !ola_out) ? TSSEP_E_NULL : TSSEP_E_SHAPE;
+  return istft_stream_launch(gated ? 2 : 1, nullptr, logit, obs, B * K, K, Tc, size, shift, wsyn, tw, ola_in, ola_out, skip,
+                             last, y, N, stream);
 }

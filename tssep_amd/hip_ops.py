@@ -369,6 +369,95 @@ def feat_fwd(X, fb, dct, n_mfcc, top_db=80.0, statistics_axis="tf"):
     return out[..., :D], ld
 
 
+def feat_causal_fwd(X, fb, dct, n_mfcc, top_db=80.0, state=None):
+    """feat_fwd('tf') with causal statistics: X complex64 [B,Tc,F], a chunk of each utterance's frames -> (view
+    [B,Tc,n_mfcc+F], ld, state_out).  state [B,2] = {running max |X|, running max dB} in front of the chunk (None: a fresh
+    stream); state_out is a new tensor, the state behind it."""
+    L = _lib.lib()
+    Xr = torch.view_as_real(X.contiguous())
+    B, T, F = X.shape
+    n_mels = fb.shape[1] if n_mfcc else 0
+    if n_mfcc:
+        fb, dct = _f32(fb).contiguous(), _f32(dct).contiguous()
+    if state is not None:
+        state = _f32(state).contiguous()
+        assert tuple(state.shape) == (B, 2), (tuple(state.shape), B)
+    D = n_mfcc + F
+    ld = round_up(D, 4)
+    out = torch.empty(B, T, ld, device=X.device, dtype=torch.float32)
+    if ld != D:
+        out[..., D:].zero_()
+    state_out = torch.empty(B, 2, device=X.device, dtype=torch.float32)
+    ws = torch.empty(int(L.tssep_feat_causal_workspace_bytes(B, T, n_mels, F)) // 4 + 4, device=X.device,
+                     dtype=torch.float32)
+    with _timed("feat_causal", 0, B * T * (16 * F + 4 * D)):
+        check(L.tssep_feat_causal_fwd(_p(Xr), B, T, F, _p(fb) if n_mfcc else None, _p(dct) if n_mfcc else None, n_mels,
+                                      n_mfcc, float(top_db), _p(state), _p(state_out), _p(out), ld, _p(ws), _stream()),
+              "feat_causal_fwd")
+    return out[..., :D], ld, state_out
+
+
+# ----------------------------------------------------------------------------- online
+def stft_stream_fwd(x_new, tail, window, size=1024, shift=256):
+    """The frames a push completes: x_new [rows, Tc * shift] behind tail [rows, size - shift] (None: a fresh stream, the
+    leading fade) -> (X complex64 [rows, Tc, size//2+1] with stft_fwd's bits for those frames, the new tail)."""
+    L = _lib.lib()
+    x_new = _f32(x_new).contiguous()
+    rows, n = x_new.shape
+    Tc = n // shift
+    if tail is not None:
+        tail = _f32(tail).contiguous()
+        assert tuple(tail.shape) == (rows, size - shift), (tuple(tail.shape), rows, size - shift)
+    tail_out = torch.empty(rows, size - shift, device=x_new.device, dtype=torch.float32)
+    X = torch.empty(rows, Tc, size // 2 + 1, 2, device=x_new.device, dtype=torch.float32)
+    check(L.tssep_stft_stream_fwd(_p(x_new), rows, n, _p(tail), _p(tail_out), size, shift, _p(window),
+                                  _p(fft_tables(size, x_new.device)), _p(X), Tc, _stream()), "stft_stream_fwd")
+    return torch.view_as_complex(X), tail_out
+
+
+def _stream_hops(Tc, skip, shift, N):
+    """(samples of y, last) for a call of Tc frames whose first `skip` hops are not stored; N: the samples that remain of
+    the utterance (the final call), None: whole hops."""
+    full = max(Tc - skip, 0) * shift
+    return (full, 0) if N is None else (min(int(N), full), 1)
+
+
+def istft_stream_fwd(X, wsyn, ola, skip, N=None, size=1024, shift=256):
+    """The hops the stream's next frames complete: X complex64 [rows, Tc, F], ola [rows, size - shift] the carry in front
+    (None: a fresh stream), skip = max(0, 3 - frames seen before) -> (y [rows, (Tc - skip) * shift], or its first N
+    samples in the utterance's final call; the carry behind)."""
+    L = _lib.lib()
+    Xr = torch.view_as_real(X.contiguous())
+    rows, Tc = X.shape[0], X.shape[1]
+    n, last = _stream_hops(Tc, skip, shift, N)
+    ola = None if ola is None else _f32(ola).contiguous()
+    y = torch.empty(rows, n, device=X.device, dtype=torch.float32)
+    ola_out = torch.empty(rows, size - shift, device=X.device, dtype=torch.float32)
+    check(L.tssep_istft_stream_fwd(_p(Xr), rows, Tc, size, shift, _p(wsyn), _p(fft_tables(size, X.device)),
+                                   _p(ola), _p(ola_out), int(skip), last,
+                                   _p(y) if n else None, n, _stream()), "istft_stream_fwd")
+    return y, ola_out
+
+
+def mask_istft_stream_fwd(logit, obs, wsyn, ola, skip, N=None, size=1024, shift=256):
+    """mask_istft_fwd on the stream's next frames: logit [B,K,Tc,F] (gated: [B,K,Tc,F+1]), obs complex64 [B,Tc,F], ola
+    [B*K, size - shift] or None -> (y [B,K,n], the carry behind); arguments as istft_stream_fwd."""
+    L = _lib.lib()
+    B, K, Tc, F, gated = _tail_rows(logit, obs)
+    logit = _f32(logit).contiguous()
+    obs_r = torch.view_as_real(obs.contiguous())
+    n, last = _stream_hops(Tc, skip, shift, N)
+    ola = None if ola is None else _f32(ola).contiguous()
+    y = torch.empty(B, K, n, device=logit.device, dtype=torch.float32)
+    ola_out = torch.empty(B * K, size - shift, device=logit.device, dtype=torch.float32)
+    with _timed("maskhead_stream", 0, B * Tc * (4 * K * logit.shape[-1] + 8 * F) + 4 * B * K * n):
+        check(L.tssep_mask_istft_stream_fwd(_p(logit), int(gated), _p(obs_r), B, K, Tc, size, shift, _p(wsyn),
+                                            _p(fft_tables(size, logit.device)),
+                                            _p(ola), _p(ola_out), int(skip), last,
+                                            _p(y) if n else None, n, _stream()), "mask_istft_stream_fwd")
+    return y, ola_out
+
+
 # ------------------------------------------------------------------------------- GEMM
 # Arithmetic of the non-recurrent GEMMs: "bf16x3" = split-bf16 on the bf16 MFMA with fp32 accumulation (fp32-class
 # accuracy: masks 3e-6 from the CPU oracle, see gemm_bf16x3.hip) -- the DEFAULT since round 5: what bench.py measures is

@@ -198,6 +198,55 @@ class STFT(Configurable):
             bce = Fn.gate_bce(logit, vad) if gated and vad is not None else None
         return (est, bce) if gated else est
 
+    # ---- a live signal in pushes: the caller carries the state between the calls -------------------------
+    causal = False        # the feature statistics span the whole utterance (the classes below take causal=True)
+
+    def _check_stream(self):
+        """The stream kernels are built for the plain 1024 / 256 STFT: say what is missing for any other."""
+        missing = []
+        if (self.size, self.shift) != (1024, 256):
+            missing.append(f"size / shift = {self.size} / {self.shift} (a stream kernel for that FFT plan)")
+        if self.window_length != self.size:
+            missing.append(f"window_length = {self.window_length} < size (a stream kernel for a zero-padded window)")
+        if self.fading not in (True, "full"):
+            missing.append(f"fading = {self.fading!r} (the carried state is the full fade)")
+        if not self.pad:
+            missing.append("pad = False (flush pads the last frame)")
+        if missing:
+            raise NotImplementedError("the online STFT / inverse STFT are built for size 1024, shift 256, a full-size "
+                                      "window, fading 'full' and pad=True; not built: " + "; ".join(missing))
+
+    def stft_chunk(self, x_new, tail=None):
+        """The frames a push completes: x_new [..., Tc * shift], tail [rows, size - shift] the state of the push before
+        (None: a fresh stream) -> (complex64 [..., Tc, F] = the frames ``stft`` gives at those indices, bit for bit; the
+        new tail).  The utterance's last 3 or 4 frames come from pushing zeros (the trailing fade): OnlineSeparator.flush."""
+        self._check_stream()
+        x = _cuda_f32(x_new)
+        if x.shape[-1] == 0 or x.shape[-1] % self.shift:
+            raise ValueError(f"stft_chunk: a push holds a positive multiple of shift = {self.shift} samples, not {x.shape[-1]}")
+        w, _ = self._windows(x.device)
+        X, tail = H.stft_stream_fwd(x.reshape(-1, x.shape[-1]), tail, w, self.size, self.shift)
+        return X.reshape(*x.shape[:-1], X.shape[-2], X.shape[-1]), tail
+
+    def istft_chunk(self, signal, ola=None, skip=0, num_samples=None):
+        """The samples the stream's next frames complete: complex64 [..., Tc, F], ola the carry of the call before (None:
+        a fresh stream), skip = max(0, 3 - frames of the earlier calls) -> ([..., (Tc - skip) * shift] -- the first
+        ``num_samples`` of them in the utterance's final call --, the new carry).  Forward only."""
+        self._check_stream()
+        X = signal.to(torch.complex64) if signal.dtype == torch.complex128 else signal
+        _, wsyn = self._windows(X.device)
+        y, ola = H.istft_stream_fwd(X.reshape(-1, X.shape[-2], X.shape[-1]), wsyn, ola, skip, num_samples, self.size,
+                                    self.shift)
+        return y.reshape(*X.shape[:-2], y.shape[-1]), ola
+
+    def masked_istft_chunk(self, logit, observation, ola=None, skip=0, num_samples=None):
+        """``masked_istft`` on the stream's next frames (plain or explicit_vad rows): logit [B,K,Tc,F(+1)], observation
+        complex64 [B,Tc,F] -> ([B,K,n], the new carry); arguments as ``istft_chunk``.  Neither mask nor masked spectrum is
+        written."""
+        self._check_stream()
+        _, wsyn = self._windows(logit.device)
+        return H.mask_istft_stream_fwd(logit, observation, wsyn, ola, skip, num_samples, self.size, self.shift)
+
     def stft_to_feature(self, stft_signals):
         raise NotImplementedError(type(self))
 
@@ -212,20 +261,39 @@ class STFT(Configurable):
 
 class Log1pMaxNormAbsSTFT(STFT):
     def __init__(self, size=1024, shift=256, window_length=None, pad=True, fading=True,
-                 output_size=None, window="blackman", statistics_axis="tf"):
+                 output_size=None, window="blackman", statistics_axis="tf", causal=False):
         super().__init__(size=size, shift=shift, window_length=window_length, pad=pad,
                          fading=fading, output_size=output_size, window=window)
         if statistics_axis not in H.STAT_AXES:
             raise ValueError(f"statistics_axis = {statistics_axis!r}: 'tf', 't' or 'f' (feature_extractor.py:239-242)")
+        if causal and statistics_axis == "t":
+            raise NotImplementedError("Log1pMaxNormAbsSTFT(causal=True, statistics_axis='t'): a running maximum per "
+                                      "(utterance, frequency) is not built ('tf': the running maximum of the utterance; "
+                                      "'f' is causal as it is)")
         self.statistics_axis = statistics_axis
+        self.causal = bool(causal)           # this project's own keyword
         self._check_feature_bins()
 
-    def stft_to_feature(self, stft_signals):
+    def stft_to_feature(self, stft_signals, state=None, return_state=False):
+        """causal=True: norm[b,t] = max over t' <= t and f of |X| (0 so far: the feature is 0).  ``state`` [rows, 2] is the
+        state a chunk's predecessor returned (None: the utterance starts here); return_state: -> (feature, state)."""
         X = stft_signals
         lead = X.shape[:-2]
-        out, _ = H.feat_fwd(X.reshape(-1, X.shape[-2], X.shape[-1]).contiguous(), None, None, 0,
-                            statistics_axis=self.statistics_axis)
-        return out.reshape(*lead, X.shape[-2], X.shape[-1])
+        X3 = X.reshape(-1, X.shape[-2], X.shape[-1]).contiguous()
+        if self.causal and self.statistics_axis == "tf":
+            out, _, state = H.feat_causal_fwd(X3, None, None, 0, state=state)
+        else:
+            if not self.causal:              # ('f' is causal as it is: a state passes through untouched)
+                _no_state(self, state)
+            out, _ = H.feat_fwd(X3, None, None, 0, statistics_axis=self.statistics_axis)
+        out = out.reshape(*lead, X.shape[-2], X.shape[-1])
+        return (out, state) if return_state else out
+
+
+def _no_state(fe, state):
+    if state is not None:
+        raise ValueError(f"{type(fe).__name__}: a carried state belongs to causal statistics (causal=True); these span "
+                         "the whole utterance")
 
 
 class TorchMFCC(STFT, torch.nn.Module):
@@ -236,9 +304,10 @@ class TorchMFCC(STFT, torch.nn.Module):
                  output_size=None, window="hann", sample_rate: int = 16000, n_mfcc: int = 40,
                  dct_norm: str = "ortho", log_mels: bool = False, f_min: float = 40,
                  f_max: float = -400, n_mels: int = 40, mel_norm: str = None,
-                 mel_scale: str = "htk"):
+                 mel_scale: str = "htk", causal: bool = False):
         torch.nn.Module.__init__(self)
         self.n_mfcc = n_mfcc
+        self.causal = bool(causal)           # this project's own keyword
         STFT.__init__(self, size=size, shift=shift, window_length=window_length, pad=pad,
                       fading=fading, output_size=output_size, window=window)
         # every option of feature_extractor_torchaudio.py:22-39 (round 5; the shipped configs use the defaults): the mel scale
@@ -271,14 +340,22 @@ class TorchMFCC(STFT, torch.nn.Module):
     def _get_output_size(self, output_size):
         return self.n_mfcc if output_size is None else output_size
 
-    def stft_to_feature(self, stft_signals):
+    def stft_to_feature(self, stft_signals, state=None, return_state=False):
+        """causal=True: floor[b,t] = max over t' <= t and m of dB - top_db, per utterance (``state`` / return_state as in
+        Log1pMaxNormAbsSTFT)."""
         X = stft_signals
         if X.dim() == 2:        # un-batched example: the dB floor is per utterance (torchaudio 2-D case)
-            return self.stft_to_feature(X[None])[0]
+            out = self.stft_to_feature(X[None], state, return_state)
+            return (out[0][0], out[1]) if return_state else out[0]
         assert X.dim() == 3, X.shape
         self._check_feature_bins()
-        out, _ = H.feat_fwd(X, self.fb, self.dct_mat, self.n_mfcc, self._db_arg)
-        return out[..., :self.n_mfcc]
+        if self.causal:
+            out, _, state = H.feat_causal_fwd(X, self.fb, self.dct_mat, self.n_mfcc, self._db_arg, state=state)
+        else:
+            _no_state(self, state)
+            out, _ = H.feat_fwd(X, self.fb, self.dct_mat, self.n_mfcc, self._db_arg)
+        out = out[..., :self.n_mfcc]
+        return (out, state) if return_state else out
 
     @property
     def _db_arg(self):
@@ -363,19 +440,25 @@ class ConcaternatedSTFTFeatures(STFT, torch.nn.Module):
     def finalize_dogmatic_config(cls, config):               # feature_extractor.py:308-321
         for fe in ["fe1", "fe2"]:
             if isinstance(config.get(fe), dict):
-                for k in ("size", "shift", "pad", "fading", "window"):
+                for k in ("size", "shift", "pad", "fading", "window", "causal"):
                     if k in config:
                         config[fe][k] = config[k]
                 if config.get("window_length") is not None:
                     config[fe]["window_length"] = config["window_length"]
 
     def __init__(self, fe1, fe2, output_size=None, size=1024, shift=256, window="blackman",
-                 window_length=None, pad=True, fading=True):
+                 window_length=None, pad=True, fading=True, causal=False):
         torch.nn.Module.__init__(self)
         self._tmp = [fe1, fe2]
         STFT.__init__(self, size=size, shift=shift, window_length=window_length, pad=pad,
                       fading=fading, output_size=output_size, window=window)
         self.fe1, self.fe2 = fe1, fe2
+        # causal (this project's own keyword) reaches the parts through finalize_dogmatic_config; what the
+        # object IS follows from the parts it holds
+        self.causal = bool(getattr(fe1, "causal", False) and getattr(fe2, "causal", False))
+        if causal and not self.causal:
+            raise ValueError("ConcaternatedSTFTFeatures(causal=True) needs causal parts: build fe1 and fe2 with causal=True "
+                             "(from a config the key is propagated to them)")
 
     def _get_output_size(self, output_size):
         fe1, fe2 = self._tmp
@@ -383,14 +466,32 @@ class ConcaternatedSTFTFeatures(STFT, torch.nn.Module):
             return fe1._get_output_size(None) + fe2._get_output_size(None)
         return output_size
 
-    def stft_to_feature(self, stft_signals):
+    def stft_to_feature(self, stft_signals, state=None, return_state=False):
+        """Both parts causal: ``state`` [B, 2] / return_state as in the parts (one state serves both: the running max |X|
+        and the running max dB)."""
         X = stft_signals
         if X.dim() == 2:
-            return self.stft_to_feature(X[None])[0]
-        if isinstance(self.fe1, TorchMFCC) and isinstance(self.fe2, Log1pMaxNormAbsSTFT) \
-                and X.dim() == 3:
+            out = self.stft_to_feature(X[None], state, return_state)
+            return (out[0][0], out[1]) if return_state else out[0]
+        fused = isinstance(self.fe1, TorchMFCC) and isinstance(self.fe2, Log1pMaxNormAbsSTFT) and X.dim() == 3
+        if fused and self.causal and self.fe2.statistics_axis == "tf":
+            out, _, state = H.feat_causal_fwd(X, self.fe1.fb, self.fe1.dct_mat, self.fe1.n_mfcc, self.fe1._db_arg,
+                                              state=state)
+            return (out, state) if return_state else out
+        if self.causal:
+            # (causal parts the fused kernel does not cover -- 'f' statistics: each part with the state, whose columns are
+            # disjoint: the MFCC's dB maximum, the log1p's |X| maximum)
+            o1, s1 = self.fe1.stft_to_feature(X, state, True)
+            o2, s2 = self.fe2.stft_to_feature(X, state, True)
+            if s2 is not None and s1 is not None:
+                s1 = torch.stack([s2[:, 0], s1[:, 1]], dim=1)
+            out = torch.concat([o1, o2], dim=-1)
+            return (out, s1) if return_state else out
+        _no_state(self, state)
+        if fused and not self.fe1.causal and not self.fe2.causal:
             # one fused pass pair writes [mfcc | log1p] side by side (feature_extractor.py:352-360)
             out, _ = H.feat_fwd(X, self.fe1.fb, self.fe1.dct_mat, self.fe1.n_mfcc, self.fe1._db_arg,
                                 statistics_axis=self.fe2.statistics_axis)
-            return out
-        return torch.concat([self.fe1.stft_to_feature(X), self.fe2.stft_to_feature(X)], dim=-1)
+        else:
+            out = torch.concat([self.fe1.stft_to_feature(X), self.fe2.stft_to_feature(X)], dim=-1)
+        return (out, None) if return_state else out

@@ -390,6 +390,15 @@ class Model(Configurable, torch.nn.Module):
         out._lazy = out._lazy0 = lazy
         return out
 
+    def online(self, aux, record=False):
+        """An `OnlineSeparator` for one stream (or one batch of streams) of this model: audio chunks in, separated audio
+        chunks out (train/online.py).  aux: what ``mask_estimator.forward_chunk`` takes at its first chunk.
+        Refused on the arguments alone: a trunk that is not rnn_typ='lstm' or features with utterance-wide statistics
+        (ValueError); an enhancer other than Masking, nmask != 1, output_resolution='t', an STFT other than the plain
+        1024 / 256 one, and whatever forward_chunk refuses (NotImplementedError)."""
+        from .online import OnlineSeparator
+        return OnlineSeparator(self, aux, record=record)
+
     def _forward_masks(self, ex):
         """nmask > 1: mask and logit [..., K, M, T, F] come out of one fused kernel (functional.head_masks) and go to the
         enhancer as they are -- TorchBF with differentiable=True while training, any TorchBF under no_grad."""

@@ -422,10 +422,25 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         embedding (computed ONCE, aux_net / aux_normalizer included; `aux` is not read again), and the frames consumed.
         Chunks of any lengths give what `forward` gives on their concatenation within the layers' error bounds: the
         recurrence continues from the very bits it stopped at; a GEMM over another number of rows may round differently."""
+        res, unbatched, state = self._chunk_logits(xs, aux, state)
+        with torch.no_grad():
+            out = self._output(tuple(r[0] for r in res) if unbatched else res)
+        return out, state
+
+    def _check_chunkable(self, aux=None):
+        """What forward_chunk refuses, from the arguments alone (nothing is launched)."""
         if self.rnn_typ != "lstm":
             raise ValueError(f"forward_chunk needs rnn_typ='lstm': {self.rnn_typ!r} reads the future of every frame")
         if self.input_normalizer is not None:
             raise NotImplementedError("forward_chunk with input_normalizer: its statistics span the utterance")
+        if aux is not None and not isinstance(self.aux_net, AuxNet) and _aux_ndim(aux) == 4:
+            raise NotImplementedError("forward_chunk with a frame-wise aux [B, K, Ta, E]: an embedding per frame "
+                                      "would have to arrive with the frames (not built)")
+
+    def _chunk_logits(self, xs, aux, state=None):
+        """forward_chunk in front of the Output: -> (what `logits` returns for these frames -- batched, the head's rows as
+        they are --, whether xs came un-batched, the new state).  The online separator feeds the rows to the fused tail."""
+        self._check_chunkable()
         unbatched = xs.dim() == 2
         if unbatched:
             xs, aux = xs[None], ([aux] if state is None else aux)
@@ -434,18 +449,15 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         B, T = xs.shape[0], xs.shape[1]
         with torch.no_grad():
             if state is None:
-                if not isinstance(self.aux_net, AuxNet) and _aux_ndim(aux) == 4:
-                    raise NotImplementedError("forward_chunk with a frame-wise aux [B, K, Ta, E]: an embedding per frame "
-                                              "would have to arrive with the frames (not built)")
+                self._check_chunkable(aux)
                 emb, perm_d, iperm_d, K = self._embedding(aux, B, T, xs.device)
                 state = ChunkState(layers=None, perm=perm_d, iperm=iperm_d, embedding=emb, K=K, frames=0)
             elif not isinstance(state, ChunkState):
                 raise TypeError(f"state: what forward_chunk returned, not {type(state).__name__}")
             layers = []
             res = self._trunk(xs, state.embedding, state.perm, state.iperm, state.K, prev=state.layers, states=layers)
-            out = self._output(tuple(r[0] for r in res) if unbatched else res)
-        return out, ChunkState(layers=layers, perm=state.perm, iperm=state.iperm, embedding=state.embedding, K=state.K,
-                               frames=state.frames + T)
+        return res, unbatched, ChunkState(layers=layers, perm=state.perm, iperm=state.iperm, embedding=state.embedding,
+                                          K=state.K, frames=state.frames + T)
 
     def _output(self, res) -> Output:
         if self.nmask > 1:                         # [..., K, M, T, F] as they are (net.py:631-659, 983)
