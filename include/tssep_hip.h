@@ -788,6 +788,28 @@ int tssep_mvdr_souden_bwd(const double* obs, const void* masks, int mask_f64, co
                           int M, int D, int64_t T, int F, int reference_channel, double eps, int masking,
                           double masking_eps, void* stream);
 
+/* Online (frame-recursive) MVDR -- this project's own, the reference has no online mode.  Per batch
+ * element b, speaker k and bin f, for the T frames of the call in order, one mask per speaker:
+ *   Phi_s = forgetting Phi_s + m y y^H          Phi_n = forgetting Phi_n + (1 - m) y y^H
+ *   phi   = solve(Phi_n + diag_load Re tr(Phi_s + Phi_n) / D I, Phi_s)       (the elimination of tssep_mvdr_weights)
+ *   enh   = (phi[:, reference_channel] / max(Re tr phi, eps))^H y            (* max(m, masking_eps) if masking)
+ * The filter of a frame uses the statistics up to and including that frame.  While the trace is exactly zero the
+ * output is zero; a singular loaded Phi_n (diag_load = 0 in front of frame D - 1) leaves Inf / NaN in that frame's
+ * output element only.  forgetting in (0, 1], diag_load >= 0 (else TSSEP_E_SHAPE).
+ * obs   [B,D,T,F] complex128 (obs_f64 = 1, 16-byte aligned) or complex64 (obs_f64 = 0, 8-byte aligned), D <= 8
+ * masks [B,K,T,F] fp32 (mask_f64 = 0) or fp64;      enh [B,K,T,F] complex128
+ * state doubles [B][K][2: Phi_s, Phi_n][D*D][F], packed Hermitian like the statistics (rows 0..D-1 the diagonal, then
+ *   for every pair i < j in row-major order the rows Re, Im): tssep_mvdr_online_state_bytes() bytes (host-only, 0 for
+ *   an unsupported shape).  state_in NULL: a fresh stream (zeros); state_in == state_out is allowed.
+ * One launch, one step per frame in a fixed order: output and state do not depend on how a stream's frames are split
+ * over calls.  Algorithmic HBM bytes: T*F*(8|16)*D (Y; once per speaker out of L2) + K*T*F*(sizeof(mask) + 16)
+ * + 2 * 16*K*D*D*F (the state in and out), per batch element.  No workspace, no atomics, no host sync. */
+int64_t tssep_mvdr_online_state_bytes(int64_t B, int K, int D, int F);
+int tssep_mvdr_online_fwd(const void* obs, int obs_f64, const void* masks, int mask_f64,
+                          const double* state_in, double* state_out, double* enh, int64_t B, int K, int D,
+                          int64_t T, int F, int reference_channel, double forgetting, double diag_load,
+                          double eps, int masking, double masking_eps, void* stream);
+
 /* Segment-wise MVDR: ClassicBF_np('mvdr_souden') of the reference with segment_bf=True,
  * tssep/train/enhancer.py:451-590, one beamformer per row (k, s, e) of a segment table:
  *   n_k         = max(sum_{j != k} m_j, distortion_eps)   mode 0, SumCrossTalker (ascending j,

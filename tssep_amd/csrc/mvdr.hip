@@ -21,7 +21,8 @@
 //                             for the speakers of a group.
 // The segment-wise pipeline of ClassicBF_np (one beamformer per activity interval of a speaker, the
 // distortion mask taken from the other speakers' masks) and the backward of the dense pipeline
-// follow in this file; the segments share the solve kernels.  The statistics pass and the first
+// follow in this file, and last the frame-recursive (online) MVDR, one kernel; the segments share the solve kernels.
+// The statistics pass and the first
 // time pass of the backward run on one frame pipeline (decode_time_tile / frame_pipeline).
 #include "common.h"
 
@@ -1588,4 +1589,256 @@ extern "C" int tssep_mvdr_souden_bwd(const double* obs, const void* masks, int m
   if (st != TSSEP_OK) return st;
   return tssep_mvdr_bwd_mask(obs, genh, wconj, herm, masks, mask_f64, dmask, B, K, M, D, T, F, masking, masking_eps,
                              stream);
+}
+
+// ------------------------------------------------------------------ online (frame-recursive) MVDR ----
+// This project's own (the reference has no online mode).  Per (b, speaker k, bin f), frame by frame:
+//   Phi_s = alpha Phi_s + m y y^H        Phi_n = alpha Phi_n + (1 - m) y y^H        l = delta Re tr(Phi_s + Phi_n) / D
+//   phi   = solve(Phi_n + l I, Phi_s)    w = phi[:, ref] / max(Re tr phi, eps)      enh = w^H y  (* max(m, masking_eps))
+// The filter of frame t is made of the statistics up to and including t.  With alpha = 1, delta = 0 the filter of the
+// last frame is the one tssep_mvdr_souden_fwd applies to the whole utterance.  While the trace is exactly zero (digital
+// silence since the stream began) the output is zero and nothing is solved.  A frame whose loaded Phi_n is singular
+// (delta = 0 in front of frame D - 1) leaves Inf / NaN in its own output element only: the statistics never read phi.
+// One launch does all T frames of a call: one wave per (b, k, 64 bins), lane = bin, the two packed Hermitian
+// accumulators in registers across the frame loop -- read from state_in (NULL: zeros) at entry, written to state_out at
+// exit -- and one step per frame in a fixed order, so the result is the same however the frames are split over calls.
+// The K waves of a (b, 64 bins) tile read the same Y frames: xcd_tile places them on one XCD, whose L2 serves the
+// tile after the first of them fetched it (a per-step workgroup barrier for an LDS hand-over would sit in a sequential
+// chain of a few microseconds per frame to save 16 D bytes per lane, and D = 7, 8 need the LDS of a CU for one wave).
+namespace {
+
+// [A | X] -> X = A^-1 X on matrices 0 (A) and 1 (X) of a Sys3: the elimination of mvdr_solve_kernel / mvdr_bwd_solve_kernel
+// (first maximum of |re| + |im| down the column, exchanges as selects, crecip of the pivot, rows top to bottom), in
+// registers or on the LDS [element][lane] layout, whatever S is.  A zero pivot divides by zero in its own lane.
+template <int D, typename S> __device__ __forceinline__ void lu_solve(S& s) {
+  enum { A = 0, X = 1 };
+#pragma unroll
+  for (int p = 0; p < D; ++p) {
+    int piv = p;
+    double best = fabs(s.get(A, p, p).x) + fabs(s.get(A, p, p).y);
+#pragma unroll
+    for (int i = p + 1; i < D; ++i) {
+      const double2 a = s.get(A, i, p);
+      const double v = fabs(a.x) + fabs(a.y);
+      if (v > best) { best = v; piv = i; }
+    }
+#pragma unroll
+    for (int i = p + 1; i < D; ++i) {
+      const bool sw = piv == i;
+#pragma unroll
+      for (int j = p; j < D; ++j) {
+        const double2 t = s.get(A, p, j), u = s.get(A, i, j);
+        s.set(A, p, j, sel(sw, u, t));
+        s.set(A, i, j, sel(sw, t, u));
+      }
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        const double2 t = s.get(X, p, j), u = s.get(X, i, j);
+        s.set(X, p, j, sel(sw, u, t));
+        s.set(X, i, j, sel(sw, t, u));
+      }
+    }
+    const double2 r = crecip(s.get(A, p, p));
+#pragma unroll
+    for (int i = p + 1; i < D; ++i) {
+      const double2 l = cmul(s.get(A, i, p), r);
+#pragma unroll
+      for (int j = p + 1; j < D; ++j) {
+        const double2 a = s.get(A, p, j), x = s.get(A, i, j);
+        s.set(A, i, j, double2{x.x - (l.x * a.x - l.y * a.y), x.y - (l.x * a.y + l.y * a.x)});
+      }
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        const double2 a = s.get(X, p, j), x = s.get(X, i, j);
+        s.set(X, i, j, double2{x.x - (l.x * a.x - l.y * a.y), x.y - (l.x * a.y + l.y * a.x)});
+      }
+    }
+  }
+#pragma unroll
+  for (int i = D - 1; i >= 0; --i) {
+    const double2 r = crecip(s.get(A, i, i));
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      double2 acc = s.get(X, i, j);
+#pragma unroll
+      for (int q = i + 1; q < D; ++q) {
+        const double2 a = s.get(A, i, q), x = s.get(X, q, j);
+        acc.x -= a.x * x.x - a.y * x.y;
+        acc.y -= a.x * x.y + a.y * x.x;
+      }
+      s.set(X, i, j, cmul(acc, r));
+    }
+  }
+}
+
+constexpr size_t online_lds(int D) { return bwd_in_registers(D) ? 0 : (size_t)2 * D * D * 64 * sizeof(double2); }
+
+// obs [B,D,T,F] complex128 (obs_f64) or complex64; masks [B,K,T,F]; state [B,K,2,D*D,F] packed Hermitian (0: Phi_s,
+// 1: Phi_n); enh [B,K,T,F] complex128.  state_in may be state_out: a lane reads its elements before it writes them.
+template <int D, typename MT>
+__global__ __launch_bounds__(64) void mvdr_online_kernel(
+    const void* __restrict__ obs, int obs_f64, const MT* __restrict__ masks, const double* state_in, double* state_out,
+    double2* __restrict__ enh, int64_t B, int K, int64_t T, int F, int ref, double alpha, double delta, double eps,
+    int masking, double masking_eps) {
+  constexpr bool REG = bwd_in_registers(D);
+  constexpr int DD = D * D, NP = D * (D - 1) / 2;
+  extern __shared__ double2 sm[];
+  const int nf = (F + 63) / 64;
+  int64_t tile;
+  int k;
+  if (!xcd_tile(blockIdx.x, K, B * nf, tile, k)) return;
+  const int64_t b = tile / nf;
+  const int f = (int)(tile % nf) * 64 + (int)threadIdx.x;
+  if (f >= F) return;                                      // (one wave, no barrier, LDS columns are per lane)
+  const int64_t bk = b * K + k;
+
+  double diag[2][D];
+  double2 off[2][NP + 1];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const double* q = state_in ? state_in + (bk * 2 + m) * (int64_t)DD * F + f : nullptr;
+#pragma unroll
+    for (int i = 0; i < D; ++i) diag[m][i] = q ? q[(int64_t)i * F] : 0.0;
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+      off[m][p] = q ? double2{q[(int64_t)(D + 2 * p) * F], q[(int64_t)(D + 2 * p + 1) * F]} : double2{0.0, 0.0};
+  }
+  const MT* mk = masks + bk * T * F + f;
+  double2* out = enh + bk * T * F + f;
+  const int64_t y0 = b * D * T * F + f;
+  Sys3<D, REG, 64> S;
+  S.s = sm + threadIdx.x;
+  enum { A = 0, X = 1 };
+
+#pragma unroll 1
+  for (int64_t t = 0; t < T; ++t) {
+    double2 y[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const int64_t i = y0 + (d * T + t) * F;
+      if (obs_f64) {
+        y[d] = static_cast<const double2*>(obs)[i];
+      } else {
+        const float2 v = static_cast<const float2*>(obs)[i];
+        y[d] = double2{(double)v.x, (double)v.y};
+      }
+    }
+    const double w0 = (double)mk[t * F];
+    const double w1 = 1.0 - w0;
+    // the statistics pass's products y_i conj(y_j), behind the forgetting factor
+    double tr = 0.0;
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const double pd = y[i].x * y[i].x + y[i].y * y[i].y;
+      diag[0][i] = alpha * diag[0][i] + w0 * pd;
+      diag[1][i] = alpha * diag[1][i] + w1 * pd;
+      tr += diag[0][i] + diag[1][i];
+#pragma unroll
+      for (int j = i + 1; j < D; ++j, ++p) {
+        const double pr = y[i].x * y[j].x + y[i].y * y[j].y;
+        const double pi = y[i].y * y[j].x - y[i].x * y[j].y;
+        off[0][p].x = alpha * off[0][p].x + w0 * pr;
+        off[0][p].y = alpha * off[0][p].y + w0 * pi;
+        off[1][p].x = alpha * off[1][p].x + w1 * pr;
+        off[1][p].y = alpha * off[1][p].y + w1 * pi;
+      }
+    }
+    double2 e = {0.0, 0.0};
+    if (tr != 0.0) {                                       // (a NaN trace goes through the solve and stays NaN)
+      const double load = delta * tr / (double)D;
+      p = 0;
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        S.set(A, i, i, double2{diag[1][i] + load, 0.0});
+        S.set(X, i, i, double2{diag[0][i], 0.0});
+#pragma unroll
+        for (int j = i + 1; j < D; ++j, ++p) {
+          S.set(A, i, j, off[1][p]);
+          S.set(A, j, i, double2{off[1][p].x, -off[1][p].y});
+          S.set(X, i, j, off[0][p]);
+          S.set(X, j, i, double2{off[0][p].x, -off[0][p].y});
+        }
+      }
+      lu_solve<D>(S);
+      double lam = 0.0;
+#pragma unroll
+      for (int i = 0; i < D; ++i) lam += S.get(X, i, i).x;
+      if (lam < eps) lam = eps;
+      const double scl = 1.0 / lam;
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        double2 v = S.get(X, d, 0);
+#pragma unroll
+        for (int c = 1; c < D; ++c) v = sel(ref == c, S.get(X, d, c), v);
+        const double2 w = {v.x * scl, -(v.y * scl)};       // conj(w_d), as mvdr_apply_kernel takes it
+        e.x += w.x * y[d].x - w.y * y[d].y;
+        e.y += w.x * y[d].y + w.y * y[d].x;
+      }
+      if (masking) {
+        double g = w0;
+        if (g < masking_eps) g = masking_eps;
+        e.x *= g;
+        e.y *= g;
+      }
+    }
+    out[t * F] = e;
+  }
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+    store_packed_herm<D>(state_out + (bk * 2 + m) * (int64_t)DD * F + f, F, diag[m], off[m]);
+}
+
+template <int D>
+int launch_online(const void* obs, int obs_f64, const void* masks, int mask_f64, const double* state_in,
+                  double* state_out, double* enh, int64_t B, int K, int64_t T, int F, int ref, double alpha,
+                  double delta, double eps, int masking, double masking_eps, hipStream_t s) {
+  const int64_t grid = xcd_grid(B * ((F + 63) / 64), K);
+  int attr = TSSEP_OK;
+  const int st = launch_mt(mask_f64, masks, [&](auto* mk) {
+    auto kernel = mvdr_online_kernel<D, mask_t<decltype(mk)>>;
+    if (online_lds(D) > 64 * 1024) {                       // D = 7, 8: more than the default 64 KB of dynamic LDS
+      static bool attr_set = false;                        // (one per instantiation of this lambda)
+      if (!attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)online_lds(D)) != hipSuccess) {
+          attr = TSSEP_E_LAUNCH;
+          return;
+        }
+        attr_set = true;
+      }
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64), online_lds(D), s, obs, obs_f64, mk, state_in,
+                       state_out, reinterpret_cast<double2*>(enh), B, K, T, F, ref, alpha, delta, eps, masking,
+                       masking_eps);
+  });
+  return attr != TSSEP_OK ? attr : st;
+}
+
+}  // namespace
+
+extern "C" int64_t tssep_mvdr_online_state_bytes(int64_t B, int K, int D, int F) {
+  if (B <= 0 || K <= 0 || D <= 0 || D > MAXD || F <= 0) return 0;
+  return B * K * 2 * (int64_t)(D * D) * F * (int64_t)sizeof(double);
+}
+
+extern "C" int tssep_mvdr_online_fwd(const void* obs, int obs_f64, const void* masks, int mask_f64,
+                                     const double* state_in, double* state_out, double* enh, int64_t B, int K,
+                                     int D, int64_t T, int F, int reference_channel, double forgetting,
+                                     double diag_load, double eps, int masking, double masking_eps, void* stream) {
+  if (!obs || !masks || !state_out || !enh) return TSSEP_E_NULL;
+  if (B <= 0 || K <= 0 || D <= 0 || T <= 0 || F <= 0 || reference_channel < 0 || reference_channel >= D ||
+      !(forgetting > 0.0 && forgetting <= 1.0) || !(diag_load >= 0.0))
+    return TSSEP_E_SHAPE;
+  if (D > MAXD) return TSSEP_E_UNSUPPORTED;
+  if (xcd_grid(B * ((F + 63) / 64), K) >= ((int64_t)1 << 31) || B * (K > D ? K : D) * T * F >= ((int64_t)1 << 40))
+    return TSSEP_E_SHAPE;
+  if (!aligned16(enh) || (((uintptr_t)obs) & (obs_f64 ? 15u : 7u)) || (((uintptr_t)state_out) & 7u) ||
+      (((uintptr_t)state_in) & 7u))
+    return TSSEP_E_ALIGN;
+#define CALL(DD)                                                                                                 \
+  launch_online<DD>(obs, obs_f64, masks, mask_f64, state_in, state_out, enh, B, K, T, F, reference_channel,      \
+                    forgetting, diag_load, eps, masking, masking_eps, (hipStream_t)stream)
+  DISPATCH_D(D, CALL)
+#undef CALL
 }

@@ -1593,6 +1593,69 @@ def mvdr_souden_bwd(genh, state):
     return dmask
 
 
+def online_mvdr_check(masks, Y, state=None, reference_channel=0, forgetting=1.0, diag_load=1e-6):
+    """What `online_mvdr` refuses, from the arguments alone (CPU tensors do: nothing is launched) -> masks [B,K,Tc,F]."""
+    if masks.dim() == 5:
+        if masks.shape[2] != 1:
+            raise NotImplementedError(f"online_mvdr with nmask = {masks.shape[2]} (masks {tuple(masks.shape)}): the "
+                                      "recursion takes one mask per speaker, the interference is 1 - mask")
+        masks = masks[:, :, 0]
+    if masks.dim() != 4 or Y.dim() != 4:
+        raise ValueError(f"online_mvdr: masks [B,K,1,Tc,F] or [B,K,Tc,F] and Y [B,D,Tc,F], got {tuple(masks.shape)} and "
+                         f"{tuple(Y.shape)}")
+    B, K, T, F = masks.shape
+    Bo, D, To, Fo = Y.shape
+    if (B, T, F) != (Bo, To, Fo):
+        raise ValueError(f"online_mvdr: masks {tuple(masks.shape)} and Y {tuple(Y.shape)} differ in batch, frames or bins")
+    if min(B, K, T, F, D) < 1 or D > 8:
+        raise ValueError(f"online_mvdr: empty axis or more than 8 channels: masks {tuple(masks.shape)}, Y {tuple(Y.shape)}")
+    if Y.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError(f"online_mvdr: Y is {Y.dtype}, complex64 or complex128 is required")
+    if masks.is_complex():
+        raise TypeError(f"online_mvdr: masks are {masks.dtype}")
+    if not 0 <= int(reference_channel) < D:
+        raise ValueError(f"online_mvdr: reference_channel = {reference_channel} of {D} channels")
+    if not 0.0 < float(forgetting) <= 1.0:
+        raise ValueError(f"online_mvdr: forgetting = {forgetting} lies outside (0, 1]")
+    if not float(diag_load) >= 0.0:
+        raise ValueError(f"online_mvdr: diag_load = {diag_load} is negative")
+    if state is not None and (state.dtype != torch.float64 or tuple(state.shape) != (B, K, 2, D * D, F)):
+        raise ValueError(f"online_mvdr: state is {state.dtype} {tuple(state.shape)}, what a call with K = {K} speakers, "
+                         f"D = {D} channels and F = {F} bins carries is float64 {(B, K, 2, D * D, F)} (a channel or "
+                         "speaker mismatch between the calls of a stream?)")
+    return masks
+
+
+def online_mvdr(masks, Y, state=None, reference_channel=0, forgetting=1.0, diag_load=1e-6, eps=None, masking=False,
+                masking_eps=0.0):
+    """The frame-recursive MVDR of DESIGN 4.18 on the next Tc frames of a stream: masks [B,K,1,Tc,F] or [B,K,Tc,F] fp32 |
+    fp64, Y [B,D,Tc,F] complex64 | complex128, state what the call before returned (None: a fresh stream) ->
+    (enh [B,K,Tc,F] complex128, the new state: float64 [B,K,2,D*D,F], the packed Hermitian Phi_s and Phi_n).  masking_eps
+    is compared in the masks' dtype, as in mvdr_souden; eps None = torch.finfo(float64).tiny.  One launch, no host sync; output and state do not depend on how the frames are split over calls."""
+    masks = online_mvdr_check(masks, Y, state, reference_channel, forgetting, diag_load)
+    L = _lib.lib()
+    assert masks.is_cuda and Y.is_cuda and (state is None or state.is_cuda), (masks.device, Y.device)
+    if masks.dtype not in (torch.float32, torch.float64):
+        masks = masks.to(torch.float64)
+    masks = masks.contiguous()
+    B, K, T, F = masks.shape
+    D = Y.shape[1]
+    y_r = torch.view_as_real(Y.contiguous())
+    state = None if state is None else state.contiguous()
+    assert L.tssep_mvdr_online_state_bytes(B, K, D, F) == 8 * B * K * 2 * D * D * F
+    state_out = torch.empty(B, K, 2, D * D, F, device=Y.device, dtype=torch.float64)
+    enh = torch.empty(B, K, T, F, 2, device=Y.device, dtype=torch.float64)
+    eps = float(torch.finfo(torch.float64).tiny) if eps is None else float(eps)
+    masking_eps = float(torch.tensor(float(masking_eps), dtype=masks.dtype))      # compared in the mask's dtype, as mvdr_souden
+    nbytes = B * T * F * (y_r.element_size() * 2 * D + K * (masks.element_size() + 16)) + 32 * B * K * D * D * F
+    with _timed("mvdr_online", 0, nbytes):
+        check(L.tssep_mvdr_online_fwd(_p(y_r), int(Y.dtype == torch.complex128), _p(masks),
+                                      int(masks.dtype == torch.float64), _p(state), _p(state_out), _p(enh), B, K, D, T, F,
+                                      int(reference_channel), float(forgetting), float(diag_load), eps,
+                                      int(bool(masking)), masking_eps, _stream()), "mvdr_online")
+    return torch.view_as_complex(enh), state_out
+
+
 DISTORTION_MODES = {"sum_cross_talker": 0, "one_minus": 1}
 
 

@@ -127,6 +127,46 @@ class TorchBF(ABC):
         return enh if batched else enh[0]
 
 
+class OnlineMVDR(ABC):
+    """Frame-recursive mask-based MVDR -- THIS PROJECT'S enhancer, the reference has no online mode: the
+    PSDs of TorchBF grow (or forget, ``forgetting`` < 1) frame by frame, and frame t is filtered with the Souden filter of
+    the statistics up to and including t, the interference PSD loaded with ``diag_load`` times the mean channel power.
+    One HIP kernel (hip_ops.online_mvdr, csrc/mvdr.hip).  Called on a whole utterance like TorchBF it runs the recursion
+    over all T frames in one launch -- what ``Model.online`` streams, chunk by chunk, bit for bit; with forgetting=1 and
+    diag_load=0 its last frame is TorchBF's.  Evaluation only (there is no backward), one mask per speaker.  Neither
+    default is tuned."""
+
+    def __init__(self, forgetting=1.0, diag_load=1e-6, eps=None, masking=False, masking_eps=0.0):
+        super().__init__()
+        self.forgetting = forgetting
+        self.diag_load = diag_load
+        self.eps = eps
+        self.masking = masking
+        self.masking_eps = masking_eps
+
+    def _kwargs(self):
+        return dict(forgetting=self.forgetting, diag_load=self.diag_load, eps=self.eps, masking=self.masking,
+                    masking_eps=self.masking_eps)
+
+    def chunk(self, masks, Y, state, reference_channel):
+        """The next frames of a stream: masks [B,K,(1,)Tc,F], Y [B,D,Tc,F] -> (enh [B,K,Tc,F] complex128, state)."""
+        return H.online_mvdr(masks, Y, state, reference_channel, **self._kwargs())
+
+    def __call__(self, masks, ex, model):
+        """masks [(B,) K, 1, T, F]; ex['Observation'] [(B,) D, T, F] complex64 | complex128 -> [(B,) K, T, F] complex128."""
+        batched = {4: False, 5: True}[len(masks.shape)]
+        Observation = ex["Observation"]
+        assert len(Observation.shape) == (4 if batched else 3), Observation.shape
+        if (masks.requires_grad or Observation.requires_grad) and torch.is_grad_enabled():
+            raise NotImplementedError("OnlineMVDR is an evaluation-time enhancer: call it under torch.no_grad() (the "
+                                      "recursion has no backward; train through Masking or TorchBF(differentiable=True))")
+        if not batched:
+            masks, Observation = masks[None], Observation[None]
+        H.online_mvdr_check(masks, Observation, None, ex["reference_channel"], self.forgetting, self.diag_load)
+        enh, _ = self.chunk(masks.detach(), Observation.detach().to(masks.device), None, ex["reference_channel"])
+        return enh if batched else enh[0]
+
+
 def normalized_intervals(ai, T):
     """One speaker's activity -> [(s, e), ...], sorted, disjoint, non-empty, inside [0, T].
     ai: anything with ``.normalized_intervals`` (paderbox's ArrayInterval), a 0/1 array of length T,

@@ -390,14 +390,16 @@ class Model(Configurable, torch.nn.Module):
         out._lazy = out._lazy0 = lazy
         return out
 
-    def online(self, aux, record=False):
+    def online(self, aux, record=False, reference_channel=0):
         """An `OnlineSeparator` for one stream (or one batch of streams) of this model: audio chunks in, separated audio
         chunks out (train/online.py).  aux: what ``mask_estimator.forward_chunk`` takes at its first chunk.
         Refused on the arguments alone: a trunk that is not rnn_typ='lstm' or features with utterance-wide statistics
-        (ValueError); an enhancer other than Masking, nmask != 1, output_resolution='t', an STFT other than the plain
-        1024 / 256 one, and whatever forward_chunk refuses (NotImplementedError)."""
+        (ValueError); an enhancer other than Masking or OnlineMVDR, nmask != 1, output_resolution='t', an STFT other than
+        the plain 1024 / 256 one, and whatever forward_chunk refuses (NotImplementedError).  With OnlineMVDR the pushes
+        hold all channels, [B, D, n], and ``reference_channel`` is the one the features are taken from and the
+        beamformer is steered to; the Masking route ignores it."""
         from .online import OnlineSeparator
-        return OnlineSeparator(self, aux, record=record)
+        return OnlineSeparator(self, aux, record=record, reference_channel=reference_channel)
 
     def _forward_masks(self, ex):
         """nmask > 1: mask and logit [..., K, M, T, F] come out of one fused kernel (functional.head_masks) and go to the

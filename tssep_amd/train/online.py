@@ -6,7 +6,9 @@
     ->  MaskEstimator_v2's chunk trunk (carried: every layer's (h, c))  ->  fused mask head + streaming inverse STFT
     (carried: the partial sums of the three pending hops)
 
-and returns the samples those frames complete.  The algorithmic latency is size - shift samples (48 ms at 16 kHz).  The
+and returns the samples those frames complete.  With the enhancer `OnlineMVDR` a push holds D channels:
+all of them go through the streaming STFT, features and trunk read the reference channel, and the tail is sigmoid ->
+frame-recursive MVDR (carried: the two PSDs per speaker and bin, a fifth state) -> streaming inverse STFT.  The algorithmic latency is size - shift samples (48 ms at 16 kHz).  The
 frame / hop bookkeeping is `schedule`, a pure function.
 """
 from collections import namedtuple
@@ -64,7 +66,7 @@ def check_online(model, aux=None):
                          "causal=True and train with it")
     if getattr(me, "nmask", 1) != 1:
         raise NotImplementedError(f"online separation with nmask = {me.nmask}: the streaming tail takes one mask per speaker")
-    if not isinstance(model.enhancer, _enh.Masking):
+    if not isinstance(model.enhancer, (_enh.Masking, _enh.OnlineMVDR)):
         raise NotImplementedError(f"online separation with the enhancer {type(model.enhancer).__name__}: only Masking has a "
                                   "streaming tail (multi-channel / beamforming enhancers are not built)")
     if getattr(me, "output_resolution", "tf") != "tf":
@@ -81,19 +83,53 @@ class OnlineSeparator:
     [K, m]), the samples this push completes: (Tc - 3) * shift for the first (none while fewer than four frames
     exist), Tc * shift afterwards.  ``flush(x_last=None)``: the ragged rest (fewer than shift samples) -> the remaining
     samples; the concatenation has exactly the utterance's length and `push` raises afterwards.  ``last``: the last
-    call's `Output` (masks, VAD), formed when read.  record=True keeps every call's ``Observation`` and ``Input``."""
+    call's `Output` (masks, VAD), formed when read.  record=True keeps every call's ``Observation`` and ``Input``.
+    With the enhancer `OnlineMVDR` x is [B, D, n] (un-batched: [D, n]), ``reference_channel`` names the channel the
+    features are taken from and the beamformer is steered to (Masking ignores it)."""
 
-    def __init__(self, model, aux, record=False):
+    def __init__(self, model, aux, record=False, reference_channel=0):
+        from . import enhancer as _enh
         check_online(model, aux)
         self.model, self.fe, self.me = model, model.fe, model.mask_estimator
         self._aux = aux
         self._tail = self._feat = self._trunk = self._ola = None       # the four carried states
+        self._bf = model.enhancer if isinstance(model.enhancer, _enh.OnlineMVDR) else None
+        self._psd = None                                               # the beamformer's fifth: Phi_s, Phi_n
+        self._ref = int(reference_channel)
+        if self._bf is not None and not 0 <= self._ref < 8:
+            raise ValueError(f"reference_channel = {reference_channel}: the beamformer takes at most 8 channels")
+        self._lead = None                                              # the axes of a push in front of the samples
         self.frames = self.samples_in = self.samples_out = 0
         self.closed = False
         self._res = self._un = None
         self.record = [] if record else None
 
+    def _run_bf(self, x, frames, num_samples=None):
+        """x [B, D, n]: STFT of all channels (rows B * D), features and trunk on the reference channel, then
+        sigmoid -> online MVDR -> streaming inverse STFT."""
+        fe = self.fe
+        if not self._ref < x.shape[1]:
+            raise ValueError(f"reference_channel = {self._ref} of {x.shape[1]} channels")
+        with torch.no_grad():
+            X, self._tail = fe.stft_chunk(x, self._tail)                                     # [B, D, Tc, F]
+            feat, self._feat = fe.stft_to_feature(X[:, self._ref].contiguous(), self._feat, True)
+            aux = None if self._trunk is not None else ([self._aux] if self._un else self._aux)
+            res, _, self._trunk = self.me._chunk_logits(feat.to(torch.float32), aux, self._trunk)
+            mask = self.me._output(res).mask                                                 # [B, K, 1, Tc, F]
+            enh, self._psd = self._bf.chunk(mask, X, self._psd, self._ref)
+            skip, _ = _step(self.frames, frames, fe.shift)
+            y, self._ola = fe.istft_chunk(enh, self._ola, skip, num_samples)
+        self._res = res
+        if self.record is not None:
+            self.record.append({"Observation": X, "Input": feat, "logit": res[0], "mask": mask, "Estimate": enh})
+        self.frames += frames
+        self.samples_out += y.shape[-1]
+        return y
+
     def _run(self, x, frames, num_samples=None):
+        self._lead = tuple(x.shape[:-1])
+        if self._bf is not None:
+            return self._run_bf(x, frames, num_samples)
         fe = self.fe
         with torch.no_grad():
             X, self._tail = fe.stft_chunk(x, self._tail)                                     # [B, Tc, F]
@@ -113,9 +149,11 @@ class OnlineSeparator:
         return y
 
     def _batched(self, x):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (1, 2):
-            raise ValueError("push / flush take a float32 tensor [B, n] or [n] on the device")
-        un = x.dim() == 1
+        nd = 1 if self._bf is None else 2
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (nd, nd + 1):
+            raise ValueError("push / flush take a float32 tensor [B, n] or [n] on the device" if nd == 1 else
+                             "push / flush take a float32 tensor [B, D, n] or [D, n] on the device (OnlineMVDR)")
+        un = x.dim() == nd
         if self._un is None:
             self._un = un
         elif un != self._un:
@@ -149,11 +187,11 @@ class OnlineSeparator:
         if self._tail is None and not r:
             raise ValueError("flush without samples on a stream that never saw any")
         owed = fe.frames(N) - self.frames                    # the trailing fade and the padding: 3 frames, or 4
-        rows = x_last.shape[0] if r else self._tail.shape[0]
+        lead = tuple(x_last.shape[:-1]) if r else self._lead
         device = x_last.device if r else self._tail.device
-        x = torch.zeros(rows, owed * fe.shift, device=device, dtype=torch.float32)
+        x = torch.zeros(*lead, owed * fe.shift, device=device, dtype=torch.float32)
         if r:
-            x[:, :r] = x_last
+            x[..., :r] = x_last
         y = self._run(x, owed, num_samples=N - self.samples_out)
         self.samples_in, self.closed = N, True
         return y[0] if self._un else y
