@@ -920,6 +920,32 @@ int tssep_wpe_fwd(const double* obs, const int32_t* segments, const int64_t* row
                   void* workspace, int* info, int S, int64_t N, int D, int64_t T, int F, int taps, int delay,
                   int iterations, int valid_mode, void* stream);
 
+/* Online WPE -- the recursive least squares form, this project's own (the reference has no online mode).
+ * Per batch element b and bin f, for the T frames of the call in order, K = taps * D, Yt as above with zeros in front of
+ * the stream's first frame, a = forgetting, c = power_context:
+ *   p    = sum_{s=t-c..t} sum_d |y_s[d]|^2 / (D (c + 1))         pmax = max(pmax, p) over the finite p
+ *   pmax == 0: x = y, nothing is updated.                        lam = max(p, 1e-10 pmax)
+ *   x    = y - G^H Yt   (the output: G of the frames before t)   u = Q Yt     den = a lam + Re(Yt^H u)
+ *   not (0 < den < inf): info[b] += 1, nothing is updated.       k = u / den
+ *   Q    = (Q - k u^H) / a    (one triangle computed and mirrored, real diagonal; Q_0 = I / load)      G = G + k x^H
+ * obs  [B,D,T,F] complex128 (obs_f64 = 1, 16-byte aligned) or complex64 (0, 8-byte aligned);  out [B,D,T,F] complex128
+ * The state, five buffers, each with a successor (x_in == x_out is allowed; all *_in NULL: a fresh stream):
+ *   q    [B,F,K(K+1)/2] complex128, the lower triangle row by row ((i, j), j <= i, at i(i+1)/2 + j); zeros while pmax == 0
+ *   g    [B,F,K,D] complex128       ring [B,F,R,D] complex128, the last R = max(delay + taps - 1, c) frames, oldest first
+ *        (R = 0: no buffer, NULL is fine)       pmax [B,F] doubles       info [B] ints, counted on over the stream
+ * A state of zeros is a fresh stream, and a stream that has seen only silence leaves zeros.
+ * Limits: D 1..8, taps >= 1, taps * D <= 80, 0 <= delay <= 256, 0 <= power_context <= 256 (TSSEP_E_UNSUPPORTED beyond);
+ * forgetting in (0, 1], load > 0 (else TSSEP_E_SHAPE).  One kernel launch, one workgroup per (b, f) with Q, G and the
+ * ring in LDS (up to 157 KiB) across the frames of the call; every sum runs in an order fixed by (D, taps, delay, c):
+ * output and state do not depend on how a stream's frames are split over calls.  No workspace, no host sync; the only
+ * atomic is the integer count into info.  tssep_wpe_online_state_bytes: the bytes of the five buffers together,
+ * host-only, 0 for an unsupported shape. */
+int64_t tssep_wpe_online_state_bytes(int64_t B, int D, int F, int taps, int delay, int power_context);
+int tssep_wpe_online_fwd(const void* obs, int obs_f64, const double* q_in, const double* g_in, const double* ring_in,
+                         const double* pmax_in, const int* info_in, double* q_out, double* g_out, double* ring_out,
+                         double* pmax_out, int* info_out, double* out, int64_t B, int D, int64_t T, int F, int taps,
+                         int delay, int power_context, double forgetting, double load, void* stream);
+
 /* -------------------------------------------------------------- optimizer -----
  * One optimizer step on flat fp32 buffers: global-norm gradient clipping
  * (torch.nn.utils.clip_grad_norm_, max_norm <= 0 disables) + Adam (torch.optim.Adam update rule,

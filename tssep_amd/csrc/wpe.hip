@@ -20,6 +20,10 @@
 //   wpe_filter_kernel<D>   lane = bin, 4 frames per lane in registers: X = Y - G^H Yt into the packed output
 // No access leaves the buffers whatever the table holds: rows are clamped to [0, T], packed indices are checked
 // against N.
+//
+// The online (recursive least squares) form, DESIGN 4.19, is one more kernel at the end of the file:
+//   wpe_online_kernel      one workgroup per (batch element, bin): Q (both triangles, rows padded to an odd count), G and
+//                          the ring of the last frames in LDS across the frames of a call, one rank-one update per frame
 #include <atomic>
 
 #include "common.h"
@@ -534,6 +538,257 @@ int check_args(int S, int64_t N, int D, int64_t T, int F, int taps, int delay) {
   return wpe_shape_ok(S, N, D, T, F, taps, delay) ? TSSEP_OK : TSSEP_E_SHAPE;
 }
 
+// --------------------------------------------------------------------------- online (RLS) ----
+// Per (b, f), frame by frame (Yt as above, zeros in front of the stream; a = forgetting, c = power_context):
+//   p = sum_{s=t-c..t} sum_d |y_s[d]|^2 / (D (c + 1))     pmax = max(pmax, p) over the finite p
+//   pmax == 0: x = y, nothing moves.   lam = max(p, 1e-10 pmax)
+//   x = y - G^H Yt (the output)        u = Q Yt      den = a lam + Re(Yt^H u)      not (0 < den < inf): info += 1, nothing moves
+//   k = u / den       Q = (Q - k u^H) / a   (lower triangle computed, mirrored, real diagonal)       G += k x^H
+// LDS: Q [K][K | 1] with both triangles (an odd row stride: the rows of a matrix-vector product fall on different banks),
+// G transposed [D][K], the ring [R + 1][D] (R = max(delay + taps - 1, c) carried frames and the current one), Yt, u, k [K],
+// x [D].  The matrix-vector products split a row over S lanes of a wave (S from K + D alone), joined by xor shuffles; den is
+// summed per wave by the same butterfly, so every thread holds the same bits and every branch is uniform.  Four barriers
+// per frame.  The state in memory holds the lower triangle only, and zeros for Q while pmax == 0 (a stream that has seen
+// nothing but silence carries the state of a fresh one: all zeros).
+constexpr int OMAXPC = 256;
+constexpr int ONTRI = (WMAXK * (WMAXK + 1) / 2 + 255) / 256;      // triangle entries per thread
+constexpr size_t OMAXLDS =
+    (size_t)(WMAXK * (WMAXK | 1) + WMAXK * WMAXD + (WMAXDELAY + WMAXK) * WMAXD + 3 * WMAXK + WMAXD) * 16;
+
+struct OLay { int K, LD, R, S, ntri; size_t lds; };
+__host__ OLay online_lay(int D, int taps, int delay, int pc) {
+  OLay l;
+  l.K = taps * D;
+  l.LD = l.K | 1;
+  const int hist = delay + taps - 1;
+  l.R = hist > pc ? hist : pc;
+  l.S = 1;
+  while (l.S < 8 && 2 * l.S * (l.K + D) <= 256) l.S *= 2;
+  l.ntri = l.K * (l.K + 1) / 2;
+  l.lds = (size_t)(l.K * l.LD + D * l.K + (l.R + 1) * D + 3 * l.K + D) * 16;
+  return l;
+}
+__host__ int online_args(int64_t B, int D, int64_t T, int F, int taps, int delay, int pc) {
+  if (B <= 0 || D < 1 || T <= 0 || F <= 0 || taps < 1 || delay < 0 || pc < 0) return TSSEP_E_SHAPE;
+  if (D > WMAXD || (int64_t)taps * D > WMAXK || delay > WMAXDELAY || pc > OMAXPC) return TSSEP_E_UNSUPPORTED;
+  if (B * F >= ((int64_t)1 << 30) || T >= ((int64_t)1 << 30) || B * D * T * F >= ((int64_t)1 << 40)) return TSSEP_E_SHAPE;
+  return TSSEP_OK;
+}
+
+__device__ __forceinline__ int tri_row(int idx) {
+  int i = (int)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);
+  while (i * (i + 1) / 2 > idx) --i;
+  while ((i + 1) * (i + 2) / 2 <= idx) ++i;
+  return i;
+}
+__device__ __forceinline__ double2 load_obs(const void* __restrict__ obs, int obs_f64, int64_t at) {
+  if (obs_f64) return static_cast<const double2*>(obs)[at];
+  const float2 v = static_cast<const float2*>(obs)[at];
+  return double2{(double)v.x, (double)v.y};
+}
+
+__global__ __launch_bounds__(256) void wpe_online_kernel(
+    const void* __restrict__ obs, int obs_f64, const double2* __restrict__ Qin, const double2* __restrict__ Gin,
+    const double2* __restrict__ ringin, const double* __restrict__ pmaxin, double2* __restrict__ Qout,
+    double2* __restrict__ Gout, double2* __restrict__ ringout, double* __restrict__ pmaxout, int* __restrict__ info,
+    double2* __restrict__ out, int D, int64_t T, int F, int taps, int delay, int pc, int R, int S, double a, double ia,
+    double load) {
+  extern __shared__ double2 osm[];
+  const int K = taps * D, LD = K | 1, ntri = K * (K + 1) / 2;
+  double2* Q = osm;                    // [K][LD]
+  double2* Gt = Q + K * LD;            // [D][K]
+  double2* ring = Gt + D * K;          // [R + 1][D]
+  double2* yt = ring + (R + 1) * D;    // [K]
+  double2* u = yt + K;                 // [K]
+  double2* kk = u + K;                 // [K]
+  double2* xs = kk + K;                // [D]
+  const int tid = threadIdx.x;
+  const int64_t bf = blockIdx.x;
+  const int64_t b = bf / F;
+  const int f = (int)(bf % F);
+  const double INF = __longlong_as_double(0x7ff0000000000000ll);
+
+  double pmax = pmaxin ? pmaxin[bf] : 0.0;
+  const bool fresh = !Qin || pmax == 0.0;
+  int ij[ONTRI];
+#pragma unroll
+  for (int q = 0; q < ONTRI; ++q) {
+    const int idx = tid + 256 * q;
+    ij[q] = -1;
+    if (idx < ntri) {
+      const int i = tri_row(idx), j = idx - i * (i + 1) / 2;
+      ij[q] = (i << 8) | j;
+      double2 v = fresh ? double2{i == j ? 1.0 / load : 0.0, 0.0} : Qin[bf * ntri + idx];
+      if (i == j) v.y = 0.0;
+      Q[i * LD + j] = v;
+      if (i != j) Q[j * LD + i] = double2{v.x, -v.y};
+    }
+  }
+  for (int idx = tid; idx < K * D; idx += 256) {
+    const int i = idx / D, d = idx - i * D;
+    Gt[d * K + i] = fresh ? double2{0.0, 0.0} : Gin[bf * K * D + idx];
+  }
+  for (int idx = tid; idx < R * D; idx += 256) ring[idx] = ringin ? ringin[bf * R * D + idx] : double2{0.0, 0.0};
+
+  const int my_tau = tid < K ? tid / D : 0;
+  const int my_d = tid < K ? tid - my_tau * D : 0;
+  const int my_lag = delay + my_tau;
+  const int r = tid / S, s = tid - r * S;
+  const int lane = tid & 63;
+  const int64_t at0 = ((b * D + (tid < D ? tid : 0)) * T) * F + f;      // frame 0 of this thread's channel
+  int cur = R;                                                          // the slot of the current frame
+  int bad = 0;
+  double2 ynext = double2{0.0, 0.0};
+  if (tid < D) ring[cur * D + tid] = load_obs(obs, obs_f64, at0);
+  __syncthreads();
+
+  for (int64_t n = 0; n < T; ++n) {
+    if (tid < D && n + 1 < T) ynext = load_obs(obs, obs_f64, at0 + (n + 1) * F);
+    if (tid < K) {
+      int slot = cur - my_lag;
+      if (slot < 0) slot += R + 1;
+      yt[tid] = ring[slot * D + my_d];
+    }
+    double p = 0.0;
+    for (int c = pc; c >= 0; --c) {
+      int slot = cur - c;
+      if (slot < 0) slot += R + 1;
+      for (int d = 0; d < D; ++d) {
+        const double2 v = ring[slot * D + d];
+        p += v.x * v.x + v.y * v.y;
+      }
+    }
+    p /= (double)(D * (pc + 1));
+    if (p > pmax && p < INF) pmax = p;
+    const bool silent = pmax == 0.0;
+    const double flo = 1e-10 * pmax;
+    const double lam = p < flo ? flo : p;                               // a NaN stays one
+    __syncthreads();
+
+    double2 acc = {0.0, 0.0};
+    if (r < K) {
+      const double2* row = Q + r * LD;
+      for (int j = s; j < K; j += S) {
+        const double2 q = row[j], y = yt[j];
+        acc.x += q.x * y.x - q.y * y.y;
+        acc.y += q.x * y.y + q.y * y.x;
+      }
+    } else if (r < K + D) {
+      const double2* col = Gt + (r - K) * K;
+      for (int i = s; i < K; i += S) {
+        const double2 g = col[i], y = yt[i];
+        acc.x += g.x * y.x + g.y * y.y;                                 // conj(g) y
+        acc.y += g.x * y.y - g.y * y.x;
+      }
+    }
+    for (int m = 1; m < S; m <<= 1) {
+      acc.x += __shfl_xor(acc.x, m);
+      acc.y += __shfl_xor(acc.y, m);
+    }
+    if (s == 0) {
+      if (r < K) {
+        u[r] = acc;
+      } else if (r < K + D) {
+        const int d = r - K;
+        const double2 y = ring[cur * D + d];
+        const double2 x = silent ? y : double2{y.x - acc.x, y.y - acc.y};
+        xs[d] = x;
+        out[((b * D + d) * T + n) * F + f] = x;
+      }
+    }
+    __syncthreads();
+
+    double part = 0.0;
+    for (int i = lane; i < K; i += 64) part += yt[i].x * u[i].x + yt[i].y * u[i].y;
+    for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m);
+    const double den = a * lam + part;
+    const bool ok = !silent && den > 0.0 && den < INF;
+    if (!silent && !ok && tid == 0) ++bad;
+    if (ok && tid < K) kk[tid] = double2{u[tid].x / den, u[tid].y / den};
+    __syncthreads();
+
+    if (ok) {
+#pragma unroll
+      for (int q = 0; q < ONTRI; ++q) {
+        if (ij[q] < 0) continue;
+        const int i = ij[q] >> 8, j = ij[q] & 255;
+        const double2 k = kk[i], w = u[j];
+        double2 v = Q[i * LD + j];
+        v.x = (v.x - (k.x * w.x + k.y * w.y)) * ia;                     // k conj(w)
+        v.y = i == j ? 0.0 : (v.y - (k.y * w.x - k.x * w.y)) * ia;
+        Q[i * LD + j] = v;
+        if (i != j) Q[j * LD + i] = double2{v.x, -v.y};
+      }
+      for (int idx = tid; idx < K * D; idx += 256) {
+        const int d = idx / K, i = idx - d * K;
+        const double2 k = kk[i], x = xs[d];
+        double2 g = Gt[idx];
+        g.x += k.x * x.x + k.y * x.y;                                   // k conj(x)
+        g.y += k.y * x.x - k.x * x.y;
+        Gt[idx] = g;
+      }
+    }
+    cur = cur == R ? 0 : cur + 1;
+    if (tid < D && n + 1 < T) ring[cur * D + tid] = ynext;
+    __syncthreads();
+  }
+
+  // `cur` is the slot frame T would take: the last R frames sit in the R slots behind it
+  const bool zero = pmax == 0.0;
+#pragma unroll
+  for (int q = 0; q < ONTRI; ++q) {
+    if (ij[q] < 0) continue;
+    const int i = ij[q] >> 8, j = ij[q] & 255;
+    Qout[bf * ntri + tid + 256 * q] = zero ? double2{0.0, 0.0} : Q[i * LD + j];
+  }
+  for (int idx = tid; idx < K * D; idx += 256) {
+    const int i = idx / D, d = idx - i * D;
+    Gout[bf * K * D + idx] = Gt[d * K + i];
+  }
+  for (int idx = tid; idx < R * D; idx += 256) {
+    const int fr = idx / D, d = idx - fr * D;
+    int slot = cur - R + fr;
+    if (slot < 0) slot += R + 1;
+    ringout[bf * R * D + idx] = ring[slot * D + d];
+  }
+  if (tid == 0) {
+    pmaxout[bf] = pmax;
+    if (bad) atomicAdd(info + b, bad);
+  }
+}
+
+int run_online(const void* obs, int obs_f64, const double* q_in, const double* g_in, const double* ring_in,
+               const double* pmax_in, const int* info_in, double* q_out, double* g_out, double* ring_out,
+               double* pmax_out, int* info_out, double* out, int64_t B, int D, int64_t T, int F, int taps, int delay,
+               int pc, double forgetting, double load, hipStream_t s) {
+  static std::atomic<bool> attr_set[64];
+  int devid = 0;
+  if (hipGetDevice(&devid) != hipSuccess) return TSSEP_E_LAUNCH;
+  if (devid < 0 || devid >= 64 || !attr_set[devid].load(std::memory_order_acquire)) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(wpe_online_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)OMAXLDS) != hipSuccess)
+      return TSSEP_E_LAUNCH;
+    if (devid >= 0 && devid < 64) attr_set[devid].store(true, std::memory_order_release);
+  }
+  const OLay l = online_lay(D, taps, delay, pc);
+  if (l.lds > OMAXLDS) return TSSEP_E_UNSUPPORTED;
+  // the count of a stream goes on: the kernel adds to what the call before left
+  if (info_in) {
+    if (info_in != info_out &&
+        hipMemcpyAsync(info_out, info_in, sizeof(int) * (size_t)B, hipMemcpyDeviceToDevice, s) != hipSuccess)
+      return TSSEP_E_LAUNCH;
+  } else if (hipMemsetAsync(info_out, 0, sizeof(int) * (size_t)B, s) != hipSuccess) {
+    return TSSEP_E_LAUNCH;
+  }
+  hipLaunchKernelGGL(wpe_online_kernel, dim3((unsigned)(B * F)), dim3(256), l.lds, s, obs, obs_f64,
+                     reinterpret_cast<const double2*>(q_in), reinterpret_cast<const double2*>(g_in),
+                     reinterpret_cast<const double2*>(ring_in), pmax_in, reinterpret_cast<double2*>(q_out),
+                     reinterpret_cast<double2*>(g_out), reinterpret_cast<double2*>(ring_out), pmax_out, info_out,
+                     reinterpret_cast<double2*>(out), D, T, F, taps, delay, pc, l.R, l.S, forgetting, 1.0 / forgetting,
+                     load);
+  return tssep_launch_status();
+}
+
 }  // namespace
 
 extern "C" int64_t tssep_wpe_workspace_bytes(int S, int64_t N, int D, int64_t T, int F, int taps, int delay) {
@@ -622,4 +877,31 @@ extern "C" int tssep_wpe_fwd(const double* obs, const int32_t* segments, const i
     if (st == TSSEP_OK) st = run_filter(obs, G, segments, row0, obs_seg, ws, l, S, N, D, T, F, taps, delay, s);
   }
   return st;
+}
+
+extern "C" int64_t tssep_wpe_online_state_bytes(int64_t B, int D, int F, int taps, int delay, int power_context) {
+  if (online_args(B, D, 1, F, taps, delay, power_context) != TSSEP_OK) return 0;
+  const OLay l = online_lay(D, taps, delay, power_context);
+  return B * F * (16 * (int64_t)(l.ntri + l.K * D + l.R * D) + 8) + 4 * B;
+}
+
+extern "C" int tssep_wpe_online_fwd(const void* obs, int obs_f64, const double* q_in, const double* g_in,
+                                    const double* ring_in, const double* pmax_in, const int* info_in, double* q_out,
+                                    double* g_out, double* ring_out, double* pmax_out, int* info_out, double* out,
+                                    int64_t B, int D, int64_t T, int F, int taps, int delay, int power_context,
+                                    double forgetting, double load, void* stream) {
+  int st = online_args(B, D, T, F, taps, delay, power_context);
+  if (st != TSSEP_OK) return st;
+  if (!(forgetting > 0.0 && forgetting <= 1.0) || !(load > 0.0 && load < __builtin_inf())) return TSSEP_E_SHAPE;
+  const bool ring = online_lay(D, taps, delay, power_context).R > 0;
+  if (!obs || !q_out || !g_out || !pmax_out || !info_out || !out || (ring && !ring_out)) return TSSEP_E_NULL;
+  const int given = (q_in != nullptr) + (g_in != nullptr) + (pmax_in != nullptr) + (info_in != nullptr) +
+                    (!ring || ring_in != nullptr);
+  if (q_in ? given != 5 : given != (ring ? 0 : 1)) return TSSEP_E_NULL;       // a whole state or none
+  if (!aligned16(out) || !aligned16(q_out) || !aligned16(g_out) || !aligned16(ring_out) || !aligned16(q_in) ||
+      !aligned16(g_in) || !aligned16(ring_in) || (((uintptr_t)obs) & (obs_f64 ? 15u : 7u)) ||
+      (((uintptr_t)pmax_in) & 7u) || (((uintptr_t)pmax_out) & 7u))
+    return TSSEP_E_ALIGN;
+  return run_online(obs, obs_f64, q_in, g_in, ring_in, pmax_in, info_in, q_out, g_out, ring_out, pmax_out, info_out, out,
+                    B, D, T, F, taps, delay, power_context, forgetting, load, (hipStream_t)stream);
 }

@@ -3,6 +3,7 @@
 PyTorch is used for device memory and the current HIP stream only; every computation below
 is a call into libtssep_hip.so.  Nothing here falls back to ATen math.
 """
+import collections
 import ctypes
 import functools
 import itertools
@@ -1969,6 +1970,87 @@ def wpe(obs, segments=None, taps=10, delay=2, iterations=3, statistics_mode="ful
                 f"wpe: the factorisation of the correlation matrix met a pivot that is not positive in "
                 f"{len(failed)} of {S} rows (start, end): {failed}")
     return out if segments is None else (out, row0)
+
+
+WPE_MAX_POWER_CONTEXT = 256
+OnlineWPEState = collections.namedtuple("OnlineWPEState", "Q G ring pmax info")
+OnlineWPEState.__doc__ = """What a stream of `online_wpe` carries: Q [B,F,K(K+1)/2] complex128 (the lower triangle of the
+inverse correlation matrix, row by row), G [B,F,K,D] complex128, ring [B,F,R,D] complex128 (the last
+R = max(delay + taps - 1, power_context) frames, oldest first), pmax [B,F] float64, info [B] int32 (the frames whose update
+was refused, counted over the stream).  All zeros: a fresh stream."""
+
+
+def online_wpe_state_shapes(B, D, F, taps, delay, power_context):
+    K = taps * D
+    R = max(delay + taps - 1, power_context)
+    return OnlineWPEState(((B, F, K * (K + 1) // 2), torch.complex128), ((B, F, K, D), torch.complex128),
+                          ((B, F, R, D), torch.complex128), ((B, F), torch.float64), ((B,), torch.int32))
+
+
+def online_wpe_check(Y, state=None, taps=10, delay=2, forgetting=0.99, load=1.0, power_context=0):
+    """What `online_wpe` refuses, from the arguments alone (CPU tensors do: nothing is launched) -> (B, D, Tc, F)."""
+    if not isinstance(Y, torch.Tensor) or Y.dim() != 4:
+        raise ValueError(f"online_wpe: Y [B,D,Tc,F], got {tuple(Y.shape) if isinstance(Y, torch.Tensor) else type(Y)}")
+    if Y.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError(f"online_wpe: Y is {Y.dtype}, complex64 or complex128 is required")
+    B, D, T, F = Y.shape
+    if int(taps) != taps or int(delay) != delay or int(power_context) != power_context:
+        raise ValueError(f"online_wpe: taps, delay and power_context are integers, got {(taps, delay, power_context)}")
+    if min(B, T, F) < 1:
+        raise ValueError(f"online_wpe: empty axis: Y {tuple(Y.shape)}")
+    if not 1 <= D <= WPE_MAX_CHANNELS:
+        raise ValueError(f"online_wpe: {D} channels: the kernel is built for 1 to {WPE_MAX_CHANNELS}")
+    if taps < 1 or taps * D > WPE_MAX_ROWS:
+        raise ValueError(f"online_wpe: taps * channels = {taps} * {D} = {taps * D}: the inverse correlation matrix is built "
+                         f"for 1 to {WPE_MAX_ROWS} rows (it lives in LDS)")
+    if not 0 <= delay <= WPE_MAX_DELAY:
+        raise ValueError(f"online_wpe: delay {delay}: 0 to {WPE_MAX_DELAY}")
+    if not 0 <= power_context <= WPE_MAX_POWER_CONTEXT:
+        raise ValueError(f"online_wpe: power_context {power_context}: 0 to {WPE_MAX_POWER_CONTEXT} frames")
+    if not 0.0 < float(forgetting) <= 1.0:
+        raise ValueError(f"online_wpe: forgetting = {forgetting} lies outside (0, 1]")
+    if not 0.0 < float(load) < float("inf"):
+        raise ValueError(f"online_wpe: load = {load} is not positive and finite (Q starts as I / load)")
+    if Y.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("online_wpe is evaluation-time only: Y requires grad and the recursion has no backward "
+                                  "(call it under torch.no_grad())")
+    if state is not None:
+        want = online_wpe_state_shapes(B, D, F, int(taps), int(delay), int(power_context))
+        if not isinstance(state, tuple) or len(state) != len(want):
+            raise ValueError(f"online_wpe: state is {type(state).__name__}, not the OnlineWPEState an earlier call returned")
+        for name, t, (shape, dtype) in zip(OnlineWPEState._fields, state, want):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape:
+                got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"online_wpe: state.{name} is {got}, what a call with B = {B}, D = {D}, F = {F}, taps = "
+                                 f"{taps}, delay = {delay}, power_context = {power_context} carries is {dtype} {shape} "
+                                 "(did the channels or the parameters change between the calls of a stream?)")
+    return B, D, T, F
+
+
+def online_wpe(Y, state=None, taps=10, delay=2, forgetting=0.99, load=1.0, power_context=0):
+    """The recursive WPE of DESIGN 4.19 on the next Tc frames of a stream: Y [B,D,Tc,F] complex64 | complex128, state what
+    the call before returned (None: a fresh stream) -> (X [B,D,Tc,F] complex128, the new `OnlineWPEState`).  The output of a
+    frame uses the filter of the frames before it.  One launch, no host sync (state.info stays on the device: read it
+    when the stream allows); output and state do not depend on how the frames are split over calls."""
+    B, D, T, F = online_wpe_check(Y, state, taps, delay, forgetting, load, power_context)
+    L = _lib.lib()
+    assert Y.is_cuda and (state is None or all(t.is_cuda for t in state)), Y.device
+    taps, delay, pc = int(taps), int(delay), int(power_context)
+    y_r = torch.view_as_real(Y.detach().contiguous())
+    shapes = online_wpe_state_shapes(B, D, F, taps, delay, pc)
+    new = OnlineWPEState(*(torch.empty(shape, device=Y.device, dtype=dtype) for shape, dtype in shapes))
+    assert L.tssep_wpe_online_state_bytes(B, D, F, taps, delay, pc) == sum(t.numel() * t.element_size() for t in new)
+    old = [None] * 5 if state is None else [t.contiguous() for t in state]
+    # (an empty tensor has no address: the ring of delay = 0, taps = 1, power_context = 0 holds no frame)
+    ptr = lambda t: _p(t) if t is not None and t.numel() else None
+    X = torch.empty(B, D, T, F, device=Y.device, dtype=torch.complex128)
+    K = taps * D
+    nbytes = B * F * (T * D * (y_r.element_size() * 2 + 16) + 32 * (K * (K + 1) // 2 + K * D + shapes.ring[0][2] * D))
+    with _timed("wpe_online", B * F * T * 8 * (K * K + K * (K + 1) // 2 + 2 * K * D), nbytes):
+        check(L.tssep_wpe_online_fwd(_p(y_r), int(Y.dtype == torch.complex128), *(ptr(t) for t in old),
+                                     *(ptr(t) for t in new), _p(torch.view_as_real(X)), B, D, T, F, taps, delay, pc,
+                                     float(forgetting), float(load), _stream()), "wpe_online")
+    return X, new
 
 
 # ----------------------------------------------------------------------------- losses

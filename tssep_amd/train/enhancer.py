@@ -134,23 +134,45 @@ class OnlineMVDR(ABC):
     One HIP kernel (hip_ops.online_mvdr, csrc/mvdr.hip).  Called on a whole utterance like TorchBF it runs the recursion
     over all T frames in one launch -- what ``Model.online`` streams, chunk by chunk, bit for bit; with forgetting=1 and
     diag_load=0 its last frame is TorchBF's.  Evaluation only (there is no backward), one mask per speaker.  Neither
-    default is tuned."""
+    default is tuned.
+    ``pre_wpe`` (an `OnlineWPE` below; default None: nothing changes) dereverberates every frame before it is
+    beamformed, the online counterpart of ClassicBF_np's pre_wpe: the masks still belong to the raw reference channel,
+    the PSDs and the filtering read the dereverberated frames, and the carried state becomes the pair
+    (the OnlineWPE's state, the PSDs)."""
 
-    def __init__(self, forgetting=1.0, diag_load=1e-6, eps=None, masking=False, masking_eps=0.0):
+    def __init__(self, forgetting=1.0, diag_load=1e-6, eps=None, masking=False, masking_eps=0.0, pre_wpe=None):
         super().__init__()
         self.forgetting = forgetting
         self.diag_load = diag_load
         self.eps = eps
         self.masking = masking
         self.masking_eps = masking_eps
+        self.pre_wpe = pre_wpe
 
     def _kwargs(self):
         return dict(forgetting=self.forgetting, diag_load=self.diag_load, eps=self.eps, masking=self.masking,
                     masking_eps=self.masking_eps)
 
-    def chunk(self, masks, Y, state, reference_channel):
-        """The next frames of a stream: masks [B,K,(1,)Tc,F], Y [B,D,Tc,F] -> (enh [B,K,Tc,F] complex128, state)."""
-        return H.online_mvdr(masks, Y, state, reference_channel, **self._kwargs())
+    def _check_pre_wpe(self):
+        if self.pre_wpe is not None and not isinstance(self.pre_wpe, OnlineWPE):
+            raise NotImplementedError(f"pre_wpe={self.pre_wpe!r}: a stream is dereverberated by this module's OnlineWPE "
+                                      "(WPE / ChannelWiseWPE iterate over whole segments)")
+
+    def chunk(self, masks, Y, state, reference_channel, with_observation=False):
+        """The next frames of a stream: masks [B,K,(1,)Tc,F], Y [B,D,Tc,F] -> (enh [B,K,Tc,F] complex128, state).
+        with_observation: -> (enh, state, the frames that were beamformed: Y, or pre_wpe's output)."""
+        self._check_pre_wpe()
+        if self.pre_wpe is None:
+            enh, state = H.online_mvdr(masks, Y, state, reference_channel, **self._kwargs())
+            return (enh, state, Y) if with_observation else (enh, state)
+        if state is not None and not (isinstance(state, tuple) and len(state) == 2):
+            raise ValueError("OnlineMVDR(pre_wpe=...): the state of a stream is the pair (OnlineWPE's state, PSDs) an "
+                             f"earlier call returned, got {type(state).__name__}")
+        wpe_state, psd = (None, None) if state is None else state
+        H.online_mvdr_check(masks, Y, psd, reference_channel, self.forgetting, self.diag_load)
+        X, wpe_state = self.pre_wpe.chunk(Y, wpe_state)
+        enh, psd = H.online_mvdr(masks, X, psd, reference_channel, **self._kwargs())
+        return (enh, (wpe_state, psd), X) if with_observation else (enh, (wpe_state, psd))
 
     def __call__(self, masks, ex, model):
         """masks [(B,) K, 1, T, F]; ex['Observation'] [(B,) D, T, F] complex64 | complex128 -> [(B,) K, T, F] complex128."""
@@ -163,8 +185,55 @@ class OnlineMVDR(ABC):
         if not batched:
             masks, Observation = masks[None], Observation[None]
         H.online_mvdr_check(masks, Observation, None, ex["reference_channel"], self.forgetting, self.diag_load)
+        self._check_pre_wpe()
+        if self.pre_wpe is not None:
+            H.online_wpe_check(Observation, None, **self.pre_wpe._kwargs())
         enh, _ = self.chunk(masks.detach(), Observation.detach().to(masks.device), None, ex["reference_channel"])
         return enh if batched else enh[0]
+
+
+class OnlineWPE(ABC):
+    """Frame-recursive WPE dereverberation -- THIS PROJECT'S class, the reference has no online mode: the
+    recursive least squares form of WPE above.  Per bin one rank-one update of the inverse correlation matrix of the
+    delayed frames per frame, weighted by the inverse of the frame's power (the mean over the channels and the last
+    ``power_context`` + 1 frames, floored at 1e-10 of the largest seen), forgotten with ``forgetting``; frame t is
+    filtered with the taps of the frames before it.  One HIP kernel (hip_ops.online_wpe, csrc/wpe.hip).  ``chunk`` takes
+    the next frames of a stream and the carried state; called on a whole utterance like WPE -- Observation [D, T, F]
+    complex128, numpy in gives numpy out -- it runs the recursion over all T frames in one launch, bit for bit what the
+    chunks give.  Evaluation only (there is no backward).  No default is tuned: taps and delay are WPE's, forgetting and
+    load are placeholders that were not searched on data."""
+
+    def __init__(self, taps=10, delay=2, forgetting=0.99, load=1.0, power_context=0):
+        super().__init__()
+        self.taps = taps
+        self.delay = delay
+        self.forgetting = forgetting
+        self.load = load
+        self.power_context = power_context
+
+    def _kwargs(self):
+        return dict(taps=self.taps, delay=self.delay, forgetting=self.forgetting, load=self.load,
+                    power_context=self.power_context)
+
+    def chunk(self, Y, state=None):
+        """The next frames of a stream: Y [B,D,Tc,F] complex64 | complex128 -> (X [B,D,Tc,F] complex128, state)."""
+        return H.online_wpe(Y, state, **self._kwargs())
+
+    def __call__(self, Observation, inplace=False):
+        if isinstance(Observation, np.ndarray):
+            obs, numpy_out = torch.from_numpy(np.ascontiguousarray(Observation)), True
+        elif isinstance(Observation, torch.Tensor):
+            obs, numpy_out = Observation, False
+        else:
+            raise NotImplementedError(type(Observation), Observation)
+        if obs.dtype != torch.complex128:
+            raise TypeError(f"{self.name}: Observation is {obs.dtype}, complex128 is required (as for WPE; `chunk` takes "
+                            "the complex64 frames of a stream too)")
+        assert obs.dim() == 3, obs.shape
+        H.online_wpe_check(obs[None], None, **self._kwargs())      # every refusal before anything touches the device
+        obs = obs.detach()
+        out, _ = self.chunk((obs if obs.is_cuda else obs.to("cuda"))[None])
+        return out[0].cpu().numpy() if numpy_out else out[0]
 
 
 def normalized_intervals(ai, T):

@@ -397,7 +397,8 @@ class Model(Configurable, torch.nn.Module):
         (ValueError); an enhancer other than Masking or OnlineMVDR, nmask != 1, output_resolution='t', an STFT other than
         the plain 1024 / 256 one, and whatever forward_chunk refuses (NotImplementedError).  With OnlineMVDR the pushes
         hold all channels, [B, D, n], and ``reference_channel`` is the one the features are taken from and the
-        beamformer is steered to; the Masking route ignores it."""
+        beamformer is steered to; the Masking route ignores it.  OnlineMVDR(pre_wpe=OnlineWPE(...)) puts the
+        recursive WPE in front of the beamformer: same pushes, the carried state grows by the WPE's."""
         from .online import OnlineSeparator
         return OnlineSeparator(self, aux, record=record, reference_channel=reference_channel)
 

@@ -8,8 +8,12 @@
 
 and returns the samples those frames complete.  With the enhancer `OnlineMVDR` a push holds D channels:
 all of them go through the streaming STFT, features and trunk read the reference channel, and the tail is sigmoid ->
-frame-recursive MVDR (carried: the two PSDs per speaker and bin, a fifth state) -> streaming inverse STFT.  The algorithmic latency is size - shift samples (48 ms at 16 kHz).  The
-frame / hop bookkeeping is `schedule`, a pure function.
+frame-recursive MVDR (carried: the two PSDs per speaker and bin, a fifth state) -> streaming inverse STFT.  With
+`OnlineMVDR(pre_wpe=OnlineWPE(...))` the frames are dereverberated by the recursive WPE between the STFT and
+the beamformer -- the masks still come from the raw reference channel -- and the fifth state is the pair (the WPE's
+inverse correlation matrices, taps and frame ring; the PSDs).  The algorithmic latency is size - shift samples (48 ms at
+16 kHz); the dereverberation adds none, its taps reach back only.  The frame / hop bookkeeping is `schedule`, a pure
+function.
 """
 from collections import namedtuple
 
@@ -83,7 +87,8 @@ class OnlineSeparator:
     [K, m]), the samples this push completes: (Tc - 3) * shift for the first (none while fewer than four frames
     exist), Tc * shift afterwards.  ``flush(x_last=None)``: the ragged rest (fewer than shift samples) -> the remaining
     samples; the concatenation has exactly the utterance's length and `push` raises afterwards.  ``last``: the last
-    call's `Output` (masks, VAD), formed when read.  record=True keeps every call's ``Observation`` and ``Input``.
+    call's `Output` (masks, VAD), formed when read.  record=True keeps every call's ``Observation`` and ``Input`` (and
+    with OnlineMVDR ``logit``, ``mask``, ``Estimate``; with its pre_wpe also ``Dereverberated``, the frames it beamformed).
     With the enhancer `OnlineMVDR` x is [B, D, n] (un-batched: [D, n]), ``reference_channel`` names the channel the
     features are taken from and the beamformer is steered to (Masking ignores it)."""
 
@@ -94,7 +99,7 @@ class OnlineSeparator:
         self._aux = aux
         self._tail = self._feat = self._trunk = self._ola = None       # the four carried states
         self._bf = model.enhancer if isinstance(model.enhancer, _enh.OnlineMVDR) else None
-        self._psd = None                                               # the beamformer's fifth: Phi_s, Phi_n
+        self._psd = None                    # the beamformer's fifth: Phi_s, Phi_n (with pre_wpe: the pair of both states)
         self._ref = int(reference_channel)
         if self._bf is not None and not 0 <= self._ref < 8:
             raise ValueError(f"reference_channel = {reference_channel}: the beamformer takes at most 8 channels")
@@ -116,12 +121,14 @@ class OnlineSeparator:
             aux = None if self._trunk is not None else ([self._aux] if self._un else self._aux)
             res, _, self._trunk = self.me._chunk_logits(feat.to(torch.float32), aux, self._trunk)
             mask = self.me._output(res).mask                                                 # [B, K, 1, Tc, F]
-            enh, self._psd = self._bf.chunk(mask, X, self._psd, self._ref)
+            enh, self._psd, Xd = self._bf.chunk(mask, X, self._psd, self._ref, with_observation=True)
             skip, _ = _step(self.frames, frames, fe.shift)
             y, self._ola = fe.istft_chunk(enh, self._ola, skip, num_samples)
         self._res = res
         if self.record is not None:
             self.record.append({"Observation": X, "Input": feat, "logit": res[0], "mask": mask, "Estimate": enh})
+            if self._bf.pre_wpe is not None:
+                self.record[-1]["Dereverberated"] = Xd
         self.frames += frames
         self.samples_out += y.shape[-1]
         return y
