@@ -318,6 +318,56 @@ int tssep_lstm1_bwd(float* gates, const float* cell, const float* dhout, int64_t
 int tssep_lstm1_unpack(const float* src, int64_t ld, int nsplit, int64_t split_stride,
                        int H, int ncols, float* dst, int accumulate, void* stream);
 
+/* -------------------------------------------------------------------- GRU ----
+ * One GRU layer over one or two directions of time (torch.nn.GRU as built at tssep/train/rnnp.py:40,87 for
+ * typ = 'gru' / 'bgru'; one layer, batch_first): the streaming decomposition of tssep_blstm_* / tssep_lstm1_* -- 8
+ * sequences x 1 direction per workgroup, no exchange between workgroups, no spin, no error flag, no concurrency
+ * contract (capturable, safe beside anything), exact fp32.  H <= 512.  torch's math, parameter rows gate-major (r, z, n):
+ *   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr)       z = sigmoid(W_iz x + b_iz + W_hz h + b_hz)
+ *   n = tanh(W_in x + b_in + r * (W_hn h + b_hn))     h' = (1 - z) * n + z * h
+ *
+ * Every unit owns FOUR slots (r, z, n, q), q = W_hn h + b_hn (apart, because r multiplies it), so every shape of the
+ * LSTM path holds: gate columns [dir][unit][slot], 4H per direction.  Packed by tssep_gru_pack (sizes in floats:
+ * tssep_gru_pack_sizes, the LSTM's struct -- they are the LSTM's sizes):
+ *                         slot 0          slot 1          slot 2      slot 3
+ *   wih_p  [nd*4H, ld_i]  W_ir[u]         W_iz[u]         W_in[u]     0          (K zero-padded to ld_i)
+ *   bias_p [nd*4H]        b_ir + b_hr     b_iz + b_hz     b_in        b_hn
+ *   whh_f / whh_b         W_hr[u]         W_hz[u]         0           W_hn[u]    (streaming layouts, forward / BPTT)
+ * nd = 1 | 2 directions; nd = 1: the *_r pointers are not read (null is fine) and every [dir] axis has one entry.
+ * w_ih [3H,I], w_hh [3H,H], b_ih [3H], b_hh [3H]. */
+int tssep_gru_pack_sizes(int nd, int H, int I, int64_t ld_i, tssep_lstm_sizes* out);
+int tssep_gru_pack(int nd, const float* w_ih_f, const float* w_hh_f, const float* b_ih_f,
+                   const float* b_hh_f, const float* w_ih_r, const float* w_hh_r,
+                   const float* b_ih_r, const float* b_hh_r, int H, int I, int64_t ld_i,
+                   float* wih_p, float* bias_p, float* whh_f, float* whh_b, void* stream);
+/* Two directions.  gates [N,T,2,H,4]: in = the input GEMM's (a_r, a_z, a_n, b_hn); out = (r, z, n, q), kept for the
+ * backward.  hout [N,T,ldo] (cols d*dstride+u; the columns outside are never written and never read, as for
+ * tssep_blstm_fwd).  There is no cell tensor: the state is h. */
+int tssep_gru_fwd(float* gates, float* hout, int64_t ldo, int64_t dstride, const float* whh_f,
+                  int64_t N, int64_t T, int H, void* stream);
+/* dhout [N,T,ldo] -> gates is overwritten with (da_r, da_z, da_n, da_q) in the same layout; reads the forward's hout
+ * (h_prev: the neighbouring frame in the direction's time order, 0 at its first frame). */
+int tssep_gru_bwd(float* gates, const float* hout, const float* dhout, int64_t ldo, int64_t dstride,
+                  const float* whh_b, int64_t N, int64_t T, int H, void* stream);
+/* ONE direction, forward in time: gates [N,T,H,4], hout / dhout [N,T,ldo] with columns 0..H-1.
+ * h0 [N,H], nullable: the state the recurrence starts from; null = zeros.  hT [N,H], nullable: the state after the
+ * last frame, the bits of hout[:, T-1, :H].  tssep_gru1_bwd assumes a ZERO initial state: a carried state exists
+ * without gradients only. */
+int tssep_gru1_fwd(float* gates, float* hout, int64_t ldo, const float* whh_f, const float* h0,
+                   float* hT, int64_t N, int64_t T, int H, void* stream);
+int tssep_gru1_bwd(float* gates, const float* hout, const float* dhout, int64_t ldo,
+                   const float* whh_b, int64_t N, int64_t T, int H, void* stream);
+/* gradient unpack + split-K reduction: a matrix with packed (dir,unit,slot) rows back to torch's [3H, ncols] rows:
+ *   dst_d[(g*H + u)*ncols + k] (+)= sum_{s<nsplit} src[s*split_stride + (d*4H + 4u + slot(g))*ld + k],  g = 0..2
+ * which = TSSEP_GRU_IH: slot(g) = (0, 1, 2) -- dW_ih, db_ih; TSSEP_GRU_HH: slot(g) = (0, 1, 3) -- dW_hh, db_hh (the one
+ * place where b_ih and b_hh stop sharing a gradient).  The unused slot's row of src is never read.  nd = 1: dst_r is
+ * not written (null is fine). */
+#define TSSEP_GRU_IH 0
+#define TSSEP_GRU_HH 1
+int tssep_gru_unpack(int nd, const float* src, int64_t ld, int nsplit, int64_t split_stride,
+                     int H, int ncols, int which, float* dst_f, float* dst_r, int accumulate,
+                     void* stream);
+
 /* Cluster (W-stationary) recurrence -- latency-optimised alternative to tssep_blstm_fwd/bwd for
  * batches that do not fill the chip (same math, same tensor layouts; see lstm_cluster.hip).
  * A cluster of ceil(H/32) co-resident workgroups keeps W_hh in registers and exchanges h / dh

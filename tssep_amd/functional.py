@@ -116,9 +116,13 @@ def _linear_wgrads(dv, ld_d, xv, ld_x, Nout, P, R, sinks, fused, bias=True):
 # ---- derived weight layouts: ONE builder per tag (hip_ops.derived keeps the first it sees and prepare_derived replays it;
 # a build reads the parameters, never a step's tensors).  D directions of time -- 2: BLSTM, 1: typ = 'lstm', the causal
 # route -- are 4 D LSTM tensors and D column blocks of the projection; memo and builder live on the parameter object, and a
-# parameter belongs to one LSTM, so both kinds share the tags.
-def _lstm_pack_of(lstm_params, Hh, I):
+# parameter belongs to one LSTM, so both kinds share the tags.  A torch.nn.GRU container (rnnp.py:87) has the
+# same 4 D tensors with three gate rows per unit; its pack (four slots per unit, gru.hip) has a tag of its own.  The cell
+# kind is decided ONCE, by rnnp_layer from the container's class, and travels as the flag `gru`.
+def _lstm_pack_of(lstm_params, Hh, I, gru=False):
     lstm_params = list(lstm_params)
+    if gru:
+        return H.derived("gru_pack", lstm_params, lambda: H.gru_pack(lstm_params, Hh, I))
     # (the library has an entry point per direction count; looked up when the build runs)
     return H.derived("lstm_pack", lstm_params,
                      lambda: (H.lstm1_pack if len(lstm_params) == 4 else H.lstm_pack)(lstm_params, Hh, I))
@@ -143,24 +147,28 @@ def _proj_T_of(w_proj, Hh, Hp):
                                                               w_proj.shape[1] // Hh * Hp))
 
 
-def _wih_T_of(lstm_params, Hh, I):
-    G = len(lstm_params) * Hh      # 4 D Hh gate rows
+def _wih_T_of(lstm_params, Hh, I, gru=False):
+    G = len(lstm_params) * Hh      # 4 D Hh gate rows (a GRU's four slots per unit likewise)
 
     def build():
-        pk = _lstm_pack_of(lstm_params, Hh, I)
+        pk = _lstm_pack_of(lstm_params, Hh, I, gru)
         return H.transposed(pk["wih_p"].view(G, pk["ld_i"]), G, I)
     return H.derived("wih_T", list(lstm_params[0::4]), build)
 
 
 # ------------------------------------------------------------------------------ RNNP
-_RNNPMeta = collections.namedtuple("_RNNPMeta", "N T I D Hh Hp hdim ld_x ld_y act combine")
+_RNNPMeta = collections.namedtuple("_RNNPMeta", "N T I D Hh Hp hdim ld_x ld_y act combine gru")
 
 
-def _rnnp_forward(x, lstm_params, w_proj, b_proj, N, T, act, combine, dropout_p, state=None, want_state=False):
+def _rnnp_forward(x, lstm_params, w_proj, b_proj, N, T, act, combine, dropout_p, state=None, want_state=False, gru=False):
     """The forward stages of one layer over D = len(lstm_params) // 4 directions of time: input GEMM with bias into gates
     [R, 4 D Hh], the recurrence (D = 1: from `state` = (h0, c0) [N, Hh] when given), the projection [hdim, D Hh] with
     act / combine / the dropout site.  Run inside _RNNP, and as they are under no_grad with a carried state (rnnp_layer).
-    -> (y, saved tensors, (drop, used), meta, the backward's (plan, W_hh layout), (hT, cT) or None)"""
+    gru: the 4 D tensors are a torch.nn.GRU's (three gate rows per unit) -- the same stages on the four slots (r, z, n, q)
+    per unit; no `cell` is allocated, the backward recurrence reads hout in its place, and the state is h alone: `state` =
+    (h0,), the last state (hT,).
+    -> (y, saved tensors, (drop, used), meta, the backward's (plan, W_hh layout), the last state -- (hT, cT), a GRU's (hT,)
+    -- or None)"""
     D = len(lstm_params) // 4
     w_ih, w_hh = lstm_params[0], lstm_params[1::4]
     dev = x.device
@@ -169,20 +177,25 @@ def _rnnp_forward(x, lstm_params, w_proj, b_proj, N, T, act, combine, dropout_p,
     xv, ld_x = H.rows_view(x)
     R, G = N * T, 4 * D * Hh
     assert xv.shape[0] == R and xv.shape[1] >= I, (xv.shape, R, I)
-    pk = _lstm_pack_of(lstm_params, Hh, I)
+    assert w_ih.shape[0] == (3 if gru else 4) * Hh, (tuple(w_ih.shape), Hh, gru)
+    pk = _lstm_pack_of(lstm_params, Hh, I, gru)
     gates = torch.empty(R, G, device=dev, dtype=torch.float32)
     H.gemm(xv, ld_x, pk["wih_p"], pk["ld_i"], gates, G, R, G, I, bias=pk["bias_p"])
     Hp = H.round_up(Hh, 4)
-    cell = torch.empty(N, T, D, Hh, device=dev, dtype=torch.float32)
+    cell = None if gru else torch.empty(N, T, D, Hh, device=dev, dtype=torch.float32)
     hout = (torch.zeros if Hp != Hh else torch.empty)(R, D * Hp, device=dev, dtype=torch.float32)
     h0 = c0 = hT = cT = None
     if state is not None:
-        h0, c0 = (H._f32(s).reshape(N, Hh).contiguous() for s in state)
+        h0 = H._f32(state[0]).reshape(N, Hh).contiguous()
+        if not gru:
+            c0 = H._f32(state[1]).reshape(N, Hh).contiguous()
     if want_state:
-        hT, cT = (torch.empty(N, Hh, device=dev, dtype=torch.float32) for _ in range(2))
+        hT = torch.empty(N, Hh, device=dev, dtype=torch.float32)
+        if not gru:
+            cT = torch.empty(N, Hh, device=dev, dtype=torch.float32)
     # the plan and BOTH directions' W_hh layouts are fetched here, once: the backward launches from what ctx keeps (a
     # step captured without prepare_derived builds a layout at every ask)
-    plan = H.recurrence_plan(N, T, Hh, H.n_cus(dev), directions=D)
+    plan = H.recurrence_plan(N, T, Hh, H.n_cus(dev), directions=D, **(dict(cell="gru") if gru else {}))
     whh = H.recurrence_packs(plan, w_hh[0], w_hh[-1], Hh, pk, memo=True)
     H.recurrence_launch(plan["fwd"], "fwd", gates, cell, hout, D * Hp, Hp, whh["fwd"], N, T, Hh, state=(h0, c0, hT, cT))
     wp = _proj_layout_of(w_proj, Hh, Hp)
@@ -201,9 +214,9 @@ def _rnnp_forward(x, lstm_params, w_proj, b_proj, N, T, act, combine, dropout_p,
     if drop:
         used = H.dropout_draw(dev)
         H.dropout_tanh_fwd(y, y, R, hdim, ld_y, combine if combine else 1, T, bool(combine), drop, used)
-    meta = _RNNPMeta(N, T, I, D, Hh, Hp, hdim, ld_x, ld_y, act, combine)
+    meta = _RNNPMeta(N, T, I, D, Hh, Hp, hdim, ld_x, ld_y, act, combine, gru)
     return (y, (xv, gates, cell, hout, y, wp), (drop, used), meta, (plan["bwd"], whh["bwd"]),
-            (hT, cT) if want_state else None)
+            ((hT,) if gru else (hT, cT)) if want_state else None)
 
 
 class _RNNP(torch.autograd.Function):
@@ -218,13 +231,15 @@ class _RNNP(torch.autograd.Function):
     projection stores plainly (act = 0) and one pass over y applies mask, 1 / (1 - p) and Tanh in place; the backward
     regenerates the mask from the {seed, draw} pair the forward drew (hip_ops.dropout_draw).
     ``want_state`` (D = 1): the state after the last frame leaves as two more outputs.  Zero initial state: a carried state
-    exists without gradients only (rnnp_layer)."""
+    exists without gradients only (rnnp_layer).
+    The 4 D tensors of a torch.nn.GRU (three gate rows per unit) run the GRU recurrence (gru.hip) through the same stages;
+    its state is one more output, h.  ``gru``: rnnp_layer's flag, the container's class."""
 
     @staticmethod
-    def forward(ctx, x, N, T, act, combine, in_tanh, in_link, out_link, dropout_p, want_state, *params):
+    def forward(ctx, x, N, T, act, combine, in_tanh, in_link, out_link, dropout_p, want_state, gru, *params):
         assert not dropout_p or (act == 1 and out_link is None), "dropout_p: a site is the Tanh behind the layer, never folded"
         y, saved, ctx.drop, ctx.meta, ctx.recurrence, last = _rnnp_forward(x, params[:-2], *params[-2:], N, T, act, combine,
-                                                                           dropout_p, want_state=want_state)
+                                                                           dropout_p, want_state=want_state, gru=gru)
         ctx.save_for_backward(*saved)
         ctx.params = params
         # Tanh-backward fold (see rnnp_layer): in_link = the link my producer hung on x, out_link = the one my
@@ -247,12 +262,13 @@ class _RNNP(torch.autograd.Function):
         sinks = [_grad_sink(p) for p in params]
         direct = _is_direct(sinks, True)
         d_w_proj, d_b_proj = _rnnp_proj_wgrads(dz, ld_dz, hout, m, sinks[-2:], direct)
-        _rnnp_bptt(dz, ld_dz, gates, cell, params[-2], m, ctx.recurrence)     # the critical path: gates <- d(pre-activations)
+        # the critical path: gates <- d(pre-activations); a GRU's backward recurrence reads hout (h_prev) where the LSTM's reads cell
+        _rnnp_bptt(dz, ld_dz, gates, hout if m.gru else cell, params[-2], m, ctx.recurrence)
         lstm_grads = _rnnp_lstm_wgrads(gates, hout, xv, m, sinks[:-2], direct)
         if direct:
             _notify_grads(params)                    # (4 D + 2 tensors: every direction's LSTM weights + the projection)
         dx = _rnnp_dx(gates, xv, params[:-2], m, ctx.x_shape, in_link, in_tanh) if ctx.needs_input_grad[0] else None
-        return (dx,) + (None,) * 9 + (*lstm_grads, d_w_proj, d_b_proj)
+        return (dx,) + (None,) * 10 + (*lstm_grads, d_w_proj, d_b_proj)
 
 
 def _rnnp_dz(dy, y, m, drop, folded):
@@ -308,7 +324,8 @@ def _rnnp_bptt(dz, ld_dz, gates, cell, w_proj, m, recurrence):
 
 def _rnnp_lstm_wgrads(gates, hout, xv, m, sinks, direct):
     """stage 4 -> the 4 D LSTM gradients in parameter order from dgates (in `gates`), or 4 D None when they went into
-    `sinks` (side stream)"""
+    `sinks` (side stream).  A GRU (m.gru): the same products over the four slots, unpacked to torch's three gate rows --
+    dW_ih and db_ih from the slots (r, z, n), dW_hh and db_hh from (r, z, q): the two biases have gradients of their own."""
     R, T, I, D, Hh, Hp, G = m.N * m.T, m.T, m.I, m.D, m.Hh, m.Hp, 4 * m.D * m.Hh
     with _wgrad_branch(gates.device, R, (gates, hout, xv), direct):
         dwhh = torch.empty(D, 4 * Hh * Hh, device=gates.device, dtype=torch.float32)
@@ -324,19 +341,25 @@ def _rnnp_lstm_wgrads(gates, hout, xv, m, sinks, direct):
         bias_src = ((part, I), ldp, S, G * ldp) if fused else (H.colsum(gates, G, R, G), 1, 1, 0)
         # (source, columns, index of the forward direction's destination: the reverse one's is 4 further)
         unpacks = [((dwhh, Hh, 1, 0), Hh, 1), ((part, ldp, S, G * ldp), I, 0), (bias_src, 1, 2)]
+        if direct or m.gru:
+            unpacks.append((bias_src, 1, 3))      # b_ih and b_hh receive the same gradient (LSTM; a GRU's differ in the n rows)
+        rows = (3 if m.gru else 4) * Hh
         if direct:
             dst = sinks
-            unpacks.append((bias_src, 1, 3))      # b_ih and b_hh receive the same gradient
         else:
             new = lambda *shape: torch.empty(*shape, device=gates.device, dtype=torch.float32)  # noqa: E731
-            dst = [t for _ in range(D) for t in (new(4 * Hh, I), new(4 * Hh, Hh), new(4 * Hh), None)]
+            dst = [t for _ in range(D) for t in (new(rows, I), new(rows, Hh), new(rows), new(rows) if m.gru else None)]
         unpack = H.lstm1_unpack if D == 1 else H.lstm_unpack      # (the library's entry point per direction count)
         for src, ncols, i in unpacks:
-            unpack(*src, Hh, ncols, *dst[i::4], accumulate=direct)
+            if m.gru:      # (the hidden side -- W_hh, b_hh: indices 1 and 3 -- reads slot q for the n rows)
+                H.gru_unpack(*src, Hh, ncols, H.GRU_HH if i % 2 else H.GRU_IH, *dst[i::4], accumulate=direct)
+            else:
+                unpack(*src, Hh, ncols, *dst[i::4], accumulate=direct)
     if direct:
         return (None,) * (4 * D)
     for d in range(D):
-        dst[4 * d + 3] = dst[4 * d + 2].clone()
+        if not m.gru:
+            dst[4 * d + 3] = dst[4 * d + 2].clone()
     return tuple(dst)
 
 
@@ -344,7 +367,7 @@ def _rnnp_dx(gates, xv, lstm_params, m, x_shape, in_link, Kc):
     """stage 5 -> d(input).  Kc > 0: my input is a Tanh output whose backward rides on this GEMM's store; the result
     travels on in_link and x receives a dummy (its true gradient is never formed -- hence not when it is watched)"""
     R, T, I, G, dev = m.N * m.T, m.T, m.I, 4 * m.D * m.Hh, gates.device
-    wihT, ld_t = _wih_T_of(lstm_params, m.Hh, I)
+    wihT, ld_t = _wih_T_of(lstm_params, m.Hh, I, m.gru)
     if not Kc or in_link.observed():
         dxb, ld_dx = H.padded(R, I, dev, zero=True)
         H.gemm(gates, G, wihT, ld_t, dxb, ld_dx, R, I, G)
@@ -370,6 +393,8 @@ def _proj_unlayout(dwp, Hh, Hp):
 def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=False, dropout_p=0.0, state=None,
                return_state=False):
     """x rows (n,t); lstm = torch.nn.LSTM parameter container, linear = nn.Linear container.
+    lstm a torch.nn.GRU container: the same layer on the GRU recurrence (gru.hip); its state is ONE tensor, h -- `state`
+    = h0 [N, H], and the result with return_state is (output, hT).
     lstm.bidirectional False: the causal route -- the same _RNNP over one direction of time.  There, and only without
     gradients, state = (h0, c0) [N, H] starts the recurrence from a carried state and / or return_state asks for the last
     frame's: the result is then (output, (hT, cT)).
@@ -386,6 +411,7 @@ def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=Fals
     import weakref
     if lstm.bidirectional and (state is not None or return_state):
         raise NotImplementedError("rnnp_layer: a state on a bidirectional layer (it reads the whole utterance)")
+    gru = isinstance(lstm, torch.nn.GRU)
     names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
     lstm_params = [getattr(lstm, n) for n in names]
     if lstm.bidirectional:
@@ -395,20 +421,22 @@ def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=Fals
         if torch.is_grad_enabled():
             raise RuntimeError("rnnp_layer: a carried state (state=(h0, c0)) exists without gradients only -- call it under "
                                "torch.no_grad() (a gradient through the state, truncated BPTT, is not implemented)")
-        if len(state) != 2:
+        if gru and not torch.is_tensor(state):
+            raise ValueError("state: h0 (a GRU carries one tensor)")
+        if not gru and len(state) != 2:
             raise ValueError("state: (h0, c0)")
         y, _, _, m, _, last = _rnnp_forward(x, lstm_params, linear.weight, linear.bias, N, T, act, combine, dropout_p,
-                                            state=state, want_state=True)
-        return (y if combine else y[:, :m.hdim]), last
+                                            state=(state,) if gru else state, want_state=True, gru=gru)
+        return (y if combine else y[:, :m.hdim]), (last[0] if gru else last)
     in_link = getattr(x, "_tssep_tanh_link", None) if in_tanh else None
     if in_link is not None and not (x.requires_grad and torch.is_grad_enabled()):
         in_link = None
     out_link = _Link() if (dz_given and act == 1 and not dropout_p and torch.is_grad_enabled()) else None
-    out = _RNNP.apply(x, N, T, act, combine, in_tanh, in_link, out_link, dropout_p, bool(return_state), *lstm_params,
+    out = _RNNP.apply(x, N, T, act, combine, in_tanh, in_link, out_link, dropout_p, bool(return_state), gru, *lstm_params,
                       linear.weight, linear.bias)
     last = None
     if return_state:
-        out, last = out[0], (out[1], out[2])
+        out, last = out[0], (out[1] if gru else (out[1], out[2]))
     if out_link is not None and out.requires_grad:
         out_link.out = weakref.ref(out)
         out._tssep_tanh_link = out_link

@@ -804,6 +804,26 @@ def lstm_pack(params, H, I):
 lstm1_pack = lstm_pack      # (a name of its own: the callers of one direction ask for it, and the tests watch each name)
 
 
+def gru_pack(params, H, I):
+    """params: the 4 tensors of one direction of time (w_ih [3H, I], w_hh [3H, H], b_ih, b_hh; torch.nn.GRU's layout, rows
+    r, z, n) or the 8 of two (forward, then reverse) -> the four-slot layouts of gru.hip, in lstm_pack's dictionary: every
+    unit has the slots (r, z, n, q), so every size is the LSTM's."""
+    L = _lib.lib()
+    nd = len(params) // 4
+    ld_i = round_up(I, 4)
+    sz = LstmSizes()
+    check(L.tssep_gru_pack_sizes(nd, H, I, ld_i, ctypes.byref(sz)), "gru_pack_sizes")
+    buf = torch.empty(sz.wih_p + round_up(sz.bias_p, 4) + sz.whh_f + sz.whh_b, device=params[0].device, dtype=torch.float32)
+    o1 = sz.wih_p
+    o2 = o1 + round_up(sz.bias_p, 4)
+    o3 = o2 + sz.whh_f
+    wih_p, bias_p, whh_f, whh_b = buf[:o1], buf[o1:o1 + sz.bias_p], buf[o2:o3], buf[o3:]
+    ps = [_f32(p.detach()).contiguous() for p in params]
+    ptrs = [_p(p) for p in ps] + [None] * (8 - len(ps))
+    check(L.tssep_gru_pack(nd, *ptrs, H, I, ld_i, _p(wih_p), _p(bias_p), _p(whh_f), _p(whh_b), _stream()), "gru_pack")
+    return dict(wih_p=wih_p, bias_p=bias_p, whh_f=whh_f, whh_b=whh_b, ld_i=ld_i, _keep=(buf, ps))
+
+
 _ERR = {}
 
 
@@ -862,7 +882,7 @@ ONCHIP16_BWD_GROUPS = 2  # at most: a backward phase is paced by its three barri
 KEEP_XBUF = None         # a list: the exchange buffers of the interleaved launches are appended (trace builds, tools)
 
 
-def recurrence_plan(N, T, H, cus, directions=2):
+def recurrence_plan(N, T, H, cus, directions=2, cell="lstm"):
     """-> {"fwd": (kernel, groups), "bwd": (kernel, groups)}: the kernel of each direction of time of a BLSTM layer over
     N sequences of T frames with H units, on a device of `cus` compute units.  directions = 1 (typ = 'lstm'): the
     streaming kernels instantiated for one direction, with a state, ("stream1_f32", 0) both ways -- the only recurrence
@@ -881,7 +901,12 @@ def recurrence_plan(N, T, H, cus, directions=2):
     sent backward launches of <= 32 sequences to the fp32 cluster kernel, which the compact granules overtook.  The fp32
     W-stationary (cluster) and streaming kernels remain selectable (RECURRENCE) as the exact-fp32 recurrences, and
     streaming is the path for H the W-stationary kernels do not support -- a fallback for a SUPPORTED H (sequence too
-    long) is announced, never silent."""
+    long) is announced, never silent.
+    cell = "gru" (torch.nn.GRU containers): gru.hip's streaming kernels, ("stream_gru_f32", 0) for two directions and
+    ("stream1_gru_f32", 0) for one, both ways -- the only GRU recurrences there are, so no policy switch is read."""
+    if cell == "gru":
+        return dict.fromkeys(("fwd", "bwd"), ("stream1_gru_f32" if directions == 1 else "stream_gru_f32", 0))
+    assert cell == "lstm", cell
     if directions == 1:
         return dict.fromkeys(("fwd", "bwd"), ("stream1_f32", 0))
     return {direction: _plan_direction(N, T, H, cus, direction == "bwd") for direction in ("fwd", "bwd")}
@@ -932,7 +957,7 @@ _VP, _I64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
 def recurrence_packs(plan, w_hh_f, w_hh_r, H, lstm_pk=None, memo=False, waves=8):
     """-> {direction: the W_hh layout its planned kernel reads} for the directions of `plan` (recurrence_plan's, or a part
-    of it).  The streaming kernels read lstm_pack's (`lstm_pk`), the W-stationary ones a layout of their own, built once
+    of it).  The streaming kernels read lstm_pack's (`lstm_pk`; the GRU ones gru_pack's), the W-stationary ones a layout of their own, built once
     here where both directions read it: through `derived` on (w_hh_f, w_hh_r) with memo=True -- the tags prepare_derived
     builds at the start of a captured step --, anew otherwise.  waves = 4: the layout of the four-wave interleaved
     forward (experiment build, `_w16`)."""
@@ -968,7 +993,7 @@ def recurrence_packs(plan, w_hh_f, w_hh_r, H, lstm_pk=None, memo=False, waves=8)
 
     built, out = {}, {}
     for direction, (kernel, _) in plan.items():
-        if kernel in ("stream_f32", "stream1_f32"):
+        if kernel in ("stream_f32", "stream1_f32", "stream_gru_f32", "stream1_gru_f32"):      # (lstm_pack's / gru_pack's)
             out[direction] = lstm_pk["whh_b" if direction == "bwd" else "whh_f"]
             continue
         tag, build, which = layout(kernel, direction == "bwd")
@@ -983,6 +1008,8 @@ def recurrence_packs(plan, w_hh_f, w_hh_r, H, lstm_pk=None, memo=False, waves=8)
 _RECURRENCE_KERNELS = {
     "stream_f32": (("tssep_blstm_fwd", "tssep_blstm_bwd"), "blstm", (0, 0)),
     "stream1_f32": (("tssep_lstm1_fwd", "tssep_lstm1_bwd"), "lstm1", (0, 0)),
+    "stream_gru_f32": (("tssep_gru_fwd", "tssep_gru_bwd"), "gru", (0, 0)),
+    "stream1_gru_f32": (("tssep_gru1_fwd", "tssep_gru1_bwd"), "gru1", (0, 0)),
     "cluster_f32": (("tssep_blstm_cluster_fwd", "tssep_blstm_cluster_bwd"), "blstm_cluster", (0, 0)),
     "onchip32_bf16x3": (("tssep_blstm_onchip_fwd", "tssep_blstm_onchip_bwd"), "blstm_onchip", (40, 44)),
     "onchip16_bf16x3": (("tssep_blstm_onchip16_fwd", "tssep_blstm_onchip16_bwd"), "blstm_onchip", (40, 44)),
@@ -997,8 +1024,12 @@ def recurrence_launch(planned, direction, gates, cell, h, ldo, dstride, whh, N, 
     four-wave workgroups, experiment build: `_w16`) go to the kernel as they are.
     "stream1_f32" (one direction: gates [N,T,H,4], cell [N,T,H], h columns 0..H-1 of [N,T,ldo]; no dstride) takes
     state = (h0, c0, hT, cT) forward: h0 / c0 [N,H] the initial state (both or neither; None = zeros), hT / cT [N,H]
-    receive the state after the last frame.  Backward it starts from a zero state."""
+    receive the state after the last frame.  Backward it starts from a zero state.
+    The GRU kernels ("stream_gru_f32", "stream1_gru_f32"; gates hold the slots (r, z, n, q)) have no cell tensor: forward
+    `cell` is ignored (None), backward it is the forward's hout, which they read for h_prev; state = (h0, None, hT, None)."""
     kernel, groups = planned
+    if kernel in ("stream_gru_f32", "stream1_gru_f32"):
+        return _gru_launch(kernel, direction, gates, cell, h, ldo, dstride, whh, N, T, H, state)
     bwd = direction == "bwd"
     entry, timed, cell_bytes = _RECURRENCE_KERNELS[kernel]
     entry = entry[bwd]
@@ -1037,6 +1068,25 @@ def recurrence_launch(planned, direction, gates, cell, h, ldo, dstride, whh, N, 
         KEEP_XBUF.append(xbuf)
     with _timed(f"{timed}_{direction}", flops, nbytes):
         check(fn(*args, _p(xbuf), _p(_err_flag(gates.device)), N, T, H, cus, *tail, _stream()), entry[6:])
+
+
+def _gru_launch(kernel, direction, gates, hout, h, ldo, dstride, whh, N, T, H, state):
+    bwd = direction == "bwd"
+    entry, timed, _ = _RECURRENCE_KERNELS[kernel]
+    entry = entry[bwd]
+    _log_recurrence(kernel, direction, N, T, H, 0)
+    one = kernel == "stream1_gru_f32"
+    D = 1 if one else 2
+    h0, c0, hT, cT = state
+    assert c0 is None and cT is None, "a GRU carries h alone"
+    assert one or (h0 is None and hT is None), "a state needs one direction of time"
+    for s in (h0, hT):
+        assert s is None or (s.is_contiguous() and tuple(s.shape) == (N, H) and _f32(s) is s), (N, H)
+    args = [_p(gates)] + ([_p(hout)] if bwd else []) + [_p(h), ldo] + ([] if one else [dstride]) + [_p(whh)]
+    if one and not bwd:
+        args += [_p(h0), _p(hT)]
+    with _timed(f"{timed}_{direction}", 2 * D * N * T * 4 * H * H, 0):
+        check(getattr(_lib.lib(), entry)(*args, N, T, H, _stream()), entry[6:])
 
 
 # Each recurrence kernel by name (the kernel tests and tools): the plan, the packs and the launcher above on one fixed
@@ -1129,6 +1179,26 @@ def lstm_unpack(src, ld, nsplit, split_stride, H, ncols, dst_f, dst_r, accumulat
 def lstm1_unpack(src, ld, nsplit, split_stride, H, ncols, dst, accumulate=False):
     check(_lib.lib().tssep_lstm1_unpack(_p(src), ld, nsplit, split_stride, H, ncols, _p(dst), int(accumulate),
                                         _stream()), "lstm1_unpack")
+
+
+def gru_fwd(gates, hout, ldo, dstride, whh_f, N, T, H, directions=2, h0=None, hT=None):
+    """directions = 1: gates [N,T,H,4], hout columns 0..H-1, dstride unused; h0 / hT [N,H] the carried state"""
+    recurrence_launch(("stream1_gru_f32" if directions == 1 else "stream_gru_f32", 0), "fwd", gates, None, hout, ldo,
+                      dstride, whh_f, N, T, H, state=(h0, None, hT, None))
+
+
+def gru_bwd(gates, hout, dhout, ldo, dstride, whh_b, N, T, H, directions=2):
+    recurrence_launch(("stream1_gru_f32" if directions == 1 else "stream_gru_f32", 0), "bwd", gates, hout, dhout, ldo,
+                      dstride, whh_b, N, T, H)
+
+
+GRU_IH, GRU_HH = 0, 1      # TSSEP_GRU_IH / TSSEP_GRU_HH: the slots (0, 1, 2) / (0, 1, 3) of a packed row quadruple
+
+
+def gru_unpack(src, ld, nsplit, split_stride, H, ncols, which, dst_f, dst_r=None, accumulate=False):
+    """packed (dir, unit, slot) rows -> torch's [3H, ncols] rows (r, z, n) of one (dst_r None) or two directions"""
+    check(_lib.lib().tssep_gru_unpack(1 if dst_r is None else 2, _p(src), ld, nsplit, split_stride, H, ncols, which,
+                                      _p(dst_f), _p(dst_r), int(accumulate), _stream()), "gru_unpack")
 
 
 # ---- side stream for weight gradients ---------------------------------------------------------
