@@ -304,7 +304,17 @@ int tssep_lstm_unpack(const float* src, int64_t ld, int nsplit, int64_t split_st
  * hout / dhout [N,T,ldo] with columns 0..H-1 (H..ldo-1 are never written and never read).  H <= 512.
  * h0 / c0 [N,H]: the state the recurrence starts from -- both or neither (one alone: TSSEP_E_NULL); null = zeros.
  * hT / cT [N,H], each nullable: the state after the last frame, the bits of hout[:, T-1, :H] / cell[:, T-1].
- * tssep_lstm1_bwd assumes a ZERO initial state: a carried state exists without gradients only. */
+ * tssep_lstm1_bwd assumes a ZERO initial state and no gradient for the final one; tssep_lstm1_bwd_state is the same
+ * kernel with the carried state's gradient (truncated or full BPTT over chunks).  Every state argument is [N,H] and
+ * nullable; all null = tssep_lstm1_bwd, bit for bit:
+ *   c0        the state the forward started from (the forget gate's gradient at frame 0 reads it); null = zeros
+ *   dhT, dcT  the gradient arriving for (hT, cT); null = zeros.  dhT stands where the four partial sums of
+ *             W_hh^T d(gates) stand at the top of a step, (dhT + 0 + 0 + 0) + dhout[T-1], and dcT where the carried
+ *             dc stands, so a backward run as chunks, last chunk first, each taking the next one's (dh0, dc0) as its
+ *             (dhT, dcT) and cell[:, first frame - 1] as its c0, writes the bits of the one launch over all frames
+ *   dh0, dc0  the gradient of (h0, c0), written when not null: the four partial sums of the last product in the
+ *             order a step adds them, and the carried dc * f
+ * The term sum_n d(gates)[n, 0]^T h0[n] of dW_hh is the caller's (the frame-shifted product pairs frame 0 with 0). */
 int tssep_lstm1_pack_sizes(int H, int I, int64_t ld_i, tssep_lstm_sizes* out);
 int tssep_lstm1_pack(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
                      int H, int I, int64_t ld_i, float* wih_p, float* bias_p, float* whh_f,
@@ -314,6 +324,9 @@ int tssep_lstm1_fwd(float* gates, float* cell, float* hout, int64_t ldo, const f
                     int64_t N, int64_t T, int H, void* stream);
 int tssep_lstm1_bwd(float* gates, const float* cell, const float* dhout, int64_t ldo,
                     const float* whh_b, int64_t N, int64_t T, int H, void* stream);
+int tssep_lstm1_bwd_state(float* gates, const float* cell, const float* dhout, int64_t ldo, const float* whh_b,
+                          const float* c0, const float* dhT, const float* dcT, float* dh0, float* dc0,
+                          int64_t N, int64_t T, int H, void* stream);
 /* dst[(g*H + u)*ncols + k] (+)= sum_{s<nsplit} src[s*split_stride + (4u + g)*ld + k] */
 int tssep_lstm1_unpack(const float* src, int64_t ld, int nsplit, int64_t split_stride,
                        int H, int ncols, float* dst, int accumulate, void* stream);
@@ -351,12 +364,19 @@ int tssep_gru_bwd(float* gates, const float* hout, const float* dhout, int64_t l
                   const float* whh_b, int64_t N, int64_t T, int H, void* stream);
 /* ONE direction, forward in time: gates [N,T,H,4], hout / dhout [N,T,ldo] with columns 0..H-1.
  * h0 [N,H], nullable: the state the recurrence starts from; null = zeros.  hT [N,H], nullable: the state after the
- * last frame, the bits of hout[:, T-1, :H].  tssep_gru1_bwd assumes a ZERO initial state: a carried state exists
- * without gradients only. */
+ * last frame, the bits of hout[:, T-1, :H].  tssep_gru1_bwd assumes a ZERO initial state and no gradient for the final
+ * one; tssep_gru1_bwd_state is the same kernel with both, every state argument [N,H] and nullable (all null =
+ * tssep_gru1_bwd, bit for bit): h0 is h_prev of frame 0, in dz = dh (h_prev - n); dhT is one more addend of dh at
+ * frame T-1, in the carry's place: (0 + dhout) + dhT; dh0 = (p0 + p1 + p2 + p3) + dh z of frame 0.  A chunked backward is NOT
+ * the whole launch's bits: the whole launch adds dhout between the partial sums and the carry, and one tensor dh0 cannot
+ * hand both over apart (one rounding of dh per boundary).  The h0 term of dW_hh is the caller's, as for the LSTM. */
 int tssep_gru1_fwd(float* gates, float* hout, int64_t ldo, const float* whh_f, const float* h0,
                    float* hT, int64_t N, int64_t T, int H, void* stream);
 int tssep_gru1_bwd(float* gates, const float* hout, const float* dhout, int64_t ldo,
                    const float* whh_b, int64_t N, int64_t T, int H, void* stream);
+int tssep_gru1_bwd_state(float* gates, const float* hout, const float* dhout, int64_t ldo, const float* whh_b,
+                         const float* h0, const float* dhT, float* dh0,
+                         int64_t N, int64_t T, int H, void* stream);
 /* gradient unpack + split-K reduction: a matrix with packed (dir,unit,slot) rows back to torch's [3H, ncols] rows:
  *   dst_d[(g*H + u)*ncols + k] (+)= sum_{s<nsplit} src[s*split_stride + (d*4H + 4u + slot(g))*ld + k],  g = 0..2
  * which = TSSEP_GRU_IH: slot(g) = (0, 1, 2) -- dW_ih, db_ih; TSSEP_GRU_HH: slot(g) = (0, 1, 3) -- dW_hh, db_hh (the one

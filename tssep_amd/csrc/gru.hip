@@ -269,7 +269,9 @@ __global__ __launch_bounds__(256, 1) void gru_fwd_kernel(
 template <int NB, int NBB, int ND>
 __global__ __launch_bounds__(256, 1) void gru_bwd_kernel(
     float* __restrict__ gates, const float* __restrict__ hout, const float* __restrict__ dhout,
-    int64_t ldo, int64_t dstride, const float* __restrict__ whh_b, int64_t N, int64_t T, int H, int KQ3) {
+    int64_t ldo, int64_t dstride, const float* __restrict__ whh_b, int64_t N, int64_t T, int H, int KQ3,
+    const float* __restrict__ h0, const float* __restrict__ dhT, float* __restrict__ dh0) {
+  // h0 / dhT / dh0: [N, H], ND == 1 only, each may be null (zeros / not wanted)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int KROW = 4 * KQ3 + 12;
   const int PROW = NBB * 64 + 4;
@@ -301,6 +303,15 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_kernel(
   float dhc[NB][2];      // dh z of the later step
 #pragma unroll
   for (int i = 0; i < NB; ++i) { dhc[i][0] = 0.f; dhc[i][1] = 0.f; }
+  if constexpr (ND == 1) {
+    if (dhT) {      // the gradient arriving for the final h: one more addend of the last frame's dh, in the carry's place
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg)
+          if (uvalid[i] && nvalid[sg]) dhc[i][sg] = dhT[nrow[sg] * H + u[i]];
+    }
+  }
 
   f32x4 w0[NBB], w1[NBB], w2[NBB];
 #define LOADW(dst, kq_)                                                  \
@@ -340,11 +351,14 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_kernel(
             const int64_t cellidx = ((nrow[sg] * T + t) * ND + dir) * (int64_t)H + u[i];
             const f32x4 g4 =
                 __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(gates + cellidx * 4));
-            const float hprev = has_prev ? __builtin_nontemporal_load(
-                                               hout + (nrow[sg] * T + tp) * ldo + dir * dstride + u[i])
-                                         : 0.f;
+            float hprev = has_prev ? __builtin_nontemporal_load(
+                                         hout + (nrow[sg] * T + tp) * ldo + dir * dstride + u[i])
+                                   : 0.f;
             dh += __builtin_nontemporal_load(dhout + (nrow[sg] * T + t) * ldo + dir * dstride + u[i]);
             dh += dhc[i][sg];
+            if constexpr (ND == 1) {
+              if (!has_prev && h0) hprev = h0[nrow[sg] * H + u[i]];      // the state the forward started from
+            }
             const float rg = g4[0], zg = g4[1], ng = g4[2], q = g4[3];
             const float dn = dh * (1.f - zg);
             const float dz = dh * (hprev - ng);
@@ -389,6 +403,20 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_kernel(
         *reinterpret_cast<f32x4*>(part + (wave * 8 + sg * 4 + j) * PROW + i * 64 + 4 * ub) =
             acc[i][sg];
     __syncthreads();
+  }
+  if constexpr (ND == 1) {
+    if (dh0) {      // the gradient of the initial state: the partial sums and the lane-local carry of one more step
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg)
+          if (uvalid[i] && nvalid[sg]) {
+            const int s = sg * 4 + j;
+            const float p = part[(0 * 8 + s) * PROW + u[i]] + part[(1 * 8 + s) * PROW + u[i]] +
+                            part[(2 * 8 + s) * PROW + u[i]] + part[(3 * 8 + s) * PROW + u[i]];
+            dh0[nrow[sg] * H + u[i]] = p + dhc[i][sg];
+          }
+    }
   }
 #undef LOADW
 #undef LOADH
@@ -436,7 +464,8 @@ int launch_fwd(float* gates, float* hout, int64_t ldo, int64_t dstride, const fl
 
 template <int ND>
 int launch_bwd(float* gates, const float* hout, const float* dhout, int64_t ldo, int64_t dstride,
-               const float* whh_b, int64_t N, int64_t T, int H, void* stream) {
+               const float* whh_b, const float* h0, const float* dhT, float* dh0, int64_t N, int64_t T,
+               int H, void* stream) {
   if (!aligned16(gates) || !aligned16(whh_b)) return TSSEP_E_ALIGN;
   const int NB = gru_nb(H), NBB = gru_nbb(H), KQ3 = gru_kq3(H);
   if (NB > 8) return TSSEP_E_UNSUPPORTED;
@@ -445,7 +474,7 @@ int launch_bwd(float* gates, const float* hout, const float* dhout, int64_t ldo,
   hipStream_t s = (hipStream_t)stream;
 #define L(NB_)                                                                                 \
   hipLaunchKernelGGL((gru_bwd_kernel<NB_, NB_, ND>), grid, dim3(256), lds, s, gates, hout,     \
-                     dhout, ldo, dstride, whh_b, N, T, H, KQ3)
+                     dhout, ldo, dstride, whh_b, N, T, H, KQ3, h0, dhT, dh0)
   // NB = ceil(ceil(H/16)/4) and NBB = ceil(H/64) are the same number
   switch (NB == NBB ? NB : 0) {
     case 1: L(1); break;
@@ -515,7 +544,7 @@ extern "C" int tssep_gru_bwd(float* gates, const float* hout, const float* dhout
                              void* stream) {
   if (!gates || !hout || !dhout || !whh_b) return TSSEP_E_NULL;
   if (N <= 0 || T <= 0 || H <= 0 || dstride < H || ldo < dstride + H) return TSSEP_E_SHAPE;
-  return launch_bwd<2>(gates, hout, dhout, ldo, dstride, whh_b, N, T, H, stream);
+  return launch_bwd<2>(gates, hout, dhout, ldo, dstride, whh_b, nullptr, nullptr, nullptr, N, T, H, stream);
 }
 
 // ---- one direction of time (typ = 'gru'): the same kernels with ND = 1 ----
@@ -526,9 +555,15 @@ extern "C" int tssep_gru1_fwd(float* gates, float* hout, int64_t ldo, const floa
   return launch_fwd<1>(gates, hout, ldo, 0, whh_f, h0, hT, N, T, H, stream);
 }
 
+extern "C" int tssep_gru1_bwd_state(float* gates, const float* hout, const float* dhout, int64_t ldo,
+                                    const float* whh_b, const float* h0, const float* dhT, float* dh0,
+                                    int64_t N, int64_t T, int H, void* stream) {
+  if (!gates || !hout || !dhout || !whh_b) return TSSEP_E_NULL;      // every state argument may be null
+  if (N <= 0 || T <= 0 || H <= 0 || ldo < H) return TSSEP_E_SHAPE;
+  return launch_bwd<1>(gates, hout, dhout, ldo, 0, whh_b, h0, dhT, dh0, N, T, H, stream);
+}
+
 extern "C" int tssep_gru1_bwd(float* gates, const float* hout, const float* dhout, int64_t ldo,
                               const float* whh_b, int64_t N, int64_t T, int H, void* stream) {
-  if (!gates || !hout || !dhout || !whh_b) return TSSEP_E_NULL;
-  if (N <= 0 || T <= 0 || H <= 0 || ldo < H) return TSSEP_E_SHAPE;
-  return launch_bwd<1>(gates, hout, dhout, ldo, 0, whh_b, N, T, H, stream);
+  return tssep_gru1_bwd_state(gates, hout, dhout, ldo, whh_b, nullptr, nullptr, nullptr, N, T, H, stream);
 }

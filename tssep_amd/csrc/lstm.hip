@@ -270,7 +270,10 @@ __global__ __launch_bounds__(256, 1) void blstm_fwd_kernel(
 template <int NB, int NBB, int ND>
 __global__ __launch_bounds__(256, 1) void blstm_bwd_kernel(
     float* __restrict__ gates, const float* __restrict__ cell, const float* __restrict__ dhout,
-    int64_t ldo, int64_t dstride, const float* __restrict__ whh_b, int64_t N, int64_t T, int H, int KQ3) {
+    int64_t ldo, int64_t dstride, const float* __restrict__ whh_b, int64_t N, int64_t T, int H, int KQ3,
+    const float* __restrict__ c0, const float* __restrict__ dhT, const float* __restrict__ dcT,
+    float* __restrict__ dh0, float* __restrict__ dc0) {
+  // c0 / dhT / dcT / dh0 / dc0: [N, H], ND == 1 only, each may be null (zeros / not wanted)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int KROW = 4 * KQ3 + 12;
   const int PROW = NBB * 64 + 4;
@@ -302,6 +305,15 @@ __global__ __launch_bounds__(256, 1) void blstm_bwd_kernel(
   float dcc[NB][2];
 #pragma unroll
   for (int i = 0; i < NB; ++i) { dcc[i][0] = 0.f; dcc[i][1] = 0.f; }
+  if constexpr (ND == 1) {
+    if (dcT) {      // the gradient arriving for the final cell state: the carry a longer launch would hold here
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg)
+          if (uvalid[i] && nvalid[sg]) dcc[i][sg] = dcT[nrow[sg] * H + u[i]];
+    }
+  }
 
   f32x4 w0[NBB], w1[NBB], w2[NBB];
 #define LOADW(dst, kq_)                                                  \
@@ -322,6 +334,16 @@ __global__ __launch_bounds__(256, 1) void blstm_bwd_kernel(
   LOADW(w0, 0);
   LOADW(w1, 1);
   __syncthreads();
+  if constexpr (ND == 1) {
+    if (dhT) {      // the gradient arriving for the final h stands where wave 0's partial sums stand: the first step reads
+                    // (dhT + 0 + 0 + 0) + dhout[T-1].  Each lane writes the very words it reads back: no barrier.
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg)
+          if (uvalid[i] && nvalid[sg]) part[(sg * 4 + j) * PROW + u[i]] = dhT[nrow[sg] * H + u[i]];
+    }
+  }
 
   for (int64_t step = 0; step < T; ++step) {
     const int64_t t = dir ? step : T - 1 - step;
@@ -342,9 +364,12 @@ __global__ __launch_bounds__(256, 1) void blstm_bwd_kernel(
             const f32x4 g4 =
                 __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(gates + cellidx * 4));
             const float ct = __builtin_nontemporal_load(cell + cellidx);
-            const float cp = has_prev ? __builtin_nontemporal_load(
-                                            cell + ((nrow[sg] * T + tp) * ND + dir) * (int64_t)H + u[i])
-                                      : 0.f;
+            float cp = has_prev ? __builtin_nontemporal_load(
+                                      cell + ((nrow[sg] * T + tp) * ND + dir) * (int64_t)H + u[i])
+                                : 0.f;
+            if constexpr (ND == 1) {
+              if (!has_prev && c0) cp = c0[nrow[sg] * H + u[i]];      // the state the forward started from
+            }
             dh += __builtin_nontemporal_load(dhout + (nrow[sg] * T + t) * ldo + dir * dstride + u[i]);
             const float tc = tanhf_acc(ct);
             const float d_o = dh * tc;
@@ -390,6 +415,21 @@ __global__ __launch_bounds__(256, 1) void blstm_bwd_kernel(
         *reinterpret_cast<f32x4*>(part + (wave * 8 + sg * 4 + j) * PROW + i * 64 + 4 * ub) =
             acc[i][sg];
     __syncthreads();
+  }
+  if constexpr (ND == 1) {
+    if (dh0 || dc0) {      // the gradient of the initial state: what the top of one more step would read
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg)
+          if (uvalid[i] && nvalid[sg]) {
+            const int s = sg * 4 + j;
+            if (dh0)
+              dh0[nrow[sg] * H + u[i]] = part[(0 * 8 + s) * PROW + u[i]] + part[(1 * 8 + s) * PROW + u[i]] +
+                                         part[(2 * 8 + s) * PROW + u[i]] + part[(3 * 8 + s) * PROW + u[i]];
+            if (dc0) dc0[nrow[sg] * H + u[i]] = dcc[i][sg];
+          }
+    }
   }
 #undef LOADW
 #undef LOADH
@@ -466,7 +506,8 @@ int launch_fwd(float* gates, float* cell, float* hout, int64_t ldo, int64_t dstr
 
 template <int ND>
 int launch_bwd(float* gates, const float* cell, const float* dhout, int64_t ldo, int64_t dstride,
-               const float* whh_b, int64_t N, int64_t T, int H, void* stream) {
+               const float* whh_b, const float* c0, const float* dhT, const float* dcT, float* dh0,
+               float* dc0, int64_t N, int64_t T, int H, void* stream) {
   if (!aligned16(gates) || !aligned16(whh_b)) return TSSEP_E_ALIGN;
   const int NB = lstm_nb(H), NBB = lstm_nbb(H), KQ3 = lstm_kq3(H);
   if (NB > 8) return TSSEP_E_UNSUPPORTED;
@@ -475,7 +516,7 @@ int launch_bwd(float* gates, const float* cell, const float* dhout, int64_t ldo,
   hipStream_t s = (hipStream_t)stream;
 #define L(NB_, NBB_)                                                                          \
   hipLaunchKernelGGL((blstm_bwd_kernel<NB_, NBB_, ND>), grid, dim3(256), lds, s, gates, cell,  \
-                     dhout, ldo, dstride, whh_b, N, T, H, KQ3)
+                     dhout, ldo, dstride, whh_b, N, T, H, KQ3, c0, dhT, dcT, dh0, dc0)
   // NB = ceil(ceil(H/16)/4), NBB = ceil(H/64): NBB is NB or NB-... enumerate the reachable pairs
   if (NB == 1) L(1, 1);
   else if (NB == 2) L(2, 2);
@@ -528,7 +569,8 @@ extern "C" int tssep_blstm_bwd(float* gates, const float* cell, const float* dho
                                void* stream) {
   if (!gates || !cell || !dhout || !whh_b) return TSSEP_E_NULL;
   if (N <= 0 || T <= 0 || H <= 0 || dstride < H || ldo < dstride + H) return TSSEP_E_SHAPE;
-  return launch_bwd<2>(gates, cell, dhout, ldo, dstride, whh_b, N, T, H, stream);
+  return launch_bwd<2>(gates, cell, dhout, ldo, dstride, whh_b, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, N, T, H, stream);
 }
 
 // ---- one direction of time (typ = 'lstm'): the same kernels with ND = 1 ----
@@ -559,9 +601,17 @@ extern "C" int tssep_lstm1_fwd(float* gates, float* cell, float* hout, int64_t l
   return launch_fwd<1>(gates, cell, hout, ldo, 0, whh_f, h0, c0, hT, cT, N, T, H, stream);
 }
 
+extern "C" int tssep_lstm1_bwd_state(float* gates, const float* cell, const float* dhout, int64_t ldo,
+                                     const float* whh_b, const float* c0, const float* dhT,
+                                     const float* dcT, float* dh0, float* dc0, int64_t N, int64_t T,
+                                     int H, void* stream) {
+  if (!gates || !cell || !dhout || !whh_b) return TSSEP_E_NULL;      // every state argument may be null
+  if (N <= 0 || T <= 0 || H <= 0 || ldo < H) return TSSEP_E_SHAPE;
+  return launch_bwd<1>(gates, cell, dhout, ldo, 0, whh_b, c0, dhT, dcT, dh0, dc0, N, T, H, stream);
+}
+
 extern "C" int tssep_lstm1_bwd(float* gates, const float* cell, const float* dhout, int64_t ldo,
                                const float* whh_b, int64_t N, int64_t T, int H, void* stream) {
-  if (!gates || !cell || !dhout || !whh_b) return TSSEP_E_NULL;
-  if (N <= 0 || T <= 0 || H <= 0 || ldo < H) return TSSEP_E_SHAPE;
-  return launch_bwd<1>(gates, cell, dhout, ldo, 0, whh_b, N, T, H, stream);
+  return tssep_lstm1_bwd_state(gates, cell, dhout, ldo, whh_b, nullptr, nullptr, nullptr, nullptr, nullptr,
+                               N, T, H, stream);
 }

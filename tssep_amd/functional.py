@@ -231,16 +231,30 @@ class _RNNP(torch.autograd.Function):
     projection stores plainly (act = 0) and one pass over y applies mask, 1 / (1 - p) and Tanh in place; the backward
     regenerates the mask from the {seed, draw} pair the forward drew (hip_ops.dropout_draw).
     ``want_state`` (D = 1): the state after the last frame leaves as two more outputs.  Zero initial state: a carried state
-    exists without gradients only (rnnp_layer).
+    exists without gradients only (rnnp_layer) -- unless ``state_grad``: then h0 / c0 [N, Hh] (None: zeros) are
+    differentiable inputs and the last state leaves as differentiable outputs.  Gradients are not
+    materialised there: a final state nobody differentiates arrives as None and reaches the recurrence as a null pointer,
+    so such a layer makes the launches of one without a state.
     The 4 D tensors of a torch.nn.GRU (three gate rows per unit) run the GRU recurrence (gru.hip) through the same stages;
     its state is one more output, h.  ``gru``: rnnp_layer's flag, the container's class."""
 
     @staticmethod
-    def forward(ctx, x, N, T, act, combine, in_tanh, in_link, out_link, dropout_p, want_state, gru, *params):
+    def forward(ctx, x, N, T, act, combine, in_tanh, in_link, out_link, dropout_p, want_state, gru, state_grad, h0, c0,
+                *params):
         assert not dropout_p or (act == 1 and out_link is None), "dropout_p: a site is the Tanh behind the layer, never folded"
+        assert state_grad or (h0 is None and c0 is None), "a state is an input under state_grad only"
+        state, ctx.state_shapes = None, (None, None)
+        if h0 is not None:
+            Hh = params[1].shape[1]
+            ctx.state_shapes = (h0.shape, None if gru else c0.shape)
+            h0 = H._f32(h0).reshape(N, Hh).contiguous()
+            c0 = None if gru else H._f32(c0).reshape(N, Hh).contiguous()
+            state = (h0,) if gru else (h0, c0)
         y, saved, ctx.drop, ctx.meta, ctx.recurrence, last = _rnnp_forward(x, params[:-2], *params[-2:], N, T, act, combine,
-                                                                           dropout_p, want_state=want_state, gru=gru)
-        ctx.save_for_backward(*saved)
+                                                                           dropout_p, state=state, want_state=want_state,
+                                                                           gru=gru)
+        ctx.save_for_backward(*saved, h0, c0)
+        ctx.state_grad = bool(state_grad)
         ctx.params = params
         # Tanh-backward fold (see rnnp_layer): in_link = the link my producer hung on x, out_link = the one my
         # consumer may answer on.  Both are decided again in backward, when it is known who else uses the tensors.
@@ -248,27 +262,43 @@ class _RNNP(torch.autograd.Function):
         assert out_link is None or act == 1, "out_link: only behind the fused Tanh"
         ctx.x_shape = x.shape
         y = y if combine else y[:, :ctx.meta.hdim]
+        if state_grad:
+            ctx.set_materialize_grads(False)
         if not want_state:
             return y
-        ctx.mark_non_differentiable(*last)      # (the last frame's state leaves without a gradient: no truncated BPTT)
+        if not state_grad:
+            ctx.mark_non_differentiable(*last)      # (the last frame's state leaves without a gradient: no truncated BPTT)
         return (y, *last)
 
     @staticmethod
-    def backward(ctx, dy, *_):
-        xv, gates, cell, hout, y, _ = ctx.saved_tensors
+    def backward(ctx, dy, *dlast):
+        xv, gates, cell, hout, y, _, h0, c0 = ctx.saved_tensors
         m, params = ctx.meta, ctx.params
         in_tanh, in_link, out_link = ctx.fold
+        bstate = None
+        if ctx.state_grad:
+            if dy is None:      # (the loss reads the final state alone)
+                dy = torch.zeros_like(y if m.combine else y[:, :m.hdim])
+            new = lambda: torch.empty(m.N, m.Hh, device=gates.device, dtype=torch.float32)  # noqa: E731
+            dlast = [None if g is None else H._f32(g).reshape(m.N, m.Hh).contiguous() for g in dlast] + [None, None]
+            dh0 = new() if h0 is not None and ctx.needs_input_grad[12] else None
+            dc0 = new() if c0 is not None and ctx.needs_input_grad[13] else None
+            bstate = (h0, dlast[0], dh0) if m.gru else (c0, dlast[0], dlast[1], dh0, dc0)
         dz, ld_dz = H.rows_view(_rnnp_dz(dy, y, m, ctx.drop, out_link.take() if out_link is not None else None))
         sinks = [_grad_sink(p) for p in params]
         direct = _is_direct(sinks, True)
         d_w_proj, d_b_proj = _rnnp_proj_wgrads(dz, ld_dz, hout, m, sinks[-2:], direct)
         # the critical path: gates <- d(pre-activations); a GRU's backward recurrence reads hout (h_prev) where the LSTM's reads cell
-        _rnnp_bptt(dz, ld_dz, gates, hout if m.gru else cell, params[-2], m, ctx.recurrence)
-        lstm_grads = _rnnp_lstm_wgrads(gates, hout, xv, m, sinks[:-2], direct)
+        _rnnp_bptt(dz, ld_dz, gates, hout if m.gru else cell, params[-2], m, ctx.recurrence, bstate)
+        lstm_grads = _rnnp_lstm_wgrads(gates, hout, xv, m, sinks[:-2], direct, h0)
         if direct:
             _notify_grads(params)                    # (4 D + 2 tensors: every direction's LSTM weights + the projection)
         dx = _rnnp_dx(gates, xv, params[:-2], m, ctx.x_shape, in_link, in_tanh) if ctx.needs_input_grad[0] else None
-        return (dx,) + (None,) * 10 + (*lstm_grads, d_w_proj, d_b_proj)
+        dstate = (None, None)
+        if bstate is not None:
+            dstate = tuple(None if g is None else g.reshape(shape)
+                           for g, shape in zip((bstate[-1], None) if m.gru else bstate[-2:], ctx.state_shapes))
+        return (dx,) + (None,) * 11 + dstate + (*lstm_grads, d_w_proj, d_b_proj)
 
 
 def _rnnp_dz(dy, y, m, drop, folded):
@@ -313,26 +343,35 @@ def _rnnp_proj_wgrads(dz, ld_dz, hout, m, sinks, direct):
     return d_w, d_b
 
 
-def _rnnp_bptt(dz, ld_dz, gates, cell, w_proj, m, recurrence):
-    """stage 3: dhout = dz W_proj, then the recurrence backwards in time: `gates` <- d(pre-activations)"""
+def _rnnp_bptt(dz, ld_dz, gates, cell, w_proj, m, recurrence, state=None):
+    """stage 3: dhout = dz W_proj, then the recurrence backwards in time: `gates` <- d(pre-activations).  state (D = 1):
+    the carried state's side, (c0, dhT, dcT, dh0, dc0) -- a GRU's (h0, dhT, dh0) -- as hip_ops.recurrence_launch takes it"""
     R, Hp, ld_h = m.N * m.T, m.Hp, m.D * m.Hp
     dhout = torch.empty(R, ld_h, device=dz.device, dtype=torch.float32)
     wpT, ld_t = _proj_T_of(w_proj, m.Hh, Hp)
     H.gemm(dz, ld_dz, wpT, ld_t, dhout, ld_h, R, ld_h, m.hdim)
-    H.recurrence_launch(recurrence[0], "bwd", gates, cell, dhout, ld_h, Hp, recurrence[1], m.N, m.T, m.Hh)
+    H.recurrence_launch(recurrence[0], "bwd", gates, cell, dhout, ld_h, Hp, recurrence[1], m.N, m.T, m.Hh,
+                        **({} if state is None else dict(state=state)))
 
 
-def _rnnp_lstm_wgrads(gates, hout, xv, m, sinks, direct):
+def _rnnp_lstm_wgrads(gates, hout, xv, m, sinks, direct, h0=None):
     """stage 4 -> the 4 D LSTM gradients in parameter order from dgates (in `gates`), or 4 D None when they went into
     `sinks` (side stream).  A GRU (m.gru): the same products over the four slots, unpacked to torch's three gate rows --
-    dW_ih and db_ih from the slots (r, z, n), dW_hh and db_hh from (r, z, q): the two biases have gradients of their own."""
+    dW_ih and db_ih from the slots (r, z, n), dW_hh and db_hh from (r, z, q): the two biases have gradients of their own.
+    h0 [N, Hh] (D = 1): the state the forward started from -- the frame-shifted product pairs frame 0 with zero, so dW_hh
+    takes sum_n dgates[n, 0]^T h0[n] from one more product over the N frame-0 rows of `gates` (row stride T G), added to
+    the packed dW_hh in a fixed order ahead of the unpack: both sink modes and a GRU's slots (r, z, q) see it alike."""
     R, T, I, D, Hh, Hp, G = m.N * m.T, m.T, m.I, m.D, m.Hh, m.Hp, 4 * m.D * m.Hh
-    with _wgrad_branch(gates.device, R, (gates, hout, xv), direct):
+    with _wgrad_branch(gates.device, R, (gates, hout, xv) + (() if h0 is None else (h0,)), direct):
         dwhh = torch.empty(D, 4 * Hh * Hh, device=gates.device, dtype=torch.float32)
         for d in range(D):   # dgates_t paired with h_{t-1} (forward dir) / h_{t+1} (reverse)
             part, S = H.wgrad((gates, d * 4 * Hh), G, (hout, d * Hp), D * Hp, 4 * Hh, Hh, R,
                               b_kshift=(-1 if d == 0 else 1), kperiod=T)
             H.reduce_splits(part, S, 4 * Hh * Hh, dwhh[d])
+        if h0 is not None:
+            h0v, ld_h0 = H.rows_view(h0)
+            part, S = H.wgrad(gates, T * G, h0v, ld_h0, 4 * Hh, Hh, m.N)
+            H.reduce_splits(part, S, 4 * Hh * Hh, dwhh[0], accumulate=True)
         # dW_ih and (split-bf16 GEMM) the bias gradient in ONE pass over dgates: a virtual ones
         # column of x makes column I of the partials the column sums
         fused = H.fused_colsum()
@@ -391,13 +430,16 @@ def _proj_unlayout(dwp, Hh, Hp):
 
 
 def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=False, dropout_p=0.0, state=None,
-               return_state=False):
+               return_state=False, state_grad=False):
     """x rows (n,t); lstm = torch.nn.LSTM parameter container, linear = nn.Linear container.
     lstm a torch.nn.GRU container: the same layer on the GRU recurrence (gru.hip); its state is ONE tensor, h -- `state`
     = h0 [N, H], and the result with return_state is (output, hT).
     lstm.bidirectional False: the causal route -- the same _RNNP over one direction of time.  There, and only without
     gradients, state = (h0, c0) [N, H] starts the recurrence from a carried state and / or return_state asks for the last
     frame's: the result is then (output, (hT, cT)).
+    state_grad (one direction): the state is part of the graph -- `state` is accepted with gradients enabled, its tensors
+    may require a gradient, and the returned state carries one back: truncated BPTT hands `[s.detach() for s in state]`
+    to the next chunk, full BPTT over chunks the state itself.  Without the flag nothing changes.
     The Tanh between two layers (net.py:623-625) runs forward in the producer's projection epilogue (act = 1);
     its BACKWARD may run in the store of the consumer's d(input) GEMM: the producer is called with dz_given and
     hangs a _Link on its output, the consumer with in_tanh (1: same row layout; K > 1: its input is the
@@ -409,7 +451,7 @@ def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=Fals
     dropout_p > 0 (with act = 1): that Tanh is an active dropout site, y = keep ? tanh(z / (1 - p)) : 0 (_RNNP); such a
     site is never folded -- the caller passes in_tanh = 0 to the consumer, and dz_given is ignored here."""
     import weakref
-    if lstm.bidirectional and (state is not None or return_state):
+    if lstm.bidirectional and (state is not None or return_state or state_grad):
         raise NotImplementedError("rnnp_layer: a state on a bidirectional layer (it reads the whole utterance)")
     gru = isinstance(lstm, torch.nn.GRU)
     names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
@@ -417,7 +459,13 @@ def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=Fals
     if lstm.bidirectional:
         lstm_params += [getattr(lstm, n + "_reverse") for n in names]
     dropout_p = float(dropout_p) if (dropout_p and act == 1) else 0.0
-    if state is not None:
+    state_grad = bool(state_grad) and torch.is_grad_enabled()      # (without gradients: the path a carried state always had)
+    if state is not None and state_grad:
+        if gru and not torch.is_tensor(state):
+            raise ValueError("state: h0 (a GRU carries one tensor)")
+        if not gru and len(state) != 2:
+            raise ValueError("state: (h0, c0)")
+    elif state is not None:
         if torch.is_grad_enabled():
             raise RuntimeError("rnnp_layer: a carried state (state=(h0, c0)) exists without gradients only -- call it under "
                                "torch.no_grad() (a gradient through the state, truncated BPTT, is not implemented)")
@@ -432,8 +480,9 @@ def rnnp_layer(x, lstm, linear, N, T, act=0, combine=0, in_tanh=0, dz_given=Fals
     if in_link is not None and not (x.requires_grad and torch.is_grad_enabled()):
         in_link = None
     out_link = _Link() if (dz_given and act == 1 and not dropout_p and torch.is_grad_enabled()) else None
-    out = _RNNP.apply(x, N, T, act, combine, in_tanh, in_link, out_link, dropout_p, bool(return_state), gru, *lstm_params,
-                      linear.weight, linear.bias)
+    h0, c0 = (None, None) if state is None else (state, None) if gru else state
+    out = _RNNP.apply(x, N, T, act, combine, in_tanh, in_link, out_link, dropout_p, bool(return_state), gru, state_grad,
+                      h0, c0, *lstm_params, linear.weight, linear.bias)
     last = None
     if return_state:
         out, last = out[0], (out[1] if gru else (out[1], out[2]))

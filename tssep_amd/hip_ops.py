@@ -1024,9 +1024,12 @@ def recurrence_launch(planned, direction, gates, cell, h, ldo, dstride, whh, N, 
     four-wave workgroups, experiment build: `_w16`) go to the kernel as they are.
     "stream1_f32" (one direction: gates [N,T,H,4], cell [N,T,H], h columns 0..H-1 of [N,T,ldo]; no dstride) takes
     state = (h0, c0, hT, cT) forward: h0 / c0 [N,H] the initial state (both or neither; None = zeros), hT / cT [N,H]
-    receive the state after the last frame.  Backward it starts from a zero state.
+    receive the state after the last frame.  Backward it starts from a zero state, or takes state = (c0, dhT, dcT, dh0,
+    dc0), each [N,H] or None: the state the forward started from, the gradient arriving for (hT, cT), and where the
+    gradient of (h0, c0) goes (tssep_lstm1_bwd_state; all None is the launch without a state, logged under one name).
     The GRU kernels ("stream_gru_f32", "stream1_gru_f32"; gates hold the slots (r, z, n, q)) have no cell tensor: forward
-    `cell` is ignored (None), backward it is the forward's hout, which they read for h_prev; state = (h0, None, hT, None)."""
+    `cell` is ignored (None), backward it is the forward's hout, which they read for h_prev; state = (h0, None, hT, None)
+    forward, (h0, dhT, dh0) backward on "stream1_gru_f32" (tssep_gru1_bwd_state)."""
     kernel, groups = planned
     if kernel in ("stream_gru_f32", "stream1_gru_f32"):
         return _gru_launch(kernel, direction, gates, cell, h, ldo, dstride, whh, N, T, H, state)
@@ -1041,8 +1044,13 @@ def recurrence_launch(planned, direction, gates, cell, h, ldo, dstride, whh, N, 
     if D == 1:
         for s in state:
             assert s is None or (s.is_contiguous() and tuple(s.shape) == (N, H) and _f32(s) is s), (N, H)
-        args = (_p(gates), _p(cell), _p(h), ldo, _p(whh), *(() if bwd else map(_p, state)))
+        with_state = bwd and any(s is not None for s in state)
+        if with_state:
+            assert len(state) == 5, "backward: state = (c0, dhT, dcT, dh0, dc0)"
+            entry += "_state"
+        args = (_p(gates), _p(cell), _p(h), ldo, _p(whh), *(map(_p, state) if with_state or not bwd else ()))
     else:
+        assert not bwd or all(s is None for s in state), "a state needs one direction of time"
         args = (_p(gates), _p(cell), _p(h), ldo, dstride, _p(whh))
     if kernel in ("stream_f32", "stream1_f32"):
         with _timed(f"{timed}_{direction}", flops, nbytes):
@@ -1077,14 +1085,24 @@ def _gru_launch(kernel, direction, gates, hout, h, ldo, dstride, whh, N, T, H, s
     _log_recurrence(kernel, direction, N, T, H, 0)
     one = kernel == "stream1_gru_f32"
     D = 1 if one else 2
-    h0, c0, hT, cT = state
-    assert c0 is None and cT is None, "a GRU carries h alone"
-    assert one or (h0 is None and hT is None), "a state needs one direction of time"
-    for s in (h0, hT):
+    if bwd and any(s is not None for s in state):
+        assert one, "a state needs one direction of time"
+        bstate = tuple(state)
+        assert len(bstate) == 3, "backward: state = (h0, dhT, dh0)"
+        h0 = hT = None
+    else:
+        bstate = ()
+        h0, c0, hT, cT = state if not bwd else (None,) * 4
+        assert c0 is None and cT is None, "a GRU carries h alone"
+        assert one or (h0 is None and hT is None), "a state needs one direction of time"
+    for s in (h0, hT) + bstate:
         assert s is None or (s.is_contiguous() and tuple(s.shape) == (N, H) and _f32(s) is s), (N, H)
     args = [_p(gates)] + ([_p(hout)] if bwd else []) + [_p(h), ldo] + ([] if one else [dstride]) + [_p(whh)]
     if one and not bwd:
         args += [_p(h0), _p(hT)]
+    if bstate:
+        entry += "_state"
+        args += [_p(s) for s in bstate]
     with _timed(f"{timed}_{direction}", 2 * D * N * T * 4 * H * H, 0):
         check(getattr(_lib.lib(), entry)(*args, N, T, H, _stream()), entry[6:])
 
@@ -1141,8 +1159,10 @@ def lstm1_fwd(gates, cell, hout, ldo, whh_f, N, T, H, h0=None, c0=None, hT=None,
     recurrence_launch(("stream1_f32", 0), "fwd", gates, cell, hout, ldo, 0, whh_f, N, T, H, state=(h0, c0, hT, cT))
 
 
-def lstm1_bwd(gates, cell, dhout, ldo, whh_b, N, T, H):
-    recurrence_launch(("stream1_f32", 0), "bwd", gates, cell, dhout, ldo, 0, whh_b, N, T, H)
+def lstm1_bwd(gates, cell, dhout, ldo, whh_b, N, T, H, c0=None, dhT=None, dcT=None, dh0=None, dc0=None):
+    """c0 / dhT / dcT / dh0 / dc0 [N,H]: the carried state's side of the backward (recurrence_launch); all None: none"""
+    recurrence_launch(("stream1_f32", 0), "bwd", gates, cell, dhout, ldo, 0, whh_b, N, T, H,
+                      state=(c0, dhT, dcT, dh0, dc0))
 
 
 def blstm_cluster_fwd(gates, cell, hout, ldo, dstride, whh_cf, N, T, H, ms=2):
@@ -1187,9 +1207,14 @@ def gru_fwd(gates, hout, ldo, dstride, whh_f, N, T, H, directions=2, h0=None, hT
                       dstride, whh_f, N, T, H, state=(h0, None, hT, None))
 
 
-def gru_bwd(gates, hout, dhout, ldo, dstride, whh_b, N, T, H, directions=2):
+def gru_bwd(gates, hout, dhout, ldo, dstride, whh_b, N, T, H, directions=2, h0=None, dhT=None, dh0=None):
+    """h0 / dhT / dh0 [N,H], directions = 1: the carried state's side of the backward; all None: none"""
     recurrence_launch(("stream1_gru_f32" if directions == 1 else "stream_gru_f32", 0), "bwd", gates, hout, dhout, ldo,
-                      dstride, whh_b, N, T, H)
+                      dstride, whh_b, N, T, H, state=(h0, dhT, dh0))
+
+
+def gru1_bwd(gates, hout, dhout, ldo, whh_b, N, T, H, h0=None, dhT=None, dh0=None):
+    gru_bwd(gates, hout, dhout, ldo, 0, whh_b, N, T, H, directions=1, h0=h0, dhT=dhT, dh0=dh0)
 
 
 GRU_IH, GRU_HH = 0, 1      # TSSEP_GRU_IH / TSSEP_GRU_HH: the slots (0, 1, 2) / (0, 1, 3) of a packed row quadruple

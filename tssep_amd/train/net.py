@@ -7,6 +7,7 @@ rearrange, trial mean, speaker un-permutation) are not separate copies here: the
 into the producing GEMM's store or one fused map kernel.
 """
 import collections
+import contextlib
 import dataclasses
 
 import numpy as np
@@ -144,7 +145,7 @@ class Output:                      # net.py:240-247
 
 @dataclasses.dataclass
 class ChunkState:
-    """What MaskEstimator_v2.forward_chunk carries from one chunk to the next (opaque to its callers)."""
+    """What MaskEstimator_v2.forward_chunk / train_chunk carries from one chunk to the next (opaque to its callers)."""
     layers: list             # per recurrent layer, pre-net first: (h, c), each [1, N, units]
     perm: torch.Tensor       # speaker permutation and its inverse, device int32 [B, K] (None: speakers in their order)
     iperm: torch.Tensor
@@ -365,9 +366,9 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
                 aux = self.aux_normalizer(aux)
         return aux.contiguous(), perm_d, iperm_d, K
 
-    def _trunk(self, xs, aux, perm_d, iperm_d, K, prev=None, states=None):
+    def _trunk(self, xs, aux, perm_d, iperm_d, K, prev=None, states=None, state_grad=False):
         """xs [B,T,idim] and what _embedding returned -> `logits`' result.  prev / states: the per-layer (h, c) lists of
-        RNNP_packed.forward_rows, pre-net first (forward_chunk; without gradients)."""
+        RNNP_packed.forward_rows, pre-net first (forward_chunk: without gradients; train_chunk: state_grad, with them)."""
         B, T = xs.shape[0], xs.shape[1]
         framewise = aux.dim() == 4
         carry = prev is not None or states is not None
@@ -375,7 +376,8 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         def st(i):      # keywords of layer i's forward_rows: its own slice of the state lists
             if not carry:
                 return {}
-            return dict(prev_state=None if prev is None else prev[i:i + 1], states=states)
+            return dict(prev_state=None if prev is None else prev[i:i + 1], states=states,
+                        **(dict(state_grad=True) if state_grad else {}))
         if self.input_normalizer is not None:           # net.py:858-859
             xs = self.input_normalizer(xs)
         if self.ts_vad is not False:
@@ -427,6 +429,21 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
             out = self._output(tuple(r[0] for r in res) if unbatched else res)
         return out, state
 
+    def train_chunk(self, xs, aux, state=None, detach=True):
+        """forward_chunk's contract WITH gradients: training a causal model (rnn_typ='lstm') on consecutive chunks of a
+        recording -> (Output for exactly these frames, the new state).  The speaker permutation is drawn once and the
+        embedding computed once, in the first chunk (state=None); later calls do not read `aux`.
+        detach=True -- truncated BPTT: the layer states in the returned state are cut from the graph, so a loss on the next
+        chunk stops at its first frame; call backward() after every chunk.  The embedding kept in the state is detached
+        too: aux_net / aux_normalizer receive a gradient from the FIRST chunk's loss only, a later chunk trains the trunk.
+        detach=False -- full BPTT over chunks: states and embedding stay in the graph; a loss on a later chunk reaches the
+        earlier chunks' frames and parameters and aux_net from every chunk, and the chunked gradient is the whole
+        utterance's within the layers' error bounds.  Hand such a state to a later call only while the
+        graph behind it is alive (backward once, after the last chunk, or with retain_graph).
+        Refuses what forward_chunk refuses."""
+        res, unbatched, state = self._chunk_logits(xs, aux, state, grad=True, detach=detach)
+        return self._output(tuple(r[0] for r in res) if unbatched else res), state
+
     def _check_chunkable(self, aux=None):
         """What forward_chunk refuses, from the arguments alone (nothing is launched)."""
         if self.rnn_typ != "lstm":
@@ -437,9 +454,11 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
             raise NotImplementedError("forward_chunk with a frame-wise aux [B, K, Ta, E]: an embedding per frame "
                                       "would have to arrive with the frames (not built)")
 
-    def _chunk_logits(self, xs, aux, state=None):
+    def _chunk_logits(self, xs, aux, state=None, grad=False, detach=True):
         """forward_chunk in front of the Output: -> (what `logits` returns for these frames -- batched, the head's rows as
-        they are --, whether xs came un-batched, the new state).  The online separator feeds the rows to the fused tail."""
+        they are --, whether xs came un-batched, the new state).  The online separator feeds the rows to the fused tail.
+        grad (train_chunk): under the caller's gradient mode, the layer states through functional.rnnp_layer's state_grad;
+        detach: what the new state keeps of the graph."""
         self._check_chunkable()
         unbatched = xs.dim() == 2
         if unbatched:
@@ -447,7 +466,7 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
         if xs.dim() != 3 or xs.shape[1] < 1:
             raise ValueError(f"xs {tuple(xs.shape)}: [B, Tc, idim] or [Tc, idim] with Tc >= 1")
         B, T = xs.shape[0], xs.shape[1]
-        with torch.no_grad():
+        with contextlib.nullcontext() if grad else torch.no_grad():
             if state is None:
                 self._check_chunkable(aux)
                 emb, perm_d, iperm_d, K = self._embedding(aux, B, T, xs.device)
@@ -455,8 +474,12 @@ class MaskEstimator_v2(Configurable, torch.nn.Module):
             elif not isinstance(state, ChunkState):
                 raise TypeError(f"state: what forward_chunk returned, not {type(state).__name__}")
             layers = []
-            res = self._trunk(xs, state.embedding, state.perm, state.iperm, state.K, prev=state.layers, states=layers)
-        return res, unbatched, ChunkState(layers=layers, perm=state.perm, iperm=state.iperm, embedding=state.embedding,
+            res = self._trunk(xs, state.embedding, state.perm, state.iperm, state.K, prev=state.layers, states=layers,
+                              state_grad=grad)
+        emb = state.embedding
+        if grad and detach:
+            layers, emb = [tuple(s.detach() for s in hc) for hc in layers], emb.detach()
+        return res, unbatched, ChunkState(layers=layers, perm=state.perm, iperm=state.iperm, embedding=emb,
                                           K=state.K, frames=state.frames + T)
 
     def _output(self, res) -> Output:

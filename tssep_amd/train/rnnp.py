@@ -8,7 +8,9 @@ initialisation order (torch.manual_seed parity) and checkpoints are interchangea
 ``typ='lstm'`` (rnnp.py:80-96: ``torch.nn.LSTM(bidirectional=False)`` + ``Linear(cdim, hdim)``) is the causal layer.  With
 ``return_states=True`` its ``forward(xs, prev_state=None)`` returns ``(h, states)``, one ``(h_n, c_n)`` [1, N, cdim] per
 layer, and accepts that list back as ``prev_state`` -- the meaning the reference's parameters sketch and then assert away
-(rnnp.py:121).  The state is carried without gradients only.
+(rnnp.py:121).  The state is carried without gradients -- unless ``forward(xs, prev_state, state_grad=True)``: then
+``prev_state`` is accepted with gradients enabled and the returned states are part of the graph, for truncated BPTT (hand
+the detached states on) or full BPTT over chunks (hand them on as they are); functional.rnnp_layer, DESIGN 4.21.
 
 ``dropout``: the ``torch.nn.Dropout`` members sit in front of a Tanh (rnnp.py:98-100).  One that is in training mode with
 p > 0 makes that Tanh a dropout site of the HIP path (functional._RNNP); its own ``.training`` / ``.p`` are read at every
@@ -51,7 +53,7 @@ class RNNP_packed(torch.nn.Module):
         return float(site.p) if site is not None and site.training and site.p > 0 else 0.0
 
     def forward_rows(self, rows, N, T, final_act=0, combine=0, in_tanh=0, next_folds=False, final_dropout=None,
-                     prev_state=None, states=None):
+                     prev_state=None, states=None, state_grad=False):
         """rows: [N*T, I] (rows (n,t)) -> [N*T, hdim]; ``final_act``/``combine`` fuse the Tanh
         that follows this module in the post-net and the speaker-combination rearrange.  ``in_tanh``: the
         rows are the output of such a fused Tanh of the module in front (K > 1: in its speaker-combined
@@ -60,12 +62,13 @@ class RNNP_packed(torch.nn.Module):
         ``torch.nn.Dropout`` container in front of that final Tanh (post-net, net.py:623-625), if there is one; a Tanh
         behind an active site is not folded, so the caller passes ``next_folds`` False and the module behind ``in_tanh`` 0.
         ``states``: a list that receives one ``(h_n, c_n)`` [1, N, cdim] per layer; ``prev_state``: such a list, the state
-        every layer starts from (typ='lstm', without gradients: functional.rnnp_layer)."""
+        every layer starts from (typ='lstm', without gradients: functional.rnnp_layer).  ``state_grad``: with gradients
+        -- ``prev_state`` may require one, and what ``states`` receives is part of the graph."""
         h = rows
         stateful = states is not None or prev_state is not None
         if stateful and self.bidir:
             raise NotImplementedError("a carried state needs typ='lstm' ('blstm' reads the whole utterance)")
-        if prev_state is not None and torch.is_grad_enabled():
+        if prev_state is not None and torch.is_grad_enabled() and not state_grad:
             raise RuntimeError("prev_state carries the recurrent state without gradients only: call the module under "
                                "torch.no_grad() (the states it returns never carry a gradient either)")
         if prev_state is not None and len(prev_state) != self.elayers:
@@ -81,7 +84,8 @@ class RNNP_packed(torch.nn.Module):
                               in_tanh=(in_tanh if i == 0 else (1 if fold_ok and not p_prev else 0)),
                               dz_given=((next_folds and final_act == 1) if last else fold_ok) and not p_site,
                               dropout_p=p_site,
-                              **(dict(state=None if prev_state is None else prev_state[i], return_state=True) if stateful else {}))
+                              **(dict(state=None if prev_state is None else prev_state[i], return_state=True) if stateful else {}),
+                              **(dict(state_grad=True) if state_grad else {}))
             if stateful:
                 h, (hT, cT) = h
                 if states is not None:
@@ -89,7 +93,7 @@ class RNNP_packed(torch.nn.Module):
             p_prev = p_site
         return h
 
-    def forward(self, xs_pack, prev_state=None):
+    def forward(self, xs_pack, prev_state=None, state_grad=False):
         if prev_state is not None and not self.return_states:
             raise ValueError("prev_state needs return_states=True (and typ='lstm')")
         if isinstance(xs_pack, torch.nn.utils.rnn.PackedSequence):
@@ -104,6 +108,7 @@ class RNNP_packed(torch.nn.Module):
         else:
             raise KeyError(len(shape))
         states = [] if self.return_states else None
-        y = self.forward_rows(xs_pack.reshape(N * T, shape[-1]), N, T, prev_state=prev_state, states=states)
+        y = self.forward_rows(xs_pack.reshape(N * T, shape[-1]), N, T, prev_state=prev_state, states=states,
+                              **(dict(state_grad=True) if state_grad else {}))
         y = y.reshape(*shape[:-1], y.shape[-1])
         return (y, states) if self.return_states else y
