@@ -1087,6 +1087,30 @@ int tssep_mask_istft_stream_fwd(const float* logit, int gated, const float* obs,
                                 int size, int shift, const float* wsyn, const float* tw, const float* ola_in,
                                 float* ola_out, int skip, int last, float* y, int64_t N, void* stream);
 
+/* ---- training on a stream: the adjoints of the two streaming tails ----
+ * tssep_istft_stream_bwd / tssep_mask_istft_stream_bwd: the backward of one call of tssep_istft_stream_fwd /
+ *   tssep_mask_istft_stream_fwd with the same Tc, skip, last and N.  dy [rows, N]: the gradient of the samples the call
+ *   completed (may be NULL when N == 0); d_ola_out [rows, 3, shift]: the gradient of the carry behind the call (NULL:
+ *   zeros -- nobody differentiates it: the stream is truncated here).  With the gradient signal g of Tc + 3 hops,
+ *     Tc <= h: d_ola_out[h - Tc] (FIRST: it holds whatever skip is -- with skip > Tc the hops Tc .. skip - 1 are pending
+ *     hops the call's frames added to);   h < min(skip, Tc): 0;   skip <= h < Tc: dy[(h - skip) shift ...], 0 from N on,
+ *   call-frame i gets the adjoint of the inverse STFT of g[i shift .. i shift + size): dX [rows, Tc, F] complex64 with the
+ *   per-frame arithmetic of tssep_istft_bwd, or dlogit (the shape of logit) with that of tssep_mask_istft_bwd /
+ *   tssep_mask_istft_gated_bwd (tgt = vad = NULL, bt_major = 0); d_ola_in [rows, 3, shift] = hops 0, 1, 2 of g, the
+ *   gradient of the carry in front (NULL: not wanted).  Run the calls of a stream last first and hand each d_ola_in on as
+ *   the earlier call's d_ola_out: the concatenated dX / dlogit equal tssep_istft_bwd / tssep_mask_istft_bwd /
+ *   tssep_mask_istft_gated_bwd of all frames on the concatenated dy bit for bit (a -0 may come out as +0).
+ *   Guards as the forward's: any plan but 1024 / 256: TSSEP_E_UNSUPPORTED; skip / last / N that no forward call takes,
+ *   Tc < 1 or Tc > 2^20, d_ola_in overlapping d_ola_out: TSSEP_E_SHAPE.  dy, d_ola_in 4-byte, d_ola_out 8-byte aligned.
+ *   One launch, and one small copy launch when d_ola_in is wanted; no atomics. */
+int tssep_istft_stream_bwd(const float* dy, const float* d_ola_out, int64_t rows, int64_t Tc, int size, int shift,
+                           const float* wsyn, const float* tw, int skip, int last, int64_t N, float* dX,
+                           float* d_ola_in, void* stream);
+int tssep_mask_istft_stream_bwd(const float* dy, const float* d_ola_out, const float* logit, int gated,
+                                const float* obs, int64_t B, int64_t K, int64_t Tc, int size, int shift,
+                                const float* wsyn, const float* tw, int skip, int last, int64_t N, float* dlogit,
+                                float* d_ola_in, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

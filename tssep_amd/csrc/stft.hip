@@ -156,7 +156,16 @@ __device__ __forceinline__ void fft512_wave(float2 (&v)[8], float2* buf, const f
 // [tail | x] at 256 t: sample pair lane + 64 r lies in the tail while 2 t + r < 6 -- for all lanes of the wave at once, so
 // each of the eight loads picks one of two descriptors by a scalar condition.  Everything behind the loads is the code of
 // the whole-signal transform: the frames carry its bits.
-template <bool MASKED, bool GATED = false, bool MAG = false, bool STREAM = false>
+//
+// STREAM == 2 (tssep_istft_stream_bwd / tssep_mask_istft_stream_bwd; plain, masked and gated): the adjoint of the streaming
+// inverse STFT.  x is dy [rows, N], the gradient of the hops the call completed, `tail` the gradient d_ola_out [rows, 768]
+// of the carry behind the call (NULL: zeros) and pad_left = 256 skip.  Call-frame t reads the virtual concatenation
+// g = [skip zero hops | dy (zeros from N on, up to hop T) | d_ola_out] at 256 t, where the hops from T on are d_ola_out
+// whatever skip is (skip > T: the zeros end at hop T).  The half hop r of the frame lies in hop t + r / 2 of g, for all
+// lanes of the wave at once, so each of the eight loads picks its descriptor -- an empty one for the zero hops -- by a
+// scalar condition.  An odd N or a dy that is not 8-byte aligned (a sample pair may straddle the end
+// of the row) reads every pair as two 4-byte loads through the same descriptors: the range check stays the only mask.
+template <bool MASKED, bool GATED = false, bool MAG = false, int STREAM = 0>
 __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     const float* __restrict__ x, int64_t rows, int64_t N, int64_t T, int shift, int pad_left,
     const float* __restrict__ window, const float2* __restrict__ tw, float2* __restrict__ X,
@@ -167,7 +176,8 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     const float* __restrict__ gbce = nullptr, float inv_kt = 0.f, const float* __restrict__ tail = nullptr) {
   static_assert(MASKED || !GATED, "the gate belongs to the mask head");
   static_assert(!MASKED || !MAG, "the frame magnitudes are the plain STFT's");
-  static_assert(!STREAM || (!MASKED && !MAG), "the stream form is the plain STFT's");
+  static_assert(STREAM != 1 || (!MASKED && !MAG), "the streaming STFT is the plain transform");
+  static_assert(STREAM != 2 || !MAG, "the stream adjoint forms spectra or logit gradients");
   constexpr int LDL = NH + 1 + (GATED ? 1 : 0);   // logit / d(logit) row length
   constexpr int C0 = GATED ? 1 : 0;               // column of bin 0
   // MASKED with tgt != NULL: x is the time-domain ESTIMATE and the frame's samples are the loss gradient
@@ -213,7 +223,45 @@ __global__ __launch_bounds__(256, TSSEP_RFFT_OCC) void rfft_frames_kernel(
     if (!valid) {
 #pragma unroll
       for (int r = 0; r < 8; ++r) v[r] = make_float2(0.f, 0.f);
-    } else if constexpr (STREAM) {
+    } else if constexpr (STREAM == 2) {
+      // (base and range of the part are picked as scalars and the descriptor built from them, and the two load widths
+      // have a loop each: with a three-way pick of whole descriptors and the width inside one loop the compiler turned
+      // every load into a chain of scalar branches, 7 % of the launch at 253 frames)
+      const float* cp = tail ? tail + row * 768 : xr;
+      const int64_t cbytes = tail ? 768 * 4 : 0;
+      const int skip_h = pad_left >> 8, Ti = (int)T;             // (T <= 2^20: the launcher's guard)
+      const bool pairs = ((N & 1) == 0) && ((((uintptr_t)x) & 7u) == 0);     // (kernel-uniform)
+      auto part = [&](int r, unsigned& vo) __attribute__((always_inline)) {
+        const int h = (int)t + (r >> 1);                         // the hop of g this half hop lies in (wave-uniform)
+        // (the carry first: with skip > T a hop T <= h < skip is a pending hop the call's frames added to -- the forward
+        // skips only hops it would have STORED)
+        const bool carry = h >= Ti, zero = !carry && h < skip_h;
+        const int h0 = carry ? h - Ti : (zero ? 0 : h - skip_h);
+        vo = (unsigned)(((h0 * 256 + (r & 1) * 128) + 2 * lane) * 4);
+        return make_srd(carry ? cp : xr, carry ? cbytes : (zero ? (int64_t)0 : N * 4));
+      };
+      float2 xv[8];
+      if (pairs) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          unsigned vo;
+          const srd_t s = part(r, vo);
+          xv[r] = bload2(s, vo);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          unsigned vo;
+          const srd_t s = part(r, vo);
+          xv[r] = make_float2(bload1(s, vo), bload1(s, vo + 4u));
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const float2 wv = wl[lane + 64 * r];
+        v[r] = make_float2(xv[r].x * wv.x, xv[r].y * wv.y);
+      }
+    } else if constexpr (STREAM == 1) {
       const srd_t sx = make_srd(xr, N * 4), st = make_srd(tail ? tail + row * 768 : xr, tail ? 768 * 4 : 0);
       const unsigned vo = (unsigned)((t * 256 + 2 * lane) * 4);
       float2 xv[8];
@@ -582,6 +630,23 @@ __global__ __launch_bounds__(256, TSSEP_ISTFT_OCC) void istft_kernel(
   }
 }
 
+// the gradient of the carry in front of a call: hop j = 0, 1, 2 of g = [skip zero hops | dy | d_ola_out] (a copy)
+__global__ __launch_bounds__(256) void stream_carry_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ d_ola_out,
+                                                               float* __restrict__ d_ola_in, int64_t rows, int64_t Tc, int skip,
+                                                               int64_t N) {
+  const int64_t row = blockIdx.x / 3;                               // (768 = 3 x 256: a block is one hop of one row)
+  const int j = (int)(blockIdx.x - row * 3);
+  if (row >= rows) return;
+  float v = 0.f;
+  if (j >= Tc) {
+    if (d_ola_out) v = d_ola_out[row * 768 + (j - Tc) * 256 + threadIdx.x];
+  } else if (j >= skip) {
+    const int64_t n = (int64_t)(j - skip) * 256 + threadIdx.x;
+    if (n < N) v = dy[row * N + n];
+  }
+  d_ola_in[row * 768 + j * 256 + threadIdx.x] = v;
+}
+
 // the sample tail a push leaves: the last 768 samples of [tail_in | x_new] (tail_in NULL: zeros)
 __global__ __launch_bounds__(256) void stream_tail_kernel(const float* __restrict__ x_new, const float* __restrict__ tail_in,
                                                           float* __restrict__ tail_out, int64_t rows, int64_t n_new) {
@@ -666,15 +731,18 @@ struct RfftLaunch {
   const int32_t* iperm;                        // the layout fold
   int bt_major;
   const float *vad, *gbce;                     // gated: the BCE fold on the gate column (vad == NULL: none)
-  const float* tail;                           // the STREAM instantiation: the samples in front of x (NULL: zeros)
+  const float* tail;                           // the STREAM instantiations: the samples in front of x / the carry's gradient
+                                               // behind dy (NULL: zeros)
+  int stream_bwd;                              // STREAM == 2: x = dy may be NULL with N == 0; skip hops of zeros in front
+  int skip;
 };
 
 // (the checks that do not depend on the plan: the general plan of stft_generic.hip takes the same arguments)
 static int rfft_check(const RfftLaunch& a) {
-  if (!a.x || !a.window || !a.tw) return TSSEP_E_NULL;
+  if ((!a.x && !(a.stream_bwd && a.N == 0)) || !a.window || !a.tw) return TSSEP_E_NULL;
   if (a.masked ? (!a.logit || !a.obs || !a.dlogit || (a.tgt && !a.gout) || (a.vad && !a.gbce)) : (!a.X && !a.amag))
     return TSSEP_E_NULL;
-  if (a.rows <= 0 || (a.masked && a.K <= 0) || a.N <= 0 || a.T <= 0) return TSSEP_E_SHAPE;
+  if (a.rows <= 0 || (a.masked && a.K <= 0) || (a.stream_bwd ? a.N < 0 : a.N <= 0) || a.T <= 0) return TSSEP_E_SHAPE;
   if (misaligned(a.tw, 8) || misaligned(a.window, 8)) return TSSEP_E_ALIGN;
   if (a.masked ? (misaligned(a.logit, 4) || misaligned(a.dlogit, 4) || misaligned(a.obs, 8))
                : (a.amag ? misaligned(a.amag, 4) : misaligned(a.X, 8)))
@@ -688,8 +756,10 @@ static int rfft_launch(const RfftLaunch& a, void* stream) {
   const int iters = 4;                         // frames per wave: 4 waves x 4 frames per workgroup
   const int64_t blocks = (a.rows * a.T + 4 * iters - 1) / (4 * iters);
   if (blocks > 0x7fffffff) return TSSEP_E_SHAPE;
+  // (pad_left: the fade in front of the signal; the stream adjoint's skipped hops)
+  const int pad_left = a.stream_bwd ? a.skip * a.shift : (a.fading ? a.size - a.shift : 0);
   hipLaunchKernelGGL(a.kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a.x, a.rows, a.N, a.T, a.shift,
-                     a.fading ? a.size - a.shift : 0, a.window, (const float2*)a.tw, (float2*)a.X, a.s_in, a.s_edge, iters,
+                     pad_left, a.window, (const float2*)a.tw, (float2*)a.X, a.s_in, a.s_edge, iters,
                      a.logit, (const float2*)a.obs, a.amag ? a.amag : a.dlogit, a.masked ? a.K : (int64_t)1, a.tgt, a.sums, a.gout, a.iperm,
                      a.bt_major, a.vad, a.gbce, a.masked ? 1.0f / ((float)a.K * (float)a.T) : 0.f, a.tail);
   return tssep_launch_status();
@@ -873,7 +943,7 @@ extern "C" int tssep_stft_stream_fwd(const float* x_new, int64_t rows, int64_t n
     return TSSEP_E_ALIGN;
   if (rows * 3 > 0x7fffffff) return TSSEP_E_SHAPE;
   // (the whole-signal launcher: no fade in front, the rows are the new samples)
-  const RfftLaunch a = {.kernel = rfft_frames_kernel<false, false, false, true>, .x = x_new, .rows = rows, .N = n_new, .T = Tc,
+  const RfftLaunch a = {.kernel = rfft_frames_kernel<false, false, false, 1>, .x = x_new, .rows = rows, .N = n_new, .T = Tc,
                         .size = size, .shift = shift, .fading = 0, .window = window, .tw = tw, .s_in = 1.0f, .s_edge = 1.0f,
                         .X = X, .tail = tail_in};
   if (int e = rfft_launch(a, stream)) return e;
@@ -921,4 +991,50 @@ extern "C" int tssep_mask_istft_stream_fwd(const float* logit, int gated, const 
   if (B <= 0 || K <= 0) return (!logit || !obs || !wsyn || !tw || !ola_out) ? TSSEP_E_NULL : TSSEP_E_SHAPE;
   return istft_stream_launch(gated ? 2 : 1, nullptr, logit, obs, B * K, K, Tc, size, shift, wsyn, tw, ola_in, ola_out, skip,
                              last, y, N, stream);
+}
+
+// ---- the adjoints of the two streaming tails: one launch of a STREAM == 2 instantiation of rfft_frames_kernel, and the
+// copy that hands the carry's gradient on.  (Named last: the kernels above keep their place in the code object.)
+static int istft_stream_bwd_launch(int variant, const float* dy, const float* d_ola_out, const float* logit, const float* obs,
+                                   int64_t rows, int64_t K, int64_t Tc, int size, int shift, const float* wsyn, const float* tw,
+                                   int skip, int last, int64_t N, float* dX, float* dlogit, float* d_ola_in, void* stream) {
+  const bool masked = variant != 0;
+  if ((masked ? (!logit || !obs || !dlogit) : !dX) || !wsyn || !tw) return TSSEP_E_NULL;
+  if (int e = check_plan(size, shift)) return e;
+  // (Tc: the frame offsets of a row are 32-bit byte offsets)
+  if (rows <= 0 || (masked && (K <= 0 || rows % K)) || Tc < 1 || Tc > (1 << 20) || skip < 0 || skip > 3 || rows * 3 > 0x7fffffff)
+    return TSSEP_E_SHAPE;
+  const int64_t hops = Tc > skip ? Tc - skip : 0;
+  if (N < 0 || N > hops * shift || (last ? N <= (hops - 1) * shift && hops > 0 : N != hops * shift)) return TSSEP_E_SHAPE;
+  if (N > 0 && !dy) return TSSEP_E_NULL;
+  if (d_ola_in && d_ola_out && overlap(d_ola_in, d_ola_out, rows * (size - shift) * 4)) return TSSEP_E_SHAPE;
+  if (misaligned(dy, 4) || misaligned(d_ola_out, 8) || misaligned(d_ola_in, 4)) return TSSEP_E_ALIGN;
+  const rfft_kernel_t kernel = variant == 0 ? rfft_frames_kernel<false, false, false, 2>
+                                             : (variant == 1 ? rfft_frames_kernel<true, false, false, 2>
+                                                             : rfft_frames_kernel<true, true, false, 2>);
+  const RfftLaunch a = {.kernel = kernel, .masked = masked, .x = dy, .rows = rows, .N = N, .T = Tc, .size = size, .shift = shift,
+                        .fading = 1, .window = wsyn, .tw = tw, .s_in = 2.0f / (float)size, .s_edge = 1.0f / (float)size,
+                        .X = dX, .logit = logit, .obs = obs, .dlogit = dlogit, .K = K, .tail = d_ola_out, .stream_bwd = 1,
+                        .skip = skip};
+  if (int e = rfft_launch(a, stream)) return e;
+  if (!d_ola_in) return TSSEP_OK;
+  hipLaunchKernelGGL(stream_carry_bwd_kernel, dim3((unsigned)(rows * 3)), dim3(256), 0, (hipStream_t)stream, dy, d_ola_out,
+                     d_ola_in, rows, Tc, skip, N);
+  return tssep_launch_status();
+}
+
+extern "C" int tssep_istft_stream_bwd(const float* dy, const float* d_ola_out, int64_t rows, int64_t Tc, int size, int shift,
+                                      const float* wsyn, const float* tw, int skip, int last, int64_t N, float* dX,
+                                      float* d_ola_in, void* stream) {
+  return istft_stream_bwd_launch(0, dy, d_ola_out, nullptr, nullptr, rows, 1, Tc, size, shift, wsyn, tw, skip, last, N, dX,
+                                 nullptr, d_ola_in, stream);
+}
+
+extern "C" int tssep_mask_istft_stream_bwd(const float* dy, const float* d_ola_out, const float* logit, int gated,
+                                           const float* obs, int64_t B, int64_t K, int64_t Tc, int size, int shift,
+                                           const float* wsyn, const float* tw, int skip, int last, int64_t N, float* dlogit,
+                                           float* d_ola_in, void* stream) {
+  if (B <= 0 || K <= 0) return (!logit || !obs || !wsyn || !tw || !dlogit) ? TSSEP_E_NULL : TSSEP_E_SHAPE;
+  return istft_stream_bwd_launch(gated ? 2 : 1, dy, d_ola_out, logit, obs, B * K, K, Tc, size, shift, wsyn, tw, skip, last, N,
+                                 nullptr, dlogit, d_ola_in, stream);
 }

@@ -818,6 +818,58 @@ def mask_istft(logit, obs, wsyn, N, size=1024, shift=256, fading=True, tgt=None,
     return y, (out[-1] if vad is not None else None)
 
 
+# ---------------------------------------------------------------- training on a stream
+# One call of a streaming tail as a node of the graph: inputs (logit | X, ola_in), outputs (y, ola_out).  The gradients
+# are not materialised: a y nobody used is zeros inside the wrapper, an ola_out nobody differentiates reaches the kernel as
+# NULL -- the stream is cut behind this call -- and d_ola_in is asked for only when ola_in wants one.
+class _MaskISTFTStream(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logit, ola_in, obs, wsyn, skip, N, size, shift):
+        ctx.set_materialize_grads(False)
+        y, ola_out = H.mask_istft_stream_fwd(logit, obs, wsyn, ola_in, skip, N, size, shift)
+        ctx.save_for_backward(logit, obs, wsyn)
+        ctx.meta = (skip, N, size, shift)
+        return y, ola_out
+
+    @staticmethod
+    def backward(ctx, dy, d_ola_out):
+        if dy is None and d_ola_out is None:        # nobody used either output: no gradient, no launch
+            return (None,) * 8
+        logit, obs, wsyn = ctx.saved_tensors
+        dlogit, d_ola_in = H.mask_istft_stream_bwd(dy, d_ola_out, logit, obs, wsyn, *ctx.meta,
+                                                   want_ola=ctx.needs_input_grad[1])
+        return (dlogit if ctx.needs_input_grad[0] else None, d_ola_in) + (None,) * 6
+
+
+class _ISTFTStream(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, ola_in, wsyn, skip, N, size, shift):
+        ctx.set_materialize_grads(False)
+        y, ola_out = H.istft_stream_fwd(X, wsyn, ola_in, skip, N, size, shift)
+        ctx.save_for_backward(wsyn)
+        ctx.meta = (X.shape[0], X.shape[1], skip, N, size, shift, X.device)
+        return y, ola_out
+
+    @staticmethod
+    def backward(ctx, dy, d_ola_out):
+        (wsyn,) = ctx.saved_tensors
+        rows, Tc, skip, N, size, shift, device = ctx.meta
+        if dy is None and d_ola_out is None:
+            return (None,) * 7
+        dX, d_ola_in = H.istft_stream_bwd(dy, d_ola_out, wsyn, Tc, skip, N, size, shift, want_ola=ctx.needs_input_grad[1])
+        return (dX if ctx.needs_input_grad[0] else None, d_ola_in) + (None,) * 5
+
+
+def mask_istft_stream(logit, obs, wsyn, ola, skip, N=None, size=1024, shift=256):
+    """hip_ops.mask_istft_stream_fwd, differentiable w.r.t. logit and the carry `ola` -> (y [B,K,n], the carry behind)."""
+    return _MaskISTFTStream.apply(logit, ola, obs, wsyn, skip, N, size, shift)
+
+
+def istft_stream(X, wsyn, ola, skip, N=None, size=1024, shift=256):
+    """hip_ops.istft_stream_fwd, differentiable w.r.t. X [rows, Tc, F] and the carry `ola` -> (y [rows, n], the carry)."""
+    return _ISTFTStream.apply(X, ola, wsyn, skip, N, size, shift)
+
+
 # ---------------------------------------------------------------- explicit_vad (gated mask head)
 # MaskEstimator_v2(explicit_vad=True) (net.py:630, 969-979): the head writes rows of F + 1 logits per (b, k, t), the
 # VAD logit v at column 0 and the mask logits l_f behind it; mask = sigmoid(l_f) sigmoid(v).  The Functions below keep

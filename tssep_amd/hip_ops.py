@@ -459,6 +459,59 @@ def mask_istft_stream_fwd(logit, obs, wsyn, ola, skip, N=None, size=1024, shift=
     return y, ola_out
 
 
+def _stream_grads(dy, d_ola_out, rows, Tc, skip, N, size, shift, device, want_ola):
+    """The gradient arguments of a stream backward: dy [rows, n] or None (the call completed no sample, or nobody used
+    them: zeros), d_ola_out [rows, size - shift] or None (the kernel's NULL) -> (dy, d_ola_out, n, last, d_ola_in)."""
+    n, last = _stream_hops(Tc, skip, shift, N)
+    if dy is None:
+        dy = torch.zeros(rows, n, device=device, dtype=torch.float32) if n else None
+    else:
+        assert dy.numel() == rows * n, (tuple(dy.shape), rows, n)
+        dy = _f32(dy).contiguous().reshape(rows, n)
+    if d_ola_out is not None:
+        d_ola_out = _f32(d_ola_out).contiguous()
+        assert tuple(d_ola_out.shape) == (rows, size - shift), (tuple(d_ola_out.shape), rows, size - shift)
+    d_ola_in = torch.empty(rows, size - shift, device=device, dtype=torch.float32) if want_ola else None
+    return dy, d_ola_out, n, last, d_ola_in
+
+
+def istft_stream_bwd(dy, d_ola_out, wsyn, Tc, skip, N=None, size=1024, shift=256, want_ola=True):
+    """The backward of istft_stream_fwd(X [rows, Tc, F], ...) with the same skip and N: dy [rows, n] (None: zeros),
+    d_ola_out [rows, size - shift] the gradient of the carry behind the call (None: the stream is cut there) ->
+    (dX complex64 [rows, Tc, F], d_ola_in or None).  `rows` is read from dy, or from d_ola_out when dy is None."""
+    L = _lib.lib()
+    ref = dy if dy is not None else d_ola_out
+    rows, device = ref.shape[0], ref.device
+    dy, d_ola_out, n, last, d_ola_in = _stream_grads(dy, d_ola_out, rows, Tc, skip, N, size, shift, device, want_ola)
+    F = size // 2 + 1
+    dX = torch.empty(rows, Tc, F, 2, device=device, dtype=torch.float32)
+    with _timed("maskhead_stream_bwd", 0, 8 * rows * Tc * F + 4 * rows * n):
+        check(L.tssep_istft_stream_bwd(_p(dy) if n else None, _p(d_ola_out), rows, Tc, size, shift, _p(wsyn),
+                                       _p(fft_tables(size, device)), int(skip), last, n, _p(dX), _p(d_ola_in), _stream()),
+              "istft_stream_bwd")
+    return torch.view_as_complex(dX), d_ola_in
+
+
+def mask_istft_stream_bwd(dy, d_ola_out, logit, obs, wsyn, skip, N=None, size=1024, shift=256, want_ola=True):
+    """The backward of mask_istft_stream_fwd(logit, obs, ...) with the same skip and N: dy [B,K,n] (None: zeros),
+    d_ola_out [B*K, size - shift] (None: the stream is cut behind this call) -> (dlogit, the shape of logit; d_ola_in
+    [B*K, size - shift] or None).  obs gets no gradient."""
+    L = _lib.lib()
+    B, K, Tc, F, gated = _tail_rows(logit, obs)
+    logit = _f32(logit).contiguous()
+    obs_r = torch.view_as_real(obs.contiguous())
+    dy, d_ola_out, n, last, d_ola_in = _stream_grads(dy, d_ola_out, B * K, Tc, skip, N, size, shift, logit.device, want_ola)
+    dlogit = torch.empty_like(logit)
+    if TAIL_LOG is not None:
+        TAIL_LOG.append(dict(kernel="maskhead_stream_bwd", B=B, K=K, T=Tc, F=F, gated=bool(gated), skip=int(skip), N=n,
+                             carry=d_ola_out is not None))
+    with _timed("maskhead_stream_bwd", 0, B * Tc * (8 * K * logit.shape[-1] + 8 * F) + 4 * B * K * n):
+        check(L.tssep_mask_istft_stream_bwd(_p(dy) if n else None, _p(d_ola_out), _p(logit), int(gated), _p(obs_r), B, K, Tc,
+                                            size, shift, _p(wsyn), _p(fft_tables(size, logit.device)), int(skip), last, n,
+                                            _p(dlogit), _p(d_ola_in), _stream()), "mask_istft_stream_bwd")
+    return dlogit, d_ola_in
+
+
 # ------------------------------------------------------------------------------- GEMM
 # Arithmetic of the non-recurrent GEMMs: "bf16x3" = split-bf16 on the bf16 MFMA with fp32 accumulation (fp32-class
 # accuracy: masks 3e-6 from the CPU oracle, see gemm_bf16x3.hip) -- the DEFAULT since round 5: what bench.py measures is

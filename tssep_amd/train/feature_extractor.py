@@ -228,23 +228,31 @@ class STFT(Configurable):
         X, tail = H.stft_stream_fwd(x.reshape(-1, x.shape[-1]), tail, w, self.size, self.shift)
         return X.reshape(*x.shape[:-1], X.shape[-2], X.shape[-1]), tail
 
-    def istft_chunk(self, signal, ola=None, skip=0, num_samples=None):
+    def istft_chunk(self, signal, ola=None, skip=0, num_samples=None, differentiable=False):
         """The samples the stream's next frames complete: complex64 [..., Tc, F], ola the carry of the call before (None:
         a fresh stream), skip = max(0, 3 - frames of the earlier calls) -> ([..., (Tc - skip) * shift] -- the first
-        ``num_samples`` of them in the utterance's final call --, the new carry).  Forward only."""
+        ``num_samples`` of them in the utterance's final call --, the new carry).  differentiable=True: the call is a node
+        of the graph with a gradient for ``signal`` and ``ola``; without it forward only."""
         self._check_stream()
         X = signal.to(torch.complex64) if signal.dtype == torch.complex128 else signal
         _, wsyn = self._windows(X.device)
-        y, ola = H.istft_stream_fwd(X.reshape(-1, X.shape[-2], X.shape[-1]), wsyn, ola, skip, num_samples, self.size,
-                                    self.shift)
+        if differentiable:
+            y, ola = Fn.istft_stream(X.reshape(-1, X.shape[-2], X.shape[-1]), wsyn, ola, skip, num_samples, self.size,
+                                     self.shift)
+        else:
+            y, ola = H.istft_stream_fwd(X.reshape(-1, X.shape[-2], X.shape[-1]), wsyn, ola, skip, num_samples, self.size,
+                                        self.shift)
         return y.reshape(*X.shape[:-2], y.shape[-1]), ola
 
-    def masked_istft_chunk(self, logit, observation, ola=None, skip=0, num_samples=None):
+    def masked_istft_chunk(self, logit, observation, ola=None, skip=0, num_samples=None, differentiable=False):
         """``masked_istft`` on the stream's next frames (plain or explicit_vad rows): logit [B,K,Tc,F(+1)], observation
         complex64 [B,Tc,F] -> ([B,K,n], the new carry); arguments as ``istft_chunk``.  Neither mask nor masked spectrum is
-        written."""
+        written.  differentiable=True: a node of the graph with a gradient for ``logit`` and ``ola``, none for the
+        observation."""
         self._check_stream()
         _, wsyn = self._windows(logit.device)
+        if differentiable:
+            return Fn.mask_istft_stream(logit, observation, wsyn, ola, skip, num_samples, self.size, self.shift)
         return H.mask_istft_stream_fwd(logit, observation, wsyn, ola, skip, num_samples, self.size, self.shift)
 
     def stft_to_feature(self, stft_signals):

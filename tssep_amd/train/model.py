@@ -390,7 +390,7 @@ class Model(Configurable, torch.nn.Module):
         out._lazy = out._lazy0 = lazy
         return out
 
-    def online(self, aux, record=False, reference_channel=0):
+    def online(self, aux, record=False, reference_channel=0, grad=False, detach=True):
         """An `OnlineSeparator` for one stream (or one batch of streams) of this model: audio chunks in, separated audio
         chunks out (train/online.py).  aux: what ``mask_estimator.forward_chunk`` takes at its first chunk.
         Refused on the arguments alone: a trunk that is not rnn_typ='lstm' or features with utterance-wide statistics
@@ -398,9 +398,15 @@ class Model(Configurable, torch.nn.Module):
         the plain 1024 / 256 one, and whatever forward_chunk refuses (NotImplementedError).  With OnlineMVDR the pushes
         hold all channels, [B, D, n], and ``reference_channel`` is the one the features are taken from and the
         beamformer is steered to; the Masking route ignores it.  OnlineMVDR(pre_wpe=OnlineWPE(...)) puts the
-        recursive WPE in front of the beamformer: same pushes, the carried state grows by the WPE's."""
+        recursive WPE in front of the beamformer: same pushes, the carried state grows by the WPE's.
+        grad=True: the stream as a training object -- STFT and features are data, the trunk and the fused
+        tail run with gradients and a push returns y in the graph, with the frames, samples and carried states of
+        inference.  detach=True cuts the layer states, the embedding and the overlap-add carry after every push
+        (truncated BPTT: backward() after every push, memory bounded by one chunk); detach=False keeps all three in the
+        graph (one backward() after flush gives the whole utterance's gradient).  grad=True with OnlineMVDR raises
+        NotImplementedError before any launch; grad=False is the inference path as it was."""
         from .online import OnlineSeparator
-        return OnlineSeparator(self, aux, record=record, reference_channel=reference_channel)
+        return OnlineSeparator(self, aux, record=record, reference_channel=reference_channel, grad=grad, detach=detach)
 
     def _forward_masks(self, ex):
         """nmask > 1: mask and logit [..., K, M, T, F] come out of one fused kernel (functional.head_masks) and go to the

@@ -92,9 +92,13 @@ class OnlineSeparator:
     With the enhancer `OnlineMVDR` x is [B, D, n] (un-batched: [D, n]), ``reference_channel`` names the channel the
     features are taken from and the beamformer is steered to (Masking ignores it)."""
 
-    def __init__(self, model, aux, record=False, reference_channel=0):
+    def __init__(self, model, aux, record=False, reference_channel=0, grad=False, detach=True):
         from . import enhancer as _enh
         check_online(model, aux)
+        if grad and isinstance(model.enhancer, _enh.OnlineMVDR):
+            raise NotImplementedError("Model.online(grad=True) with the enhancer OnlineMVDR: the frame-recursive beamformer "
+                                      "is evaluation-time and has no backward; train the stream with Masking")
+        self.grad, self.detach = bool(grad), bool(detach)
         self.model, self.fe, self.me = model, model.fe, model.mask_estimator
         self._aux = aux
         self._tail = self._feat = self._trunk = self._ola = None       # the four carried states
@@ -137,6 +141,8 @@ class OnlineSeparator:
         self._lead = tuple(x.shape[:-1])
         if self._bf is not None:
             return self._run_bf(x, frames, num_samples)
+        if self.grad:
+            return self._run_grad(x, frames, num_samples)
         fe = self.fe
         with torch.no_grad():
             X, self._tail = fe.stft_chunk(x, self._tail)                                     # [B, Tc, F]
@@ -148,6 +154,26 @@ class OnlineSeparator:
             # the head's rows as they are ([B,K,Tc,F], explicit_vad: [B,K,Tc,F+1]) into the fused tail: no mask, no masked
             # spectrum
             y, self._ola = fe.masked_istft_chunk(res[0], X, self._ola, skip, num_samples)
+        self._res = res
+        if self.record is not None:
+            self.record.append({"Observation": X, "Input": feat, "logit": res[0]})
+        self.frames += frames
+        self.samples_out += y.shape[-1]
+        return y
+
+    def _run_grad(self, x, frames, num_samples=None):
+        """`_run` as a training step: STFT and features are data, without gradients; the trunk runs through
+        `_chunk_logits(grad=True)` and the tail through the differentiable chunk, so y is in the graph.  detach: the layer
+        states, the embedding and the overlap-add carry are cut after the call (truncated BPTT)."""
+        fe = self.fe
+        with torch.no_grad():
+            X, self._tail = fe.stft_chunk(x, self._tail)                                     # [B, Tc, F]
+            feat, self._feat = fe.stft_to_feature(X, self._feat, True)
+        aux = None if self._trunk is not None else ([self._aux] if self._un else self._aux)
+        res, _, self._trunk = self.me._chunk_logits(feat.to(torch.float32), aux, self._trunk, grad=True, detach=self.detach)
+        skip, _ = _step(self.frames, frames, fe.shift)
+        y, ola = fe.masked_istft_chunk(res[0], X, self._ola, skip, num_samples, differentiable=True)
+        self._ola = ola.detach() if self.detach else ola
         self._res = res
         if self.record is not None:
             self.record.append({"Observation": X, "Input": feat, "logit": res[0]})
@@ -210,3 +236,37 @@ class OnlineSeparator:
             return None
         with torch.no_grad():
             return self.me._output(self._res)
+
+
+def stream_loss_step(model, ex_audio, targets, aux, loss, pushes, detach=True):
+    """One batch as a stream: ex_audio [B, N] is pushed through ``model.online(aux, grad=True,
+    detach=detach)`` in `pushes` (frames per push; the rest, fewer than shift samples, goes to flush) and every call's
+    samples meet their part of targets [B, K, N] in ``loss(y_chunk, target_chunk) -> [B]`` -- a TimeDomain loss module
+    or any callable.  Calls that complete no sample are skipped.  detach=True: ``backward()`` of the call's mean loss
+    after every call (truncated BPTT, memory bounded by one chunk); detach=False: one ``backward()`` of the sum after
+    flush, the whole utterance's gradient.  -> the per-call losses [B], detached, in order.  The gradients accumulate in
+    the parameters' ``.grad``: no optimizer step and no zero_grad inside."""
+    N, shift = ex_audio.shape[-1], model.fe.shift
+    schedule(pushes, N, shift, model.fe.size)                  # (raises on pushes that do not fit the utterance)
+    stream = model.online(aux, grad=True, detach=detach)
+    losses, total, pos, at = [], None, 0, 0
+    calls = [int(p) * shift for p in pushes] + [None]
+    for n in calls:
+        if n is None:
+            y = stream.flush(ex_audio[..., at:] if at < N else None)
+        else:
+            y = stream.push(ex_audio[..., at:at + n])
+            at += n
+        m = y.shape[-1]
+        if not m:
+            continue
+        per = loss(y, targets[..., pos:pos + m].contiguous())
+        pos += m
+        losses.append(per.detach())
+        if detach:
+            per.mean().backward()
+        else:
+            total = per.mean() if total is None else total + per.mean()
+    if total is not None:
+        total.backward()
+    return losses
