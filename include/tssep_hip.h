@@ -160,6 +160,34 @@ int tssep_feat_fwd(const float* X, int64_t B, int64_t T, int F,
                    const float* fb, const float* dct, int n_mels, int n_mfcc,
                    float top_db, int stat_axis, float* out, int64_t ld_out, void* ws, void* stream);
 
+/* Spectral features without a maximum (csrc/specfeat.hip): AbsSTFT, Log1pAbsSTFT and MVNLog1pAbsSTFT
+ * (tssep/train/feature_extractor.py:112-168 and the padertorch classes it star-imports).
+ *   X     [B, T, F] complex64, 1 <= F <= 1025, 8-byte aligned
+ *   out   float32, row pitch ld_out >= F, 4-byte aligned: columns [0, F) of each of the B T rows are written and nothing
+ *         else (the caller may point it at column n_mfcc of a wider [B, T, ld] buffer)
+ *   kind  0 = |X|;  1 = L = log1p(|X|);  2 = L - mean over the T frames of L, one mean per (b, f)
+ *         (np.mean(feature, axis=-2, keepdims=True), feature_extractor.py:161); any other: TSSEP_E_UNSUPPORTED
+ *   ws    tssep_specfeat_workspace_bytes(B, T, F, kind) bytes, 8-byte aligned: B F float64 means for kind 2; 0 bytes for
+ *         kinds 0 and 1, whose ws may be NULL
+ * |X| = sqrt(re re + im im) with every operation rounded to float32, L = log1pf of it: one routine for every kind and for
+ * the causal call.  The mean is S / T with S the float64 sum of the frames' L in frame order.  Kinds 0 and 1 are one
+ * launch, kind 2 two.  No atomics, the same bits on every run; no host sync, no allocation, capturable.  F > 1025, a
+ * non-positive size, ld_out < F or a grid past 2^31 - 1 blocks (B F / 256, B T F / 1024): TSSEP_E_SHAPE.
+ *
+ * tssep_specfeat_causal_fwd: the running-mean form of kind 2 over a chunk of Tc >= 1 frames per utterance (this
+ * project's own).  state [B, F + 1] float64, 8-byte aligned: columns 0..F-1 the sums S[b, f], column F the weight n[b];
+ * state_in NULL = zeros (a fresh stream), state_out NULL = not written, a state_out overlapping state_in: TSSEP_E_SHAPE.
+ * Per frame in frame order, a = forgetting in (0, 1] (else TSSEP_E_SHAPE), each operation rounded to float64:
+ *     S = a S + (double)L;   n = a n + 1;   out = (float)((double)L - S / n)
+ * One strict chain per (b, f): any split of an utterance into calls gives the bits of one call, the first frame of a
+ * fresh stream is exactly 0, and with a = 1 the last frame equals kind 2's of the same frames.  One launch. */
+int64_t tssep_specfeat_workspace_bytes(int64_t B, int64_t T, int F, int kind);
+int tssep_specfeat_fwd(const float* X, int64_t B, int64_t T, int F, int kind,
+                       float* out, int64_t ld_out, void* ws, void* stream);
+int tssep_specfeat_causal_fwd(const float* X, int64_t B, int64_t Tc, int F, double forgetting,
+                              const double* state_in, double* state_out,
+                              float* out, int64_t ld_out, void* stream);
+
 /* ------------------------------------------------------------------- GEMM ----
  * Exact-fp32 MFMA GEMM (v_mfma_f32_32x32x2_f32): C = epilogue(A x B).
  * Replaces nn.Linear / the LSTM input GEMM (tssep/train/rnnp.py:88-96,146-161,

@@ -398,6 +398,81 @@ def feat_causal_fwd(X, fb, dct, n_mfcc, top_db=80.0, state=None):
     return out[..., :D], ld, state_out
 
 
+SPECFEAT_KINDS = {"abs": 0, "log1p": 1, "mvn": 2}      # tssep_specfeat_fwd's `kind`
+SPECFEAT_MAX_BINS = 1025
+
+
+def _specfeat_args(name, X, out, col0):
+    """Shared argument work of the two spectral-feature calls -> (X as float32 pairs, B, T, F, the [B,T,>= col0 + F] buffer,
+    its row pitch).  `out` None: a fresh buffer whose padding columns are zeroed (as feat_fwd's)."""
+    if not isinstance(X, torch.Tensor) or X.dim() != 3 or X.dtype != torch.complex64:
+        got = f"{X.dtype} {tuple(X.shape)}" if isinstance(X, torch.Tensor) else type(X).__name__
+        raise ValueError(f"{name}: X is complex64 [B,T,F], got {got}")
+    assert X.is_cuda, X.device
+    B, T, F = X.shape
+    col0 = int(col0)
+    if out is None:
+        if col0:
+            raise ValueError(f"{name}: col0 = {col0} names a column of `out`, and no `out` was given")
+        ld = round_up(F, 4)
+        out = torch.empty(B, T, ld, device=X.device, dtype=torch.float32)
+        if ld != F:
+            out[..., F:].zero_()
+    else:
+        ok = isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 3
+        if not ok or tuple(out.shape[:2]) != (B, T) or col0 < 0 or col0 + F > out.shape[2] or out.stride(2) != 1 \
+                or out.stride(1) < out.shape[2] or (B > 1 and out.stride(0) != T * out.stride(1)):
+            got = f"{out.dtype} {tuple(out.shape)} strides {out.stride()}" if isinstance(out, torch.Tensor) else type(out).__name__
+            raise ValueError(f"{name}: out is a float32 [B = {B}, T = {T}, >= col0 + F = {col0} + {F}] buffer with unit "
+                             f"column stride and one row pitch, got {got}")
+    return torch.view_as_real(X.contiguous()), B, T, F, out, out.stride(1)
+
+
+def specfeat_fwd(X, kind, out=None, col0=0):
+    """X complex64 [B,T,F] -> view [B,T,F]: kind 0 | 'abs' = |X|, 1 | 'log1p' = log1p|X|, 2 | 'mvn' = log1p|X| minus its
+    mean over the T frames.  out / col0: write columns [col0, col0 + F) of an existing float32 [B,T,ld] buffer (or a view
+    of one) and return that view -- no copy, nothing else of the buffer is touched."""
+    L = _lib.lib()
+    kind = SPECFEAT_KINDS.get(kind, kind)
+    Xr, B, T, F, out, ld = _specfeat_args("specfeat_fwd", X, out, col0)
+    nws = int(L.tssep_specfeat_workspace_bytes(B, T, F, int(kind)))
+    ws = torch.empty(nws // 8, device=X.device, dtype=torch.float64) if nws else None
+    with _timed("specfeat", 0, B * T * F * (12 if kind != 2 else 20)):
+        check(L.tssep_specfeat_fwd(_p(Xr), B, T, F, int(kind), _p((out, int(col0))), ld, _p(ws), _stream()), "specfeat_fwd")
+    return out[..., int(col0):int(col0) + F]
+
+
+def specfeat_causal_state_check(state, B, F):
+    """A carried state of `specfeat_causal_fwd` is float64 [B, F + 1]: say what arrived instead."""
+    if state is None:
+        return
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or tuple(state.shape) != (B, F + 1):
+        got = f"{state.dtype} {tuple(state.shape)}" if isinstance(state, torch.Tensor) else type(state).__name__
+        raise ValueError(f"specfeat_causal_fwd: state is {got}, what a call with B = {B}, F = {F} carries is torch.float64 "
+                         f"{(B, F + 1)}: the sums S[b, f] and the weight n[b] (did the batch or the FFT size change between "
+                         "the calls of a stream, or was the state of another feature passed?)")
+
+
+def specfeat_causal_fwd(X, state=None, forgetting=1.0, out=None, col0=0):
+    """The running-mean form of kind 2 on the next Tc frames of a stream: X complex64 [B,Tc,F], state what the call before
+    returned (None: a fresh stream) -> (view [B,Tc,F], state_out float64 [B, F + 1], a new tensor).  Per frame
+    S = a S + L, n = a n + 1, out = L - S / n with a = forgetting in (0, 1]; outputs and state do not depend on how the
+    frames are split over calls.  out / col0 as in `specfeat_fwd`."""
+    L = _lib.lib()
+    if not 0.0 < float(forgetting) <= 1.0:
+        raise ValueError(f"specfeat_causal_fwd: forgetting = {forgetting} lies outside (0, 1]")
+    Xr, B, T, F, out, ld = _specfeat_args("specfeat_causal_fwd", X, out, col0)
+    specfeat_causal_state_check(state, B, F)
+    if state is not None:
+        assert state.is_cuda, state.device
+        state = state.contiguous()
+    state_out = torch.empty(B, F + 1, device=X.device, dtype=torch.float64)
+    with _timed("specfeat_causal", 0, B * T * F * 12 + 16 * B * (F + 1)):
+        check(L.tssep_specfeat_causal_fwd(_p(Xr), B, T, F, float(forgetting), _p(state), _p(state_out),
+                                          _p((out, int(col0))), ld, _stream()), "specfeat_causal_fwd")
+    return out[..., int(col0):int(col0) + F], state_out
+
+
 # ----------------------------------------------------------------------------- online
 def stft_stream_fwd(x_new, tail, window, size=1024, shift=256):
     """The frames a push completes: x_new [rows, Tc * shift] behind tail [rows, size - shift] (None: a fresh stream, the

@@ -2,7 +2,8 @@
 padertorch ``STFT`` base it star-imports, feature_extractor.py:8) on the HIP kernels.
 
 Implemented: ``STFT`` (base: stft / istft / __call__), ``Log1pMaxNormAbsSTFT`` (:183-263),
-``ConcaternatedSTFTFeatures`` (:290-367), ``TorchMFCC`` (feature_extractor_torchaudio.py).
+``ConcaternatedSTFTFeatures`` (:290-367), ``TorchMFCC`` (feature_extractor_torchaudio.py), ``AbsSTFT`` / ``Log1pAbsSTFT``
+(padertorch's), ``MVNLog1pAbsSTFT`` (:112-168), ``NoFeatureSTFT`` (:171-180).  Not built: the two IPD classes, KaldiTorch*.
 Inputs must be CUDA tensors: there is no CPU path in this package.
 """
 import math
@@ -304,6 +305,108 @@ def _no_state(fe, state):
                          "the whole utterance")
 
 
+def _spectrum3(X):
+    """[..., T, F] (a 2-D spectrum is one utterance) on the device -> (complex64 [rows, T, F], the leading dimensions)."""
+    if isinstance(X, np.ndarray):
+        X = torch.as_tensor(X)
+    if not X.is_cuda:
+        raise RuntimeError("tssep_amd runs on the GPU only: move the spectrum to cuda first (no CPU fallback)")
+    if X.dim() < 2:
+        raise ValueError(f"stft_to_feature: a spectrum [..., T, F], got {tuple(X.shape)}")
+    if X.dtype != torch.complex64:
+        X = X.to(torch.complex64)
+    return X.reshape(-1, X.shape[-2], X.shape[-1]).contiguous(), X.shape[:-2]
+
+
+class AbsSTFT(STFT):
+    """padertorch.contrib.cb.feature_extractor.AbsSTFT (star-imported at feature_extractor.py:8): |X|.  No statistics, so
+    ``causal=True`` (this project's own keyword) changes nothing: a state passes through untouched."""
+    _kind = "abs"
+
+    def __init__(self, size=1024, shift=256, window_length=None, pad=True, fading=True,
+                 output_size=None, window="blackman", causal=False):
+        super().__init__(size=size, shift=shift, window_length=window_length, pad=pad,
+                         fading=fading, output_size=output_size, window=window)
+        self.causal = bool(causal)
+        self._check_feature_bins()
+
+    def _check_feature_bins(self):
+        F = self.size // 2 + 1
+        if F > H.SPECFEAT_MAX_BINS:
+            raise RuntimeError(f"{type(self).__name__}: size={self.size} gives {F} frequency bins; the spectral feature "
+                               f"kernels of libtssep_hip.so take at most {H.SPECFEAT_MAX_BINS} (size <= "
+                               f"{2 * (H.SPECFEAT_MAX_BINS - 1)}); the STFT / iSTFT themselves support this plan")
+
+    def _feature(self, X3, state, out=None, col0=0):
+        """[rows, T, F] -> (view [rows, T, F] -- of ``out`` from column ``col0`` when given --, the state)"""
+        if not self.causal:
+            _no_state(self, state)
+        return H.specfeat_fwd(X3, self._kind, out=out, col0=col0), state
+
+    def stft_to_feature(self, stft_signals, state=None, return_state=False):
+        X3, lead = _spectrum3(stft_signals)
+        out, state = self._feature(X3, state)
+        out = out.reshape(*lead, X3.shape[-2], X3.shape[-1])
+        return (out, state) if return_state else out
+
+
+class Log1pAbsSTFT(AbsSTFT):
+    """padertorch's Log1pAbsSTFT: log1p(|X|) (the doctest at feature_extractor.py:117-119)."""
+    _kind = "log1p"
+
+
+class MVNLog1pAbsSTFT(Log1pAbsSTFT):
+    """feature_extractor.py:112-168: log1p(|X|) minus its mean over the utterance's frames, one mean per frequency.
+    ``causal=True`` (this project's own): the mean of the frames so far -- a running sum S and a weight n per
+    utterance, ``S = a S + L, n = a n + 1, out = L - S / n`` with ``a = forgetting`` in (0, 1] (1: every frame counts
+    alike; < 1: a frame's weight decays by a per hop, the stream forgets).  ``state`` float64 [rows, F + 1] is what a
+    chunk's predecessor returned (None: the utterance starts here)."""
+    _kind = "mvn"
+
+    def __init__(self, size=1024, shift=256, window_length=None, pad=True, fading=True,
+                 output_size=None, window="blackman", norm_means: bool = True, norm_vars: bool = False,
+                 eps: float = 1.0e-20, causal=False, forgetting=1.0):
+        super().__init__(size=size, shift=shift, window_length=window_length, pad=pad, fading=fading,
+                         output_size=output_size, window=window, causal=causal)
+        self.norm_means, self.norm_vars, self.eps = norm_means, norm_vars, eps
+        if not 0.0 < float(forgetting) <= 1.0:
+            raise ValueError(f"MVNLog1pAbsSTFT: forgetting = {forgetting} lies outside (0, 1]")
+        if float(forgetting) != 1.0 and not self.causal:
+            raise ValueError(f"MVNLog1pAbsSTFT: forgetting = {forgetting} belongs to the running mean (causal=True); the "
+                             "mean of causal=False spans the whole utterance")
+        self.forgetting = float(forgetting)
+
+    def _feature(self, X3, state, out=None, col0=0):
+        if not self.norm_means:
+            raise NotImplementedError()              # (feature_extractor.py:165-166)
+        if self.norm_vars:
+            raise NotImplementedError()              # (:163-164)
+        if self.causal:
+            return H.specfeat_causal_fwd(X3, state, self.forgetting, out=out, col0=col0)
+        return super()._feature(X3, state, out, col0)
+
+
+class NoFeatureSTFT(STFT):
+    """feature_extractor.py:171-180: no spectral feature at all (host only: a slice).  ``causal`` is accepted because
+    ConcaternatedSTFTFeatures copies the key into its parts; there is nothing it could change."""
+
+    def __init__(self, size=1024, shift=256, window_length=None, pad=True, fading=True,
+                 output_size=None, window="blackman", causal=False):
+        super().__init__(size=size, shift=shift, window_length=window_length, pad=pad,
+                         fading=fading, output_size=output_size, window=window)
+        self.causal = bool(causal)
+
+    def stft_to_feature(self, stft_signals, state=None, return_state=False):
+        out = stft_signals[..., :0]
+        return (out, state) if return_state else out
+
+    def _get_output_size(self, output_size):
+        if output_size is None:
+            return 0
+        assert output_size == 0, (output_size, self.frequencies)
+        return output_size
+
+
 class TorchMFCC(STFT, torch.nn.Module):
     """feature_extractor_torchaudio.py:11-106; filterbank / DCT tables restated from
     torchaudio 2.0.2 (absent here; parity unpinned, see oracle/features.py)."""
@@ -486,6 +589,30 @@ class ConcaternatedSTFTFeatures(STFT, torch.nn.Module):
             out, _, state = H.feat_causal_fwd(X, self.fe1.fb, self.fe1.dct_mat, self.fe1.n_mfcc, self.fe1._db_arg,
                                               state=state)
             return (out, state) if return_state else out
+        # TorchMFCC beside a feature of csrc/specfeat.hip (AbsSTFT and its subclasses), both causal or neither: feat_fwd
+        # lays out the final [B, T, ld] buffer and writes the MFCC columns (and a log1p block it cannot skip), then the
+        # spectral kernel writes columns [n_mfcc, n_mfcc + F) over that block in place -- no concat, no third buffer.
+        # Causal: the carried state is the pair (TorchMFCC's, the spectral part's).
+        placed = isinstance(self.fe1, TorchMFCC) and isinstance(self.fe2, AbsSTFT) and X.dim() == 3 \
+            and self.fe1.causal == self.fe2.causal
+        if placed:
+            self.fe1._check_feature_bins()
+            X3, _ = _spectrum3(X)
+            if self.causal:
+                if state is None:
+                    state = (None, None)
+                if not isinstance(state, (tuple, list)) or len(state) != 2:
+                    got = f"{state.dtype} {tuple(state.shape)}" if isinstance(state, torch.Tensor) else type(state).__name__
+                    raise ValueError(f"ConcaternatedSTFTFeatures(TorchMFCC, {type(self.fe2).__name__}): the carried state is "
+                                     f"the pair (state of fe1, state of fe2) an earlier call returned, got {got}")
+                out, _, s1 = H.feat_causal_fwd(X3, self.fe1.fb, self.fe1.dct_mat, self.fe1.n_mfcc, self.fe1._db_arg,
+                                               state=state[0])
+                _, s2 = self.fe2._feature(X3, state[1], out=out, col0=self.fe1.n_mfcc)
+                return (out, (s1, s2)) if return_state else out
+            _no_state(self, state)
+            out, _ = H.feat_fwd(X3, self.fe1.fb, self.fe1.dct_mat, self.fe1.n_mfcc, self.fe1._db_arg)
+            self.fe2._feature(X3, None, out=out, col0=self.fe1.n_mfcc)
+            return (out, None) if return_state else out
         if self.causal:
             # (causal parts the fused kernel does not cover -- 'f' statistics: each part with the state, whose columns are
             # disjoint: the MFCC's dB maximum, the log1p's |X| maximum)

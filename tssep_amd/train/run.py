@@ -17,9 +17,25 @@ import yaml
 from .experiment import Experiment
 
 
+def _drop_foreign_keys(dst, src):
+    """A later file names another factory for a node (toy_tssep_mvn.yaml: fe2): the earlier files' keys that the new class
+    does not take are dropped -- they could only be a TypeError at construction; the keys it does take stay inherited."""
+    import inspect
+    from ..configurable import resolve
+    new, old = src.get("factory"), dst.get("factory")
+    if new is None or old is None or new == old:
+        return
+    params = inspect.signature(resolve(new).__init__).parameters
+    if any(p.kind == p.VAR_KEYWORD for p in params.values()):
+        return
+    for key in [k for k in dst if k != "factory" and k not in params]:
+        del dst[key]
+
+
 def _deep_update(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
+            _drop_foreign_keys(dst[k], v)
             _deep_update(dst[k], v)
         else:
             dst[k] = v
