@@ -1139,6 +1139,36 @@ int tssep_mask_istft_stream_bwd(const float* dy, const float* d_ola_out, const f
                                 const float* wsyn, const float* tw, int skip, int last, int64_t N, float* dlogit,
                                 float* d_ola_in, void* stream);
 
+/* ---- guided source separation: a cACGMM with the activities as hard priors ----
+ * This project's own definition (the reference has no GSS).  obs [D,T,F] complex128, activity uint8 [K,T] with
+ * entries 0 / 1, 1 <= D <= 8, 1 <= K <= 8; classes c = 0..K, class K is noise and active in every frame.  blocks
+ * int32 [P,4] on the device, rows (s_fit, e_fit, s_out, e_out) with s_fit <= s_out < e_out <= e_fit; every (block, bin)
+ * is one problem fitted on [s_fit, e_fit) whose posteriors are written for [s_out, e_out).  Per problem:
+ *   nrm_t = sqrt(sum_d |y_t[d]|^2), ok_t = nrm_t finite and > 0, yh_t = y_t / nrm_t; a frame that is not ok takes part
+ *   in no sum and gets gamma = 0.  Start: gamma_tc = a_tc / sum_c' a_c't, q_tc = 1.  `iterations` times:
+ *     n_c = sum_t gamma_tc (n_c == 0: the class is empty in this problem, log p = -inf)
+ *     B_c = (D / n_c) sum_t (gamma_tc / q_tc) yh_t yh_t^H;  B_c = B_c D / Re tr B_c + load I
+ *     L_c = chol(B_c), ld_c = 2 sum_i log L_c[i,i], q_tc = max(|L_c^-1 yh_t|^2, DBL_MIN)
+ *     log p_tc = log pi_c - ld_c - D log q_tc where a_tc = 1, else -inf;  pi_c = n_c / sum n (uniform_weights: 1)
+ *     gamma_tc = softmax_c(log p_tc)
+ * out [K+1,T,F] float32 (out_f64 = 0: the rounding of the float64 value) or float64.  The block table is built and
+ * checked by the host caller (the out ranges tile [0,T)); the kernels clamp every row to [0,T] and the fit range to
+ * max_fit frames (the host's maximum of e_fit - s_fit), so no access leaves the buffers whatever the table holds.
+ * All arithmetic float64; every sum over frames has one owner thread and an order fixed by the shape: no atomics,
+ * two calls give the same bits.  2 * iterations + 2 launches whatever P, T and the content; no host sync.
+ * workspace: tssep_gss_workspace_bytes() bytes (host only; 0 for an unsupported shape), 16-byte aligned.
+ * TSSEP_E_UNSUPPORTED for D or K outside 1..8, TSSEP_E_SHAPE for load <= 0 (or not finite), iterations < 1, P, T, F
+ * or max_fit < 1, P > 65535 -- before any launch.
+ *
+ * tssep_segments_to_activity: the segment table int32 [S,3] of rows (k, s, e) -> activity uint8 [K,T], 1 inside the
+ * rows.  A row with k outside [0,K), s < 0, e > T or s >= e is ignored (as tssep_mvdr_segments_fwd ignores it).
+ * S = 0 is legal (all zeros; table may be NULL then).  Two launches, no host sync. */
+int64_t tssep_gss_workspace_bytes(int P, int D, int K, int64_t T, int F, int64_t max_fit);
+int tssep_gss_fit(const double* obs, const uint8_t* activity, const int32_t* blocks, void* out, int out_f64,
+                  void* workspace, int P, int D, int K, int64_t T, int F, int64_t max_fit, int iterations,
+                  double load, int uniform_weights, void* stream);
+int tssep_segments_to_activity(const int32_t* table, int64_t S, int K, int64_t T, uint8_t* activity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2276,6 +2276,171 @@ def online_wpe(Y, state=None, taps=10, delay=2, forgetting=0.99, load=1.0, power
     return X, new
 
 
+# ------------------------------------------------- guided source separation (csrc/gss.hip)
+GSS_MAX_CHANNELS, GSS_MAX_SPEAKERS, GSS_MAX_BLOCKS, GSS_CHUNK = 8, 8, 65535, 256
+GSS_WEIGHTS = {"bin": 0, "uniform": 1}
+
+
+def gss_uniform_blocks(T, block=None, context=0):
+    """The block table of GSS(block, context): rows (s_fit, e_fit, s_out, e_out), out ranges of `block` frames, each
+    fitted with `context` more frames on either side, clipped to [0, T).  block None: the single row (0, T, 0, T)."""
+    if int(T) != T or T < 1:
+        raise ValueError(f"gss: T = {T!r}: at least one frame")
+    T = int(T)
+    if block is None:
+        if context not in (0, None):
+            raise ValueError(f"gss: context={context!r} without block: the whole recording is one fit")
+        return np.array([[0, T, 0, T]], dtype=np.int32)
+    if int(block) != block or block < 1:
+        raise ValueError(f"gss: block={block!r}: a positive number of frames, or None")
+    if int(context) != context or context < 0:
+        raise ValueError(f"gss: context={context!r}: a number of frames >= 0")
+    block, context = int(block), int(context)
+    return np.array([[max(0, s - context), min(T, s + block + context), s, min(T, s + block)]
+                     for s in range(0, T, block)], dtype=np.int32)
+
+
+def gss_blocks_check(blocks, T):
+    """blocks None | rows (s_fit, e_fit, s_out, e_out) -> int32 [P, 4] numpy, or ValueError: every row has
+    0 <= s_fit <= s_out < e_out <= e_fit <= T and the out ranges, in the order given, tile [0, T)."""
+    if blocks is None:
+        return gss_uniform_blocks(T)
+    if isinstance(blocks, torch.Tensor):
+        if blocks.is_cuda:
+            raise ValueError("gss: the block table is built on the host (a list or an array of rows), it is checked there")
+        blocks = blocks.numpy()
+    arr = np.asarray(blocks)
+    if arr.ndim != 2 or arr.shape[1] != 4 or arr.shape[0] < 1:
+        raise ValueError(f"gss: blocks {arr.shape}: rows (s_fit, e_fit, s_out, e_out)")
+    if not np.issubdtype(arr.dtype, np.integer):
+        if not np.all(np.isfinite(arr)) or not np.all(arr == np.floor(arr)):
+            raise ValueError("gss: the block table holds integers")
+    if arr.shape[0] > GSS_MAX_BLOCKS:
+        raise ValueError(f"gss: {arr.shape[0]} blocks: at most {GSS_MAX_BLOCKS}")
+    arr = arr.astype(np.int64)
+    at = 0
+    for sf, ef, so, eo in arr.tolist():
+        if not (0 <= sf <= so < eo <= ef <= T):
+            raise ValueError(f"gss: block ({sf}, {ef}, {so}, {eo}) breaks 0 <= s_fit <= s_out < e_out <= e_fit <= {T}")
+        if so != at:
+            raise ValueError(f"gss: the out ranges must tile [0, {T}): the block ({sf}, {ef}, {so}, {eo}) starts its out "
+                             f"range at {so}, the one before ended at {at}")
+        at = eo
+    if at != T:
+        raise ValueError(f"gss: the out ranges must tile [0, {T}): they end at {at}")
+    return arr.astype(np.int32)
+
+
+def guided_cacgmm_check(obs, activity, iterations=20, load=1e-6, weights="bin", blocks=None, out_dtype=torch.float32):
+    """What `guided_cacgmm` refuses, from the arguments alone (CPU tensors do: nothing is launched)
+    -> (D, K, T, F, block table int32 [P, 4] numpy)."""
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 3:
+        raise ValueError(f"guided_cacgmm: obs [D,T,F], got "
+                         f"{tuple(obs.shape) if isinstance(obs, torch.Tensor) else type(obs)}")
+    if obs.dtype != torch.complex128:
+        raise TypeError(f"guided_cacgmm: obs is {obs.dtype}, complex128 is required (all arithmetic is float64)")
+    if not isinstance(activity, torch.Tensor) or activity.dim() != 2:
+        raise ValueError(f"guided_cacgmm: activity [K,T], got "
+                         f"{tuple(activity.shape) if isinstance(activity, torch.Tensor) else type(activity)}")
+    if activity.is_complex():
+        raise TypeError(f"guided_cacgmm: activity is {activity.dtype}: 0 / 1 entries")
+    D, T, F = obs.shape
+    K, Ta = activity.shape
+    if min(T, F) < 1:
+        raise ValueError(f"guided_cacgmm: empty axis: obs {tuple(obs.shape)}")
+    if Ta != T:
+        raise ValueError(f"guided_cacgmm: activity {tuple(activity.shape)} does not match the {T} frames of obs")
+    if not 1 <= D <= GSS_MAX_CHANNELS:
+        raise ValueError(f"guided_cacgmm: {D} channels: the kernels are built for 1 to {GSS_MAX_CHANNELS}")
+    if not 1 <= K <= GSS_MAX_SPEAKERS:
+        raise ValueError(f"guided_cacgmm: {K} speakers: the kernels are built for 1 to {GSS_MAX_SPEAKERS} (plus noise)")
+    if isinstance(iterations, bool) or int(iterations) != iterations or iterations < 1:
+        raise ValueError(f"guided_cacgmm: iterations = {iterations!r}: an integer >= 1")
+    if not 0.0 < float(load) < float("inf"):
+        raise ValueError(f"guided_cacgmm: load = {load} is not positive and finite (it keeps every B_c positive definite)")
+    if weights not in GSS_WEIGHTS:
+        raise ValueError(f"guided_cacgmm: weights {weights!r}: 'bin' or 'uniform'")
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"guided_cacgmm: out_dtype {out_dtype}: float32 or float64")
+    if not activity.is_cuda and not bool(((activity == 0) | (activity == 1)).all()):
+        raise ValueError("guided_cacgmm: the activity holds only 0 and 1 (soft priors are not built)")
+    if obs.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("guided_cacgmm is evaluation-time only: obs requires grad and the EM has no backward")
+    return D, K, T, F, gss_blocks_check(blocks, T)
+
+
+_GSS_TABLES = {}        # (device, table bytes) -> int32 [P,4] on the device
+
+
+def _gss_table(tab, device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, tab.tobytes())
+    hit = _GSS_TABLES.get(key)
+    if hit is None:
+        if len(_GSS_TABLES) >= 64:
+            _GSS_TABLES.pop(next(iter(_GSS_TABLES)))
+        hit = _GSS_TABLES[key] = torch.from_numpy(tab).to(device)
+    return hit
+
+
+def gss_fma_per_frame_class(D):
+    """fp64 FMAs per (frame, class, iteration): the triangular product L^-1 yh and its squared norm (4 ntri + 2 D) and
+    the weighted outer product's lower triangle (6 ntri), ntri = D (D + 1) / 2."""
+    ntri = D * (D + 1) // 2
+    return 10 * ntri + 2 * D
+
+
+def guided_cacgmm(obs, activity, iterations=20, load=1e-6, weights="bin", blocks=None, out_dtype=torch.float32):
+    """The guided cACGMM of DESIGN 4.24: obs [D,T,F] complex128 and activity [K,T] of 0 / 1 on the device ->
+    gamma [K+1,T,F] (class K: noise), the posteriors after `iterations` EM steps with the activities as hard priors.
+    blocks: host rows (s_fit, e_fit, s_out, e_out) whose out ranges tile [0, T) (None: one fit over everything).
+    2 * iterations + 2 launches whatever the table, T and the content; no host sync (a block table seen before is not
+    copied again); float64 arithmetic in a fixed order: two calls give the same bits; out_dtype float32 is the rounding
+    of the float64 result.  No default is tuned.  The values of a device activity are not read by the host: anything
+    non-zero counts as 1."""
+    D, K, T, F, tab = guided_cacgmm_check(obs, activity, iterations, load, weights, blocks, out_dtype)
+    assert obs.is_cuda and activity.is_cuda, (obs.device, activity.device)
+    L = _lib.lib()
+    P = tab.shape[0]
+    fit = (tab[:, 1] - tab[:, 0]).astype(np.int64)
+    max_fit, sum_fit = int(fit.max()), int(fit.sum())
+    ws_bytes = L.tssep_gss_workspace_bytes(P, D, K, T, F, max_fit)
+    if ws_bytes <= 0:
+        raise RuntimeError(f"guided_cacgmm: unsupported shape obs {(D, T, F)} with {K} speakers and {P} blocks")
+    ws = torch.empty(ws_bytes // 8 + 2, device=obs.device, dtype=torch.float64)
+    act = (activity.detach() != 0).to(torch.uint8).contiguous()
+    obs_r = torch.view_as_real(obs.detach().contiguous())
+    out = torch.empty(K + 1, T, F, device=obs.device, dtype=out_dtype)
+    C, nent = K + 1, D * (D + 1) // 2 + 1
+    chunks = int(((fit + GSS_CHUNK - 1) // GSS_CHUNK).sum())
+    flops = 2 * int(iterations) * sum_fit * F * C * gss_fma_per_frame_class(D)
+    nbytes = 32 * D * T * F + out.element_size() * C * T * F \
+        + (int(iterations) + 1) * 16 * D * sum_fit * F + int(iterations) * 2 * 16 * chunks * F * C * nent
+    with _timed("gss_fit", flops, nbytes):
+        check(L.tssep_gss_fit(_p(obs_r), _p(act), _p(_gss_table(tab, obs.device)), _p(out),
+                              int(out_dtype == torch.float64), _p(ws), P, D, K, T, F, max_fit, int(iterations),
+                              float(load), GSS_WEIGHTS[weights], _stream()), "guided_cacgmm")
+    return out
+
+
+def segments_to_activity(table, K, T):
+    """The segment table int32 [S,3] of rows (k, s, e) on the device -> activity uint8 [K,T], 1 inside the rows.  A row
+    outside speakers [0, K) x frames [0, T] or an empty one is ignored, as segment_mvdr ignores it.  No host read."""
+    assert isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.int32, (type(table),)
+    assert table.dim() == 2 and table.shape[1] == 3, table.shape
+    if int(K) != K or K < 1 or int(T) != T or T < 1:
+        raise ValueError(f"segments_to_activity: K = {K!r}, T = {T!r}: both at least 1")
+    tab = table.contiguous()
+    S = tab.shape[0]
+    act = torch.empty(int(K), int(T), device=tab.device, dtype=torch.uint8)
+    with _timed("segments_to_activity", 0, 12 * S + int(K) * int(T)):
+        check(_lib.lib().tssep_segments_to_activity(_p(tab) if S else None, S, int(K), int(T), _p(act), _stream()),
+              "segments_to_activity")
+    return act
+
+
 # ----------------------------------------------------------------------------- losses
 def logmae_fwd(est, tgt):
     L = _lib.lib()

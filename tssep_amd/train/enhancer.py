@@ -449,3 +449,107 @@ class ClassicBF_np(ABC):
 
 
 ClassicBF = ClassicBF_np
+
+
+class GSS(ABC):
+    """Guided source separation -- THIS PROJECT'S class, the reference has none: what turns the speaker
+    activities of a TS-VAD model into audio.  Per frequency bin a complex angular central Gaussian mixture model with
+    one class per speaker and one for noise is fitted by ``iterations`` EM steps, the activities as hard priors on the
+    class affiliations (a speaker who is silent in a frame cannot own it; noise is always allowed); the posteriors are
+    the masks of the segment-wise MVDR.  One pipeline of HIP kernels (hip_ops.guided_cacgmm, csrc/gss.hip), float64.
+    ``block`` / ``context``: the model is fitted on windows of block + 2 context frames and read in their middle
+    (nobody moves inside a window); None: one fit over the recording.  ``weights``: 'bin' (mixture weights per bin) or
+    'uniform'.  ``load``: the diagonal loading of every B_c, relative to its mean eigenvalue 1.  No default is tuned.
+    ``masks`` returns the posteriors [K+1, 1, T, F] (class K: noise); calling the object runs the chain
+    pre_wpe (once) -> masks -> ``bf`` (default ClassicBF_np with SumCrossTalker), the noise class as a (K+1)-th speaker
+    without rows, so that the distortion mask of a speaker sums every other class, noise included.  Dereverberation
+    belongs to this class's ``pre_wpe``: a ``bf`` with a pre_wpe of its own is refused, the masks and the filter would
+    see different observations."""
+
+    @classmethod
+    def finalize_dogmatic_config(cls, config):
+        config["bf"] = {"factory": ClassicBF_np}
+
+    def __init__(self, iterations=20, load=1e-6, weights="bin", block=None, context=0, pre_wpe=None, bf=None):
+        super().__init__()
+        self.iterations = iterations
+        self.load = load
+        self.weights = weights
+        self.block = block
+        self.context = context
+        self.pre_wpe = pre_wpe
+        self.bf = bf if bf is not None else ClassicBF_np(distortion_mask=enhancer_distortion_mask.SumCrossTalker())
+
+    def _observation(self, Observation):
+        if not isinstance(Observation, torch.Tensor):
+            Observation = torch.as_tensor(np.ascontiguousarray(Observation))
+        if Observation.dtype != torch.complex128:
+            raise TypeError(f"{self.name}: Observation is {Observation.dtype}, complex128 is required")
+        assert Observation.dim() == 3, Observation.shape
+        return Observation.detach()
+
+    def _activity(self, dia, T, K, device):
+        """dia -> (activity [K, T] on `device`, what the beamformer takes as dia for K + 1 'speakers')"""
+        if isinstance(dia, torch.Tensor) and dia.dtype == torch.int32 and dia.dim() == 2 and dia.shape[1] == 3:
+            if T == 3:
+                raise ValueError(f"{self.name}: an int32 [*, 3] tensor with T = 3 frames is a segment table or an activity: "
+                                 "pass the activity as uint8 or bool, or the table's speakers as lists of intervals")
+            if K is None:
+                raise ValueError(f"{self.name}: a segment table comes with K, the number of speakers")
+            table = dia.to(device)
+            return H.segments_to_activity(table, K, T), table          # stays on the device
+        if isinstance(dia, (torch.Tensor, np.ndarray)):
+            act = torch.as_tensor(dia)
+            if act.dim() != 2 or act.shape[1] != T:
+                raise ValueError(f"{self.name}: an activity array is [K, {T}], got {tuple(act.shape)}")
+            rows = list(act.detach().cpu().numpy())
+        else:
+            assert isinstance(dia, (tuple, list)), ("Expect list of ArrayInterval", type(dia), dia)
+            rows = dia
+        if K is not None and len(rows) != K:
+            raise ValueError(f"{self.name}: {len(rows)} activities for K = {K} speakers")
+        intervals = [normalized_intervals(ai, T) for ai in rows]
+        host = np.zeros((len(intervals), T), dtype=np.uint8)
+        for k, iv in enumerate(intervals):
+            for s, e in iv:
+                host[k, s:e] = 1
+        return torch.from_numpy(host).to(device), intervals + [[]]      # the noise class has no rows
+
+    def _masks(self, obs, act):
+        blocks = H.gss_uniform_blocks(obs.shape[1], self.block, self.context)
+        return H.guided_cacgmm(obs, act, self.iterations, self.load, self.weights, blocks)[:, None]
+
+    def masks(self, Observation, dia, K=None):
+        """Observation [D, T, F] complex128 (D >= 1), dia: one activity per speaker (see normalized_intervals), a 0/1
+        array [K, T], or a segment table int32 [S, 3] together with K (that route stays on the device; an int32 [*, 3]
+        tensor is always read as a table, and refused as ambiguous when T = 3) -> float32 [K+1, 1, T, F] on the device."""
+        obs = self._observation(Observation)
+        device = obs.device if obs.is_cuda else torch.device("cuda")
+        act, _ = self._activity(dia, obs.shape[1], K, device)
+        H.guided_cacgmm_check(obs, act, self.iterations, self.load, self.weights)      # before obs moves
+        return self._masks(obs.to(device), act)
+
+    def __call__(self, Observation, dia, numpy_out=False, K=None):
+        """The whole chain; the output is ClassicBF_np's for the K speakers: numpy_out=True the dense [K, T, F] device
+        tensor, False per speaker a dict {(s, e): [e - s, F]} of views (not with a segment table: its rows stay on
+        the device)."""
+        if not isinstance(self.bf, ClassicBF_np):
+            raise NotImplementedError(f"bf={self.bf!r}: the masks go to this module's ClassicBF_np")
+        if self.pre_wpe is not None and not isinstance(self.pre_wpe, WPE):
+            raise NotImplementedError(f"pre_wpe={self.pre_wpe!r}: only this module's WPE / ChannelWiseWPE are built")
+        if self.bf.pre_wpe is not None:
+            raise ValueError(f"{self.name}: bf.pre_wpe is set: the masks would be fitted on another observation than the "
+                             f"beamformer filters (or, with pre_wpe here as well, it would be dereverberated twice); give "
+                             f"pre_wpe to {self.name} alone")
+        obs = self._observation(Observation)
+        assert obs.shape[0] >= 6, obs.shape      # all channels loaded? (ClassicBF_np's own check)
+        device = obs.device if obs.is_cuda else torch.device("cuda")
+        act, bf_dia = self._activity(dia, obs.shape[1], K, device)
+        H.guided_cacgmm_check(obs, act, self.iterations, self.load, self.weights)
+        if isinstance(bf_dia, torch.Tensor) and not numpy_out:
+            raise NotImplementedError(f"{self.name}: a segment table gives the dense output (numpy_out=True)")
+        obs = obs.to(device)
+        if self.pre_wpe is not None:
+            obs = self.pre_wpe(obs)
+        out = self.bf(self._masks(obs, act), obs, bf_dia, numpy_out=numpy_out)
+        return out[:act.shape[0]]
